@@ -2,7 +2,7 @@
 """Benchmark of the hot path: whole internal steps of the mode-split time step (one `advance`:
 lateral_viscosity, mode_interaction, isplit external substeps, mode_internal, check_velocity).
 
-    python bench.py --gpus N --steps K --warmup W [--workload basin2048|seamount256|basin1024|...]
+    python bench.py --gpus N --steps K --warmup W [--workload basin2048|seamount256|basin1024|...] [--dump-outputs DIR]
 
 N=1 runs in this process.  N>1: one rank per GPU, the global grid split into N tiles (strong scaling: the
 global grid is fixed) -- started by the caller under torch.distributed.run (WORLD_SIZE set), or, when
@@ -132,6 +132,27 @@ def gpu_initialise(st, device, stream, libpath=None):
     finish_initial(st, dens, baropg)
     g.upload(st)
     return g
+
+
+DUMP_VALUES_PER_ARRAY = 1 << 17     # 1 MiB of float64: the 37 arrays of the restart list stay under 64 MB in all
+
+
+def dump_outputs(st, outdir):
+    """--dump-outputs: the state the last timed step left, as a caller of `advance` receives it -- every array of the reference's
+    restart list (layout.RESTART_2D / RESTART_3D) -- written as outdir/<name>.npy in float64.  An array of more than
+    DUMP_VALUES_PER_ARRAY values is written as a fixed sample of them: the same seeded, sorted flat indices for every array of
+    its size, in every run, so that two builds can be compared output for output."""
+    import numpy as np
+    from extpom_amd.layout import RESTART_2D, RESTART_3D
+    os.makedirs(outdir, exist_ok=True)
+    picks = {}
+    for name in RESTART_2D + RESTART_3D:
+        a = np.asarray(st.field(name), dtype=np.float64)
+        if a.size > DUMP_VALUES_PER_ARRAY:
+            if a.size not in picks:
+                picks[a.size] = np.sort(np.random.default_rng(0).choice(a.size, DUMP_VALUES_PER_ARRAY, replace=False))
+            a = a.reshape(-1)[picks[a.size]]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def _sample_dims(workload):
@@ -619,7 +640,13 @@ def main():
     ap.add_argument("--storage", choices=["f64", "f32"], default="f64",
                     help="f32: BASELINE configs[4]'s STUDY variant (libpomgpu_f32.so: 3-D arrays stored as fp32, arithmetic and the external "
                          "mode fp64).  Not a parity path (DESIGN.md section 8) and never the headline: the line says so in `dtype`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps write the state they leave as DIR/<name>.npy (float64; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs: one GPU only (--gpus 1)")
     if args.cpu_sample:
         v, what, n, dt = _reference_sample(args.workload) if args.reference else _cpu_run(args.workload, args.full_grid)
         print(json.dumps({"value": v, "what": what, "n": n, "seconds": dt}))
@@ -705,6 +732,9 @@ def measure(args):
             placement = g.tune_placement(3, 10)
         except Exception as e:                                     # noqa: BLE001 -- the measurement does not depend on it
             print(f"bench: placement not tuned ({e})", file=sys.stderr)
+        # how many layouts fit (and so how many steps the trials took) depends on the free memory: the warm-up starts from the
+        # initial state again, so that the timed steps get the same inputs in every run (the placement survives the upload)
+        g.upload(st)
     build_id = g.L.pomgpu_build_id().decode()
     exchange = "none"
     rccl_nranks = 0
@@ -802,6 +832,9 @@ def measure(args):
         dt = float(t.item())
     g.get_con()
     err = int(st.error_status)
+    if args.dump_outputs:                                      # one GPU only (main)
+        g.download()
+        dump_outputs(st, args.dump_outputs)
     if world > 1:                                              # a rank whose step failed fails the pass: every rank learns it
         t = torch.tensor([float(err)], dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)

@@ -183,3 +183,16 @@ def ref_finish_initial(st):
         lib.get(s)
 
     return finish_initial(st, dens, baropg)
+
+
+def state_digests(st):
+    """{array: digest} of a whole state -- every COMMON array, bdry and each blkcon member -- as the first 16 hex digits of the
+    SHA-256 of its bytes: equal digests, equal bits.  What tests/golden/make_golden.py `refcheck` stores of the reference's state
+    and tests/test_oracle_vs_reference.py computes of the oracle's."""
+    import hashlib
+    from extpom_amd.layout import BLK2D, BLK3D
+    h = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:16]
+    d = {n: h(st.field(n)) for n in BLK2D + BLK3D}
+    d["bdry"] = h(st.bdry)
+    d.update({"con." + n: h(st.con[n]) for n in st.con.dtype.names})
+    return d

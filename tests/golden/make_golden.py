@@ -2,7 +2,7 @@
 (oracle/_ref/libpomref_65x49x21.so, built from the unmodified sources by oracle/build_ref.sh) on
 the inputs of extpom_amd.cases.  Run from the repo root in a container that has /root/reference:
 
-    oracle/build_ref.sh 65 49 21 && oracle/build_ref.sh 256 192 50 && python tests/golden/make_golden.py [kb50 | kb50long NAME | forced]
+    oracle/build_ref.sh 65 49 21 && oracle/build_ref.sh 256 192 50 && python tests/golden/make_golden.py [kb50 | kb50long NAME | forced | refcheck]
 
 The fixture holds, per configuration and checkpoint step, the SHA-256 of every restart-list field
 (the prognostic state, reference io_pnetcdf.F:1724-1886) exactly as the reference left it in its
@@ -96,7 +96,135 @@ def generate_forced():
     print("forced_advance done", flush=True)
 
 
+# tests/test_oracle_vs_reference.py: the reference's WHOLE state (every COMMON array, bdry, blkcon; oracle.refharness.state_digests)
+# after every step and after each hot-path routine on its own, so that the oracle is held to it where oracle/_ref cannot be built.
+# A record after the first of a sequence holds only the arrays whose digest changed (tests/test_oracle_vs_reference.py rebuilds it).
+REFCHECK_FULL_STATE = [("seamount", dict(dte=6.0, isplit=30)), ("island", dict(dte=6.0, isplit=30, nadv=1)),
+                       ("basin", dict(dte=6.0, isplit=10, nitera=2)), ("island", dict(dte=6.0, isplit=30, npg=2))]
+REFCHECK_FORCING_STEPS = (1, 2, 19, 20, 21, 40, 41, 59, 60, 61, 62)
+
+
+def refcheck_key(case, nml):
+    return json.dumps([case, nml], sort_keys=True)
+
+
+def _delta(prev, cur):
+    return {k: v for k, v in cur.items() if prev.get(k) != v}
+
+
+def generate_refcheck():
+    import ctypes
+    from extpom_amd.cases import make_forcing_records, make_lateral_records
+    from oracle.refharness import state_digests
+    out = {"grid": [65, 49, 21], "full_state": {}}
+    for case, nml in REFCHECK_FULL_STATE:
+        a = make_case(case, 65, 49, 21, **nml)
+        ref_finish_initial(a)
+        prev = state_digests(a)
+        rec = {"init": prev, "steps": {}}
+        lib = RefLib(65, 49, 21)
+        lib.put(a)
+        for n in range(1, 13):
+            lib.con["iint"][0] = n
+            lib.advance()
+            lib.get(a)
+            cur = state_digests(a)
+            rec["steps"][str(n)] = _delta(prev, cur)
+            prev = cur
+        out["full_state"][refcheck_key(case, nml)] = rec
+
+    # each routine on its own, from the state after three steps (all branches live)
+    a = make_case("seamount", 65, 49, 21, dte=6.0, isplit=30)
+    ref_finish_initial(a)
+    lib = RefLib(65, 49, 21)
+    lib.put(a)
+    for n in range(1, 4):
+        lib.con["iint"][0] = n
+        lib.advance()
+    lib.get(a)
+    a.iint = 4
+    a.iext = 7
+    warm = state_digests(a)
+    calls = {}
+
+    def ref_call(label, name, args=()):
+        x = a.copy()
+        lib.put(x)
+        lib.call(name, *args(lib) if callable(args) else args)
+        lib.get(x)
+        calls[label] = _delta(warm, state_digests(x))
+
+    i = lambda v: ctypes.byref(ctypes.c_int(v))
+    for name in ("advave", "advct", "advu", "advv", "baropg", "baropg_mcc", "profq", "profu", "profv", "vertvl", "realvertvl",
+                 "lateral_viscosity", "mode_interaction", "mode_external", "mode_internal", "check_velocity"):
+        ref_call(name, name)
+    ref_call("advq", "advq", lambda l: (l.f3("q2b"), l.f3("q2"), l.f3("uf")))
+    for r in ("advt1", "advt2"):
+        ref_call(r, r, lambda l: (l.f3("tb"), l.f3("t"), l.f3("tclim"), l.f3("uf")))
+    ref_call("dens", "dens", lambda l: (l.f3("s"), l.f3("t"), l.f3("rho")))
+    for nbc in (1, 2, 3, 4):
+        ref_call(f"proft/{nbc}", "proft", lambda l: (l.f3("uf"), l.f2("wtsurf"), l.f2("tsurf"), i(nbc)))
+    for idx in (1, 2, 4, 5, 6):
+        ref_call(f"bcond/{idx}", "bcond", (i(idx),))
+    for idx in (3, 5):
+        ref_call(f"bcondorl/{idx}", "bcondorl", (i(idx),))
+    out["each_routine"] = {"warm": warm, "calls": calls}
+
+    # domain_stats (the SUM intrinsic) after five steps of the island case
+    a = make_case("island", 65, 49, 21, dte=6.0, isplit=30)
+    ref_finish_initial(a)
+    lib = RefLib(65, 49, 21)
+    lib.put(a)
+    for n in range(1, 6):
+        lib.con["iint"][0] = n
+        lib.advance()
+    lib.get(a)
+    lib.mpi_init()
+    vals = [ctypes.c_double() for _ in range(8)]
+    lib.call("domain_stats", *[ctypes.byref(v) for v in vals])
+    out["domain_stats"] = {"state": state_digests(a), "values": [v.value.hex() for v in vals]}
+
+    # forcing records changing inside the run
+    a = make_case("seamount", 65, 49, 21, dte=6.0, isplit=30, days=0.4)
+    ref_finish_initial(a)
+    make_forcing_records(a, 4)
+    make_lateral_records(a, 5)
+    prev = state_digests(a)
+    rec = {"init": prev, "steps": {}}
+    lib = RefLib(65, 49, 21)
+    lib.put(a)
+    for n in range(1, max(REFCHECK_FORCING_STEPS) + 1):
+        lib.con["iint"][0] = n
+        lib.advance()
+        if n in REFCHECK_FORCING_STEPS:
+            lib.get(a)
+            cur = state_digests(a)
+            rec["steps"][str(n)] = _delta(prev, cur)
+            prev = cur
+    out["forcing"] = rec
+
+    # lramp = .true.
+    a = make_case("seamount", 65, 49, 21, dte=6.0, isplit=30)
+    a.lramp = True
+    ref_finish_initial(a)
+    init = state_digests(a)
+    lib = RefLib(65, 49, 21)
+    lib.put(a)
+    for n in range(1, 7):
+        lib.con["iint"][0] = n
+        lib.advance()
+    lib.get(a)
+    out["ramped"] = {"init": init, "steps": {"6": _delta(init, state_digests(a))}}
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(here, "oracle_vs_reference_65x49x21.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+    print("refcheck done", flush=True)
+
+
 def main():
+    if "refcheck" in sys.argv[1:]:
+        return generate_refcheck()
     if "forced" in sys.argv[1:]:
         return generate_forced()
     if "kb50long" in sys.argv[1:]:

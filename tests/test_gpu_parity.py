@@ -871,3 +871,32 @@ def test_tune_placement_refuses_once_a_3d_address_has_been_handed_out(monkeypatc
     assert int(b.error_status) == 1 and not diff(a, b), diff(a, b)
     g.close()
 
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_hold_the_state_after_the_warm_up_profiled_and_timed_steps(tmp_path):
+    """bench.py --dump-outputs: what the timed path computed in its last step.  The placement trials (forced on this small grid:
+    POMGPU_TUNE_FORCE) advance the model by as many steps as layouts fit in free memory; the bench starts its warm-up from the
+    initial state again, so the dump is the oracle's state after exactly warm-up + one profiled + K timed steps, bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from extpom_amd import dist as pdist
+    from extpom_amd.layout import RESTART_2D, RESTART_3D
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    OracleTile, oracle_finish_initial = _oracle()
+    env = dict(os.environ, POMGPU_TUNE_FORCE="1")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "seamount65", "--steps", "3", "--warmup", "2",
+                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["error_status"] == 0, line
+    assert line["config"]["placement"]["tried"] > 0, line["config"]["placement"]
+    sys.path.insert(0, root)
+    import bench
+    a = bench.build_state("seamount65", pdist.tile_for_rank(0, 1, 65, 49))
+    oracle_finish_initial(a)
+    OracleTile(a).run(2 + 1 + 3)
+    bad = [n for n in RESTART_2D + RESTART_3D if not same_bits(np.load(tmp_path / f"{n}.npy"), a.field(n))]
+    assert not bad, bad

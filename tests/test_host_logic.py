@@ -203,6 +203,35 @@ def test_bench_tile_grids_follow_baseline_configs():
         bench.tile_grids("basin2048", 8, "3x3")
 
 
+def test_bench_dump_outputs_writes_the_restart_list_within_64_mb(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every restart-list array as <name>.npy in float64, whole where it is small, else the same seeded
+    sample in every run; at the flagship grid (2048x1536x50) the files stay under 64 MB in all"""
+    sys.path.insert(0, ROOT)
+    import bench
+    from extpom_amd.layout import RESTART_2D, RESTART_3D
+    names = RESTART_2D + RESTART_3D
+    assert len(names) * (bench.DUMP_VALUES_PER_ARRAY * 8 + 128) < 64e6
+    st = make_case("seamount", 65, 49, 21)
+    bench.dump_outputs(st, str(tmp_path / "whole"))
+    for n in names:
+        a = np.load(tmp_path / "whole" / f"{n}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, st.field(n)), n
+    monkeypatch.setattr(bench, "DUMP_VALUES_PER_ARRAY", 1000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(st, str(tmp_path / d))
+    for n in names:
+        a, b = np.load(tmp_path / "s1" / f"{n}.npy"), np.load(tmp_path / "s2" / f"{n}.npy")
+        assert a.dtype == np.float64 and a.shape == (1000,) and np.array_equal(a, b), n
+        assert np.isin(a, st.field(n)).all(), n
+    assert sorted(p.name for p in (tmp_path / "s1").iterdir()) == sorted(n + ".npy" for n in names)
+
+
+@pytest.mark.parametrize("extra", [["--steps", "0"], ["--gpus", "2", "--dump-outputs", "x"]])
+def test_bench_refuses_what_it_cannot_measure(extra):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *extra], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and not r.stdout and "error" in r.stderr, r.stdout + r.stderr
+
+
 def test_short_wave_term_in_double_double_equals_the_quad_evaluation(tmp_path):
     """csrc/dd_exp.h (what the proft kernels evaluate for solver.f:1608-1611) against the REAL(16) expression as libquadmath
     evaluates it, on arguments of proft's ranges (tools/check_dd_exp.cpp; 2e7 arguments there, 3e5 here): no result may differ."""

@@ -1,141 +1,141 @@
-"""The CPU oracle against the reference build itself (oracle/_ref, only where /root/reference was
-available to oracle/build_ref.sh).  ALL COMMON-block arrays -- not only the restart list -- must be
-bit-identical after every step, and so must each hot-path routine called on its own."""
+"""The CPU oracle against the reference itself.  ALL COMMON-block arrays -- not only the restart list -- and bdry and blkcon
+must be bit-identical after every step, and so must each hot-path routine called on its own.  The reference's side is stored
+in tests/golden/oracle_vs_reference_65x49x21.json: per array a digest of the state of the reference build (oracle/_ref, the
+unmodified sources, oracle/build_ref.sh) on the same inputs, written by `tests/golden/make_golden.py refcheck`."""
 import ctypes
+import json
+import os
 
 import numpy as np
 import pytest
 
 from extpom_amd.cases import make_case
 from extpom_amd.layout import BLK2D, BLK3D
-from oracle.pyoracle import OracleTile
-from oracle.refharness import RefLib, have_ref, ref_finish_initial
+from oracle.pyoracle import OracleTile, oracle_finish_initial
+from oracle.refharness import state_digests
 
-pytestmark = pytest.mark.skipif(not have_ref(65, 49, 21), reason="oracle/_ref not built (no /root/reference)")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vs_reference_65x49x21.json")
 
 
-def _diff(a, b):
-    bad = [n for n in BLK2D + BLK3D if not np.array_equal(a.field(n), b.field(n))]
-    if not np.array_equal(a.bdry, b.bdry):
-        bad.append("bdry")
-    bad += ["con." + n for n in a.con.dtype.names if a.con[n][0] != b.con[n][0]]
-    return bad
+@pytest.fixture(scope="module")
+def ref():
+    with open(GOLDEN) as f:
+        return json.load(f)
+
+
+def _diff(st, want):
+    """what of st differs from the reference's bits; a NaN counts as a difference wherever it is (it equals nothing)"""
+    got = state_digests(st)
+    bad = [n for n in want if got[n] != want[n]]
+    floats = [(n, st.field(n)) for n in BLK2D + BLK3D] + [("bdry", st.bdry)]
+    floats += [("con." + n, st.con[n]) for n in st.con.dtype.names if st.con.dtype[n].kind == "f"]
+    return bad + [n for n, a in floats if n not in bad and np.isnan(a).any()]
+
+
+def _steps(rec):
+    """(step, whole expected state) in order: a stored record after the first holds only the arrays that changed"""
+    cur = dict(rec["init"])
+    for n in sorted(rec["steps"], key=int):
+        cur.update(rec["steps"][n])
+        yield int(n), dict(cur)
 
 
 @pytest.mark.parametrize("case,nml", [("seamount", dict(dte=6.0, isplit=30)),
                                       ("island", dict(dte=6.0, isplit=30, nadv=1)),
                                       ("basin", dict(dte=6.0, isplit=10, nitera=2)),
                                       ("island", dict(dte=6.0, isplit=30, npg=2))])
-def test_full_state_bit_identical(case, nml):
-    a = make_case(case, 65, 49, 21, **nml)
-    ref_finish_initial(a)
-    b = a.copy()
-    lib = RefLib(65, 49, 21)
-    lib.put(a)
+def test_full_state_bit_identical(ref, case, nml):
+    rec = ref["full_state"][json.dumps([case, nml], sort_keys=True)]
+    b = make_case(case, 65, 49, 21, **nml)
+    oracle_finish_initial(b)
+    assert not _diff(b, rec["init"]), f"initial state: {_diff(b, rec['init'])}"
     ot = OracleTile(b)
-    for n in range(1, 13):
-        lib.con["iint"][0] = n
-        lib.advance()
-        lib.get(a)
+    want = list(_steps(rec))
+    assert [n for n, _ in want] == list(range(1, 13))
+    for n, w in want:
         ot.run(1)
-        assert not _diff(a, b), f"step {n}: {_diff(a, b)}"
+        assert not _diff(b, w), f"step {n}: {_diff(b, w)}"
 
 
-def test_each_routine_bit_identical():
-    """call the reference's routines one by one on a warm state (step 3: all branches live)"""
+def test_each_routine_bit_identical(ref):
+    """call the routines one by one on a warm state (step 3: all branches live)"""
     a = make_case("seamount", 65, 49, 21, dte=6.0, isplit=30)
-    ref_finish_initial(a)
-    lib = RefLib(65, 49, 21)
-    lib.put(a)
-    for n in range(1, 4):
-        lib.con["iint"][0] = n
-        lib.advance()
-    lib.get(a)
+    oracle_finish_initial(a)
+    OracleTile(a).run(3)
     a.iint = 4
     a.iext = 7
+    warm, calls = ref["each_routine"]["warm"], ref["each_routine"]["calls"]
+    assert not _diff(a, warm), f"warm state: {_diff(a, warm)}"
+    done = []
 
-    def both(name, ref_args=(), or_args=()):
-        x, y = a.copy(), a.copy()
-        lib.put(x)
-        lib.call(name, *ref_args(lib) if callable(ref_args) else ref_args)
-        lib.get(x)
+    def both(label, name, or_args=()):
+        y = a.copy()
         ot = OracleTile(y)
         ot.call(name, *or_args(ot) if callable(or_args) else or_args)
-        assert not _diff(x, y), f"{name}: {_diff(x, y)}"
+        want = dict(warm, **calls[label])
+        assert not _diff(y, want), f"{label}: {_diff(y, want)}"
+        done.append(label)
 
-    i = lambda v: ctypes.byref(ctypes.c_int(v))
     for name in ("advave", "advct", "advu", "advv", "baropg", "baropg_mcc", "profq", "profu", "profv", "vertvl", "realvertvl",
                  "lateral_viscosity", "mode_interaction", "mode_external", "mode_internal", "check_velocity"):
-        both(name)
-    both("advq", lambda l: (l.f3("q2b"), l.f3("q2"), l.f3("uf")), lambda o: (o.a3("q2b"), o.a3("q2"), o.a3("uf")))
+        both(name, name)
+    both("advq", "advq", lambda o: (o.a3("q2b"), o.a3("q2"), o.a3("uf")))
     for r in ("advt1", "advt2"):
-        both(r, lambda l: (l.f3("tb"), l.f3("t"), l.f3("tclim"), l.f3("uf")),
-             lambda o: (o.a3("tb"), o.a3("t"), o.a3("tclim"), o.a3("uf")))
-    both("dens", lambda l: (l.f3("s"), l.f3("t"), l.f3("rho")), lambda o: (o.a3("s"), o.a3("t"), o.a3("rho")))
+        both(r, r, lambda o: (o.a3("tb"), o.a3("t"), o.a3("tclim"), o.a3("uf")))
+    both("dens", "dens", lambda o: (o.a3("s"), o.a3("t"), o.a3("rho")))
     for nbc in (1, 2, 3, 4):
-        both("proft", lambda l: (l.f3("uf"), l.f2("wtsurf"), l.f2("tsurf"), i(nbc)),
-             lambda o: (o.a3("uf"), o.a2("wtsurf"), o.a2("tsurf"), ctypes.c_int(nbc)))
+        both(f"proft/{nbc}", "proft", lambda o: (o.a3("uf"), o.a2("wtsurf"), o.a2("tsurf"), ctypes.c_int(nbc)))
     for idx in (1, 2, 4, 5, 6):
-        both("bcond", (i(idx),), (ctypes.c_int(idx),))
+        both(f"bcond/{idx}", "bcond", (ctypes.c_int(idx),))
     for idx in (3, 5):
-        both("bcondorl", (i(idx),), (ctypes.c_int(idx),))
+        both(f"bcondorl/{idx}", "bcondorl", (ctypes.c_int(idx),))
+    assert sorted(done) == sorted(calls)
 
 
-def test_domain_stats_matches_reference_to_rounding():
+def test_domain_stats_matches_reference_to_rounding(ref):
     """advance.f:644-756 uses the SUM intrinsic (order of additions is the compiler's): 1e-13 relative"""
     a = make_case("island", 65, 49, 21, dte=6.0, isplit=30)
-    ref_finish_initial(a)
-    lib = RefLib(65, 49, 21)
-    lib.put(a)
-    for n in range(1, 6):
-        lib.con["iint"][0] = n
-        lib.advance()
-    lib.get(a)
-    lib.mpi_init()
-    vals = [ctypes.c_double() for _ in range(8)]
-    lib.call("domain_stats", *[ctypes.byref(v) for v in vals])
+    oracle_finish_initial(a)
+    OracleTile(a).run(5)
+    rec = ref["domain_stats"]
+    assert not _diff(a, rec["state"]), f"step 5: {_diff(a, rec['state'])}"
     out = (ctypes.c_double * 8)()
     OracleTile(a).call("domain_stats", out, ctypes.c_int(0))
-    np.testing.assert_allclose(np.array(list(out)), np.array([v.value for v in vals]), rtol=1e-13, atol=0)
+    np.testing.assert_allclose(np.array(list(out)), np.array([float.fromhex(v) for v in rec["values"]]), rtol=1e-13, atol=0)
 
 
-def test_forcing_bit_identical_across_record_changes():
+def test_forcing_bit_identical_across_record_changes(ref):
     """surface_forcing (wind, heat, surface: bounds_forcing.f:871-983) and lateral_bc (:593-868) inside advance
     (advance.f:14-18), fed with the same records through the readers' entry points.  62 steps: the surface records
     shift at step 60 (0.125 d / 180 s), the lateral ones every 20 steps (1/24 d).  The whole bdry block is compared
     (incl. the members the reference never refreshes, :742-753)."""
     from extpom_amd.cases import make_forcing_records, make_lateral_records
-    a = make_case("seamount", 65, 49, 21, dte=6.0, isplit=30, days=0.4)
-    ref_finish_initial(a)
-    make_forcing_records(a, 4)
-    make_lateral_records(a, 5)
-    b = a.copy()
-    lib = RefLib(65, 49, 21)
-    lib.put(a)
+    b = make_case("seamount", 65, 49, 21, dte=6.0, isplit=30, days=0.4)
+    oracle_finish_initial(b)
+    make_forcing_records(b, 4)
+    make_lateral_records(b, 5)
+    rec = ref["forcing"]
+    assert not _diff(b, rec["init"]), f"initial state: {_diff(b, rec['init'])}"
+    want = dict(_steps(rec))
+    assert sorted(want) == [1, 2, 19, 20, 21, 40, 41, 59, 60, 61, 62]
     ot = OracleTile(b)
     for n in range(1, 63):
-        lib.con["iint"][0] = n
-        lib.advance()
         ot.run(1)
-        if n in (1, 2, 19, 20, 21, 40, 41, 59, 60, 61, 62):
-            lib.get(a)
-            assert not _diff(a, b), f"step {n}: {_diff(a, b)}"
-    assert float(np.abs(a.tsurf).max()) > 0 and not np.array_equal(a.wusurfb, a.wusurff)
+        if n in want:
+            assert not _diff(b, want[n]), f"step {n}: {_diff(b, want[n])}"
+    assert float(np.abs(b.tsurf).max()) > 0 and not np.array_equal(b.wusurfb, b.wusurff)
 
 
-def test_ramped_forcing_bit_identical():
+def test_ramped_forcing_bit_identical(ref):
     """lramp = .true.: ramp = time/period grows every step (advance.f:66-72) and scales the open-boundary
     velocities and the pressure gradient"""
-    a = make_case("seamount", 65, 49, 21, dte=6.0, isplit=30)
-    a.lramp = True
-    ref_finish_initial(a)
-    b = a.copy()
-    lib = RefLib(65, 49, 21)
-    lib.put(a)
+    b = make_case("seamount", 65, 49, 21, dte=6.0, isplit=30)
+    b.lramp = True
+    oracle_finish_initial(b)
+    rec = ref["ramped"]
+    assert not _diff(b, rec["init"]), f"initial state: {_diff(b, rec['init'])}"
     ot = OracleTile(b)
-    for n in range(1, 7):
-        lib.con["iint"][0] = n
-        lib.advance()
+    for _ in range(6):
         ot.run(1)
-    lib.get(a)
-    assert 0.0 < a.ramp < 1.0 and not _diff(a, b), _diff(a, b)
+    (n, want), = _steps(rec)
+    assert n == 6 and 0.0 < b.ramp < 1.0 and not _diff(b, want), _diff(b, want)
