@@ -442,34 +442,35 @@ template <int TAU> __global__ void k_ts_update(KP P, double fold, double fnew, i
   MARCH3(c_ts_update<TAU>(P, i, j, k, fold, fnew, rt, store_rst, tau_b, tau_f))
 }
 template <int TAU> __device__ __forceinline__ void c_ts_update(const KP &P, const int i, const int j, const int k, double fold, double fnew, int rt, int store_rst, double tau_b, double tau_f) {
+  // pomgpu_ct: fp32 in the fp32-arithmetic variant (pomgpu_internal.hpp) -- all but dens, which takes the widened t, s
   const bool act = (i <= P.im && j <= P.jm), lev = (k <= P.kbm1);
-  const double m = F2(fsm, i, j);
-  double uf = F3(uf, i, j, k), vf = F3(vf, i, j, k);
+  const pomgpu_ct m = F2(fsm, i, j);
+  pomgpu_ct uf = F3(uf, i, j, k), vf = F3(vf, i, j, k);
   if (lev && act) {                                                    // bcond(4) mask
     uf = uf * m;                                                       // not stored: the only reader of the masked uf/vf is this
     vf = vf * m;                                                       // filter; advu/advv rewrite both arrays next (advance.f:459-460)
   }
-  double tb = F3(tb, i, j, k), sb = F3(sb, i, j, k);
+  pomgpu_ct tb = F3(tb, i, j, k), sb = F3(sb, i, j, k);
   if (rt) {                                                            // fb = fb-fclim ... fb = fb+fclim
-    const double tc = F3(tclim, i, j, k), sc = F3(sclim, i, j, k);
+    const pomgpu_ct tc = F3(tclim, i, j, k), sc = F3(sclim, i, j, k);
     tb = (tb - tc) + tc;
     sb = (sb - sc) + sc;
   }
-  const double t0 = F3(t, i, j, k), s0 = F3(s, i, j, k);
-  double tbn = t0 + .5 * P.smoth * (uf + tb - 2. * t0);                // advance.f:444-449
-  double sbn = s0 + .5 * P.smoth * (vf + sb - 2. * s0);
-  double tn = uf, sn = vf;
+  const pomgpu_ct t0 = F3(t, i, j, k), s0 = F3(s, i, j, k);
+  pomgpu_ct tbn = t0 + CT(.5) * CT(P.smoth) * (uf + tb - CT(2.) * t0);  // advance.f:444-449
+  pomgpu_ct sbn = s0 + CT(.5) * CT(P.smoth) * (vf + sb - CT(2.) * s0);
+  pomgpu_ct tn = uf, sn = vf;
   if (lev) {
     if (act) {                                                         // restore_interior
-      const double tr = fold * F3(trstrb, i, j, k) + fnew * F3(trstrf, i, j, k);
-      const double sr = fold * F3(srstrb, i, j, k) + fnew * F3(srstrf, i, j, k);
-      const double ta = TAU ? fold * tau_b + fnew * tau_f : fold * F3(taurstrb, i, j, k) + fnew * F3(taurstrf, i, j, k);
+      const pomgpu_ct tr = CT(fold) * CT(F3(trstrb, i, j, k)) + CT(fnew) * CT(F3(trstrf, i, j, k));
+      const pomgpu_ct sr = CT(fold) * CT(F3(srstrb, i, j, k)) + CT(fnew) * CT(F3(srstrf, i, j, k));
+      const pomgpu_ct ta = TAU ? CT(fold) * CT(tau_b) + CT(fnew) * CT(tau_f) : CT(fold) * CT(F3(taurstrb, i, j, k)) + CT(fnew) * CT(F3(taurstrf, i, j, k));
       if (store_rst) {                                                 // else left to k_restore_fields (on demand)
         F3(trstr, i, j, k) = tr;
         F3(srstr, i, j, k) = sr;
         F3(taurstr, i, j, k) = ta;
       }
-      const double c = 2. * P.dti / 86400.;
+      const pomgpu_ct c = CT(2.) * CT(P.dti) / CT(86400.);
       tn = tn + c * ta * (tr - tn);
       tbn = tbn + c * ta * (tr - tbn);
       sn = sn + c * ta * (sr - sn);

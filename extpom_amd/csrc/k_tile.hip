@@ -53,10 +53,12 @@ __global__ void k_coef_eta(KP P) {
 }
 
 // ---- advt2, nitera == 1 -- solver.f:577-731 with smol_adif's mask (:1898-1900) --------------------
-__device__ __forceinline__ double upw_(double m, double lo, double hi) {     // solver.f:631-635
-  return 0.5 * ((m + fabs(m)) * lo + (m - fabs(m)) * hi);
+__device__ __forceinline__ pomgpu_ct upw_(pomgpu_ct m, pomgpu_ct lo, pomgpu_ct hi) {     // solver.f:631-635
+  return CT(0.5) * ((m + fabs(m)) * lo + (m - fabs(m)) * hi);
 }
-struct FaceT { double adv, dif; };
+// the values of k_advt2_col, k_advq_col, k_advct_col and k_advuv_col are pomgpu_ct: fp32 in the fp32-arithmetic variant
+// (pomgpu_internal.hpp), where every 2-D coefficient is narrowed once per column, before the level loop
+struct FaceT { pomgpu_ct adv, dif; };
 // ---- advt2, nitera == 1, COLUMN-MARCHING version -----------------------------------------------------
 // PMC profile of the row-marching kernel above (2048x1536x50): 31 GB of L2-miss traffic per launch
 // against 7.5 GB algorithmic -- the 14 two-dimensional coefficient operands of a cell are re-fetched
@@ -76,22 +78,22 @@ struct TFields { const double *fb[2], *f[2], *fcl[2]; double *ff[2]; };
 // Operands of a level.  Shared with the rows above and below through the workgroup's LDS slab (RowShare,
 // pomgpu_internal.hpp), in this order: fb[0..NF-1], fclim[0..NF-1], aam, v; this row only: u, w.
 // c: the wavefront's own row, h: its share of the two rows outside the workgroup.
-template <int NF> struct LevT { double c[2 * NF + 2], o[2], h[ROWSHARE_SLOTS(2 * NF + 2)]; };
-template <int NS> struct NbrT { double s[NS], n[NS]; };
-struct CoefT { double cm, hs, msk, ds_num; InvD den; };   // mass-flux coefficient, h sum, mask, metric sums of one face
+template <int NF> struct LevT { pomgpu_ct c[2 * NF + 2], o[2], h[ROWSHARE_SLOTS(2 * NF + 2)]; };
+template <int NS> struct NbrT { pomgpu_ct s[NS], n[NS]; };
+struct CoefT { pomgpu_ct cm, hs, msk, ds_num; InvDc den; };   // mass-flux coefficient, h sum, mask, metric sums of one face
 __device__ __forceinline__ CoefT coef_x(const KP &P, int i, int j) {
-  CoefT c; c.cm = K2(CMX, i, j); c.hs = K2(HSX, i, j); c.msk = F2(dum, i, j); c.ds_num = K2(DYSX, i, j); c.den = inv_of(K2(DXSX, i, j)); return c;
+  CoefT c; c.cm = K2(CMX, i, j); c.hs = K2(HSX, i, j); c.msk = F2(dum, i, j); c.ds_num = K2(DYSX, i, j); c.den = inv_of(CT(K2(DXSX, i, j))); return c;
 }
 __device__ __forceinline__ CoefT coef_y(const KP &P, int i, int j) {
-  CoefT c; c.cm = K2(CMY, i, j); c.hs = K2(HSY, i, j); c.msk = F2(dvm, i, j); c.ds_num = K2(DXSY, i, j); c.den = inv_of(K2(DYSY, i, j)); return c;
+  CoefT c; c.cm = K2(CMY, i, j); c.hs = K2(HSY, i, j); c.msk = F2(dvm, i, j); c.ds_num = K2(DXSY, i, j); c.den = inv_of(CT(K2(DYSY, i, j))); return c;
 }
 // face between a "lo" cell (west / south) and a "hi" cell; vel = u or v on that face
-__device__ __forceinline__ FaceT advt2_face(const KP &P, const CoefT &c, double vel, double fb_hi, double fb_lo, double fc_hi,
-                                            double fc_lo, double am_hi, double am_lo) {
+__device__ __forceinline__ FaceT advt2_face(const pomgpu_ct tprni, const CoefT &c, pomgpu_ct vel, pomgpu_ct fb_hi, pomgpu_ct fb_lo, pomgpu_ct fc_hi,
+                                            pomgpu_ct fc_lo, pomgpu_ct am_hi, pomgpu_ct am_lo) {
   FaceT f;
   f.adv = upw_(c.cm * vel, fb_lo, fb_hi);
-  const double am = 0.5 * (am_hi + am_lo);
-  f.dif = divi(-am * c.hs * P.tprni * ((fb_hi - fc_hi) - (fb_lo - fc_lo)) * c.msk * c.ds_num * 0.5, c.den);
+  const pomgpu_ct am = CT(0.5) * (am_hi + am_lo);
+  f.dif = divi(-am * c.hs * tprni * ((fb_hi - fc_hi) - (fb_lo - fc_lo)) * c.msk * c.ds_num * CT(0.5), c.den);
   return f;
 }
 #if COL_WX != 1
@@ -120,11 +122,12 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
   const int iw = i > 1 ? i - 1 : 1, ie = i < P.iml ? i + 1 : P.iml;
   const int js = jc > 1 ? jc - 1 : 1, jn = jc < P.jml ? jc + 1 : P.jml;
   const bool in = icol && (i >= 2 && i <= P.imm1 && jc >= 2 && jc <= P.jmm1);
-  const double fsm = F2(fsm, i, jc);
+  const pomgpu_ct fsm = F2(fsm, i, jc);
   // column-resident coefficients of the west, south and north faces and of the cell
   const CoefT cw = coef_x(P, i, jc), cs = coef_y(P, i, jc), cn = coef_y(P, i, jn);
-  const double art = F2(art, i, jc), hea = K2(HEA, i, jc);
-  const InvD hfa = inv_of(K2(HFA, i, jc));
+  const pomgpu_ct art = F2(art, i, jc), hea = K2(HEA, i, jc);
+  const InvDc hfa = inv_of(CT(K2(HFA, i, jc)));
+  const pomgpu_ct tprni = P.tprni, dti2 = P.dti2;
   BufA bs[NS], bo[2], bff[NF], bh[NH];
   const double *ps[NS];
 #pragma unroll
@@ -138,23 +141,23 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
   const unsigned oc = BOFF2(i, jc), lvb = LVB;
   const unsigned ost = in ? oc : BOFF_NONE;
 #ifndef POMGPU_EMU
-  __shared__ double slab[2][NS][ROWSHARE_ROWS][64];
+  __shared__ pomgpu_ct slab[2][NS][ROWSHARE_ROWS][64];
 #else
   const unsigned os = BOFF2(i, js), on = BOFF2(i, jn);
 #endif
   auto load = [&](LevT<NF> &L, unsigned lv) {
 #pragma unroll
-    for (int x = 0; x < NS; x++) L.c[x] = bld(bs[x], oc, lv);
-    L.o[0] = bld(bo[0], oc, lv); L.o[1] = bld(bo[1], oc, lv);
+    for (int x = 0; x < NS; x++) L.c[x] = bldc(bs[x], oc, lv);
+    L.o[0] = bldc(bo[0], oc, lv); L.o[1] = bldc(bo[1], oc, lv);
 #pragma unroll
-    for (int q = 0; q < NH; q++) L.h[q] = bld(bh[q], S.hoff[q], lv);
+    for (int q = 0; q < NH; q++) L.h[q] = bldc(bh[q], S.hoff[q], lv);
   };
-  double f1[NF];
+  pomgpu_ct f1[NF];
 #pragma unroll
   for (int f = 0; f < NF; f++) f1[f] = G3(A.f[f], i, jc, 1);
   const int kbm1 = P.kbm1;
   // carried from level L-1 to its completion in iteration L
-  double p_adv[NF], p_dif[NF], p_fb[NF], p_zu[NF];
+  pomgpu_ct p_adv[NF], p_dif[NF], p_fb[NF], p_zu[NF];
 #pragma unroll
   for (int f = 0; f < NF; f++) p_adv[f] = p_dif[f] = p_fb[f] = p_zu[f] = 0.;
   // one iteration: request level L+1 into `nxt`, park level L (`cur`) in the slab, evaluate its faces, finish level L-1.
@@ -175,42 +178,42 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
 #else
     const unsigned lvc = (unsigned)((L <= kbm1 ? L : kbm1) - 1) * lvb;
 #pragma unroll
-    for (int x = 0; x < NS; x++) { nb.s[x] = bld(bs[x], os, lvc); nb.n[x] = bld(bs[x], on, lvc); }
+    for (int x = 0; x < NS; x++) { nb.s[x] = bldc(bs[x], os, lvc); nb.n[x] = bldc(bs[x], on, lvc); }
 #endif
-    const double am_c = cur.c[AM], u_c = cur.o[0], w_c = cur.o[1];
-    const double am_w = halo_w(am_c, [&] { return F3(aam, iw, jc, L); });
-    InvD dzk; dzk.b = dzk.y = 0.;
+    const pomgpu_ct am_c = cur.c[AM], u_c = cur.o[0], w_c = cur.o[1];
+    const pomgpu_ct am_w = halo_w(am_c, [&] { return F3(aam, iw, jc, L); });
+    InvDc dzk; dzk.b = dzk.y = 0.;
     if (L >= 2) { dzk.b = F1(dz, L - 1); dzk.y = R1(dz, L - 1); }
 #pragma unroll
     for (int f = 0; f < NF; f++) {
-      const double fb_c = cur.c[f], fc_c = cur.c[NF + f];
-      double zu = 0.;                                                              // top face of level L (0 below kbm1)
-      double s_adv = 0., s_dif = 0.;
+      const pomgpu_ct fb_c = cur.c[f], fc_c = cur.c[NF + f];
+      pomgpu_ct zu = 0.;                                                           // top face of level L (0 below kbm1)
+      pomgpu_ct s_adv = 0., s_dif = 0.;
       if (L <= kbm1) {
-        const double fb_w = halo_w(fb_c, [&] { return G3(A.fb[f], iw, jc, L); });
-        const double fc_w = halo_w(fc_c, [&] { return G3(A.fcl[f], iw, jc, L); });
-        const FaceT xw = advt2_face(P, cw, u_c, fb_c, fb_w, fc_c, fc_w, am_c, am_w);
+        const pomgpu_ct fb_w = halo_w(fb_c, [&] { return G3(A.fb[f], iw, jc, L); });
+        const pomgpu_ct fc_w = halo_w(fc_c, [&] { return G3(A.fcl[f], iw, jc, L); });
+        const FaceT xw = advt2_face(tprni, cw, u_c, fb_c, fb_w, fc_c, fc_w, am_c, am_w);
         auto east = [&] {                                   // emulation only: the east face from memory
-          return advt2_face(P, coef_x(P, ie, jc), F3(u, ie, jc, L), G3(A.fb[f], ie, jc, L), fb_c, G3(A.fcl[f], ie, jc, L), fc_c,
+          return advt2_face(tprni, coef_x(P, ie, jc), F3(u, ie, jc, L), G3(A.fb[f], ie, jc, L), fb_c, G3(A.fcl[f], ie, jc, L), fc_c,
                             F3(aam, ie, jc, L), am_c);
         };
         FaceT xe;
         xe.adv = halo_e(xw.adv, [&] { return east().adv; });
         xe.dif = halo_e(xw.dif, [&] { return east().dif; });
-        const FaceT ys = advt2_face(P, cs, cur.c[VV], fb_c, nb.s[f], fc_c, nb.s[NF + f], am_c, nb.s[AM]);
-        const FaceT yn = advt2_face(P, cn, nb.n[VV], nb.n[f], fb_c, nb.n[NF + f], fc_c, nb.n[AM], am_c);
+        const FaceT ys = advt2_face(tprni, cs, cur.c[VV], fb_c, nb.s[f], fc_c, nb.s[NF + f], am_c, nb.s[AM]);
+        const FaceT yn = advt2_face(tprni, cn, nb.n[VV], nb.n[f], fb_c, nb.n[NF + f], fc_c, nb.n[AM], am_c);
         s_adv = xe.adv - xw.adv + yn.adv - ys.adv;                                            // solver.f:670-671
         s_dif = xe.dif - xw.dif + yn.dif - ys.dif;                                            // :721-722
         zu = (L == 1) ? w_c * f1[f] * art : upw_(w_c, fb_c, p_fb[f]) * art;                   // :646-662
       }
       {                                                     // finish level L-1: its bottom face is this level's top face
-        double rr = p_adv[f] + divi(p_zu[f] - zu, dzk);                                       // :670-672
-        rr = divi(p_fb[f] * hea - P.dti2 * rr, hfa);                                          // :673-674
+        pomgpu_ct rr = p_adv[f] + divi(p_zu[f] - zu, dzk);                                    // :670-672
+        rr = divi(p_fb[f] * hea - dti2 * rr, hfa);                                            // :673-674
         rr = rr * fsm;                                                                        // :1899
-        rr = rr - divi(P.dti2 * p_dif[f], hfa);                                               // :721-723
+        rr = rr - divi(dti2 * p_dif[f], hfa);                                                 // :721-723
         // every lane stores, every iteration: lanes without an interior column (and the first iteration, which has
         // no finished level yet) aim outside the buffer and the hardware drops the store
-        bst(bff[f], (L >= 2 && L <= kbm1 + 1) ? ost : BOFF_NONE, (unsigned)(L >= 2 ? L - 2 : 0) * lvb, rr);
+        bstc(bff[f], (L >= 2 && L <= kbm1 + 1) ? ost : BOFF_NONE, (unsigned)(L >= 2 ? L - 2 : 0) * lvb, rr);
       }
       p_adv[f] = s_adv; p_dif[f] = s_dif; p_fb[f] = fb_c; p_zu[f] = zu;
     }
@@ -228,7 +231,7 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
   if (icol) {
     for (int k = in ? P.kb : 1; k <= P.kb; k++) {
 #pragma unroll
-      for (int f = 0; f < NF; f++) G3(A.ff[f], i, jc, k) = G3(A.ff[f], i, jc, k) * fsm;
+      for (int f = 0; f < NF; f++) G3(A.ff[f], i, jc, k) = CT(G3(A.ff[f], i, jc, k)) * fsm;
     }
   }
 }
@@ -242,20 +245,20 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
 // face coefficient are read once for both -- 12.5 array passes instead of 2 x 9.5.
 struct QFields { const double *q[2], *qb[2]; double *qf[2]; };
 // operands of a level, shared through the workgroup's LDS slab in this order: q[0..NF-1], qb[0..NF-1], aam, v; own row only: u, w
-template <int NF> struct LevQa { double c[2 * NF + 2], o[2], h[ROWSHARE_SLOTS(2 * NF + 2)]; };
-struct CoefQ { double dts, hs, msk, ds_num; InvD den; };
+template <int NF> struct LevQa { pomgpu_ct c[2 * NF + 2], o[2], h[ROWSHARE_SLOTS(2 * NF + 2)]; };
+struct CoefQ { pomgpu_ct dts, hs, msk, ds_num; InvDc den; };
 __device__ __forceinline__ CoefQ coefq_x(const KP &P, int i, int j) {
-  CoefQ c; c.dts = K2(DTSX, i, j); c.hs = K2(HSX, i, j); c.msk = F2(dum, i, j); c.den = inv_of(K2(DXSX, i, j)); c.ds_num = K2(DYSX, i, j); return c;
+  CoefQ c; c.dts = K2(DTSX, i, j); c.hs = K2(HSX, i, j); c.msk = F2(dum, i, j); c.den = inv_of(CT(K2(DXSX, i, j))); c.ds_num = K2(DYSX, i, j); return c;
 }
 __device__ __forceinline__ CoefQ coefq_y(const KP &P, int i, int j) {
-  CoefQ c; c.dts = K2(DTSY, i, j); c.hs = K2(HSY, i, j); c.msk = F2(dvm, i, j); c.den = inv_of(K2(DYSY, i, j)); c.ds_num = K2(DXSY, i, j); return c;
+  CoefQ c; c.dts = K2(DTSY, i, j); c.hs = K2(HSY, i, j); c.msk = F2(dvm, i, j); c.den = inv_of(CT(K2(DYSY, i, j))); c.ds_num = K2(DXSY, i, j); return c;
 }
 // flux through the face between a "lo" (west/south) and a "hi" cell at w-level k (:428-453)
-__device__ __forceinline__ double advq_face(const CoefQ &c, double q_hi, double q_lo, double vel_k, double vel_km1, double am_hi_k,
-                                            double am_lo_k, double am_hi_m, double am_lo_m, double qb_hi, double qb_lo) {
-  double x = .125 * (q_hi + q_lo) * c.dts * (vel_k + vel_km1);
-  x = x - divi(.25 * (am_hi_k + am_lo_k + am_hi_m + am_lo_m) * c.hs * (qb_hi - qb_lo) * c.msk, c.den);
-  return .5 * c.ds_num * x;
+__device__ __forceinline__ pomgpu_ct advq_face(const CoefQ &c, pomgpu_ct q_hi, pomgpu_ct q_lo, pomgpu_ct vel_k, pomgpu_ct vel_km1, pomgpu_ct am_hi_k,
+                                               pomgpu_ct am_lo_k, pomgpu_ct am_hi_m, pomgpu_ct am_lo_m, pomgpu_ct qb_hi, pomgpu_ct qb_lo) {
+  pomgpu_ct x = CT(.125) * (q_hi + q_lo) * c.dts * (vel_k + vel_km1);
+  x = x - divi(CT(.25) * (am_hi_k + am_lo_k + am_hi_m + am_lo_m) * c.hs * (qb_hi - qb_lo) * c.msk, c.den);
+  return CT(.5) * c.ds_num * x;
 }
 // loop discipline and row sharing as in k_advt2_col
 template <int NF>
@@ -274,8 +277,8 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
   const int js = jc > 1 ? jc - 1 : 1, jn = jc < P.jml ? jc + 1 : P.jml;
   const bool in = icol && (i >= 2 && i <= P.imm1 && jc >= 2 && jc <= P.jmm1);
   const CoefQ cw = coefq_x(P, i, jc), cs = coefq_y(P, i, jc), cn = coefq_y(P, i, jn);
-  const double art = F2(art, i, jc), hea = K2(HEA, i, jc);
-  const InvD hfa = inv_of(K2(HFA, i, jc));
+  const pomgpu_ct art = F2(art, i, jc), hea = K2(HEA, i, jc);
+  const InvDc hfa = inv_of(CT(K2(HFA, i, jc)));
   const int kb = P.kb, kbm1 = P.kbm1;
   BufA bs[NS], bo[2], bqf[NF], bh[NH];
   const double *ps[NS];
@@ -291,22 +294,22 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
   // interior columns get the new value, every other owned column a zero (zero_else) or nothing
   const unsigned ost = in ? oc : ((zero_else && icol) ? oc : BOFF_NONE);
 #ifndef POMGPU_EMU
-  __shared__ double slab[2][NS][ROWSHARE_ROWS][64];
+  __shared__ pomgpu_ct slab[2][NS][ROWSHARE_ROWS][64];
 #else
   const unsigned os = BOFF2(i, js), on = BOFF2(i, jn);
 #endif
   auto load = [&](LevQa<NF> &L, int k) {
     const unsigned lv = (unsigned)WAVE_UNIFORM(k - 1) * lvb;
 #pragma unroll
-    for (int x = 0; x < NS; x++) L.c[x] = bld(bs[x], oc, lv);
-    L.o[0] = bld(bo[0], oc, lv); L.o[1] = bld(bo[1], oc, lv);
+    for (int x = 0; x < NS; x++) L.c[x] = bldc(bs[x], oc, lv);
+    L.o[0] = bldc(bo[0], oc, lv); L.o[1] = bldc(bo[1], oc, lv);
 #pragma unroll
-    for (int q = 0; q < NH; q++) L.h[q] = bld(bh[q], S.hoff[q], lv);
+    for (int q = 0; q < NH; q++) L.h[q] = bldc(bh[q], S.hoff[q], lv);
   };
-  double u_m = 0., v_m = 0., vn_m = 0., am_m = 0., ams_m = 0., amn_m = 0.;   // u, v, v(j+1), aam (c, s, n) of level L-1
-  double am_w_prv = 0.;                       // aam(i-1,j,L-1) as seen by this lane
-  double wq_pp[NF], wq_p[NF];                 // w*q of levels L-2 and L-1
-  double xe_p[NF], xw_p[NF], yn_p[NF], ys_p[NF], qb_p[NF];   // faces and qb of level L-1, waiting for w(L)*q(L)
+  pomgpu_ct u_m = 0., v_m = 0., vn_m = 0., am_m = 0., ams_m = 0., amn_m = 0.;   // u, v, v(j+1), aam (c, s, n) of level L-1
+  pomgpu_ct am_w_prv = 0.;                    // aam(i-1,j,L-1) as seen by this lane
+  pomgpu_ct wq_pp[NF], wq_p[NF];              // w*q of levels L-2 and L-1
+  pomgpu_ct xe_p[NF], xw_p[NF], yn_p[NF], ys_p[NF], qb_p[NF];   // faces and qb of level L-1, waiting for w(L)*q(L)
 #pragma unroll
   for (int f = 0; f < NF; f++) wq_pp[f] = wq_p[f] = xe_p[f] = xw_p[f] = yn_p[f] = ys_p[f] = qb_p[f] = 0.;
   auto step = [&](const int L, const int par, const LevQa<NF> &cur, LevQa<NF> &nxt) {
@@ -323,22 +326,22 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
 #else
     const unsigned lvc = (unsigned)((L <= kb ? L : kb) - 1) * lvb;
 #pragma unroll
-    for (int x = 0; x < NS; x++) { nb.s[x] = bld(bs[x], os, lvc); nb.n[x] = bld(bs[x], on, lvc); }
+    for (int x = 0; x < NS; x++) { nb.s[x] = bldc(bs[x], os, lvc); nb.n[x] = bldc(bs[x], on, lvc); }
 #endif
-    const double am_c = cur.c[AM], v_c = cur.c[VV], u_c = cur.o[0], w_c = cur.o[1];
-    const double am_s = nb.s[AM], am_n = nb.n[AM], v_n = nb.n[VV];
-    const double am_w = halo_w(am_c, [&] { return F3(aam, iw, jc, L); });
+    const pomgpu_ct am_c = cur.c[AM], v_c = cur.c[VV], u_c = cur.o[0], w_c = cur.o[1];
+    const pomgpu_ct am_s = nb.s[AM], am_n = nb.n[AM], v_n = nb.n[VV];
+    const pomgpu_ct am_w = halo_w(am_c, [&] { return F3(aam, iw, jc, L); });
     const int k = L - 1;                                    // level completed in this iteration
-    InvD dz2; dz2.b = dz2.y = 0.;
-    if (k >= 2 && k <= kbm1) { dz2.b = F1(dz, k) + F1(dz, k - 1); dz2.y = 1.0 / dz2.b; }
+    InvDc dz2; dz2.b = dz2.y = 0.;
+    if (k >= 2 && k <= kbm1) { dz2.b = CT(F1(dz, k)) + CT(F1(dz, k - 1)); dz2.y = CT(1.0) / dz2.b; }
 #pragma unroll
     for (int f = 0; f < NF; f++) {
-      const double q_c = cur.c[f], qb_c = cur.c[NF + f];
-      double xe_c = 0., xw_c = 0., yn_c = 0., ys_c = 0.;
+      const pomgpu_ct q_c = cur.c[f], qb_c = cur.c[NF + f];
+      pomgpu_ct xe_c = 0., xw_c = 0., yn_c = 0., ys_c = 0.;
       if (L >= 2 && L <= kbm1) {
-        const double q_w = halo_w(q_c, [&] { return G3(A.q[f], iw, jc, L); });
-        const double qb_w = halo_w(qb_c, [&] { return G3(A.qb[f], iw, jc, L); });
-        const double xw = advq_face(cw, q_c, q_w, u_c, u_m, am_c, am_w, am_m, am_w_prv, qb_c, qb_w);
+        const pomgpu_ct q_w = halo_w(q_c, [&] { return G3(A.q[f], iw, jc, L); });
+        const pomgpu_ct qb_w = halo_w(qb_c, [&] { return G3(A.qb[f], iw, jc, L); });
+        const pomgpu_ct xw = advq_face(cw, q_c, q_w, u_c, u_m, am_c, am_w, am_m, am_w_prv, qb_c, qb_w);
         xw_c = xw;
         xe_c = halo_e(xw, [&] {                             // emulation only: the east face from memory
           return advq_face(coefq_x(P, ie, jc), G3(A.q[f], ie, jc, L), q_c, F3(u, ie, jc, L), F3(u, ie, jc, L - 1), F3(aam, ie, jc, L), am_c,
@@ -347,18 +350,18 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
         ys_c = advq_face(cs, q_c, nb.s[f], v_c, v_m, am_c, am_s, am_m, ams_m, qb_c, nb.s[NF + f]);
         yn_c = advq_face(cn, nb.n[f], q_c, v_n, vn_m, am_n, am_c, amn_m, am_m, nb.n[NF + f], qb_c);
       }
-      const double wq_c = w_c * q_c;
+      const pomgpu_ct wq_c = w_c * q_c;
       {
-        double rr = 0.;
+        pomgpu_ct rr = 0.;
         if (in && k >= 2 && k <= kbm1) {
           rr = divi((wq_pp[f] - wq_c) * art, dz2) + xe_p[f] - xw_p[f] + yn_p[f] - ys_p[f];    // :465-468
-          rr = divi(hea * qb_p[f] - P.dti2 * rr, hfa);                                        // :469-471
+          rr = divi(hea * qb_p[f] - CT(P.dti2) * rr, hfa);                                    // :469-471
         }
         // levels 2..kbm1 of interior columns: the new value; with zero_else every other owned cell (levels 1..kb-1 here,
         // kb below): zero; everything else aims outside the buffer
         const bool lev_in = (k >= 2 && k <= kbm1);
         const unsigned o = (k >= 1) ? (lev_in ? ost : ((zero_else && icol) ? oc : BOFF_NONE)) : BOFF_NONE;
-        bst(bqf[f], o, (unsigned)WAVE_UNIFORM(k >= 1 ? k - 1 : 0) * lvb, rr);
+        bstc(bqf[f], o, (unsigned)WAVE_UNIFORM(k >= 1 ? k - 1 : 0) * lvb, rr);
       }
       wq_pp[f] = wq_p[f]; wq_p[f] = wq_c; qb_p[f] = qb_c;
       xe_p[f] = xe_c; xw_p[f] = xw_c; yn_p[f] = yn_c; ys_p[f] = ys_c;
@@ -475,7 +478,7 @@ __global__ void k_advct_fix(KP P, const double *from_w, const double *from_s) {
 // Loop discipline and row sharing as in k_advt2_col.
 // ROWS rows per workgroup: 8 (LDS_ROWS) on large grids; 4 on low tiles, where a launch is only three or four rounds of workgroups and two
 // workgroups per compute unit leave the last round fuller (launch_advct_col)
-template <int ROWS> struct LevCaT { double c[5], h[(2 * 5 + ROWS - 1) / ROWS]; };
+template <int ROWS> struct LevCaT { pomgpu_ct c[5], h[(2 * 5 + ROWS - 1) / ROWS]; };
 template <int ROWS>
 __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
   constexpr int NS = 5, NH = (2 * NS + ROWS - 1) / ROWS, U = 0, V = 1, UB = 2, VB = 3, AM = 4;
@@ -498,23 +501,23 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
   const bool iin = (i0 >= 2 && i0 <= P.imm1);
   const bool in = out && iin && jrow;
   const int kb = P.kb, kbm1 = P.kbm1;
-  double ax2 = 0., ay2 = 0.;
+  double ax2 = 0., ay2 = 0.;                                // the vertical sums stay fp64 in every build: they feed the external mode
   // column-resident coefficients
-  const double dtsx_c = K2(DTSX, i, jc), dtsx_s = K2(DTSX, i, js);
-  const double dtsx_e = halo_e(dtsx_c, [&] { return K2(DTSX, ie, jc); });
-  const double dtsy_c = K2(DTSY, i, jc), dtsy_n = K2(DTSY, i, jn), dtsy_s = K2(DTSY, i, js);
-  const double dtsy_w = halo_w(dtsy_c, [&] { return K2(DTSY, iw, jc); });
-  const double dtsy_nw = halo_w(dtsy_n, [&] { return K2(DTSY, iw, jn); });
-  const double dt4_c = K2(DT4, i, jc), dt4_n = K2(DT4, i, jn);
-  const double dx4_c = K2(DX4, i, jc), dx4_n = K2(DX4, i, jn);
-  const InvD dy4_c = inv_of(K2(DY4, i, jc)), dy4_n = inv_of(K2(DY4, i, jn)), idx4_c = inv_of(dx4_c), idx4_n = inv_of(dx4_n);
-  const double dt_c = F2(dt, i, jc), dy_c = F2(dy, i, jc), dx_c = F2(dx, i, jc);
-  const double dt_s = F2(dt, i, js), dx_s = F2(dx, i, js);
-  const InvD idx_c = inv_of(dx_c), idy_c = inv_of(dy_c), idy_s = inv_of(F2(dy, i, js));
-  const double cva_c = K2(CVA, i, jc), cvb_c = K2(CVB, i, jc);
-  const double cva_s = K2(CVA, i, js), cvb_s = K2(CVB, i, js);
-  const InvD art_c = inv_of(F2(art, i, jc)), art_s = inv_of(F2(art, i, js));
-  const double aru = F2(aru, i, jc), arv = F2(arv, i, jc);
+  const pomgpu_ct dtsx_c = K2(DTSX, i, jc), dtsx_s = K2(DTSX, i, js);
+  const pomgpu_ct dtsx_e = halo_e(dtsx_c, [&] { return K2(DTSX, ie, jc); });
+  const pomgpu_ct dtsy_c = K2(DTSY, i, jc), dtsy_n = K2(DTSY, i, jn), dtsy_s = K2(DTSY, i, js);
+  const pomgpu_ct dtsy_w = halo_w(dtsy_c, [&] { return K2(DTSY, iw, jc); });
+  const pomgpu_ct dtsy_nw = halo_w(dtsy_n, [&] { return K2(DTSY, iw, jn); });
+  const pomgpu_ct dt4_c = K2(DT4, i, jc), dt4_n = K2(DT4, i, jn);
+  const pomgpu_ct dx4_c = K2(DX4, i, jc), dx4_n = K2(DX4, i, jn);
+  const InvDc dy4_c = inv_of(CT(K2(DY4, i, jc))), dy4_n = inv_of(CT(K2(DY4, i, jn))), idx4_c = inv_of(dx4_c), idx4_n = inv_of(dx4_n);
+  const pomgpu_ct dt_c = F2(dt, i, jc), dy_c = F2(dy, i, jc), dx_c = F2(dx, i, jc);
+  const pomgpu_ct dt_s = F2(dt, i, js), dx_s = F2(dx, i, js);
+  const InvDc idx_c = inv_of(dx_c), idy_c = inv_of(dy_c), idy_s = inv_of(CT(F2(dy, i, js)));
+  const pomgpu_ct cva_c = K2(CVA, i, jc), cvb_c = K2(CVB, i, jc);
+  const pomgpu_ct cva_s = K2(CVA, i, js), cvb_s = K2(CVB, i, js);
+  const InvDc art_c = inv_of(CT(F2(art, i, jc))), art_s = inv_of(CT(F2(art, i, js)));
+  const pomgpu_ct aru = F2(aru, i, jc), arv = F2(arv, i, jc);
   const bool srow = (jc - 1 >= 2);                          // row j-1 carries y-eq. fluxes / curv
   const bool curvx = (i0 >= (P.W ? 3 : 2)), curvy = (jc >= (P.S ? 3 : 2));
   BufA bs[NS], bh[NH];
@@ -528,16 +531,16 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
   const unsigned oc = BOFF2(i, jc), lvb = LVB;
   const unsigned ost = (out && jrow) ? oc : BOFF_NONE;      // rim rows are zeroed after the loop
 #ifndef POMGPU_EMU
-  __shared__ double slab[2][NS][ROWS + 3][64];
+  __shared__ pomgpu_ct slab[2][NS][ROWS + 3][64];
 #else
   const unsigned os = BOFF2(i, js), on = BOFF2(i, jn);
 #endif
   auto load = [&](LevCa &L, int k) {
     const unsigned lv = (unsigned)WAVE_UNIFORM(k - 1) * lvb;
 #pragma unroll
-    for (int x = 0; x < NS; x++) L.c[x] = bld(bs[x], oc, lv);
+    for (int x = 0; x < NS; x++) L.c[x] = bldc(bs[x], oc, lv);
 #pragma unroll
-    for (int q = 0; q < NH; q++) L.h[q] = bld(bh[q], S.hoff[q], lv);
+    for (int q = 0; q < NH; q++) L.h[q] = bldc(bh[q], S.hoff[q], lv);
   };
   auto step = [&](const int k, const int par, const LevCa &cur, LevCa &nxt) {
     load(nxt, k + 1 <= kbm1 ? k + 1 : kbm1);                // in flight during this iteration (the last one re-requests level kbm1)
@@ -553,70 +556,70 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
 #else
     const unsigned lvc = (unsigned)(k - 1) * lvb;
 #pragma unroll
-    for (int x = 0; x < NS; x++) { nb.s[x] = bld(bs[x], os, lvc); nb.n[x] = bld(bs[x], on, lvc); }
+    for (int x = 0; x < NS; x++) { nb.s[x] = bldc(bs[x], os, lvc); nb.n[x] = bldc(bs[x], on, lvc); }
 #endif
-    const double u_c = cur.c[U], v_c = cur.c[V], ub_c = cur.c[UB], vb_c = cur.c[VB], am_c = cur.c[AM];
-    const double u_s = nb.s[U], v_s = nb.s[V], ub_s = nb.s[UB], vb_s = nb.s[VB], am_s = nb.s[AM];
-    const double u_n = nb.n[U], v_n = nb.n[V], ub_n = nb.n[UB], vb_n = nb.n[VB], am_n = nb.n[AM];
-    const double u_e = halo_e(u_c, [&] { return F3(u, ie, jc, k); });
-    const double u_se = halo_e(u_s, [&] { return F3(u, ie, js, k); });
-    const double ub_e = halo_e(ub_c, [&] { return F3(ub, ie, jc, k); });
-    const double v_w = halo_w(v_c, [&] { return F3(v, iw, jc, k); });
-    const double v_nw = halo_w(v_n, [&] { return F3(v, iw, jn, k); });
-    const double vb_w = halo_w(vb_c, [&] { return F3(vb, iw, jc, k); });
-    const double vb_nw = halo_w(vb_n, [&] { return F3(vb, iw, jn, k); });
-    const double am_w = halo_w(am_c, [&] { return F3(aam, iw, jc, k); });
-    const double am_sw = halo_w(am_s, [&] { return F3(aam, iw, js, k); });
-    const double am_nw = halo_w(am_n, [&] { return F3(aam, iw, jn, k); });
+    const pomgpu_ct u_c = cur.c[U], v_c = cur.c[V], ub_c = cur.c[UB], vb_c = cur.c[VB], am_c = cur.c[AM];
+    const pomgpu_ct u_s = nb.s[U], v_s = nb.s[V], ub_s = nb.s[UB], vb_s = nb.s[VB], am_s = nb.s[AM];
+    const pomgpu_ct u_n = nb.n[U], v_n = nb.n[V], ub_n = nb.n[UB], vb_n = nb.n[VB], am_n = nb.n[AM];
+    const pomgpu_ct u_e = halo_e(u_c, [&] { return F3(u, ie, jc, k); });
+    const pomgpu_ct u_se = halo_e(u_s, [&] { return F3(u, ie, js, k); });
+    const pomgpu_ct ub_e = halo_e(ub_c, [&] { return F3(ub, ie, jc, k); });
+    const pomgpu_ct v_w = halo_w(v_c, [&] { return F3(v, iw, jc, k); });
+    const pomgpu_ct v_nw = halo_w(v_n, [&] { return F3(v, iw, jn, k); });
+    const pomgpu_ct vb_w = halo_w(vb_c, [&] { return F3(vb, iw, jc, k); });
+    const pomgpu_ct vb_nw = halo_w(vb_n, [&] { return F3(vb, iw, jn, k); });
+    const pomgpu_ct am_w = halo_w(am_c, [&] { return F3(aam, iw, jc, k); });
+    const pomgpu_ct am_sw = halo_w(am_s, [&] { return F3(aam, iw, js, k); });
+    const pomgpu_ct am_nw = halo_w(am_n, [&] { return F3(aam, iw, jn, k); });
     // x-equation xflux at the cell centre (:233-239, :257-262, :275); 0 outside 2..imm1
-    double xf = 0., cv = 0.;
+    pomgpu_ct xf = 0., cv = 0.;
     if (iin) {
-      xf = .125 * (dtsx_e * u_e + dtsx_c * u_c) * (u_e + u_c);
-      xf = xf - divi(dt_c * am_c * 2. * (ub_e - ub_c), idx_c);
+      xf = CT(.125) * (dtsx_e * u_e + dtsx_c * u_c) * (u_e + u_c);
+      xf = xf - divi(dt_c * am_c * CT(2.) * (ub_e - ub_c), idx_c);
       xf = dy_c * xf;
-      cv = divi(.25 * ((v_n + v_c) * cva_c - (u_e + u_c) * cvb_c), art_c);                     // :217-227
+      cv = divi(CT(.25) * ((v_n + v_c) * cva_c - (u_e + u_c) * cvb_c), art_c);                     // :217-227
     }
-    const double ctx = cv * dt_c * (v_n + v_c);                                                // :296-297
-    const double xf_w = halo_w(xf, [&] { return advct_xf_mem(P, i - 1, jc, k); });
-    const double ctx_w = halo_w(ctx, [&] {
+    const pomgpu_ct ctx = cv * dt_c * (v_n + v_c);                                                // :296-297
+    const pomgpu_ct xf_w = halo_w(xf, [&] { return advct_xf_mem(P, i - 1, jc, k); });
+    const pomgpu_ct ctx_w = halo_w(ctx, [&] {
       return advct_curv_mem(P, i - 1, jc, k) * F2(dt, i - 1, jc) * (F3(v, i - 1, jc + 1, k) + F3(v, i - 1, jc, k));
     });
     // corner (i,j): y-flux of the x-equation and x-flux of the y-equation share dtaam and the shear bracket
-    const double dtaam = .25 * dt4_c * (am_c + am_w + am_s + am_sw);                           // :264-266
-    const double br = divi(ub_c - ub_s, dy4_c) + divi(vb_c - vb_w, idx4_c);
-    double yf_c = .125 * (dtsy_c * v_c + dtsy_w * v_w) * (u_c + u_s);                          // :244-250
+    const pomgpu_ct dtaam = CT(.25) * dt4_c * (am_c + am_w + am_s + am_sw);                           // :264-266
+    const pomgpu_ct br = divi(ub_c - ub_s, dy4_c) + divi(vb_c - vb_w, idx4_c);
+    pomgpu_ct yf_c = CT(.125) * (dtsy_c * v_c + dtsy_w * v_w) * (u_c + u_s);                          // :244-250
     yf_c = yf_c - dtaam * br;                                                                  // :267-272
-    yf_c = .25 * dx4_c * yf_c;                                                                 // :276-277
-    double xg = .125 * (dtsx_c * u_c + dtsx_s * u_s) * (v_c + v_w);                            // :322-328
+    yf_c = CT(.25) * dx4_c * yf_c;                                                                 // :276-277
+    pomgpu_ct xg = CT(.125) * (dtsx_c * u_c + dtsx_s * u_s) * (v_c + v_w);                            // :322-328
     xg = xg - dtaam * br;                                                                      // :348-353
-    xg = .25 * dy4_c.b * xg;                                                                   // :363-364
-    const double xg_e = halo_e(xg, [&] { return advct_xg_mem(P, i + 1, jc, k); });
+    xg = CT(.25) * dy4_c.b * xg;                                                                   // :363-364
+    const pomgpu_ct xg_e = halo_e(xg, [&] { return advct_xg_mem(P, i + 1, jc, k); });
     // corner (i,j+1): y-flux of the x-equation only
-    const double dtaam_n = .25 * dt4_n * (am_n + am_nw + am_c + am_w);
-    double yf_n = .125 * (dtsy_n * v_n + dtsy_nw * v_nw) * (u_n + u_c);
+    const pomgpu_ct dtaam_n = CT(.25) * dt4_n * (am_n + am_nw + am_c + am_w);
+    pomgpu_ct yf_n = CT(.125) * (dtsy_n * v_n + dtsy_nw * v_nw) * (u_n + u_c);
     yf_n = yf_n - dtaam_n * (divi(ub_n - ub_c, dy4_n) + divi(vb_n - vb_nw, idx4_n));
-    yf_n = .25 * dx4_n * yf_n;
+    yf_n = CT(.25) * dx4_n * yf_n;
     // y-equation yflux at the centres of rows j and j-1 (:333-339, :355-358, :365)
-    double yg_c = .125 * (dtsy_n * v_n + dtsy_c * v_c) * (v_n + v_c);
-    yg_c = yg_c - divi(dt_c * am_c * 2. * (vb_n - vb_c), idy_c);
+    pomgpu_ct yg_c = CT(.125) * (dtsy_n * v_n + dtsy_c * v_c) * (v_n + v_c);
+    yg_c = yg_c - divi(dt_c * am_c * CT(2.) * (vb_n - vb_c), idy_c);
     yg_c = dx_c * yg_c;
-    double yg_s = 0., cv_s = 0.;
+    pomgpu_ct yg_s = 0., cv_s = 0.;
     if (srow) {
-      yg_s = .125 * (dtsy_c * v_c + dtsy_s * v_s) * (v_c + v_s);
-      yg_s = yg_s - divi(dt_s * am_s * 2. * (vb_c - vb_s), idy_s);
+      yg_s = CT(.125) * (dtsy_c * v_c + dtsy_s * v_s) * (v_c + v_s);
+      yg_s = yg_s - divi(dt_s * am_s * CT(2.) * (vb_c - vb_s), idy_s);
       yg_s = dx_s * yg_s;
-      if (iin) cv_s = divi(.25 * ((v_c + v_s) * cva_s - (u_se + u_s) * cvb_s), art_s);
+      if (iin) cv_s = divi(CT(.25) * ((v_c + v_s) * cva_s - (u_se + u_s) * cvb_s), art_s);
     }
-    double ax = 0., ay = 0.;
+    pomgpu_ct ax = 0., ay = 0.;
     if (in) {
       ax = xf - xf_w + yf_n - yf_c;                                                            // :284-288
-      if (curvx) ax = ax - aru * .25 * (ctx + ctx_w);                                          // :291-301
+      if (curvx) ax = ax - aru * CT(.25) * (ctx + ctx_w);                                          // :291-301
       ay = xg_e - xg + yg_c - yg_s;                                                            // :374-378
-      if (curvy) ay = ay + arv * .25 * (cv * dt_c * (u_e + u_c) + cv_s * dt_s * (u_se + u_s));   // :381-391
+      if (curvy) ay = ay + arv * CT(.25) * (cv * dt_c * (u_e + u_c) + cv_s * dt_s * (u_se + u_s));   // :381-391
     }
     const unsigned lv = (unsigned)WAVE_UNIFORM(k - 1) * lvb;
-    bst(bax, ost, lv, ax);
-    bst(bay, ost, lv, ay);
+    bstc(bax, ost, lv, ax);
+    bstc(bay, ost, lv, ay);
     const double dzk = F1(dz, k);
     ax2 = ax2 + ax * dzk;
     ay2 = ay2 + ay * dzk;
@@ -666,7 +669,7 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
 // level k+1 and reads that of level k, and the slab it will overwrite two iterations later is out of everybody's reach
 // behind two barriers.  (PMC before: 14.8 array passes of HBM-side traffic for 11 algorithmic -- the three neighbour rows
 // were never L2 hits.)
-struct LevUV { double c[3], h[ROWSHARE_SLOTS(3)], ub, vb, advx, advy, drhox, drhoy; };
+struct LevUV { pomgpu_ct c[3], h[ROWSHARE_SLOTS(3)], ub, vb, advx, advy, drhox, drhoy; };
 // Same loop discipline as k_advt2_col: one batch of loads per level, issued a whole iteration ahead and never inside a
 // branch, stores of lanes without an output column aimed outside the buffer, buffer addressing, two register sets.
 __global__ void __launch_bounds__(64 * LDS_ROWS) k_advuv_col(KP P) {
@@ -684,20 +687,22 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advuv_col(KP P) {
   const int js = jc > 1 ? jc - 1 : 1, jn = jc < P.jml ? jc + 1 : P.jml;
   const bool in = out && (i >= 2 && i <= P.imm1 && jc >= 2 && jc <= P.jmm1);
   const int kb = P.kb, kbm1 = P.kbm1;
-  // column-resident coefficients
-  const double aru = F2(aru, i, jc), arv = F2(arv, i, jc);
-  const double dt_c = F2(dt, i, jc), dt_w = F2(dt, iw, jc), dt_s = F2(dt, i, js);
-  const double cd_c = F2(cor, i, jc) * dt_c, cd_s = F2(cor, i, js) * dt_s;                  // cor*dt of this column and of (i,j-1)
-  const double hcu = P.grav * .125 * (dt_c + dt_w) *
-                     (F2(egf, i, jc) - F2(egf, iw, jc) + F2(egb, i, jc) - F2(egb, iw, jc) + (F2(e_atmos, i, jc) - F2(e_atmos, iw, jc)) * 2.) *
-                     (F2(dy, i, jc) + F2(dy, iw, jc));                                          // :765-770
-  const double hcv = P.grav * .125 * (dt_c + dt_s) *
-                     (F2(egf, i, jc) - F2(egf, i, js) + F2(egb, i, jc) - F2(egb, i, js) + (F2(e_atmos, i, jc) - F2(e_atmos, i, js)) * 2.) *
-                     (F2(dx, i, jc) + F2(dx, i, js));                                          // :822-827
-  const double hb = F2(h, i, jc) + F2(etb, i, jc), hf = F2(h, i, jc) + F2(etf, i, jc);
-  const double sau = (hb + F2(h, iw, jc) + F2(etb, iw, jc)) * aru;                            // :758
-  const double sav = (hb + F2(h, i, js) + F2(etb, i, js)) * arv;                            // :815
-  const InvD sdu = inv_of((hf + F2(h, iw, jc) + F2(etf, iw, jc)) * aru), sdv = inv_of((hf + F2(h, i, js) + F2(etf, i, js)) * arv);   // :781, :838
+  // column-resident coefficients (in the fp32-arithmetic variant every 2-D operand is narrowed first: no fp64 operation)
+#define C2_(name, i, j) CT(F2(name, i, j))
+  const pomgpu_ct aru = F2(aru, i, jc), arv = F2(arv, i, jc), dti2 = P.dti2;
+  const pomgpu_ct dt_c = F2(dt, i, jc), dt_w = F2(dt, iw, jc), dt_s = F2(dt, i, js);
+  const pomgpu_ct cd_c = C2_(cor, i, jc) * dt_c, cd_s = C2_(cor, i, js) * dt_s;              // cor*dt of this column and of (i,j-1)
+  const pomgpu_ct hcu = CT(P.grav) * CT(.125) * (dt_c + dt_w) *
+                        (C2_(egf, i, jc) - C2_(egf, iw, jc) + C2_(egb, i, jc) - C2_(egb, iw, jc) + (C2_(e_atmos, i, jc) - C2_(e_atmos, iw, jc)) * CT(2.)) *
+                        (C2_(dy, i, jc) + C2_(dy, iw, jc));                                     // :765-770
+  const pomgpu_ct hcv = CT(P.grav) * CT(.125) * (dt_c + dt_s) *
+                        (C2_(egf, i, jc) - C2_(egf, i, js) + C2_(egb, i, jc) - C2_(egb, i, js) + (C2_(e_atmos, i, jc) - C2_(e_atmos, i, js)) * CT(2.)) *
+                        (C2_(dx, i, jc) + C2_(dx, i, js));                                      // :822-827
+  const pomgpu_ct hb = C2_(h, i, jc) + C2_(etb, i, jc), hf = C2_(h, i, jc) + C2_(etf, i, jc);
+  const pomgpu_ct sau = (hb + C2_(h, iw, jc) + C2_(etb, iw, jc)) * aru;                       // :758
+  const pomgpu_ct sav = (hb + C2_(h, i, js) + C2_(etb, i, js)) * arv;                       // :815
+  const InvDc sdu = inv_of((hf + C2_(h, iw, jc) + C2_(etf, iw, jc)) * aru), sdv = inv_of((hf + C2_(h, i, js) + C2_(etf, i, js)) * arv);   // :781, :838
+#undef C2_
   BufA bs[NS], bh[NH];
   const double *ps[NS] = {A3(w), A3(u), A3(v)};
 #pragma unroll
@@ -710,20 +715,20 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advuv_col(KP P) {
   const unsigned oc = BOFF2(i, jc), lvb = LVB;
   const unsigned ost = out ? oc : BOFF_NONE;
 #ifndef POMGPU_EMU
-  __shared__ double slab[3][NS][ROWSHARE_ROWS][64];
+  __shared__ pomgpu_ct slab[3][NS][ROWSHARE_ROWS][64];
 #else
   const unsigned os = BOFF2(i, js), on = BOFF2(i, jn);
 #endif
   auto load = [&](LevUV &L, int k) {                        // shared operands of level k+1, own-row operands of level k
     const unsigned lv = (unsigned)WAVE_UNIFORM(k - 1) * lvb, lv1 = lv + lvb;
 #pragma unroll
-    for (int x = 0; x < NS; x++) L.c[x] = bld(bs[x], oc, lv1);
+    for (int x = 0; x < NS; x++) L.c[x] = bldc(bs[x], oc, lv1);
 #pragma unroll
-    for (int q = 0; q < NH; q++) L.h[q] = bld(bh[q], S.hoff[q], lv1);
-    L.ub = bld(bub, oc, lv);  L.vb = bld(bvb, oc, lv);
-    L.advx = bld(bax, oc, lv); L.advy = bld(bay, oc, lv); L.drhox = bld(bdx, oc, lv); L.drhoy = bld(bdy, oc, lv);
+    for (int q = 0; q < NH; q++) L.h[q] = bldc(bh[q], S.hoff[q], lv1);
+    L.ub = bldc(bub, oc, lv);  L.vb = bldc(bvb, oc, lv);
+    L.advx = bldc(bax, oc, lv); L.advy = bldc(bay, oc, lv); L.drhox = bldc(bdx, oc, lv); L.drhoy = bldc(bdy, oc, lv);
   };
-  auto park = [&](const double (&cv)[3], const double (&hv)[NH], const int sl) {
+  auto park = [&](const pomgpu_ct (&cv)[3], const pomgpu_ct (&hv)[NH], const int sl) {
 #ifndef POMGPU_EMU
 #pragma unroll
     for (int x = 0; x < NS; x++) slab[sl][x][r + 1][lane] = cv[x];
@@ -732,50 +737,50 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advuv_col(KP P) {
 #endif
   };
   // level 1 of u, v (and w, unused) into slab 0: what the first iteration reads as its "level k" neighbours
-  double u_k, v_k;                                          // u, v of this column at level k
+  pomgpu_ct u_k, v_k;                                       // u, v of this column at level k
   {
-    double c1[3], h1[NH];
+    pomgpu_ct c1[3], h1[NH];
 #pragma unroll
-    for (int x = 0; x < NS; x++) c1[x] = bld(bs[x], oc, 0u);
+    for (int x = 0; x < NS; x++) c1[x] = bldc(bs[x], oc, 0u);
 #pragma unroll
-    for (int q = 0; q < NH; q++) h1[q] = bld(bh[q], S.hoff[q], 0u);
+    for (int q = 0; q < NH; q++) h1[q] = bldc(bh[q], S.hoff[q], 0u);
     park(c1, h1, 0);
     u_k = c1[U]; v_k = c1[V];
   }
-  double fu_k = 0., fv_k = 0.;                              // vertical fluxes at level k (0 at the surface)
+  pomgpu_ct fu_k = 0., fv_k = 0.;                              // vertical fluxes at level k (0 at the surface)
   auto step = [&](const int k, const int sl, const LevUV &c, LevUV &nxt) {   // sl = k % 3: the slab of level k+1
     load(nxt, k + 1 <= kbm1 ? k + 1 : kbm1);                // in flight during this iteration (the last one re-requests level kbm1)
     park(c.c, c.h, sl);
     const int slm = sl == 0 ? 2 : sl - 1;                   // the slab of level k
 #ifndef POMGPU_EMU
     __syncthreads();
-    const double w_s = slab[sl][W][S.ss][lane], u_s = slab[slm][U][S.ss][lane], v_n = slab[slm][V][S.sn][lane];
+    const pomgpu_ct w_s = slab[sl][W][S.ss][lane], u_s = slab[slm][U][S.ss][lane], v_n = slab[slm][V][S.sn][lane];
 #else
-    const double w_s = bld(bs[W], os, (unsigned)k * lvb), u_s = bld(bs[U], os, (unsigned)(k - 1) * lvb), v_n = bld(bs[V], on, (unsigned)(k - 1) * lvb);
+    const pomgpu_ct w_s = bldc(bs[W], os, (unsigned)k * lvb), u_s = bldc(bs[U], os, (unsigned)(k - 1) * lvb), v_n = bldc(bs[V], on, (unsigned)(k - 1) * lvb);
 #endif
-    const double w_c = c.c[W], u_c = c.c[U], v_c = c.c[V];  // level k+1
-    const double w_w = halo_w(w_c, [&] { return F3(w, iw, jc, k + 1); });
-    const double tc = cd_c * (v_n + v_k);                                                   // cor*dt*(v(i,j+1,k)+v(i,j,k))
-    const double tw = halo_w(tc, [&] { return F2(cor, iw, jc) * F2(dt, iw, jc) * (F3(v, iw, jn, k) + F3(v, iw, jc, k)); });
-    const double u_e = halo_e(u_k, [&] { return F3(u, ie, jc, k); });
-    const double u_se = halo_e(u_s, [&] { return F3(u, ie, js, k); });
+    const pomgpu_ct w_c = c.c[W], u_c = c.c[U], v_c = c.c[V];   // level k+1
+    const pomgpu_ct w_w = halo_w(w_c, [&] { return F3(w, iw, jc, k + 1); });
+    const pomgpu_ct tc = cd_c * (v_n + v_k);                                                // cor*dt*(v(i,j+1,k)+v(i,j,k))
+    const pomgpu_ct tw = halo_w(tc, [&] { return F2(cor, iw, jc) * F2(dt, iw, jc) * (F3(v, iw, jn, k) + F3(v, iw, jc, k)); });
+    const pomgpu_ct u_e = halo_e(u_k, [&] { return F3(u, ie, jc, k); });
+    const pomgpu_ct u_se = halo_e(u_s, [&] { return F3(u, ie, js, k); });
     // vertical fluxes at level k+1 (:744-751, :801-808); zero below kbm1, and where the column has no west / south neighbour
-    double fu_n = 0., fv_n = 0.;
+    pomgpu_ct fu_n = 0., fv_n = 0.;
     if (k + 1 <= kbm1) {
-      if (i >= 2) fu_n = .25 * (w_c + w_w) * (u_c + u_k);
-      if (jc >= 2) fv_n = .25 * (w_c + w_s) * (v_c + v_k);
+      if (i >= 2) fu_n = CT(.25) * (w_c + w_w) * (u_c + u_k);
+      if (jc >= 2) fv_n = CT(.25) * (w_c + w_s) * (v_c + v_k);
     }
-    double ru = fu_k, rv = fv_k;                                                            // outside the interior: the flux itself
+    pomgpu_ct ru = fu_k, rv = fv_k;                                                         // outside the interior: the flux itself
     if (in) {
-      InvD dzk; dzk.b = F1(dz, k); dzk.y = R1(dz, k);
-      ru = divi(sau * c.ub - 2. * P.dti2 * (c.advx + divi((fu_k - fu_n) * aru, dzk) - aru * .25 * (tc + tw) + hcu + c.drhox), sdu);   // :758-782
+      InvDc dzk; dzk.b = F1(dz, k); dzk.y = R1(dz, k);
+      ru = divi(sau * c.ub - CT(2.) * dti2 * (c.advx + divi((fu_k - fu_n) * aru, dzk) - aru * CT(.25) * (tc + tw) + hcu + c.drhox), sdu);   // :758-782
       rv = divi(sav * c.vb -
-                    2. * P.dti2 * (c.advy + divi((fv_k - fv_n) * arv, dzk) + arv * .25 * (cd_c * (u_e + u_k) + cd_s * (u_se + u_s)) + hcv + c.drhoy),
+                    CT(2.) * dti2 * (c.advy + divi((fv_k - fv_n) * arv, dzk) + arv * CT(.25) * (cd_c * (u_e + u_k) + cd_s * (u_se + u_s)) + hcv + c.drhoy),
                 sdv);                                                                       // :815-839
     }
     const unsigned lv = (unsigned)WAVE_UNIFORM(k - 1) * lvb;
-    bst(buf, ost, lv, ru);
-    bst(bvf, ost, lv, rv);
+    bstc(buf, ost, lv, ru);
+    bstc(bvf, ost, lv, rv);
     fu_k = fu_n; fv_k = fv_n;
     u_k = u_c; v_k = v_c;
   };

@@ -170,7 +170,11 @@ static void sync_scalars(pomgpu_ctx *c) {
 #endif
 extern "C" const char *pomgpu_build_id(void) { return POMGPU_BUILD_ID; }
 #ifdef POMGPU_STORE_F32
+#ifdef POMGPU_COMPUTE_F32   // the stencil kernels of the internal mode also compute in fp32 (pomgpu_internal.hpp); same context layout
+extern "C" const char *pomgpu_version(void) { return "extpom_amd pomgpu 0.2 (gfx950) fp32-storage fp32-arithmetic variant"; }
+#else
 extern "C" const char *pomgpu_version(void) { return "extpom_amd pomgpu 0.2 (gfx950) fp32-storage variant"; }
+#endif
 #define F32_REFUSE(c, what) return fail(c, POMGPU_EINVAL, what ": not in the fp32-storage variant (3-D arrays are not doubles there)")
 #else
 extern "C" const char *pomgpu_version(void) { return "extpom_amd pomgpu 0.2 (gfx950)"; }

@@ -74,6 +74,23 @@ typedef float pomgpu_st;
 typedef double pomgpu_st;
 #endif
 #define POMGPU_ST_BYTES ((unsigned)sizeof(pomgpu_st))
+// ---- compute type of the stencil kernels ------------------------------------------------------------------------------
+// -DPOMGPU_COMPUTE_F32 (on top of -DPOMGPU_STORE_F32: libpomgpu_f32a.so) builds the fp32-ARITHMETIC
+// variant: the row-sharing stencil kernels of the default internal path (k_advt2_col, k_advq_col, k_advuv_col, k_advct_col
+// but its vertical sums) and k_ts_update but dens compute in fp32 on the stored fp32 values, with no widening.  Everything
+// else -- the Thomas solves, baropg, vertvl, aam, the vertical integrals, the external mode, the edge kernels and the
+// non-default branches -- stays fp64 exactly as in libpomgpu_f32.so.  Those kernels name their values pomgpu_ct and wrap
+// every fp64 literal or KP scalar in CT(): in the two other builds pomgpu_ct is double and CT() a no-op cast, so they compile
+// to the same device code as without it (an unsuffixed .5 next to a float would silently promote the expression to fp64).
+#if defined(POMGPU_COMPUTE_F32) && !defined(POMGPU_STORE_F32)
+#error "POMGPU_COMPUTE_F32 is the fp32-arithmetic variant of the fp32-storage build: it needs POMGPU_STORE_F32"
+#endif
+#ifdef POMGPU_COMPUTE_F32
+typedef float pomgpu_ct;
+#else
+typedef double pomgpu_ct;
+#endif
+#define CT(x) ((pomgpu_ct)(x))
 #ifdef POMGPU_STORE_F32
 struct Ref3 {
   pomgpu_st *p;
@@ -163,9 +180,19 @@ __device__ __forceinline__ double wave_dn1(double x) {      // lane n <- lane n+
   hi = __builtin_amdgcn_update_dpp(hi, hi, 0x130, 0xf, 0xf, false);
   return __hiloint2double(hi, lo);
 }
+__device__ __forceinline__ float wave_up1(float x) {        // fp32: one DPP move
+  const int v = __float_as_int(x);
+  return __int_as_float(__builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float wave_dn1(float x) {
+  const int v = __float_as_int(x);
+  return __int_as_float(__builtin_amdgcn_update_dpp(v, v, 0x130, 0xf, 0xf, false));
+}
 #else
 static inline double wave_up1(double x) { return x; }
 static inline double wave_dn1(double x) { return x; }
+static inline float wave_up1(float x) { return x; }
+static inline float wave_dn1(float x) { return x; }
 #endif
 template <class F> __device__ __forceinline__ double lane_w(double x, F fb) {
   const double t = wave_up1(x);
@@ -183,9 +210,13 @@ template <class F> __device__ __forceinline__ double lane_e(double x, F fb) {
 #ifdef POMGPU_EMU   // host emulation runs one lane at a time: neighbour values are recomputed from memory
 template <class F> __device__ __forceinline__ double halo_w(double, F fb) { return fb(); }
 template <class F> __device__ __forceinline__ double halo_e(double, F fb) { return fb(); }
+template <class F> __device__ __forceinline__ float halo_w(float, F fb) { return (float)fb(); }
+template <class F> __device__ __forceinline__ float halo_e(float, F fb) { return (float)fb(); }
 #else
 template <class F> __device__ __forceinline__ double halo_w(double x, F) { return wave_up1(x); }
 template <class F> __device__ __forceinline__ double halo_e(double x, F) { return wave_dn1(x); }
+template <class F> __device__ __forceinline__ float halo_w(float x, F) { return wave_up1(x); }
+template <class F> __device__ __forceinline__ float halo_e(float x, F) { return wave_dn1(x); }
 #endif
 // nothing may be scheduled across this point (keeps a block of prefetch loads together and early)
 #ifdef POMGPU_EMU
@@ -238,8 +269,27 @@ __device__ __forceinline__ void bst(const BufA &b, unsigned voff, unsigned soff,
 #else
 struct BufA { double *p; };
 static inline BufA buf_of(const double *p, size_t) { BufA b; b.p = (double *)p; return b; }
+#ifndef POMGPU_STORE_F32
 static inline double bld(const BufA &b, unsigned voff, unsigned soff) { return voff >= 0xFFFFFFF0u ? 0. : b.p[((size_t)voff + soff) >> 3]; }
 static inline void bst(const BufA &b, unsigned voff, unsigned soff, double x) { if (voff < 0xFFFFFFF0u) b.p[((size_t)voff + soff) >> 3] = x; }
+#else   // the offsets count 4-byte elements of the array p names
+static inline double bld(const BufA &b, unsigned voff, unsigned soff) {
+  return voff >= 0xFFFFFFF0u ? 0. : (double)((const pomgpu_st *)b.p)[((size_t)voff + soff) >> 2];
+}
+static inline void bst(const BufA &b, unsigned voff, unsigned soff, double x) { if (voff < 0xFFFFFFF0u) ((pomgpu_st *)b.p)[((size_t)voff + soff) >> 2] = (pomgpu_st)x; }
+#endif
+#endif
+// the same in the compute type: the fp32-arithmetic variant moves the stored fp32 value as it is, without widening
+#if defined(POMGPU_COMPUTE_F32) && !defined(POMGPU_EMU)
+__device__ __forceinline__ pomgpu_ct bldc(const BufA &b, unsigned voff, unsigned soff) {
+  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(b.r, (int)voff, (int)soff, 0));
+}
+__device__ __forceinline__ void bstc(const BufA &b, unsigned voff, unsigned soff, pomgpu_ct x) {
+  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x), b.r, (int)voff, (int)soff, 0);
+}
+#else
+__device__ __forceinline__ pomgpu_ct bldc(const BufA &b, unsigned voff, unsigned soff) { return (pomgpu_ct)bld(b, voff, soff); }
+__device__ __forceinline__ void bstc(const BufA &b, unsigned voff, unsigned soff, pomgpu_ct x) { bst(b, voff, soff, x); }
 #endif
 // 2-D arrays are fp64 in every build: buffer helpers that do not follow the storage type of the 3-D arrays
 #ifndef POMGPU_EMU
@@ -346,8 +396,13 @@ template <int NS> __device__ __forceinline__ const double *rowshare_pick(const d
 // rounded, q1 faithful; Muller et al., Handbook of Floating-Point Arithmetic, Thm. 4.9) -- five full-rate
 // instructions, no special cases as long as nothing over- or underflows (metric sums and depths: never).
 // tools/micro/f64_rates.hip compares it with the hardware quotient on 3e9 operand pairs; tests compare whole steps.
-struct InvD { double b, y; };
+// InvDc / the float overloads: the same for the compute type of the fp32-arithmetic variant (with y = RN32(1/b); where y is a
+// narrowed fp64 reciprocal, R1(), the quotient is faithful rather than correctly rounded)
+template <class T> struct InvDT { T b, y; };
+typedef InvDT<double> InvD;
+typedef InvDT<pomgpu_ct> InvDc;
 __device__ __forceinline__ InvD inv_of(double b) { InvD d; d.b = b; d.y = 1.0 / b; return d; }
+__device__ __forceinline__ InvDT<float> inv_of(float b) { InvDT<float> d; d.b = b; d.y = 1.0f / b; return d; }
 #ifndef POMGPU_EMU
 // A zero numerator keeps its sign: masked flux numerators such as -am * ... * msk are -0.0 on land, a/b is then -0.0 (b > 0),
 // but the corrections give (+0) + (-0) = +0 -- the product a*y has the quotient's sign, one select hands it through (array_equal
@@ -362,8 +417,17 @@ __device__ __forceinline__ double divi(double a, const InvD &d) {
   q = __builtin_fma(r, d.y, q);
   return a == 0. ? q0 : q;
 }
+__device__ __forceinline__ float divi(float a, const InvDT<float> &d) {
+  const float q0 = a * d.y;
+  float r = __builtin_fmaf(-d.b, q0, a);
+  float q = __builtin_fmaf(r, d.y, q0);
+  r = __builtin_fmaf(-d.b, q, a);
+  q = __builtin_fmaf(r, d.y, q);
+  return a == 0.f ? q0 : q;
+}
 #else
 static inline double divi(double a, const InvD &d) { return a / d.b; }
+static inline float divi(float a, const InvDT<float> &d) { return a / d.b; }
 #endif
 // XCD-aware placement of the column kernels' workgroups (64 x 4 columns each).  Workgroups are dealt
 // to the 8 XCDs round-robin in linear-id order, and every XCD has its own 4 MiB L2.  A plain

@@ -13,6 +13,9 @@ LIBPATH = os.path.join(HERE, "csrc", "libpomgpu.so")
 # the study variant of BASELINE configs[4]: 3-D arrays stored as fp32, arithmetic and the 2-D external mode fp64
 # (same sources, -DPOMGPU_STORE_F32); never the default, never loaded unless asked for by path
 LIBPATH_F32 = os.path.join(HERE, "csrc", "libpomgpu_f32.so")
+# the same with the stencil kernels of the internal mode computing in fp32 as well (-DPOMGPU_COMPUTE_F32; the Thomas solves, the
+# vertical integrals, dens and the external mode stay fp64); loaded by path only, like LIBPATH_F32
+LIBPATH_F32A = os.path.join(HERE, "csrc", "libpomgpu_f32a.so")
 
 
 class PomGpuError(RuntimeError):
