@@ -210,6 +210,10 @@ __device__ __forceinline__ void c_advq_step(const KP &P, const int i, const int 
 }
 
 // bcond(6) mask + Asselin filter + rotation of q2/q2l -- bounds_forcing.f:315-322, advance.f:416-421
+// the cells of the open edges k_bcond6_edges writes: it applies their mask itself
+__device__ __forceinline__ bool bcond6_edge_cell(const KP &P, const int i, const int j) {
+  return (P.W && i == 1) || (P.E && i == P.im) || (P.S && j == 1) || (P.N && j == P.jm);
+}
 __device__ __forceinline__ void c_q_filter(const KP &P, const int i, const int j, const int k, int mask);
 __global__ void k_q_filter(KP P, int mask) {
   MARCH3(c_q_filter(P, i, j, k, mask))
@@ -217,9 +221,11 @@ __global__ void k_q_filter(KP P, int mask) {
 __device__ __forceinline__ void c_q_filter(const KP &P, const int i, const int j, const int k, int mask) {
   double uf = F3(uf, i, j, k), vf = F3(vf, i, j, k);
   if (mask && i <= P.im && j <= P.jm) {
-    const double m = F2(fsm, i, j);
-    uf = uf * m + 1.e-10;                                  // bcond(6)
-    vf = vf * m + 1.e-10;
+    if (!bcond6_edge_cell(P, i, j)) {
+      const double m = F2(fsm, i, j);
+      uf = uf * m + 1.e-10;                                // bcond(6)
+      vf = vf * m + 1.e-10;
+    }
     // stored only where somebody still reads them: advt1/advt2 write the interior of levels 1..kbm1
     // and leave the rim columns and level kb of uf, vf as they are (solver.f:577-731) -- those
     // left-overs flow on into t, s.  Everywhere else the next writer replaces the value unread.
@@ -254,7 +260,7 @@ __global__ void k_mask_q(KP P) {   // the mask of bcond(6) alone
   MARCH3(c_mask_q(P, i, j, k))
 }
 __device__ __forceinline__ void c_mask_q(const KP &P, const int i, const int j, const int k) {
-  if (i > P.im || j > P.jm) return;
+  if (i > P.im || j > P.jm || bcond6_edge_cell(P, i, j)) return;
   const double m = F2(fsm, i, j);
   F3(uf, i, j, k) = F3(uf, i, j, k) * m + 1.e-10;
   F3(vf, i, j, k) = F3(vf, i, j, k) * m + 1.e-10;

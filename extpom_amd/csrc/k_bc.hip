@@ -85,7 +85,9 @@ __global__ void k_bcond4_edges(KP P) {
   F3(vf, i, j, k) = sv;
 }
 
-// bcond(6): upstream q2, q2l on the open edges (uf = q2, vf = q2l), k = 1..kb -- :261-313
+// bcond(6): upstream q2, q2l on the open edges (uf = q2, vf = q2l), k = 1..kb -- :261-313, with the mask of :315-322
+// applied here (uf*fsm + 1.e-10 on the value in registers): stored first and masked by a later kernel, the fp32-storage
+// build rounded these cells twice.  The later mask (c_mask_q, c_q_filter) skips them (bcond6_edge_cell).
 __global__ void k_bcond6_edges(KP P) {
   EDGE_CELL(1)
   if (k > P.kb) return;
@@ -127,8 +129,9 @@ __global__ void k_bcond6_edges(KP P) {
       lv = F3(q2l, i, P.jm, k) - u1 * (F3(q2l, i, P.jm, k) - F3(q2l, i, P.jmm1, k));
     }
   }
-  F3(uf, i, j, k) = qv;
-  F3(vf, i, j, k) = lv;
+  const double m = F2(fsm, i, j);
+  F3(uf, i, j, k) = qv * m + 1.e-10;
+  F3(vf, i, j, k) = lv * m + 1.e-10;
 }
 
 // bcondorl(3): Orlanski radiation for uf, vf -- bounds_forcing.f:422-476, then the dum/dvm mask
