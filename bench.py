@@ -2,7 +2,11 @@
 """Benchmark of the hot path: whole internal steps of the mode-split time step (one `advance`:
 lateral_viscosity, mode_interaction, isplit external substeps, mode_internal, check_velocity).
 
-    python bench.py --gpus N --steps K --warmup W [--workload basin2048|seamount256|basin1024|...] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload basin2048|seamount256|basin1024|...] [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs: it sets up (the placement trials included), warms up, runs the profiled
+step (the timed steps start from the state it leaves and bracket the kernel it names), times the K steps, writes the
+outputs with --dump-outputs and prints the line.  --full also measures what the headline does not need: the CPU baselines.
 
 N=1 runs in this process.  N>1: one rank per GPU, the global grid split into N tiles (strong scaling: the
 global grid is fixed) -- started by the caller under torch.distributed.run (WORLD_SIZE set), or, when
@@ -22,8 +26,9 @@ Extra objects on the same line:
   roofline      dominant kernel (largest share of device time in a profiled step): ALGORITHMIC bytes
                 per launch / its mean launch duration measured with HIP events on the kernels' own
                 stream inside the timed region (only that kernel is bracketed there).
-  cpu_baseline  the CPU oracle (plain-C restatement, bit-identical to the reference build) timed on
-                this box's host, 1 core, on a bounded sample of the same workload.
+  cpu_baseline  (--full) the CPU oracle (plain-C restatement, bit-identical to the reference build) timed on
+                this box's host, 1 core, on the bench's own grid; beside it all cores by tiles and a 1/8 x 1/8
+                sample with the oracle and with the reference's own build (cpu_baseline_all_cores, _sample_*).
 """
 import argparse
 import json
@@ -163,7 +168,7 @@ def _sample_dims(workload):
 def _cpu_run(workload, full, seconds=12.0, reference=False):
     """ONE host core.  full=True: the bench's OWN grid and state (identical inputs: same case, namelist, im x jm x kb), internal
     steps 1-2, of which step 2 is timed (step 1 skips the 3-D body, advance.f:362; one full-grid step is ~40 s of one core, and
-    the default run has to stay within minutes); full=False: a bounded sample on a
+    a --full run has to stay within minutes); full=False: a bounded sample on a
     1/8 x 1/8 horizontal grid for `seconds`.  reference=False: the plain-C oracle; True: the flang build of the reference's own
     sources (oracle/_ref, present only where /root/reference was at build time), driven in the order of its own `advance`."""
     from extpom_amd.cases import make_case
@@ -626,7 +631,11 @@ def main():
                                                   "GPUs, as BASELINE configs[2] names it); the alternate grid is measured beside it")
     ap.add_argument("--no-alternate", action="store_true", help="N > 1: skip the pass on the alternate tile grid")
     ap.add_argument("--only-pass", type=int, default=None, help="N > 1, developer: run only pass 0 (overlap off), 1 (overlap on) or 2 (alternate grid)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also measure what the headline figure does not need -- the CPU baselines (cpu_baseline*: the oracle on the "
+                         "bench's grid on one core and on every core, the 1/8 x 1/8 sample with the oracle and with the reference's own build). "
+                         "Off by default: a plain run sets up, warms up, times its steps and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--no-tune-placement", action="store_true", help="N = 1: leave the 3-D arrays where the allocator put them (pomgpu_tune_placement is not called)")
     ap.add_argument("--side-config", action="store_true",
                     help="N=1: also time BASELINE configs[1] (seamount 256x256x30) in the same run; off by default so that a profile "
@@ -938,8 +947,9 @@ def measure(args):
             "efficiency_bound_from_tile_probe": _tile_probe_bounds(args.workload),
             "host_libc": _libc_version(),     # bit-parity with the reference leans on this libm's pow (THIRD_PARTY_NOTICES.md)
         }
-        if not args.no_cpu_baseline and world == 1:
-            # the oracle on the bench's own grid (kind "port") is THE cpu_baseline; the sample figures are labelled extras
+        if args.full and not args.no_cpu_baseline and world == 1:
+            # --full only: a plain run stops at the GPU line.  The oracle on the bench's own grid (kind "port") is THE cpu_baseline;
+            # the sample figures are labelled extras
             free_state = args.workload in ("basin2048", "basin1024")
             if free_state and not args.side_config:
                 g.close()                                         # the CPU legs need the host's memory, not the GPU's

@@ -900,3 +900,31 @@ def test_bench_dump_outputs_hold_the_state_after_the_warm_up_profiled_and_timed_
     OracleTile(a).run(2 + 1 + 3)
     bad = [n for n in RESTART_2D + RESTART_3D if not same_bits(np.load(tmp_path / f"{n}.npy"), a.field(n))]
     assert not bad, bad
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_leaves_the_cpu_baselines_to_full():
+    """bench.py without --full does what its headline figure needs: no CPU leg runs and none is on the line.  --full measures
+    them as before -- THE cpu_baseline (the oracle on the bench's own grid, one core) and the sample beside it (the grid itself on
+    the smallest workload) -- and --no-cpu-baseline still leaves them out of a --full run."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def line(*extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "seamount65", "--steps", "2", "--warmup", "1", *extra],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+
+    cpu_legs = lambda out: sorted(k for k in out if k.startswith("cpu_baseline"))
+    plain = line()
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["ms_per_step"] > 0 and plain["error_status"] == 0, plain
+    assert plain["dtype"] == "f64" and plain["unit"] == "cell-updates/s" and plain["higher_is_better"] is True, plain
+    assert cpu_legs(plain) == [], cpu_legs(plain)
+    full = line("--full")
+    assert full["cpu_baseline"]["kind"] == "port" and full["cpu_baseline"]["value"] > 0, full.get("cpu_baseline")
+    assert full["cpu_baseline_sample_port"]["value"] > 0, cpu_legs(full)
+    assert cpu_legs(line("--full", "--no-cpu-baseline")) == []

@@ -8,7 +8,7 @@ PART=${2:-A}
 export TMPDIR=/tmp
 O=gpurun_out/$TAG; mkdir -p $O
 if [ $PART = A ]; then
-  timeout -k 10 700 python bench.py --steps 20 --warmup 5 > $O/bench_basin2048.json 2> $O/bench_basin2048.err; echo "bench rc=$?"; tail -c 300 $O/bench_basin2048.json; echo
+  timeout -k 10 700 python bench.py --steps 20 --warmup 5 --full > $O/bench_basin2048.json 2> $O/bench_basin2048.err; echo "bench rc=$?"; tail -c 300 $O/bench_basin2048.json; echo
   python bench.py --workload seamount256 --steps 40 --no-cpu-baseline > $O/bench_seamount256.json 2>/dev/null
   python bench.py --workload basin1024 --steps 10 --no-cpu-baseline > $O/bench_basin1024.json 2>/dev/null
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_line_under_rocprofv3_kernel_trace.json 2> $O/stats.err
