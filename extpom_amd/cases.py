@@ -16,6 +16,10 @@ Cases
   basin    : closed basin (land rim), gently sloping bottom with bumps, linear stratification plus
              a seeded (12345) 1e-3 degC perturbation, steady zonal wind stress.
   island   : open on all four sides around a shoaling bank (exercises N/S open-boundary code).
+  archipelago : the island case made rough -- a curved grid (dx varies with j, dy with i, cor with i and j), land inside
+             the domain (islands, straits, lakes, blocks on the open edges, scattered cells), cell-to-cell bottom
+             roughness, noisy T / S away from their climatology, flow of both signs on every open edge and every
+             surface forcing field non-zero: what the three cases above leave identically zero or one.
 """
 from __future__ import annotations
 
@@ -50,6 +54,59 @@ def _hash_noise(gi, gj, k, seed=12345):
     return 2.0 * (x - np.floor(x)) - 1.0
 
 
+def archipelago_land(gI, gJ, im, jm):
+    """Land of the archipelago case at the GLOBAL (1-based) points gI, gJ: True where a cell is land.  Features sit at
+    fractions of im, jm; a grid too short for one (jm < 40: the 12-row grids) does without the interior ones.  The
+    scattered single cells keep one cell clear of every placed feature, so that a strait stays open, a lake stays a
+    lake and the one-cell island stays alone; their density (among the cells
+    away from the edges) tops the placed features up to about 4.5 % land."""
+    I = lambda f: int(round(f * im))
+    J = lambda f: int(round(f * jm))
+    boxes, wet = [], []                       # (i0, i1, j0, j1), inclusive, 1-based
+
+    def box(i0, i1, j0, j1, hole=None):
+        boxes.append((i0, i1, j0, j1))
+        if hole:
+            wet.append(hole)
+
+    if jm >= 40:
+        box(I(.15), I(.15), J(.22), J(.22))                                   # one cell
+        box(I(.30), I(.30) + 1, J(.30), J(.30))                               # 2 x 1
+        box(I(.45), I(.45), J(.42), J(.42))                                   # two cells that touch at a corner only
+        box(I(.45) + 1, I(.45) + 1, J(.42) + 1, J(.42) + 1)
+        li, lj = max(10, int(.18 * im)), max(10, int(.30 * jm))
+        a, b = I(.70), J(.78)
+        box(a, a, J(.38), J(.38) + lj - 1)                                    # strait along j between two walls ...
+        box(a + 2, a + 2, J(.38), J(.38) + lj - 1)
+        box(I(.5) - li // 2, I(.5) - li // 2 + li - 1, b, b)                  # ... and one along i; both cross a tile seam
+        box(I(.5) - li // 2, I(.5) - li // 2 + li - 1, b + 2, b + 2)
+        c, d = I(.85), J(.14)
+        box(c - 1, c + 1, d - 1, d + 1, hole=(c, c, d, d))                    # a lake of one cell
+        c, d = I(.22), J(.55)
+        box(c - 1, c + 2, d - 1, d + 2, hole=(c, c + 1, d, d + 1))            # a lake of 2 x 2
+        box(1, 3, J(.66), J(.66) + 2)                                         # blocks on the open edges: west,
+        box(im - 3, im, J(.25), J(.25) + 1)                                   # east (the last columns of a row),
+    else:
+        box(1, 3, J(.5), J(.5) + 1)
+        box(im - 3, im, J(.25), J(.25) + 1)
+    box(I(.38), I(.38) + 3, 1, 2)                                             # south,
+    box(I(.58), I(.58) + 3, jm - 1, jm)                                       # north,
+    box(im, im, jm, jm)                                                       # and the north-east corner cell
+    inside = lambda q, m=0: (gI >= q[0] - m) & (gI <= q[1] + m) & (gJ >= q[2] - m) & (gJ <= q[3] + m)
+    land = np.zeros(np.broadcast(gI, gJ).shape, dtype=bool)
+    near = np.zeros_like(land)
+    for q in boxes:
+        land |= inside(q)
+        near |= inside(q, 2)
+    for q in wet:
+        land &= ~inside(q)
+    placed = sum((q[1] - q[0] + 1) * (q[3] - q[2] + 1) for q in boxes) - sum((q[1] - q[0] + 1) * (q[3] - q[2] + 1) for q in wet)
+    p = min(0.12, max(0.012, (0.045 * im * jm - placed) / float(max(1, (im - 6) * (jm - 6)))))
+    n = _hash_noise(gI.astype(np.float64), gJ.astype(np.float64), 0.0, seed=777)
+    land |= (n > 1.0 - 2.0 * p) & ~near & (gI > 3) & (gI < im - 2) & (gJ > 3) & (gJ < jm - 2)
+    return land
+
+
 def make_case(name: str, im: int, jm: int, kb: int, tile=None, **nml) -> PomState:
     """State of one tile (default: the whole im x jm grid as a single tile) holding everything the
     reference's readers + read_grid provide.  Every value is a function of GLOBAL indices and 1-D
@@ -82,6 +139,11 @@ def make_case(name: str, im: int, jm: int, kb: int, tile=None, **nml) -> PomStat
     ee1 = ec1 + 0.5 * dx1
     ne1 = nc1 + 0.5 * dy1
     lx, ly = float(ee1[-1]), float(ne1[-1])
+    rough = name == "archipelago"
+    # archipelago: a grid that does not separate -- dx(i,j) = dx1(i) fy(j), dy(i,j) = dy1(j) fx(i), cor scaled by fc(i)
+    fy1 = 1.0 + 0.08 * np.sin(2.0 * math.pi * gj1 / jm + 0.3) if rough else np.ones(jm)
+    fx1 = 1.0 + 0.08 * np.cos(2.0 * math.pi * gi1 / im + 0.7) if rough else np.ones(im)
+    fc1 = 1.0 + 0.2 * np.sin(2.0 * math.pi * gi1 / im) if rough else np.ones(im)
     x0, y0 = float(ee1[(im + 1) // 2 - 1]), float(ne1[(jm + 1) // 2 - 1])
 
     # ---- window = tile plus one extra column/row on the low side (for the u/v masks) ------
@@ -98,7 +160,7 @@ def make_case(name: str, im: int, jm: int, kb: int, tile=None, **nml) -> PomStat
         ra = 0.12 * min(lx, ly) + 12500.0
         hw = 4500.0 * (1.0 - 0.9 * np.exp(-(xc * xc + yc * yc) / (ra * ra)))
         vel = 0.2
-    elif name == "island":
+    elif name in ("island", "archipelago"):
         ra = 0.10 * min(lx, ly) + 10000.0
         hw = 3000.0 * (1.0 - 0.85 * np.exp(-(xc * xc + 1.7 * yc * yc) / (ra * ra)))
         vel = 0.1
@@ -115,6 +177,10 @@ def make_case(name: str, im: int, jm: int, kb: int, tile=None, **nml) -> PomStat
         hw = np.where((gJ <= 1) | (gJ >= jm), 1.0, hw)          # closed north/south walls
     if name == "basin":
         hw = np.where((gI <= 1) | (gI >= im), 1.0, hw)          # land rim all round
+    if rough:
+        fI, fJ = gI.astype(np.float64), gJ.astype(np.float64)
+        hw = np.maximum(hw * (1.0 + 0.3 * _hash_noise(fI, fJ, 1.0, seed=99)), 10.0)      # cell-to-cell roughness
+        hw = np.where(archipelago_land(gI, gJ, im, jm), 1.0, hw)
     fw = np.where(hw > 1.0, 1.0, 0.0)
     # masks (io_pnetcdf.F:2243-2256): a u/v point is closed when the cell behind it is land
     dumw = fw.copy()
@@ -135,6 +201,9 @@ def make_case(name: str, im: int, jm: int, kb: int, tile=None, **nml) -> PomStat
     li, lj = ci[1:], cj[1:]
     st.dx[A] = dx1[li][None, :] + 0.0 * dy1[lj][:, None]
     st.dy[A] = dy1[lj][:, None] + 0.0 * dx1[li][None, :]
+    if rough:
+        st.dx[A] = dx1[li][None, :] * fy1[lj][:, None]
+        st.dy[A] = dy1[lj][:, None] * fx1[li][None, :]
     st.east_c[A] = ec1[li][None, :] + 0.0 * nc1[lj][:, None]
     st.north_c[A] = nc1[lj][:, None] + 0.0 * ec1[li][None, :]
     st.east_e[A] = st.east_c[A] + 0.5 * st.dx[A]
@@ -153,6 +222,15 @@ def make_case(name: str, im: int, jm: int, kb: int, tile=None, **nml) -> PomStat
     # aru/arv for global i,j >= 2; row/column 1 copy their neighbour (initialize.f:362-378)
     aruw = 0.25 * (dxw[None, 1:] + dxw[None, :-1]) * (dyw[1:, None] + dyw[1:, None]) + 0.0
     arvw = 0.25 * (dxw[None, 1:] + dxw[None, 1:]) * (dyw[1:, None] + dyw[:-1, None]) + 0.0
+    if rough:                                # the same formulas on the 2-D spacings of the window
+        dx2, dy2 = dx1[ci][None, :] * fy1[cj][:, None], dy1[cj][:, None] * fx1[ci][None, :]
+        st.cor[A] = st.cor[A] * fc1[li][None, :]
+        # period from cor(im/2, jm/2) as read_grid forms it (initialize.f:357), restated from the 1-D vectors so that every tile gets it
+        im2, jm2 = im // 2 - 1, jm // 2 - 1
+        lat_mid = 30.0 + 15.0 * (nc1[jm2] + 0.5 * (dy1[jm2] * fx1[im2])) / ly
+        st.period = (2.0 * st.pi) / abs(2.0 * 7.29e-5 * math.sin(lat_mid * (st.pi / 180.0)) * float(fc1[im2])) / 86400.0
+        aruw = 0.25 * (dx2[1:, 1:] + dx2[1:, :-1]) * (dy2[1:, 1:] + dy2[1:, :-1])
+        arvw = 0.25 * (dx2[1:, 1:] + dx2[:-1, 1:]) * (dy2[1:, 1:] + dy2[:-1, 1:])
     st.aru[A] = aruw
     st.arv[A] = arvw
     if io == 0:
@@ -181,18 +259,29 @@ def make_case(name: str, im: int, jm: int, kb: int, tile=None, **nml) -> PomStat
         st.sb[A3] = 35.0 - st.sbias
         st.tclim[A3] = st.tb[A3]
         st.sclim[A3] = st.sb[A3]
+    if rough:                                # T, S off their climatology by seeded noise: the relaxation terms are live
+        kk = np.arange(1, kb + 1, dtype=np.float64)[:, None, None]
+        fI, fJ = gI[W][None].astype(np.float64), gJ[W][None].astype(np.float64)
+        st.tb[A3] = st.tclim[A3] + 0.05 * _hash_noise(fI, fJ, kk)
+        st.sb[A3] = st.sclim[A3] + 0.02 * _hash_noise(fI, fJ, kk, seed=4)
     for f in (st.tb, st.sb, st.tclim, st.sclim):
         f[kb - 1] = f[kb - 2]
         f[...] *= st.fsm[None]
 
     # ---- initial flow and open-boundary data ------------------------------------------------
-    st.ub[:kb - 1] = vel * st.dum[None]
-    st.uab[...] = vel * st.dum
+    if rough:                                # both signs of the normal velocity along every open edge
+        su, sv = np.zeros_like(st.dum), np.zeros_like(st.dvm)
+        su[A] = (0.1 * np.sin(2.0 * math.pi * gj1 / jm))[lj][:, None] + 0.0 * dx1[li][None, :]
+        sv[A] = (0.05 * np.cos(2.0 * math.pi * gi1 / im))[li][None, :] + 0.0 * dy1[lj][:, None]
+    else:
+        su, sv = vel, 0.25 * vel
+    st.ub[:kb - 1] = (su * st.dum)[None]
+    st.uab[...] = su * st.dum
     st.uabe[...] = st.uab[:, ti - 2]
     st.uabw[...] = st.uab[:, 1]
-    if name == "island":
-        st.vb[:kb - 1] = 0.25 * vel * st.dvm[None]
-        st.vab[...] = 0.25 * vel * st.dvm
+    if name in ("island", "archipelago"):
+        st.vb[:kb - 1] = (sv * st.dvm)[None]
+        st.vab[...] = sv * st.dvm
         st.vabn[...] = st.vab[tj - 2, :]
         st.vabs[...] = st.vab[1, :]
         st.vabe[...] = st.vab[:, ti - 1]
@@ -207,7 +296,21 @@ def make_case(name: str, im: int, jm: int, kb: int, tile=None, **nml) -> PomStat
     st.ubw[...] = st.ub[:, :, 1]
 
     # ---- surface forcing, constant in time (the reference's wind/heat readers are out of scope)
-    if name == "basin":
+    if rough:
+        st.ele[:tj] = (0.02 * np.sin(2.0 * math.pi * (gj1 - 1.0) / jm))[lj]
+        st.elw[:tj] = -st.ele[:tj]
+        st.eln[:ti] = (0.01 * np.cos(2.0 * math.pi * (gi1 - 1.0) / im))[li]
+        st.els[:ti] = -st.eln[:ti]
+        fI, fJ = gI[W].astype(np.float64), gJ[W].astype(np.float64)
+        noise = lambda k: _hash_noise(fI, fJ, k)
+        st.wusurf[A] = -2.0e-5 * (1.0 + 0.5 * noise(2.0)) * st.fsm[A]
+        st.wvsurf[A] = 1.0e-5 * noise(3.0) * st.fsm[A]
+        st.wtsurf[A] = 2.0e-6 * noise(4.0) * st.fsm[A]
+        st.wssurf[A] = 1.0e-7 * noise(5.0) * st.fsm[A]
+        st.swrad[A] = -5.0e-5 * (1.0 + 0.5 * noise(6.0)) * st.fsm[A]
+        st.vfluxf[A] = 1.0e-7 * noise(7.0) * st.fsm[A]
+        st.e_atmos[A] = 0.01 * noise(8.0) * st.fsm[A]
+    elif name == "basin":
         st.wusurf[A] = -1.0e-4 * np.cos(math.pi * st.north_e[A] / ly) * st.fsm[A]
         st.wtsurf[A] = 2.0e-6 * np.sin(2.0 * math.pi * st.east_e[A] / lx) * st.fsm[A]
     else:

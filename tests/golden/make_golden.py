@@ -2,7 +2,7 @@
 (oracle/_ref/libpomref_65x49x21.so, built from the unmodified sources by oracle/build_ref.sh) on
 the inputs of extpom_amd.cases.  Run from the repo root in a container that has /root/reference:
 
-    oracle/build_ref.sh 65 49 21 && oracle/build_ref.sh 256 192 50 && python tests/golden/make_golden.py [kb50 | kb50long NAME | forced | refcheck]
+    oracle/build_ref.sh 65 49 21 && oracle/build_ref.sh 256 192 50 && python tests/golden/make_golden.py [kb50 | kb50long NAME | forced | refcheck | archipelago]
 
 The fixture holds, per configuration and checkpoint step, the SHA-256 of every restart-list field
 (the prognostic state, reference io_pnetcdf.F:1724-1886) exactly as the reference left it in its
@@ -112,29 +112,30 @@ def _delta(prev, cur):
     return {k: v for k, v in cur.items() if prev.get(k) != v}
 
 
-def generate_refcheck():
-    import ctypes
-    from extpom_amd.cases import make_forcing_records, make_lateral_records
+def _refcheck_full_state(case, nml):
+    """every COMMON array, bdry and blkcon of the reference after each of 12 steps"""
     from oracle.refharness import state_digests
-    out = {"grid": [65, 49, 21], "full_state": {}}
-    for case, nml in REFCHECK_FULL_STATE:
-        a = make_case(case, 65, 49, 21, **nml)
-        ref_finish_initial(a)
-        prev = state_digests(a)
-        rec = {"init": prev, "steps": {}}
-        lib = RefLib(65, 49, 21)
-        lib.put(a)
-        for n in range(1, 13):
-            lib.con["iint"][0] = n
-            lib.advance()
-            lib.get(a)
-            cur = state_digests(a)
-            rec["steps"][str(n)] = _delta(prev, cur)
-            prev = cur
-        out["full_state"][refcheck_key(case, nml)] = rec
+    a = make_case(case, 65, 49, 21, **nml)
+    ref_finish_initial(a)
+    prev = state_digests(a)
+    rec = {"init": prev, "steps": {}}
+    lib = RefLib(65, 49, 21)
+    lib.put(a)
+    for n in range(1, 13):
+        lib.con["iint"][0] = n
+        lib.advance()
+        lib.get(a)
+        cur = state_digests(a)
+        rec["steps"][str(n)] = _delta(prev, cur)
+        prev = cur
+    return rec
 
-    # each routine on its own, from the state after three steps (all branches live)
-    a = make_case("seamount", 65, 49, 21, dte=6.0, isplit=30)
+
+def _refcheck_each_routine(case):
+    """each routine on its own, from the state after three steps (all branches live)"""
+    import ctypes
+    from oracle.refharness import state_digests
+    a = make_case(case, 65, 49, 21, dte=6.0, isplit=30)
     ref_finish_initial(a)
     lib = RefLib(65, 49, 21)
     lib.put(a)
@@ -168,7 +169,51 @@ def generate_refcheck():
         ref_call(f"bcond/{idx}", "bcond", (i(idx),))
     for idx in (3, 5):
         ref_call(f"bcondorl/{idx}", "bcondorl", (i(idx),))
-    out["each_routine"] = {"warm": warm, "calls": calls}
+    return {"warm": warm, "calls": calls}
+
+
+# The fourth case (extpom_amd.cases: archipelago -- curved grid, interior land, both signs on the open edges, every forcing field
+# live), in files of its own: `make_golden.py archipelago` writes oracle_vs_reference_archipelago_65x49x21.json (refcheck style),
+# archipelago_65x49x21.json and archipelago_256x192x50.json (restart-list digests).  The files above are not touched by it.
+ARCH = dict(dte=6.0, isplit=30)
+REFCHECK_ARCHIPELAGO = [dict(ARCH), dict(ARCH, nadv=1), dict(ARCH, nitera=2), dict(ARCH, npg=2), dict(ARCH, mode=2)]
+CONFIGS_ARCHIPELAGO = {
+    "archipelago_default": ("archipelago", dict(ARCH), [1, 2, 3, 10, 100]),
+    "archipelago_nadv1": ("archipelago", dict(ARCH, nadv=1), [3, 20]),
+    "archipelago_nitera2": ("archipelago", dict(ARCH, nitera=2), [3, 20]),
+    "archipelago_npg2": ("archipelago", dict(ARCH, npg=2), [3, 20]),
+    "archipelago_mode2": ("archipelago", dict(ARCH, mode=2), [3, 20]),
+    "archipelago_mode4": ("archipelago", dict(ARCH, mode=4), [3, 20]),
+    "archipelago_nbct2": ("archipelago", dict(ARCH, nbct=2), [3, 20]),
+    "archipelago_nbc3": ("archipelago", dict(ARCH, nbct=3, nbcs=3), [3, 20]),
+}
+CONFIGS_ARCHIPELAGO_KB50 = {
+    "archipelago50_default": ("archipelago", dict(ARCH), [1, 3]),
+    "archipelago50_npg2": ("archipelago", dict(ARCH, npg=2), [1, 3]),
+}
+
+
+def generate_archipelago():
+    out = {"grid": [65, 49, 21], "full_state": {}}
+    for nml in REFCHECK_ARCHIPELAGO:
+        out["full_state"][refcheck_key("archipelago", nml)] = _refcheck_full_state("archipelago", nml)
+    out["each_routine"] = _refcheck_each_routine("archipelago")
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(here, "oracle_vs_reference_archipelago_65x49x21.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+    print("archipelago refcheck done", flush=True)
+    generate(65, 49, 21, CONFIGS_ARCHIPELAGO, {}, "archipelago_65x49x21")
+    generate(256, 192, 50, CONFIGS_ARCHIPELAGO_KB50, {}, "archipelago_256x192x50")
+
+
+def generate_refcheck():
+    import ctypes
+    from extpom_amd.cases import make_forcing_records, make_lateral_records
+    from oracle.refharness import state_digests
+    out = {"grid": [65, 49, 21], "full_state": {}}
+    for case, nml in REFCHECK_FULL_STATE:
+        out["full_state"][refcheck_key(case, nml)] = _refcheck_full_state(case, nml)
+    out["each_routine"] = _refcheck_each_routine("seamount")
 
     # domain_stats (the SUM intrinsic) after five steps of the island case
     a = make_case("island", 65, 49, 21, dte=6.0, isplit=30)
@@ -223,6 +268,8 @@ def generate_refcheck():
 
 
 def main():
+    if "archipelago" in sys.argv[1:]:
+        return generate_archipelago()
     if "refcheck" in sys.argv[1:]:
         return generate_refcheck()
     if "forced" in sys.argv[1:]:

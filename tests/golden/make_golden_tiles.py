@@ -1,7 +1,7 @@
 """Generates tests/golden/tiles_65x49x21_2x2.json by running the REFERENCE ITSELF on four MPI ranks:
 
     oracle/build_ref.sh 65 49 21 34 26 4
-    /opt/conda/bin/mpiexec -n 4 python tests/golden/make_golden_tiles.py
+    /opt/conda/bin/mpiexec -n 4 python tests/golden/make_golden_tiles.py [archipelago]
 
 Every rank loads oracle/_ref/libpomref_65x49x21_34x26p4.so (the unmodified solver.f advance.f bounds_forcing.f
 initialize.f parallel_mpi.f, n_proc = 4, im_local x jm_local = 34 x 26), calls the reference's own initialize_mpi and
@@ -11,6 +11,8 @@ between the four processes.  Recorded per rank: what distribute_mpi put into blk
 j_global, the four neighbours) and the SHA-256 of every restart-list field over the tile's (jm, im) cells, ghost cells
 INCLUDED, at several steps, for npg = 1 and npg = 2.  tests/test_oracle_golden.py holds extpom_amd.decomp against the
 first and the oracle + extpom_amd.halo tiles against the second; tests/test_gpu_multitile.py the HIP tiles.
+With `archipelago`: the fourth case (land on the tile seams, curved grid) into tiles_archipelago_65x49x21_2x2.json; the file
+above is not touched.
 """
 import ctypes
 import hashlib
@@ -35,6 +37,11 @@ CONFIGS = {
     "seamount_2x2_isplit10": ("seamount", dict(dte=6.0, isplit=10), [1, 3, 10]),     # tiles wide enough for the wide-halo external mode (w = 14)
     "seamount_2x2_isplit10_npg2": ("seamount", dict(dte=6.0, isplit=10, npg=2), [3, 10]),
 }
+# the fourth case in a file of its own (isplit = 10: tiles wide enough for the wide-halo external mode too)
+CONFIGS_ARCHIPELAGO = {"archipelago_2x2": ("archipelago", dict(dte=6.0, isplit=10), [1, 3, 10])}
+STEM = "tiles_65x49x21_2x2"
+if "archipelago" in sys.argv[1:]:
+    CONFIGS, STEM = CONFIGS_ARCHIPELAGO, "tiles_archipelago_65x49x21_2x2"
 
 
 def digest(a):
@@ -99,9 +106,9 @@ def main():
                 "configs": {name: {"case": allr[0]["configs"][name]["case"], "nml": allr[0]["configs"][name]["nml"],
                                    "steps": {s: [a["configs"][name]["steps"][s] for a in allr] for s in allr[0]["configs"][name]["steps"]}}
                             for name in CONFIGS}}
-        with open(os.path.join(ROOT, "tests", "golden", "tiles_65x49x21_2x2.json"), "w") as f:
+        with open(os.path.join(ROOT, "tests", "golden", STEM + ".json"), "w") as f:
             json.dump(gold, f, indent=1, sort_keys=True)
-        print("wrote tiles_65x49x21_2x2.json", flush=True)
+        print("wrote " + STEM + ".json", flush=True)
     lib.call("finalize_mpi")
 
 

@@ -10,7 +10,9 @@ included), the wide-halo external mode with its rounds on the second stream.  Af
 that is not pure scratch.  The single-tile path itself is pinned to the oracle at this size for steps 1-3
 (test_config4_2048x1536x50_full_size); this carries that pin over STEPS steps and over the multi-tile code path.
 
-    python tests/gpu_tiles_threads.py [IMxJMxKB] [N | AxB[,CxD...]] [STEPS] [f32]
+    python tests/gpu_tiles_threads.py [IMxJMxKB] [N | AxB[,CxD...]] [STEPS] [f32] [case=NAME]
+
+case=NAME: another case of extpom_amd.cases than the closed basin (archipelago: land on the seams and open edges, curved grid).
 """
 import ctypes
 import os
@@ -84,10 +86,11 @@ def main():
         os.environ["POMGPU_SUM2D_OFF"] = "1"
         os.environ["POMGPU_QFILTER_SPLIT"] = "1"
     im, jm, kb = (int(v) for v in grid.split("x"))
+    case = next((v[5:] for v in sys.argv[4:] if v.startswith("case=")), "basin")
     nml = dict(dte=6.0, isplit=30, mode=3, nadv=2, nitera=1, npg=1)
     dev = torch.device("cuda", 0)
     # ---- one tile ----------------------------------------------------------------------------------------------------
-    a = make_case("basin", im, jm, kb, **nml)
+    a = make_case(case, im, jm, kb, **nml)
     ga = PomGpu(a, device=0, libpath=libpath)
     gpu_finish(a, ga)
     ga.run(steps)
@@ -96,10 +99,10 @@ def main():
     assert a.error_status == 0
     beat(f"single tile: {steps} steps done")
     for nx, ny in splits:                             # every split against the same single-tile run
-        run_split(a, grid, im, jm, kb, nml, nx, ny, steps, libpath, dev, exact)
+        run_split(a, grid, im, jm, kb, nml, nx, ny, steps, libpath, dev, exact, case)
 
 
-def run_split(a, grid, im, jm, kb, nml, nx, ny, steps, libpath, dev, exact):
+def run_split(a, grid, im, jm, kb, nml, nx, ny, steps, libpath, dev, exact, case="basin"):
     world = nx * ny
     # ---- nx x ny tiles, one host thread each -------------------------------------------------------------------------
     iml, jml = decomp.local_size(im, jm, nx, ny)
@@ -112,7 +115,7 @@ def run_split(a, grid, im, jm, kb, nml, nx, ny, steps, libpath, dev, exact):
         try:
             torch.cuda.set_device(0)
             tile = tiles[r]
-            st = make_case("basin", im, jm, kb, tile=tile, **nml)
+            st = make_case(case, im, jm, kb, tile=tile, **nml)
             ts = torch.cuda.Stream()
             torch.cuda.set_stream(ts)                 # thread-local: this thread's torch work goes to its context's stream
             g = PomGpu(st, device=0, stream=ts.cuda_stream, libpath=libpath)

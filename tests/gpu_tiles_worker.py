@@ -28,6 +28,7 @@ SCRATCH = {"tps", "fluxua", "fluxva", "zflux"}
 def worker(rank, world, split, port, out, nml):
     nml = dict(nml)
     mode = nml.pop("_exchange", "hook")
+    case = nml.pop("_case", "island")
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -37,7 +38,7 @@ def worker(rank, world, split, port, out, nml):
     nx, ny = {"x": (2, 1), "y": (1, 2), "xy": (2, 2), "y4": (1, 4)}[split]
     iml, jml = decomp.local_size(IM, JM, nx, ny)
     tile = decomp.make_tile(rank, IM, JM, iml, jml, n_proc=world)
-    st = make_case("island", IM, JM, KB, tile=tile, dte=6.0, isplit=ISPLIT, **nml)
+    st = make_case(case, IM, JM, KB, tile=tile, dte=6.0, isplit=ISPLIT, **nml)
     # kernels and torch's pack/unpack must share ONE stream; torch's default stream has handle 0, which
     # the C ABI reads as "create your own", so make a real stream current and hand that over
     ts = torch.cuda.Stream()
@@ -83,14 +84,14 @@ def worker(rank, world, split, port, out, nml):
     dist.destroy_process_group()
 
 
-def main(split, nml, exchange="hook"):
+def main(split, nml, exchange="hook", case="island"):
     import tempfile
     from oracle.pyoracle import OracleTile, oracle_finish_initial
     out = tempfile.mkdtemp()
     port = 29700 + (os.getpid() % 200)
     world = 4 if split in ("xy", "y4") else 2
-    mp.spawn(worker, args=(world, split, port, out, dict(nml, _exchange=exchange)), nprocs=world, join=True)
-    g = make_case("island", IM, JM, KB, dte=6.0, isplit=ISPLIT, **nml)
+    mp.spawn(worker, args=(world, split, port, out, dict(nml, _exchange=exchange, _case=case)), nprocs=world, join=True)
+    g = make_case(case, IM, JM, KB, dte=6.0, isplit=ISPLIT, **nml)
     oracle_finish_initial(g)
     OracleTile(g).run(STEPS)
     bad = []
@@ -128,4 +129,5 @@ def main(split, nml, exchange="hook"):
 
 if __name__ == "__main__":
     main(sys.argv[1] if len(sys.argv) > 1 else "x", dict(npg=2) if "npg2" in sys.argv[2:] else {},
-         "rccl" if "rccl" in sys.argv[2:] else ("wide" if "wide" in sys.argv[2:] else ("transport" if "transport" in sys.argv[2:] else "hook")))
+         "rccl" if "rccl" in sys.argv[2:] else ("wide" if "wide" in sys.argv[2:] else ("transport" if "transport" in sys.argv[2:] else "hook")),
+         next((a[5:] for a in sys.argv[2:] if a.startswith("case=")), "island"))       # case=archipelago: land on the seams, curved grid

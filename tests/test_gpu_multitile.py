@@ -127,3 +127,46 @@ def test_hip_tiles_equal_the_references_own_mpi_run(args):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "tiles_golden_worker.py")] + args, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0 and "TILES-GOLDEN-OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+# ---- the fourth case (extpom_amd.cases: archipelago): land on the seams, in the ghost lines, in the wide-halo rim and on the open edges, a
+# curved grid.  The device's lane shifts and LDS slabs carry dum, dvm, dt, cor and the curvature coefficients between lanes and rows; the
+# emulated build reads them from memory, so these runs are the authority for them (tests/test_host_logic.py asserts the land per split)
+@pytest.mark.gpu
+@pytest.mark.parametrize("args", [["x"], ["y"], ["xy"], ["x", "transport"], ["y", "transport"], ["xy", "transport"], ["x", "wide"], ["y", "wide"], ["xy", "wide"],
+                                  ["xy", "npg2", "wide"]], ids="-".join)
+def test_archipelago_tiles_on_one_gpu_match_single_tile_oracle(args):
+    """2 x 1, 1 x 2 and 2 x 2 tiles of 97x61x16 with the per-point hooks, the library exchange and the wide-halo external mode;
+    baropg_mcc once: owned cells equal the single-tile oracle bit for bit"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "gpu_tiles_worker.py")] + args + ["case=archipelago"], capture_output=True,
+                       text=True, timeout=900)
+    assert r.returncode == 0 and "TILES-OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+@pytest.mark.gpu
+def test_archipelago_whole_row_tiles():
+    """1 x 4 whole-row tiles (72x150x12), wide-halo mode: the two inner tiles extended on both sides, land in their rims"""
+    env = dict(os.environ, POM_TILES_GRID="72x150x12")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "gpu_tiles_worker.py"), "y4", "wide", "case=archipelago"], capture_output=True,
+                       text=True, timeout=900, env=env)
+    assert r.returncode == 0 and "TILES-OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+@pytest.mark.gpu
+def test_archipelago_256x192x50_as_2x4_tiles_event_ordered_mover():
+    """the asynchronous (event-ordered) mover of gpu_tiles_threads.py, rounds on the second stream really beside the kernels: 2 x 4 tiles
+    of 256x192x50, 10 internal steps, every owned cell against the single tile (which the reference digests pin,
+    test_gpu_reproduces_reference_digests_archipelago_kb50)"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "gpu_tiles_threads.py"), "256x192x50", "2x4", "10", "case=archipelago"], capture_output=True,
+                       text=True, timeout=900)
+    assert r.returncode == 0 and "TILES-THREADS-OK 256x192x50 2x4 10" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("args", [["archipelago_2x2", "hook"], ["archipelago_2x2", "transport"], ["archipelago_2x2", "wide"]])
+def test_hip_tiles_equal_the_references_own_mpi_run_archipelago(args):
+    """as test_hip_tiles_equal_the_references_own_mpi_run, on the reference's four-process run of the fourth case
+    (tests/golden/tiles_archipelago_65x49x21_2x2.json): ghost cells included"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "tiles_golden_worker.py")] + args, capture_output=True, text=True,
+                       timeout=900)
+    assert r.returncode == 0 and "TILES-GOLDEN-OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]

@@ -13,6 +13,7 @@ import pytest
 
 from extpom_amd.cases import make_case
 from extpom_amd.layout import BLK2D, BLK3D, PROGNOSTIC
+from golden_files import golden_file
 
 pytestmark = pytest.mark.gpu
 SCRATCH = {"tps", "fluxua", "fluxva", "zflux"}
@@ -66,6 +67,27 @@ def _digest(a):
     return hashlib.sha256(np.ascontiguousarray(a, dtype="<f8").tobytes()).hexdigest()
 
 
+def _reproduces(gold, name):
+    """the initial state and every restart-list field after every checkpoint hash to what the REFERENCE produced"""
+    OracleTile, oracle_finish_initial = _oracle()
+    cfg = gold["configs"][name]
+    im, jm, kb = gold["grid"]
+    st = make_case(cfg["case"], im, jm, kb, **cfg["nml"])
+    oracle_finish_initial(st)
+    bad = [f for f in gold["fields"] if _digest(st.field(f)) != cfg["init"][f]]
+    assert not bad, f"{name}: initial state: {bad}"
+    g = _gpu(st)
+    done = 0
+    for step in sorted(int(s) for s in cfg["steps"]):
+        g.run(step - done)
+        done = step
+        g.download()
+        bad = [f for f in gold["fields"] if _digest(st.field(f)) != cfg["steps"][str(step)][f]]
+        assert not bad, f"{name}: step {step}: {bad} differ from the reference"
+    g.close()
+    assert st.error_status == 0
+
+
 def test_native_library_is_the_one_running():
     from extpom_amd import lib
     L = lib.load()
@@ -78,20 +100,7 @@ def test_native_library_is_the_one_running():
                                   "seamount_npg2", "island_npg2"])
 def test_gpu_reproduces_reference_digests(golden, name):
     """every restart-list field after every checkpoint hashes to what the REFERENCE produced"""
-    OracleTile, oracle_finish_initial = _oracle()
-    cfg = golden["configs"][name]
-    im, jm, kb = golden["grid"]
-    st = make_case(cfg["case"], im, jm, kb, **cfg["nml"])
-    oracle_finish_initial(st)
-    g = _gpu(st)
-    done = 0
-    for step in sorted(int(s) for s in cfg["steps"]):
-        g.run(step - done)
-        done = step
-        g.download()
-        bad = [f for f in golden["fields"] if _digest(st.field(f)) != cfg["steps"][str(step)][f]]
-        assert not bad, f"{name}: step {step}: {bad} differ from the reference"
-    assert st.error_status == 0
+    _reproduces(golden, name)
 
 
 def test_gpu_initialisation_matches_reference(golden):
@@ -141,10 +150,17 @@ ROUTINES = [
 ]
 
 
-@pytest.mark.parametrize("name,fields,ints", ROUTINES, ids=[f"{r[0]}{''.join(map(str, r[2]))}" for r in ROUTINES])
-def test_each_routine_bit_identical_to_oracle(name, fields, ints):
+# island: no land at all (dum = dvm = fsm = 1), no curvature; archipelago: every mask, the curvature terms and cor(i-1,j) live, and
+# proft's short-wave branches on a non-uniform swrad.  (The island ids stay as they were.)
+ROUTINES_ARCHIPELAGO = ROUTINES + [("proft", ("uf", "wtsurf", "tsurf"), (2,)), ("proft", ("uf", "wtsurf", "tsurf"), (4,))]
+_rid = lambda r: f"{r[0]}{''.join(map(str, r[2]))}"
+
+
+@pytest.mark.parametrize("case,name,fields,ints", [("island",) + r for r in ROUTINES] + [("archipelago",) + r for r in ROUTINES_ARCHIPELAGO],
+                         ids=[_rid(r) for r in ROUTINES] + ["archipelago-" + _rid(r) for r in ROUTINES_ARCHIPELAGO])
+def test_each_routine_bit_identical_to_oracle(case, name, fields, ints):
     OracleTile, oracle_finish_initial = _oracle()
-    a = make_case("island", 65, 49, 21, dte=6.0, isplit=30)
+    a = make_case(case, 65, 49, 21, dte=6.0, isplit=30)
     oracle_finish_initial(a)
     OracleTile(a).run(3)
     a.iint, a.iext = 4, 7
@@ -154,7 +170,22 @@ def test_each_routine_bit_identical_to_oracle(name, fields, ints):
     g = _gpu(b)
     g.call(name, *fields, *ints)
     g.download()
-    assert not diff(a, b), f"{name}: {diff(a, b)}"
+    assert not diff(a, b) and same_bits(a.bdry, b.bdry), f"{name}: {diff(a, b)}"
+
+
+@pytest.mark.parametrize("name", ["archipelago_default", "archipelago_nadv1", "archipelago_nitera2", "archipelago_npg2", "archipelago_mode2",
+                                  "archipelago_mode4", "archipelago_nbct2", "archipelago_nbc3"])
+def test_gpu_reproduces_reference_digests_archipelago(name):
+    """the fourth case against digests of the REFERENCE's own state (tests/golden/archipelago_65x49x21.json): steps 1, 2, 3, 10, 100 of the
+    default namelist, 3 and 20 of the others.  The lane shifts and LDS slabs that carry masks, cor and the curvature coefficients between
+    lanes and rows exist on the device only: no emulated test stands in for this one."""
+    _reproduces(golden_file("archipelago_65x49x21"), name)
+
+
+@pytest.mark.parametrize("name", ["archipelago50_default", "archipelago50_npg2"])
+def test_gpu_reproduces_reference_digests_archipelago_kb50(name):
+    """256x192x50 (tests/golden/archipelago_256x192x50.json): the <50> instantiations, rows of four wavefronts"""
+    _reproduces(golden_file("archipelago_256x192x50"), name)
 
 
 def test_check_velocity_wavefront_reduction():
@@ -361,10 +392,13 @@ def test_config2_seamount_256x256x30_matches_oracle():
     assert not diff(a, b), diff(a, b)
 
 
-@pytest.mark.parametrize("switches", [("POMGPU_THOMAS_SCRATCH", "POMGPU_NO_PAIR", "POMGPU_EXT_SPLIT", "POMGPU_ADVQ_SINGLE", "POMGPU_ADVT2_SINGLE",
-                                       "POMGPU_REALVERTVL_CELLS", "POMGPU_BAROPG_CELLS", "POMGPU_VERTVL_CELLS"), ("POMGPU_ADVAVE_SEPARATE", "POMGPU_EXT_RIM_KERNEL"),
-                                      ("POMGPU_EXT_LOOP",), ("POMGPU_RHO_ROUNDTRIP", "POMGPU_TAU_ARRAYS", "POMGPU_IO_SYNC"),
-                                      ("POMGPU_PROFQ_ROWS8", "POMGPU_COL_STRIP", "POMGPU_EXT_MARCH"), ("POMGPU_PROFQ_ROWS2", "POMGPU_PROFQ_NOPACE", "POMGPU_EXT_NOMARCH", "POMGPU_NO_LIN", "POMGPU_EXT_TWO_SETS")])
+SWITCH_SETS = [("POMGPU_THOMAS_SCRATCH", "POMGPU_NO_PAIR", "POMGPU_EXT_SPLIT", "POMGPU_ADVQ_SINGLE", "POMGPU_ADVT2_SINGLE",
+                "POMGPU_REALVERTVL_CELLS", "POMGPU_BAROPG_CELLS", "POMGPU_VERTVL_CELLS"), ("POMGPU_ADVAVE_SEPARATE", "POMGPU_EXT_RIM_KERNEL"),
+               ("POMGPU_EXT_LOOP",), ("POMGPU_RHO_ROUNDTRIP", "POMGPU_TAU_ARRAYS", "POMGPU_IO_SYNC"),
+               ("POMGPU_PROFQ_ROWS8", "POMGPU_COL_STRIP", "POMGPU_EXT_MARCH"), ("POMGPU_PROFQ_ROWS2", "POMGPU_PROFQ_NOPACE", "POMGPU_EXT_NOMARCH", "POMGPU_NO_LIN", "POMGPU_EXT_TWO_SETS")]
+
+
+@pytest.mark.parametrize("switches", SWITCH_SETS)
 def test_general_kernels_behind_the_fast_paths(monkeypatch, switches):
     """the scratch-vector / one-column-per-lane / split kernels that serve kb > 64, odd im_local and
     multi-tile runs, selected through the library's developer switches, on an even and an odd grid; second set: the
@@ -387,6 +421,48 @@ def test_general_kernels_behind_the_fast_paths(monkeypatch, switches):
         g.download()
         g.close()
         assert not diff(a, b), (im, jm, diff(a, b))
+
+
+@pytest.mark.parametrize("switches", SWITCH_SETS)
+def test_general_kernels_behind_the_fast_paths_archipelago(monkeypatch, switches):
+    """the six switch sets of the test above on the fourth case, 65x49 and 128x96: the general kernels see interior land and a curved grid"""
+    OracleTile, oracle_finish_initial = _oracle()
+    for v in switches:
+        monkeypatch.setenv(v, "1")
+    for im, jm in ((65, 49), (128, 96)):
+        a = make_case("archipelago", im, jm, 21, dte=6.0, isplit=30)
+        oracle_finish_initial(a)
+        b = a.copy()
+        OracleTile(a).run(3)
+        g = _gpu(b)
+        g.run(3)
+        g.download()
+        g.close()
+        assert not diff(a, b), (im, jm, diff(a, b))
+
+
+def test_kb_above_the_register_kernels_bound_archipelago():
+    """kb = 70 on the fourth case, short-wave penetration (nbct = 2) on its non-uniform swrad included"""
+    OracleTile, oracle_finish_initial = _oracle()
+    a = make_case("archipelago", 64, 48, 70, dte=6.0, isplit=30, nbct=2)
+    oracle_finish_initial(a)
+    b = a.copy()
+    OracleTile(a).run(3)
+    g = _gpu(b)
+    g.run(3)
+    g.download()
+    g.close()
+    assert not diff(a, b), diff(a, b)
+
+
+@pytest.mark.bg_oracle("archipelago", 1024, 1024, 40, 3)
+def test_archipelago_1024x1024x40_matches_the_background_oracle(bg_oracle):
+    """the default kernel shapes of a large grid (paced k_profq rows, banded XCD order) with land and curvature: steps 1, 2 and 3 on every
+    COMMON array that is not scratch against the oracle a child process computes beside the other tests (tests/oracle_bg.py)"""
+    OracleTile, oracle_finish_initial = _oracle()
+    e = make_case("archipelago", 1024, 1024, 40, dte=6.0, isplit=30)
+    oracle_finish_initial(e)
+    _against_background_oracle(e, bg_oracle, 3, beat=lambda msg: print(msg, flush=True))
 
 
 def test_kb_above_the_register_kernels_bound():
@@ -447,23 +523,7 @@ def test_gpu_reproduces_reference_digests_kb50(golden_kb50, name):
     """256x192x50: the <50> instantiations of k_proft_reg / k_profuv_reg / k_uv_filter_reg / k_int_uvmean_reg (what the
     2048x1536x50 bench dispatches) against digests of the REFERENCE's own state (oracle/_ref/libpomref_256x192x50.so,
     tests/golden/make_golden.py kb50)"""
-    OracleTile, oracle_finish_initial = _oracle()
-    cfg = golden_kb50["configs"][name]
-    im, jm, kb = golden_kb50["grid"]
-    st = make_case(cfg["case"], im, jm, kb, **cfg["nml"])
-    oracle_finish_initial(st)
-    bad = [f for f in golden_kb50["fields"] if _digest(st.field(f)) != cfg["init"][f]]
-    assert not bad, f"{name}: initial state: {bad}"
-    g = _gpu(st)
-    done = 0
-    for step in sorted(int(s) for s in cfg["steps"]):
-        g.run(step - done)
-        done = step
-        g.download()
-        bad = [f for f in golden_kb50["fields"] if _digest(st.field(f)) != cfg["steps"][str(step)][f]]
-        assert not bad, f"{name}: step {step}: {bad} differ from the reference"
-    g.close()
-    assert st.error_status == 0
+    _reproduces(golden_kb50, name)
 
 
 @pytest.mark.parametrize("name", ["basin50_default", "seamount50_default"])
@@ -472,34 +532,17 @@ def test_1000_internal_steps_kb50_hash_to_the_reference(name):
     REFERENCE ITSELF: digests of every restart-list field after 100 / 500 / 1000 steps of oracle/_ref/libpomref_256x192x50.so
     (tests/golden/kb50_1000steps_<name>.json, make_golden.py kb50long; ten minutes of one core each in the build container).
     north_star asks for 1e-10 relative; equal digests mean the difference is exactly zero."""
-    import json
-    import os
-    OracleTile, oracle_finish_initial = _oracle()
-    here = os.path.dirname(os.path.abspath(__file__))
-    gold = json.load(open(os.path.join(here, "golden", f"kb50_1000steps_{name}.json")))
-    cfg = gold["configs"][name]
+    gold = golden_file(f"kb50_1000steps_{name}")
     im, jm, kb = gold["grid"]
-    assert kb == 50 and sorted(int(s) for s in cfg["steps"]) == [100, 500, 1000]
-    st = make_case(cfg["case"], im, jm, kb, **cfg["nml"])
-    oracle_finish_initial(st)
-    bad = [f for f in gold["fields"] if _digest(st.field(f)) != cfg["init"][f]]
-    assert not bad, f"{name}: initial state: {bad}"
-    g = _gpu(st)
-    done = 0
-    for step in (100, 500, 1000):
-        g.run(step - done)
-        done = step
-        g.download()
-        bad = [f for f in gold["fields"] if _digest(st.field(f)) != cfg["steps"][str(step)][f]]
-        assert not bad, f"{name}: step {step}: {bad} differ from the reference"
-    g.close()
-    assert st.error_status == 0
+    assert kb == 50 and sorted(int(s) for s in gold["configs"][name]["steps"]) == [100, 500, 1000]
+    _reproduces(gold, name)
 
 
 @pytest.mark.parametrize("case,kb,nml", [("basin", 50, {}), ("basin", 50, dict(nadv=1)), ("basin", 50, dict(npg=2)), ("island", 50, {}),
                                          ("basin", 5, {}), ("basin", 6, {}), ("seamount", 7, {}), ("seamount", 24, {}), ("basin", 25, {}), ("seamount", 32, {}),
                                          ("basin", 33, {}), ("basin", 40, {}), ("seamount", 41, {}), ("seamount", 44, {}), ("basin", 45, {}), ("seamount", 56, {}), ("basin", 57, {}),
-                                         ("seamount", 64, {})])
+                                         ("seamount", 64, {}),
+                                         ("archipelago", 24, {}), ("archipelago", 25, {}), ("archipelago", 50, {}), ("archipelago", 64, {})])
 def test_every_register_kernel_instantiation_matches_oracle(case, kb, nml):
     """ALL fields after 3 steps array_equal to the oracle at the level counts either side of every template bound of
     the register-resident column kernels (k_vert.hip launchers: 24, 32, 40, 44, 50, 56, 64) and at the smallest kb they take"""
@@ -515,7 +558,8 @@ def test_every_register_kernel_instantiation_matches_oracle(case, kb, nml):
     assert not diff(a, b), (case, kb, nml, diff(a, b))
 
 
-@pytest.mark.parametrize("case,im,jm,kb", [("basin", 2048, 24, 12), ("seamount", 2050, 20, 50), ("basin", 2047, 16, 8)])
+@pytest.mark.parametrize("case,im,jm,kb", [("basin", 2048, 24, 12), ("seamount", 2050, 20, 50), ("basin", 2047, 16, 8),
+                                           ("archipelago", 2050, 20, 50)])                       # land in the last columns of the row
 def test_wide_rows_band_geometry_matches_oracle(case, im, jm, kb):
     """iml >= 2047: the launch geometry of the bench grid's rows (set_band_geometry picks 4-row bands, 33-34 workgroups
     per block-row in HALO_XCD_DECODE), all fields after 2 steps array_equal to the oracle"""
@@ -735,7 +779,8 @@ def test_marching_external_substep_with_and_without_canonical_areas(monkeypatch,
 
 
 @pytest.mark.parametrize("case,im,jm,kb,isplit,rows2", [("seamount", 200, 93, 11, 10, "6"), ("island", 130, 97, 9, 7, "5"), ("seamount", 65, 49, 21, 30, None),
-                                                        ("basin", 257, 64, 6, 8, "30"), ("seamount", 121, 60, 8, 4, "2")])
+                                                        ("basin", 257, 64, 6, 8, "30"), ("seamount", 121, 60, 8, 4, "2"),
+                                                        ("archipelago", 200, 93, 11, 10, "6")])
 def test_two_external_substeps_per_pass(monkeypatch, case, im, jm, kb, isplit, rows2):
     """k_ext_march2 (two substeps per pass over memory: the second generation marches one row behind the first, the rim's
     intermediate generation through a third buffer set) forced onto small grids -- its default use is the full-size test:

@@ -56,7 +56,7 @@ def test_decomposition_matches_distribute_mpi():
     assert decomp.choose_tile_grid(4, 65, 49) == (2, 2)
 
 
-@pytest.mark.parametrize("case", ["seamount", "island", "basin"])
+@pytest.mark.parametrize("case", ["seamount", "island", "basin", "archipelago"])
 def test_tile_generation_equals_cut_of_global(case):
     g = make_case(case, 65, 49, 21, dte=6.0, isplit=30)
     for r in range(4):
@@ -65,6 +65,145 @@ def test_tile_generation_equals_cut_of_global(case):
         assert not [n for n in BLK2D + BLK3D if not np.array_equal(a.field(n), b.field(n))]
         for (x, y), (p, q) in zip(a.restore_records, b.restore_records):
             assert np.array_equal(x, p) and np.array_equal(y, q)
+
+
+# ---- the archipelago case: what it must have, on every grid (and tile split) a test runs it on ---------------------------------------
+# (im, jm, kb, [(nx, ny, isplit of the wide-halo run or None)]): tests/test_kernels_emulated*.py, test_gpu_parity.py, test_gpu_multitile.py
+ARCHIPELAGO_GRIDS = [
+    (65, 49, 21, [(2, 2, 10)]), (66, 50, 21, []), (128, 12, 21, []), (64, 48, 70, []), (256, 192, 50, [(2, 4, 30)]), (128, 96, 21, []),
+    (200, 30, 21, []), (200, 93, 11, []), (2050, 20, 50, []), (1024, 1024, 40, []),
+    (41, 35, 11, [(2, 1, None), (1, 2, None), (2, 2, None), (3, 2, None), (1, 3, None)]),
+    (67, 59, 11, [(2, 2, 7), (2, 1, 7), (1, 2, 7)]), (97, 59, 11, [(3, 2, 7), (2, 2, 7)]), (41, 101, 11, [(1, 3, 7)]),
+    (43, 75, 11, [(2, 4, 7)]), (59, 53, 11, [(3, 3, 7)]),
+    (97, 61, 16, [(2, 1, 10), (1, 2, 10), (2, 2, 10)]), (72, 150, 12, [(1, 4, 10)]),
+]
+
+
+def _shift(a, dj, di):
+    """a(j+dj, i+di), False beyond the grid"""
+    out = np.zeros_like(a)
+    jm, im = a.shape
+    out[max(0, -dj):jm - max(0, dj), max(0, -di):im - max(0, di)] = a[max(0, dj):jm + min(0, dj), max(0, di):im + min(0, di)]
+    return out
+
+
+def _runs(mask):
+    """longest run of True along the last axis"""
+    best = run = np.zeros(mask.shape[0], dtype=int)
+    for i in range(mask.shape[1]):
+        run = np.where(mask[:, i], run + 1, 0)
+        best = np.maximum(best, run)
+    return int(best.max())
+
+
+@pytest.mark.parametrize("im,jm,kb,splits", ARCHIPELAGO_GRIDS, ids=[f"{g[0]}x{g[1]}x{g[2]}" for g in ARCHIPELAGO_GRIDS])
+def test_archipelago_has_what_the_other_cases_lack(im, jm, kb, splits):
+    """The properties the parity tests on this case lean on, asserted on the generated state: a case smoothed
+    later turns this test red, not the kernels' tests blind.  A 12- or 20-row grid is too short for the straits and lakes; the rest
+    is demanded there too."""
+    if im * jm * kb > 4.0e6:
+        kb = 4                                                   # the horizontal properties do not depend on kb
+    st = make_case("archipelago", im, jm, kb, dte=6.0, isplit=30)
+    dx, dy, cor, h = st.dx, st.dy, st.cor, st.h
+    # grid: the differences behind the curvature terms, and the cross-direction neighbours, are not zero
+    assert np.abs(dy[:, 2:] - dy[:, :-2]).max() > 0 and np.abs(dx[2:, :] - dx[:-2, :]).max() > 0
+    assert np.abs(cor[:, 1:] - cor[:, :-1]).max() > 0 and np.abs(cor[1:, :] - cor[:-1, :]).max() > 0
+    assert np.isclose(float(st.period), 2.0 * np.pi / abs(cor[jm // 2 - 1, im // 2 - 1]) / 86400.0, rtol=1e-14, atol=0)     # initialize.f:357
+    assert np.array_equal(st.art, dx * dy)
+    assert np.array_equal(st.aru[1:, 1:], 0.25 * (dx[1:, 1:] + dx[1:, :-1]) * (dy[1:, 1:] + dy[1:, :-1]))
+    assert np.array_equal(st.arv[1:, 1:], 0.25 * (dx[1:, 1:] + dx[:-1, 1:]) * (dy[1:, 1:] + dy[:-1, 1:]))
+    assert np.array_equal(st.aru[:, 0], st.aru[:, 1]) and np.array_equal(st.arv[0, :], st.arv[1, :])
+    # land: 3-6 % of the cells, h = 1 there, masks as io_pnetcdf.F:2243-2256
+    land = st.fsm == 0.0
+    assert 0.03 <= land.mean() <= 0.06, land.mean()
+    assert (h[land] == 1.0).all() and (h[~land] >= 10.0).all()
+    dum, dvm = (~land).astype(float), (~land).astype(float)
+    dum[:, 1:][land[:, :-1]] = 0.0
+    dvm[1:, :][land[:-1, :]] = 0.0
+    assert np.array_equal(st.dum, dum) and np.array_equal(st.dvm, dvm)
+    wet = ~land
+    n4 = lambda a: _shift(a, 0, 1) & _shift(a, 0, -1) & _shift(a, 1, 0) & _shift(a, -1, 0)
+    n8 = lambda a: n4(a) & _shift(a, 1, 1) & _shift(a, 1, -1) & _shift(a, -1, 1) & _shift(a, -1, -1)
+    assert (land & n8(wet)).any()                                                # a one-cell island
+    # land on each of the four open edges and in a domain corner; at the end of the first wavefront / of a wide row
+    assert land[1:-1, 0].any() and land[1:-1, -1].any() and land[0, 1:-1].any() and land[-1, 1:-1].any() and land[-1, -1]
+    if im == 65:
+        assert land[:, 63].any() and land[:, 64].any()
+    if im >= 2047:
+        assert land[:, 2046:].any()
+    if jm >= 40:
+        pair = land & _shift(land, 0, 1) & ~_shift(land, 0, -1) & ~_shift(land, 0, 2)
+        alone = ~_shift(land, 1, 0) & ~_shift(land, -1, 0) & ~_shift(land, 1, 1) & ~_shift(land, -1, 1)
+        assert (pair & alone).any()                                              # a 2 x 1 island
+        diag = land & _shift(land, 1, 1) & ~_shift(land, 0, 1) & ~_shift(land, 1, 0)
+        assert diag.any()                                                        # two cells touching at a corner only
+        strait_j = wet & _shift(land, 0, -1) & _shift(land, 0, 1)                # one wet cell between two land cells ...
+        strait_i = wet & _shift(land, -1, 0) & _shift(land, 1, 0)
+        assert _runs(strait_j.T) >= 10 and _runs(strait_i) >= 10                 # ... ten times in a row, in each direction
+        assert (wet & n8(land)).any()                                            # a lake of one cell
+        q = wet & _shift(wet, 0, 1) & _shift(wet, 1, 0) & _shift(wet, 1, 1)      # a 2 x 2 lake: its twelve neighbours are land
+        ring = np.ones_like(land)
+        for dj in (-1, 0, 1, 2):
+            for di in (-1, 0, 1, 2):
+                if not (dj in (0, 1) and di in (0, 1)):
+                    ring &= _shift(land, dj, di)
+        assert (q & ring).any()
+    # bottom roughness, T / S away from the climatology, forcing: all live, all masked
+    r = np.abs(h[:, 1:] / h[:, :-1] - 1.0)[wet[:, 1:] & wet[:, :-1]]
+    assert np.median(r) > 0.05
+    assert np.abs(st.tb - st.tclim).max() > 0.01 and np.abs(st.sb - st.sclim).max() > 0.005
+    for n in ("wusurf", "wvsurf", "wtsurf", "wssurf", "swrad", "vfluxf", "e_atmos"):
+        f = st.field(n)
+        assert (f[land] == 0.0).all() and np.unique(f[wet]).size > wet.sum() // 2, n
+    for n in ("ele", "elw", "eln", "els"):
+        assert np.abs(st.field(n)).max() > 0 and st.field(n).min() < 0 < st.field(n).max(), n
+    for f, edge in ((st.uab, (slice(None), 1)), (st.uab, (slice(None), -1)), (st.vab, (1, slice(None))), (st.vab, (-1, slice(None)))):
+        assert f[edge].min() < 0 < f[edge].max()                                 # both signs of the normal velocity on every edge
+    # tiles: land on a line two neighbours share (the owned edge line of one is the ghost line of the other) at some seam, and in
+    # the rim of w = isplit + 4 cells by which the wide-halo mode extends a tile
+    for nx, ny, isplit in splits:
+        iml, jml = decomp.local_size(im, jm, nx, ny)
+        edge = ghost = rim = False
+        for rk in range(nx * ny):
+            t = decomp.make_tile(rk, im, jm, iml, jml, n_proc=nx * ny)
+            tl = land[t.j_off:t.j_off + t.jm, t.i_off:t.i_off + t.im]
+            if t.n_east >= 0:
+                edge, ghost = edge or tl[1:-1, -2].any(), ghost or tl[1:-1, -1].any()
+            if t.n_west >= 0:
+                edge, ghost = edge or tl[1:-1, 1].any(), ghost or tl[1:-1, 0].any()
+            if t.n_north >= 0:
+                edge, ghost = edge or tl[-2, 1:-1].any(), ghost or tl[-1, 1:-1].any()
+            if t.n_south >= 0:
+                edge, ghost = edge or tl[1, 1:-1].any(), ghost or tl[0, 1:-1].any()
+            if isplit:
+                w = isplit + 4
+                j0, j1, i0, i1 = max(0, t.j_off - w), min(jm, t.j_off + t.jm + w), max(0, t.i_off - w), min(im, t.i_off + t.im + w)
+                ext = land[j0:j1, i0:i1].sum() - tl.sum()
+                rim = rim or ext > 0
+        assert edge and ghost and (rim or not isplit), (nx, ny, edge, ghost, rim)
+
+
+@pytest.mark.parametrize("im,jm,kb,steps,nml", [(65, 49, 21, 100, {}), (65, 49, 21, 100, dict(nadv=1)), (65, 49, 21, 100, dict(nitera=2)),
+                                                (65, 49, 21, 100, dict(npg=2)), (65, 49, 21, 100, dict(nbct=2)), (65, 49, 21, 100, dict(mode=2)),
+                                                (65, 49, 21, 20, dict(mode=4)), (65, 49, 21, 20, dict(nbct=3, nbcs=3)), (65, 49, 21, 20, dict(nbct=4)),
+                                                (66, 50, 21, 12, {}), (256, 192, 50, 10, {}), (67, 59, 21, 12, {}), (64, 48, 70, 3, {}), (128, 12, 21, 12, {})])
+def test_archipelago_is_stable_under_the_oracle(im, jm, kb, steps, nml):
+    """stability is a condition of the case, not of the code under test: every COMMON array and bdry finite, error_status = 0 and
+    vamax < 1 (vmaxl = 100) under the CPU oracle; after the three warm-up steps the normal velocity has both signs on each open edge"""
+    from oracle.pyoracle import OracleTile, oracle_finish_initial
+    st = make_case("archipelago", im, jm, kb, dte=6.0, isplit=30, **nml)
+    oracle_finish_initial(st)
+    ot = OracleTile(st)
+    ot.run(3)
+    wet_u, wet_v = st.dum != 0, st.dvm != 0
+    for f, m, edge in ((st.ua, wet_u, (slice(None), 1)), (st.ua, wet_u, (slice(None), -1)), (st.va, wet_v, (1, slice(None))), (st.va, wet_v, (-1, slice(None)))):
+        assert f[edge][m[edge]].min() < 0 < f[edge][m[edge]].max()
+    if int(st.mode) != 2:
+        for f, edge in ((st.u[0], (slice(None), 1)), (st.u[0], (slice(None), -1)), (st.v[0], (1, slice(None))), (st.v[0], (-1, slice(None)))):
+            assert f[edge].min() < 0 < f[edge].max()
+    ot.run(steps - 3)
+    assert all(np.isfinite(st.field(n)).all() for n in BLK2D + BLK3D) and np.isfinite(st.bdry).all()
+    assert int(st.error_status) == 0 and 0.0 < ot.vamax[0] < 1.0, ot.vamax
 
 
 def test_c_abi_library_exports_every_declared_symbol():

@@ -26,8 +26,14 @@ def emu_lib():
     subprocess.check_call([os.path.join(ROOT, "tests", "emu", "build_emu.sh")], stdout=subprocess.DEVNULL)
 
 
+def same_bits(x, y):
+    """bit for bit (uint64 view): unlike array_equal this sees the sign of a zero -- what `x * mask` leaves on a land cell -- and takes
+    equal NaN patterns for equal"""
+    return x.shape == y.shape and np.array_equal(np.ascontiguousarray(x).view(np.uint64), np.ascontiguousarray(y).view(np.uint64))
+
+
 def diff(a, b, skip=SCRATCH):
-    return [n for n in BLK2D + BLK3D if n not in skip and not np.array_equal(a.field(n), b.field(n))]
+    return [n for n in BLK2D + BLK3D if n not in skip and not same_bits(a.field(n), b.field(n))]
 
 
 @pytest.mark.parametrize("case,nml,steps", [
@@ -49,6 +55,31 @@ def test_steps_bit_identical(case, nml, steps):
         g.run(1)
         g.download()
         assert not diff(a, b), f"step {n}: {diff(a, b)}"
+        assert a.iint == b.iint == n
+    assert g.check_velocity() == ot.vamax
+
+
+# The fourth case (extpom_amd.cases: archipelago).  On seamount, island and basin dx depends on i only, dy on j only and cor on j only,
+# and there is no land away from the rim: the curvature terms of advct / advave / advu / advv are identically zero, dy(i-1,j) cannot be
+# told from dy(i,j) nor cor(i-1,j) from cor(i,j), and every mask factor of the interior is one (DESIGN.md section 3 has the mutants that
+# pass every test above and fail these).
+ARCHIPELAGO_NML = [dict(), dict(nadv=1), dict(nitera=2), dict(npg=2), dict(nbct=2), dict(mode=2), dict(mode=4), dict(nbct=3, nbcs=3), dict(nbct=4)]
+
+
+@pytest.mark.parametrize("im,jm,nml,steps", [(65, 49, n, 12 if not n else 4) for n in ARCHIPELAGO_NML] + [(66, 50, dict(), 4), (128, 12, dict(), 4),
+                                                                                                       (66, 50, dict(npg=2, nadv=1), 3)], ids=str)
+def test_steps_bit_identical_archipelago(im, jm, nml, steps):
+    """every namelist branch on the curved grid with interior land; 66 x 50 and 128 x 12: the two-columns-per-lane kernels"""
+    a = make_case("archipelago", im, jm, 21, dte=6.0, isplit=30, **nml)
+    oracle_finish_initial(a)
+    b = a.copy()
+    ot = OracleTile(a)
+    g = PomGpu(b, libpath=EMU)
+    for n in range(1, steps + 1):
+        ot.run(1)
+        g.run(1)
+        g.download()
+        assert not diff(a, b) and same_bits(a.bdry, b.bdry), f"step {n}: {diff(a, b)}"
         assert a.iint == b.iint == n
     assert g.check_velocity() == ot.vamax
 
@@ -130,7 +161,7 @@ def test_surface_and_lateral_forcing_across_record_changes():
         g.run(1)
         if n in (1, 2, 9, 10, 11, 20, 21, 29, 30, 31, 32):
             g.download()
-            assert not diff(a, b) and np.array_equal(a.bdry, b.bdry), f"step {n}: {diff(a, b)}"
+            assert not diff(a, b) and same_bits(a.bdry, b.bdry), f"step {n}: {diff(a, b)}"
 
 
 def test_output_and_restart_files_read_back(tmp_path):
@@ -214,8 +245,43 @@ FALLBACK_ENV = ("POMGPU_THOMAS_SCRATCH", "POMGPU_NO_PAIR", "POMGPU_EXT_SPLIT", "
                 "POMGPU_REALVERTVL_CELLS", "POMGPU_BAROPG_CELLS", "POMGPU_VERTVL_CELLS")
 
 
-@pytest.mark.parametrize("switches", [FALLBACK_ENV, ("POMGPU_ADVAVE_SEPARATE", "POMGPU_EXT_RIM_KERNEL"), ("POMGPU_PROFQ_ROWS8", "POMGPU_COL_STRIP", "POMGPU_EXT_MARCH"),
-                                      ("POMGPU_PROFQ_ROWS8", "POMGPU_COL_STRIP", "POMGPU_EXT_MARCH", "POMGPU_NO_LIN")])
+SWITCH_SETS = [FALLBACK_ENV, ("POMGPU_ADVAVE_SEPARATE", "POMGPU_EXT_RIM_KERNEL"), ("POMGPU_PROFQ_ROWS8", "POMGPU_COL_STRIP", "POMGPU_EXT_MARCH"),
+               ("POMGPU_PROFQ_ROWS8", "POMGPU_COL_STRIP", "POMGPU_EXT_MARCH", "POMGPU_NO_LIN")]
+
+
+@pytest.mark.parametrize("switches", SWITCH_SETS)
+def test_general_kernels_behind_the_fast_paths_archipelago(monkeypatch, switches):
+    """the same switch sets as below, on the case whose curvature terms and interior masks are live"""
+    for v in switches:
+        monkeypatch.setenv(v, "3" if v == "POMGPU_COL_STRIP" else "1")
+    im, jm = (200, 30) if "POMGPU_COL_STRIP" in switches else (65, 49)
+    a = make_case("archipelago", im, jm, 21, dte=6.0, isplit=30)
+    oracle_finish_initial(a)
+    b = a.copy()
+    ot = OracleTile(a)
+    g = PomGpu(b, libpath=EMU)
+    for n in range(1, 4):
+        ot.run(1)
+        g.run(1)
+        g.download()
+        assert not diff(a, b), f"step {n}: {diff(a, b)}"
+
+
+def test_kb_above_the_register_kernels_bound_archipelago():
+    """kb = 70: the column kernels with private work vectors on land columns next to water, short-wave radiation included"""
+    a = make_case("archipelago", 64, 48, 70, dte=6.0, isplit=30, nbct=2)
+    oracle_finish_initial(a)
+    b = a.copy()
+    ot = OracleTile(a)
+    g = PomGpu(b, libpath=EMU)
+    for n in range(1, 4):
+        ot.run(1)
+        g.run(1)
+        g.download()
+        assert not diff(a, b), f"step {n}: {diff(a, b)}"
+
+
+@pytest.mark.parametrize("switches", SWITCH_SETS)
 def test_general_kernels_behind_the_fast_paths(monkeypatch, switches):
     """the scratch-vector / one-column-per-lane / split kernels that serve kb > 64, odd im_local and
     multi-tile runs stay bit-identical too (selected here through the library's developer switches); second set:
@@ -271,11 +337,38 @@ def test_routine_bit_identical(name, fields, ints):
     assert not diff(a, b), f"{name}: {diff(a, b)}"
 
 
+ROUTINES_ARCHIPELAGO = ROUTINES + [("proft", ("uf", "wtsurf", "tsurf"), (2,)), ("proft", ("uf", "wtsurf", "tsurf"), (4,))]
+
+
+@pytest.mark.parametrize("name,fields,ints", ROUTINES_ARCHIPELAGO, ids=[f"{r[0]}{''.join(map(str, r[2]))}" for r in ROUTINES_ARCHIPELAGO])
+def test_routine_bit_identical_archipelago(name, fields, ints):
+    """each routine alone on the warm state of the fourth case: a difference names the routine"""
+    a = warm_state("archipelago")
+    b = a.copy()
+    ot = OracleTile(a)
+    ot.call(name, *[ot.a3(f) for f in fields], *[ctypes.c_int(i) for i in ints])
+    g = PomGpu(b, libpath=EMU)
+    g.call(name, *fields, *ints)
+    g.download()
+    assert not diff(a, b) and same_bits(a.bdry, b.bdry), f"{name}: {diff(a, b)}"
+
+
 def test_trimmed_tile_padding_is_inert():
     """a tile whose active extent is smaller than its leading dimensions (east/north-most tiles,
     parallel_mpi.f:83-87) gives the same active-region result as the tight layout"""
+    _trimmed_tile("basin")
+
+
+def test_trimmed_tile_padding_is_inert_archipelago():
+    """the same where the last owned column and row (and the corner cell) hold land next to the padding"""
+    _trimmed_tile("archipelago")
+
+
+def _trimmed_tile(case):
     from extpom_amd.layout import PomState
-    a = make_case("basin", 65, 49, 21, dte=6.0, isplit=30)
+    a = make_case(case, 65, 49, 21, dte=6.0, isplit=30)
+    if case == "archipelago":
+        assert (a.fsm[:, 64] == 0).any() and (a.fsm[48, :] == 0).any() and (a.fsm[:, 63] == 0).any() and (a.fsm[47, :] == 0).any()
     oracle_finish_initial(a)
     b = PomState(72, 53, 21, im=65, jm=49)
     b.blk1d[...] = a.blk1d
@@ -301,7 +394,7 @@ def test_trimmed_tile_padding_is_inert():
     gb.download()
     for n in BLK2D:
         if n not in SCRATCH:
-            assert np.array_equal(a.field(n), b.field(n)[:49, :65]), n
+            assert same_bits(a.field(n), b.field(n)[:49, :65]), n
     for n in BLK3D:
         if n not in SCRATCH:
-            assert np.array_equal(a.field(n), b.field(n)[:, :49, :65]), n
+            assert same_bits(a.field(n), b.field(n)[:, :49, :65]), n

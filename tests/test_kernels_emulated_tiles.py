@@ -45,6 +45,11 @@ def side_stream_timing(request, monkeypatch):
         monkeypatch.delenv("POMGPU_EMU_DEFER_SIDE", raising=False)
 
 
+def same_bits(x, y):
+    """bit for bit (uint64 view): unlike array_equal this sees the sign of a zero, what `x * mask` leaves on a land cell"""
+    return x.shape == y.shape and np.array_equal(np.ascontiguousarray(x).view(np.uint64), np.ascontiguousarray(y).view(np.uint64))
+
+
 class Board:
     """what the ranks of one run share: a mailbox per (sender, receiver) and a barrier"""
 
@@ -260,6 +265,15 @@ def test_tiles_match_single_tile_oracle(nx, ny, nml, single_round):
     compare_with_single_tile(out, nml)
 
 
+@pytest.mark.parametrize("nx,ny,nml,single_round", [(2, 1, {}, False), (1, 2, {}, False), (2, 2, {}, False), (3, 2, dict(npg=2), False), (1, 3, dict(nadv=1), False),
+                                                    (2, 1, {}, True), (1, 2, {}, True), (2, 2, {}, True), (3, 2, dict(npg=2), True), (1, 3, dict(nadv=1), True)])
+def test_tiles_match_single_tile_oracle_archipelago(nx, ny, nml, single_round):
+    """the per-point hooks (two phases and one round) on the case with land on the seams, in the ghost lines and on the open edges,
+    a curved grid and flow of both signs through every open edge (tests/test_host_logic.py asserts that of each split used here)"""
+    out = run_tiles(nx, ny, nml, single_round, case="archipelago")
+    compare_with_single_tile(out, nml, case="archipelago")
+
+
 def compare_with_single_tile(out, nml, grid=None, isplit=10, case="island", steps=None, min_rounds=20, ghosts=False):
     IMg, JMg = grid or (IM, JM)
     g = make_case(case, IMg, JMg, KB, dte=6.0, isplit=isplit, **nml)
@@ -278,7 +292,7 @@ def compare_with_single_tile(out, nml, grid=None, isplit=10, case="island", step
                 continue
             ref = g.field(n)[..., jo:jo + jm, io:io + im][..., sl_j, sl_i]
             got = st.field(n)[..., :jm, :im][..., sl_j, sl_i]
-            if not np.array_equal(ref, got):
+            if not same_bits(ref, got):
                 bad.append((r, n))
     assert not bad, bad
     return {r: v[2] for r, v in out.items()}
@@ -291,11 +305,18 @@ def test_library_transport_serves_every_exchange_point(nx, ny, nml):
     compare_with_single_tile(out, nml)
 
 
+@pytest.mark.parametrize("nx,ny,nml", [(2, 1, {}), (1, 2, dict(nadv=1)), (2, 2, {}), (3, 2, dict(npg=2)), (1, 3, {})])
+def test_library_transport_serves_every_exchange_point_archipelago(nx, ny, nml):
+    out = run_tiles(nx, ny, nml, library_exchange=True, case="archipelago")
+    compare_with_single_tile(out, nml, case="archipelago")
+
+
 WIDE_GRID, WIDE_ISPLIT = (67, 59), 7        # w = 7 + 4 = 11 extra cells; 2x2 tiles of ~35 x 31
 
 
 @pytest.mark.parametrize("nx,ny,case,nml", [(2, 2, "island", {}), (2, 1, "seamount", {}), (1, 2, "seamount", dict(npg=2)), (3, 2, "island", dict(nadv=1)),
-                                            (1, 3, "seamount", {})])
+                                            (1, 3, "seamount", {}), (2, 2, "archipelago", {}), (2, 1, "archipelago", {}), (1, 2, "archipelago", dict(npg=2)),
+                                            (3, 2, "archipelago", dict(nadv=1)), (1, 3, "archipelago", {})])
 def test_wide_halo_external_mode(nx, ny, case, nml):
     """pomgpu_set_wide_external: ONE wide exchange per internal step instead of six narrow ones per external substep;
     owned cells equal the single-tile oracle bit for bit, with a fraction of the message rounds.  (1 x 3: whole-row tiles, the
@@ -315,11 +336,12 @@ def test_wide_halo_external_mode(nx, ny, case, nml):
     for r in wide:
         for n in ("ua", "va", "el", "elb", "d", "uab", "vab", "etf", "egf", "utf", "vtf", "adx2d", "ady2d", "advua", "advva", "elf", "uaf", "vaf"):
             t = wide[r][0]
-            assert np.array_equal(wide[r][1].field(n)[:t.jm, :t.im], narrow[r][1].field(n)[:t.jm, :t.im]), (r, n)
+            assert same_bits(wide[r][1].field(n)[:t.jm, :t.im], narrow[r][1].field(n)[:t.jm, :t.im]), (r, n)
 
 
 @pytest.mark.parametrize("nx,ny,grid,case,nml", [(2, 4, (43, 75), "island", {}), (2, 4, (43, 75), "seamount", dict(npg=2)), (3, 3, (59, 53), "seamount", {}),
-                                                 (3, 3, (59, 53), "island", dict(nadv=1))])
+                                                 (3, 3, (59, 53), "island", dict(nadv=1)), (2, 4, (43, 75), "archipelago", {}),
+                                                 (3, 3, (59, 53), "archipelago", dict(npg=2))])
 def test_baselines_own_2x4_split_and_a_tile_with_eight_neighbours(nx, ny, grid, case, nml):
     """BASELINE configs[2] / [3] name a 2 x 4 tile decomposition: (43, 75) splits into tiles of 23 x 21 whose north row is TRIMMED
     (jm = 18 of jm_local = 21, parallel_mpi.f:96-103) and every tile has a diagonal neighbour; 3 x 3 has a centre tile with all EIGHT
@@ -342,7 +364,7 @@ def test_baselines_own_2x4_split_and_a_tile_with_eight_neighbours(nx, ny, grid, 
     for r in lib:
         t = lib[r][0]
         for n in BLK2D + BLK3D:
-            if n not in SCRATCH and not np.array_equal(lib[r][1].field(n)[..., :t.jm, :t.im], wide[r][1].field(n)[..., :t.jm, :t.im]):
+            if n not in SCRATCH and not same_bits(lib[r][1].field(n)[..., :t.jm, :t.im], wide[r][1].field(n)[..., :t.jm, :t.im]):
                 bad.append((r, n))
     assert not bad, bad[:10]
 
@@ -404,7 +426,7 @@ def test_rim_rounds_can_be_kept_on_the_kernels_stream(switch, per_full_step, fir
     for r in a:
         t = a[r][0]
         for n in BLK2D + BLK3D:
-            if n not in SCRATCH and not np.array_equal(a[r][1].field(n)[..., :t.jm, :t.im], b[r][1].field(n)[..., :t.jm, :t.im]):
+            if n not in SCRATCH and not same_bits(a[r][1].field(n)[..., :t.jm, :t.im], b[r][1].field(n)[..., :t.jm, :t.im]):
                 bad.append((r, n))
     assert not bad, bad[:10]
     for r in a:                                                        # the total number of rounds does not change
@@ -420,7 +442,7 @@ def test_wide_halo_too_narrow_shows_up(monkeypatch):
         compare_with_single_tile(out, {}, grid=WIDE_GRID, isplit=WIDE_ISPLIT, min_rounds=2)
 
 
-@pytest.mark.parametrize("nx,ny,case,nml", [(3, 2, "seamount", {}), (2, 2, "island", dict(npg=2))])
+@pytest.mark.parametrize("nx,ny,case,nml", [(3, 2, "seamount", {}), (2, 2, "island", dict(npg=2)), (3, 2, "archipelago", {}), (2, 2, "archipelago", dict(npg=2))])
 def test_library_paths_leave_the_same_ghost_cells_as_the_reference_exchanges(nx, ny, case, nml):
     """The tile shortcuts of the library's own exchange (advct through edge lines, advq without its redundant flux
     exchange, profq's production term exchanged on the rim lines only, merged rounds, wide-halo external mode) against
@@ -436,7 +458,7 @@ def test_library_paths_leave_the_same_ghost_cells_as_the_reference_exchanges(nx,
             for n in BLK2D + BLK3D:
                 if n in SCRATCH:
                     continue
-                if not np.array_equal(hooks[r][1].field(n)[..., :t.jm, :t.im], lib[r][1].field(n)[..., :t.jm, :t.im]):
+                if not same_bits(hooks[r][1].field(n)[..., :t.jm, :t.im], lib[r][1].field(n)[..., :t.jm, :t.im]):
                     bad.append((r, n))
         assert not bad, (wide, bad[:10])
 
@@ -472,7 +494,7 @@ def test_wide_halo_mode_with_file_forcing_records():
         for n in BLK2D + BLK3D:
             if n in SCRATCH:
                 continue
-            if not np.array_equal(g.field(n)[..., jo:jo + jm, io:io + im][..., sl_j, sl_i], st.field(n)[..., :jm, :im][..., sl_j, sl_i]):
+            if not same_bits(g.field(n)[..., jo:jo + jm, io:io + im][..., sl_j, sl_i], st.field(n)[..., :jm, :im][..., sl_j, sl_i]):
                 bad.append((r, n))
     assert not bad, bad[:12]
 

@@ -1,7 +1,9 @@
 """The CPU oracle against the reference itself.  ALL COMMON-block arrays -- not only the restart list -- and bdry and blkcon
 must be bit-identical after every step, and so must each hot-path routine called on its own.  The reference's side is stored
 in tests/golden/oracle_vs_reference_65x49x21.json: per array a digest of the state of the reference build (oracle/_ref, the
-unmodified sources, oracle/build_ref.sh) on the same inputs, written by `tests/golden/make_golden.py refcheck`."""
+unmodified sources, oracle/build_ref.sh) on the same inputs, written by `tests/golden/make_golden.py refcheck`.
+oracle_vs_reference_archipelago_65x49x21.json (`make_golden.py archipelago`) holds the same for the fourth case, the only one on
+which the oracle's curvature terms, its cross-direction metric neighbours, cor(i-1,j) and its interior masks are not trivial."""
 import ctypes
 import json
 import os
@@ -15,6 +17,13 @@ from oracle.pyoracle import OracleTile, oracle_finish_initial
 from oracle.refharness import state_digests
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vs_reference_65x49x21.json")
+GOLDEN_ARCHIPELAGO = os.path.join(os.path.dirname(GOLDEN), "oracle_vs_reference_archipelago_65x49x21.json")
+
+
+@pytest.fixture(scope="module")
+def ref_archipelago():
+    with open(GOLDEN_ARCHIPELAGO) as f:
+        return json.load(f)
 
 
 @pytest.fixture(scope="module")
@@ -45,6 +54,16 @@ def _steps(rec):
                                       ("basin", dict(dte=6.0, isplit=10, nitera=2)),
                                       ("island", dict(dte=6.0, isplit=30, npg=2))])
 def test_full_state_bit_identical(ref, case, nml):
+    _full_state(ref, case, nml)
+
+
+@pytest.mark.parametrize("nml", [dict(), dict(nadv=1), dict(nitera=2), dict(npg=2), dict(mode=2)], ids=str)
+def test_full_state_bit_identical_archipelago(ref_archipelago, nml):
+    """12 steps of the fourth case: curved grid, interior land, both signs on the open edges, every forcing field live"""
+    _full_state(ref_archipelago, "archipelago", dict(dte=6.0, isplit=30, **nml))
+
+
+def _full_state(ref, case, nml):
     rec = ref["full_state"][json.dumps([case, nml], sort_keys=True)]
     b = make_case(case, 65, 49, 21, **nml)
     oracle_finish_initial(b)
@@ -59,7 +78,16 @@ def test_full_state_bit_identical(ref, case, nml):
 
 def test_each_routine_bit_identical(ref):
     """call the routines one by one on a warm state (step 3: all branches live)"""
-    a = make_case("seamount", 65, 49, 21, dte=6.0, isplit=30)
+    _each_routine(ref, "seamount")
+
+
+def test_each_routine_bit_identical_archipelago(ref_archipelago):
+    """the same on the warm state of the fourth case (proft with nbc 1-4 on a non-zero swrad and wssurf)"""
+    _each_routine(ref_archipelago, "archipelago")
+
+
+def _each_routine(ref, case):
+    a = make_case(case, 65, 49, 21, dte=6.0, isplit=30)
     oracle_finish_initial(a)
     OracleTile(a).run(3)
     a.iint = 4
