@@ -1,5 +1,6 @@
-// cdf_out.hip -- the output and restart files of the reference WITHOUT PnetCDF (host code; nothing here runs
-// on the GPU except the device-to-host copies).  io_pnetcdf.F writes NetCDF "64-bit offset" files
+// cdf_out.hip -- the library's file I/O unit: the output and restart files of the reference WITHOUT PnetCDF, written and (the
+// restart file) read back.  Writing is host code plus device-to-host copies; reading has the one kernel of this file, k_cdf_unpack.
+// io_pnetcdf.F writes NetCDF "64-bit offset" files
 // (nf_64bit_offset = CDF-2) through the parallel library: write_output_pnetcdf (:57-410) and
 // write_restart_pnetcdf (:1661-2083).  The classic format is simple enough to emit directly: a header (dimensions,
 // global attributes, variables with their attributes and byte offsets) followed by every variable's values as
@@ -10,7 +11,10 @@
 // it (create = 1), the others open it afterwards (create = 0; the caller orders the two with a barrier).
 // One deliberate difference: the reference passes length 26 for the 10-character text of vtot's
 // formula_terms attribute (:133-135, reading past the literal); here the attribute is the 10 characters.
+// pomgpu_read_restart (the end of this file) is read_restart_pnetcdf (:2420-2768): a parser of the classic header that finds
+// the variables by name, raw big-endian bytes through pinned buffers to the device, byte reversal and scatter in a kernel.
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <cstdint>
@@ -343,4 +347,276 @@ extern "C" int pomgpu_write_restart(pomgpu_ctx *c, const char *path, const pomgp
       {"q2lb", "q2 x l at time -dt", "metre^3/sec^2", "east_e north_e zz", P3_q2lb}};
   for (auto &q : p3) S.vars.push_back(mk(q.n, {Z, Y, X}, q.ln, q.u, q.co, VOLUME3D, q.slot, P.kb));
   return write_file(c, path, m, S);
+}
+
+// ---- reading the restart file back (read_restart_pnetcdf, io_pnetcdf.F:2420-2768) -----------------------------------------------
+// The header is parsed as it stands in the file (CDF-1 or CDF-2; dimension list, attributes skipped, every variable's type,
+// dimension ids and `begin`), because a file written by PnetCDF itself aligns its data section differently from the writer
+// above and may hold its variables in another order.  Everything is checked before the first mirror is written.
+namespace {
+struct RVar { std::string name; std::vector<uint32_t> dimids; uint32_t type = 0; uint64_t begin = 0; };
+struct RHeader { std::vector<uint64_t> dimlen; std::vector<RVar> vars; };
+struct Cur {                                                    // big-endian cursor over the bytes read so far
+  const unsigned char *p; size_t n, at = 0; bool shortfall = false;
+  bool need(size_t k) { if (at + k > n) { shortfall = true; return false; } return true; }
+  uint32_t u32() { if (!need(4)) return 0; uint32_t v = 0; for (int q = 0; q < 4; q++) v = (v << 8) | p[at + q]; at += 4; return v; }
+  uint64_t u64() { if (!need(8)) return 0; uint64_t v = 0; for (int q = 0; q < 8; q++) v = (v << 8) | p[at + q]; at += 8; return v; }
+  void skip(uint64_t k) { k = (k + 3) & ~(uint64_t)3; if (need(k)) at += k; }
+  std::string name() { const uint32_t len = u32(); std::string s; if (need(((size_t)len + 3) & ~(size_t)3)) { s.assign((const char *)p + at, len); at += ((size_t)len + 3) & ~(size_t)3; } return s; }
+};
+const unsigned NC_TYPE_BYTES[7] = {0, 1, 1, 2, 4, 4, 8};      // byte, char, short, int, float, double
+// 0 = parsed, 1 = more bytes needed, -1 = not a classic header (why: `what`)
+int parse_atts(Cur &c, std::string &what) {
+  const uint32_t tag = c.u32(), cnt = c.u32();
+  if (c.shortfall) return 1;
+  if (tag == 0 && cnt == 0) return 0;
+  if (tag != 0x0C) { what = "attribute list expected"; return -1; }
+  for (uint32_t a = 0; a < cnt; a++) {
+    (void)c.name();
+    const uint32_t type = c.u32(), nel = c.u32();
+    if (c.shortfall) return 1;
+    if (type < 1 || type > 6) { what = "unknown attribute type"; return -1; }
+    c.skip((uint64_t)nel * NC_TYPE_BYTES[type]);
+    if (c.shortfall) return 1;
+  }
+  return 0;
+}
+int parse_header(const unsigned char *buf, size_t n, RHeader &H, std::string &what) {
+  Cur c{buf, n};
+  if (n < 4) return 1;
+  if (memcmp(buf, "CDF", 3) != 0 || (buf[3] != 1 && buf[3] != 2)) {
+    what = buf[0] == 'C' && buf[1] == 'D' && buf[2] == 'F' ? "CDF version " + std::to_string((int)buf[3]) + " (only the classic formats CDF-1 and CDF-2 are read)"
+           : (n >= 4 && memcmp(buf, "\x89HDF", 4) == 0 ? std::string("an HDF5 / NetCDF-4 file (only the classic formats CDF-1 and CDF-2 are read)") : std::string("no NetCDF magic"));
+    return -1;
+  }
+  const bool wide = buf[3] == 2;
+  c.at = 4;
+  (void)c.u32();                                                // numrecs
+  uint32_t tag = c.u32(), cnt = c.u32();
+  if (c.shortfall) return 1;
+  H.dimlen.clear(); H.vars.clear();
+  if (!(tag == 0 && cnt == 0)) {
+    if (tag != 0x0A) { what = "dimension list expected"; return -1; }
+    for (uint32_t d = 0; d < cnt; d++) { (void)c.name(); H.dimlen.push_back(c.u32()); if (c.shortfall) return 1; }
+  }
+  int rc = parse_atts(c, what);
+  if (rc) return rc;
+  tag = c.u32(); cnt = c.u32();
+  if (c.shortfall) return 1;
+  if (tag == 0 && cnt == 0) return 0;
+  if (tag != 0x0B) { what = "variable list expected"; return -1; }
+  for (uint32_t v = 0; v < cnt; v++) {
+    RVar r;
+    r.name = c.name();
+    const uint32_t nd = c.u32();
+    if (c.shortfall) return 1;
+    if (nd > 1024) { what = "variable with more than 1024 dimensions"; return -1; }
+    for (uint32_t d = 0; d < nd; d++) r.dimids.push_back(c.u32());
+    if (c.shortfall) return 1;
+    rc = parse_atts(c, what);
+    if (rc) return rc;
+    r.type = c.u32();
+    (void)c.u32();                                              // vsize: recomputed from the dimensions (it saturates at 4 GiB)
+    r.begin = wide ? c.u64() : (uint64_t)c.u32();
+    if (c.shortfall) return 1;
+    for (uint32_t id : r.dimids) if (id >= H.dimlen.size()) { what = "variable " + r.name + " names a dimension the file does not define"; return -1; }
+    H.vars.push_back(r);
+  }
+  return 0;
+}
+std::string lengths_of(const RHeader &H, const RVar &v) {
+  std::string s = "(";
+  for (size_t d = 0; d < v.dimids.size(); d++) { if (d) s += ", "; const uint64_t len = H.dimlen[v.dimids[d]]; s += len ? std::to_string(len) : std::string("unlimited"); }
+  return s + ")";
+}
+struct RItem { const RVar *v; int slot; int nlev; };            // nlev = kb: blk3d slot; 1: blk2d slot
+}  // namespace
+
+// One lane, one value: threadIdx.x runs along i, so a wavefront loads a contiguous piece of a file row (raw big-endian bytes in
+// `src`, `rows` rows per level, src_pitch values per row, the tile's first column at src_i0) and stores a contiguous piece of
+// the mirror's row.  T = pomgpu_st for the arrays of blk3d (the rounding k_cvt_to_st applies on upload), double for blk2d.
+template <class T>
+__global__ void k_cdf_unpack(T *dst, const unsigned long long *src, int im, int jm, int iml, size_t n2, int rows, int src_pitch, int src_i0) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x), j = (int)(blockIdx.y * blockDim.y + threadIdx.y), k = (int)blockIdx.z;
+  if (i >= im || j >= jm) return;
+  const unsigned long long u = __builtin_bswap64(src[((size_t)k * rows + j) * (size_t)src_pitch + (size_t)(src_i0 + i)]);
+  double x;
+  __builtin_memcpy(&x, &u, 8);
+  dst[(size_t)k * n2 + (size_t)j * iml + i] = (T)x;
+}
+// d = h + el, dt = h + et over the active cells (io_pnetcdf.F:2757-2762)
+__global__ void k_restart_depths(KP P) {
+  const int i = TID_I, j = TID_J;
+  if (i > P.im || j > P.jm) return;
+  F2(d, i, j) = F2(h, i, j) + F2(el, i, j);
+  F2(dt, i, j) = F2(h, i, j) + F2(et, i, j);
+}
+
+static int pread_all(int fd, void *buf, size_t n, uint64_t off) {
+  char *p = (char *)buf;
+  while (n) { const ssize_t r = pread(fd, p, n, (off_t)off); if (r <= 0) return -1; p += r; off += (uint64_t)r; n -= (size_t)r; }
+  return 0;
+}
+
+extern "C" int pomgpu_read_restart(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m, double *time0_out, double *iint_out) {
+  if (!c || !path || !m) return POMGPU_EINVAL;
+  (void)hipSetDevice(c->device);
+  { const int rcw = pomgpu_io_wait(c); if (rcw) return rcw; }  // the file may be the one this context is still writing
+  const KP &P = c->P;
+  if (m->i0 < 1 || m->j0 < 1 || m->i0 + P.im - 1 > m->im_global || m->j0 + P.jm - 1 > m->jm_global)
+    return fail(c, POMGPU_EINVAL, "read_restart: %s: the tile (%d..%d, %d..%d) does not fit the global grid %d x %d", path, m->i0, m->i0 + P.im - 1,
+                m->j0, m->j0 + P.jm - 1, m->im_global, m->jm_global);
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return fail(c, POMGPU_EINVAL, "read_restart: cannot open %s", path);
+  struct stat sb;
+  if (fstat(fd, &sb)) { (void)close(fd); return fail(c, POMGPU_EINVAL, "read_restart: cannot stat %s", path); }
+  const uint64_t fsize = (uint64_t)sb.st_size;
+  // ---- the header, whole, before anything is written ----
+  RHeader H;
+  {
+    std::vector<unsigned char> hb;
+    std::string what;
+    int rc = 1;
+    for (size_t want = 1 << 16; rc == 1; want *= 4) {
+      const size_t n = (size_t)(want < fsize ? want : fsize);
+      hb.resize(n);
+      if (n && pread_all(fd, hb.data(), n, 0)) { (void)close(fd); return fail(c, POMGPU_EINVAL, "read_restart: I/O error on %s (header)", path); }
+      rc = parse_header(hb.data(), n, H, what);
+      if (rc == 1 && n == fsize) { what = fsize ? "the file ends inside its header" : "the file is empty"; rc = -1; }
+    }
+    if (rc < 0) { (void)close(fd); return fail(c, POMGPU_EINVAL, "read_restart: %s is not a restart file this library reads: %s", path, what.c_str()); }
+  }
+  auto find = [&](const char *name) -> const RVar * { for (const RVar &v : H.vars) if (v.name == name) return &v; return NULL; };
+  auto refuse = [&](const std::string &why) { (void)close(fd); return fail(c, POMGPU_EINVAL, "read_restart: %s: %s", path, why.c_str()); };
+  // a variable of `want` = (d0, d1, ...) doubles, not a record variable, inside the file
+  auto check = [&](const char *name, const std::vector<uint64_t> &want, bool one_value, const RVar **out) -> std::string {
+    const RVar *v = find(name);
+    if (!v) return std::string("variable ") + name + " is absent";
+    if (v->type != 6) return std::string("variable ") + name + " has NetCDF type " + std::to_string(v->type) + ", not NC_DOUBLE (6)";
+    uint64_t count = 1;
+    bool same = v->dimids.size() == want.size();
+    for (size_t d = 0; d < v->dimids.size(); d++) {
+      const uint64_t len = H.dimlen[v->dimids[d]];
+      if (len == 0) return std::string("variable ") + name + " is a record variable (unlimited dimension)";
+      if (__builtin_mul_overflow(count, len, &count)) count = UINT64_MAX / 8;   // a hostile header: saturate, the checks below refuse it
+      if (same && len != want[d]) same = false;
+    }
+    if (one_value ? count != 1 : !same) {
+      std::string w = "(";
+      for (size_t d = 0; d < want.size(); d++) w += (d ? ", " : "") + std::to_string(want[d]);
+      return std::string("variable ") + name + " has the dimension lengths " + lengths_of(H, *v) + ", wanted " + (one_value ? std::string("one value") : w + ")");
+    }
+    if (v->begin > fsize || count * 8 > fsize - v->begin)
+      return std::string("variable ") + name + " (" + std::to_string(count * 8) + " bytes at " + std::to_string(v->begin) + ") reaches beyond the file's " + std::to_string(fsize) + " bytes";
+    *out = v;
+    return std::string();
+  };
+  static const struct { const char *n; int slot; } r2[] = {
+      {"wubot", P2_wubot}, {"wvbot", P2_wvbot}, {"aam2d", P2_aam2d}, {"ua", P2_ua}, {"uab", P2_uab}, {"va", P2_va}, {"vab", P2_vab}, {"el", P2_el},
+      {"elb", P2_elb}, {"et", P2_et}, {"etb", P2_etb}, {"egb", P2_egb}, {"utb", P2_utb}, {"vtb", P2_vtb}, {"adx2d", P2_adx2d}, {"ady2d", P2_ady2d},
+      {"advua", P2_advua}, {"advva", P2_advva}};
+  static const struct { const char *n; int slot; } r3[] = {
+      {"u", P3_u}, {"ub", P3_ub}, {"v", P3_v}, {"vb", P3_vb}, {"w", P3_w}, {"t", P3_t}, {"tb", P3_tb}, {"s", P3_s}, {"sb", P3_sb}, {"rho", P3_rho},
+      {"km", P3_km}, {"kh", P3_kh}, {"kq", P3_kq}, {"l", P3_l}, {"q2", P3_q2}, {"q2b", P3_q2b}, {"aam", P3_aam}, {"q2l", P3_q2l}, {"q2lb", P3_q2lb}};
+  const uint64_t img = (uint64_t)m->im_global, jmg = (uint64_t)m->jm_global;
+  const RVar *v_iint = NULL, *v_time = NULL;
+  std::vector<RItem> items;
+  {
+    std::string why = check("iint", {}, true, &v_iint);
+    if (why.empty()) why = check("time", {}, true, &v_time);
+    for (auto &q : r2) { if (!why.empty()) break; const RVar *v = NULL; why = check(q.n, {jmg, img}, false, &v); items.push_back({v, q.slot, 1}); }
+    for (auto &q : r3) { if (!why.empty()) break; const RVar *v = NULL; why = check(q.n, {(uint64_t)P.kb, jmg, img}, false, &v); items.push_back({v, q.slot, P.kb}); }
+    if (!why.empty()) return refuse(why);
+  }
+  // ---- from here on the state changes ----
+  { const int rcm = pomgpu_materialize(c); if (rcm) { (void)close(fd); return rcm; } }
+  int bad = 0;
+  double sc[2] = {0., 0.};                                       // iint, time
+  for (int q = 0; q < 2 && !bad; q++) {
+    uint64_t u;
+    if (pread_all(fd, &u, 8, (q ? v_time : v_iint)->begin)) { bad = 1; break; }
+    u = __builtin_bswap64(u);
+    memcpy(&sc[q], &u, 8);
+  }
+  // runs: whole levels of the band of rows j0 .. j0+jm-1 at the file's full width, as many as a buffer holds
+  const size_t band = (size_t)P.jm * (size_t)img;               // values of one level's band
+  size_t cap = (SW(c, IO_CHUNK_KB) && SWV(c, IO_CHUNK_KB) > 0 ? (size_t)SWV(c, IO_CHUNK_KB) << 10 : (size_t)64 << 20) / 8;   // values per buffer
+  if (cap < band) cap = band;
+  if (cap > band * (size_t)P.kb) cap = band * (size_t)P.kb;
+  const int lev_per_run = (int)(cap / band);
+  const bool whole_rows = (uint64_t)P.jm == jmg;                // the bands of consecutive levels touch: one pread per run
+  // the pinned buffers, the staging buffer, the stream and the events live for this call only: the reader is initialisation, called once
+  // per run, and their creation is a few milliseconds of the time the call takes
+  unsigned long long *pin[2] = {NULL, NULL}, *stage = NULL;
+#ifdef POMGPU_EMU
+  // host emulation: a plain loop, one buffer, the same kernel through the emulated launch
+  if (!bad && hipMalloc((void **)&pin[0], cap * 8) != hipSuccess) bad = 1;
+  stage = pin[0];
+  hipStream_t rs = c->stream;
+#else
+  hipStream_t rs = NULL;
+  hipEvent_t ev[2] = {NULL, NULL};                              // the copy out of pin[b] has completed
+  if (!bad && (hipHostMalloc((void **)&pin[0], cap * 8, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void **)&pin[1], cap * 8, hipHostMallocDefault) != hipSuccess ||
+               hipMalloc((void **)&stage, cap * 8) != hipSuccess || hipStreamCreateWithFlags(&rs, hipStreamNonBlocking) != hipSuccess ||
+               hipEventCreateWithFlags(&ev[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ev[1], hipEventDisableTiming) != hipSuccess ||
+               hipStreamSynchronize(c->stream) != hipSuccess))  // what pomgpu_materialize enqueued precedes the first store below
+    bad = 2;
+  int used[2] = {0, 0};
+#endif
+  const hipStream_t cur0 = c->cur;
+  c->cur = rs;                                                   // LAUNCH goes to the copy stream: each kernel behind the copy that feeds it
+  int b = 0;
+  for (const RItem &it : items) {
+    for (int k0 = 0; k0 < it.nlev && !bad; k0 += lev_per_run) {
+      const int nl = it.nlev - k0 < lev_per_run ? it.nlev - k0 : lev_per_run;
+#ifndef POMGPU_EMU
+      if (used[b] && hipEventSynchronize(ev[b]) != hipSuccess) { bad = 2; break; }   // the buffer's last run has left it
+#endif
+      const uint64_t first = it.v->begin + (((uint64_t)k0 * jmg + (uint64_t)(m->j0 - 1)) * img) * 8;
+      if (whole_rows) { if (pread_all(fd, pin[b], (size_t)nl * band * 8, first)) bad = 1; }
+      else for (int k = 0; k < nl && !bad; k++) if (pread_all(fd, pin[b] + (size_t)k * band, band * 8, first + (uint64_t)k * jmg * img * 8)) bad = 1;
+      if (bad) break;
+#ifndef POMGPU_EMU
+      if (hipMemcpyAsync(stage, pin[b], (size_t)nl * band * 8, hipMemcpyHostToDevice, rs) != hipSuccess || hipEventRecord(ev[b], rs) != hipSuccess) { bad = 2; break; }
+      used[b] = 1;
+#endif
+      const dim3 grid((unsigned)((P.im + 63) / 64), (unsigned)((P.jm + 3) / 4), (unsigned)nl);
+      if (it.nlev == 1)
+        LAUNCHN(c, "k_cdf_unpack", k_cdf_unpack<double>, grid, blk2(), P.b2 + (size_t)it.slot * P.n2, (const unsigned long long *)stage, P.im, P.jm, P.iml, P.n2, P.jm, (int)img, m->i0 - 1);
+      else
+        LAUNCHN(c, "k_cdf_unpack", k_cdf_unpack<pomgpu_st>, grid, blk2(), (pomgpu_st *)(P.b3 + (size_t)it.slot * P.a3) + (size_t)k0 * P.n2, (const unsigned long long *)stage, P.im, P.jm,
+                P.iml, P.n2, P.jm, (int)img, m->i0 - 1);
+#ifndef POMGPU_EMU
+      b ^= 1;
+#endif
+    }
+    if (bad) break;
+  }
+  if (!bad) LAUNCH(c, k_restart_depths, grid2(P), blk2(), P);
+  c->cur = cur0;
+  if (hipStreamSynchronize(rs) != hipSuccess && !bad) bad = 2;
+#ifndef POMGPU_EMU
+  if (ev[0]) (void)hipEventDestroy(ev[0]);
+  if (ev[1]) (void)hipEventDestroy(ev[1]);
+  if (rs) (void)hipStreamDestroy(rs);
+  if (pin[0]) (void)hipHostFree(pin[0]);
+  if (pin[1]) (void)hipHostFree(pin[1]);
+  if (stage) (void)hipFree(stage);
+#else
+  (void)hipFree(pin[0]);
+#endif
+  (void)close(fd);
+  if (bad || c->launch_err) {
+    if (bad == 2) (void)hipGetLastError();
+    return fail(c, bad == 1 ? POMGPU_EINVAL : POMGPU_EHIP, bad == 1 ? "read_restart: I/O error on %s (the state is unspecified)" : "read_restart: a HIP call failed while reading %s (the state is unspecified)", path);
+  }
+  pomgpu_mirrors_written(c);
+  pom_blkcon con = c->con;
+  con.time0 = con.time = sc[1];
+  if (con.cont_bry != 0) con.cont_bry = (int)sc[0];
+  (void)pomgpu_set_con(c, &con, c->lramp);
+  if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, POMGPU_EHIP, "read_restart: %s: synchronise failed", path);
+  if (time0_out) *time0_out = sc[1];
+  if (iint_out) *iint_out = sc[0];
+  return POMGPU_OK;
 }

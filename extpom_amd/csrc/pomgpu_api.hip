@@ -948,6 +948,13 @@ int pomgpu_materialize(pomgpu_ctx *c) {
   NEED(c);
   return POMGPU_OK;
 }
+// pomgpu_read_restart (cdf_out.hip) has written 2-D and 3-D mirrors with its own kernel: what pomgpu_upload_2d invalidates for
+// those slots (none of them is a mask or a taurstr array; upload_3d invalidates nothing else)
+void pomgpu_mirrors_written(pomgpu_ctx *c) {
+  c->wide.static_done = 0;
+  early_invalidate(c);
+  refresh_coefs(c);
+}
 extern "C" int pomgpu_get_time(pomgpu_ctx *c) {               // advance.f:62-75
   NEED_HOT(c);
   pom_blkcon &k = c->con;

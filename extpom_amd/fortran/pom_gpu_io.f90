@@ -1,8 +1,9 @@
-! pom_gpu_io.f90 -- write_output_pnetcdf and write_restart_pnetcdf (reference pom/io_pnetcdf.F:57-410, :1661-2083)
-! without PnetCDF: the file names are built as the reference builds them, the files themselves (CDF-2, same
+! pom_gpu_io.f90 -- write_output_pnetcdf, write_restart_pnetcdf and read_restart_pnetcdf (reference pom/io_pnetcdf.F:57-410,
+! :1661-2083, :2420-2768) without PnetCDF: the file names are built as the reference builds them, the files themselves (CDF-2, same
 ! dimensions / variables / attributes) are written by the library straight from the device state
 ! (pomgpu_write_output / pomgpu_write_restart); every rank writes its patch, rank 0 creates the file first.
-! Link instead of the reference's two writers.  pomgpu_barrier_mpi is the integrator's one-liner
+! read_restart_pnetcdf reads such a file (or one PnetCDF wrote) back into the device state and the COMMON blocks.
+! Link instead of the reference's two writers and its restart reader.  pomgpu_barrier_mpi is the integrator's one-liner
 ! (call mpi_barrier(pom_comm, ierr); nothing on a single rank): this file does not include mpif.h.
 subroutine write_output_pnetcdf
   use pomgpu_iface
@@ -70,4 +71,46 @@ subroutine pomgpu_write_file(fname, restart)
     if (pomgpu_io_wait(pom_ctx) /= 0) error_status = 1
     call pomgpu_barrier_mpi
   end if
+end subroutine
+
+! read_restart_pnetcdf (io_pnetcdf.F:2420-2768): the reference calls it from initialize (initialize.f:39); a host without PnetCDF
+! calls it after pomgpu_upload_state.  Every rank reads its own patch (no ordering between ranks is needed); afterwards the
+! device state AND the COMMON blocks hold what the reference's reader would have left: the 37 restart fields, d, dt, time0, time
+! and -- if cont_bry was non-zero -- cont_bry = the file's iint.
+subroutine read_restart_pnetcdf
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  type(pomgpu_file_meta) :: m
+  character(len=400) :: fname
+  character(kind=c_char, len=401), target :: cname
+  character(kind=c_char), pointer :: msg(:)
+  type(c_ptr) :: pm
+  integer(c_int) :: rc
+  integer :: n
+  write(fname, '(a,''in/'',a)') trim(wrk_pth), trim(read_rst_file)
+  cname = trim(fname)//c_null_char
+  if (my_task == 0) write(*,'(/''reading file '',a)') trim(fname)
+  call pomgpu_push_con                             ! cont_bry as read_input left it
+  m%title = c_null_ptr; m%time_start = c_null_ptr; m%stats = c_null_ptr; m%create = 0
+  m%im_global = im_global; m%jm_global = jm_global
+  m%i0 = i_global(1); m%j0 = j_global(1)
+  rc = pomgpu_read_restart(pom_ctx, c_loc(cname), m, c_null_ptr, c_null_ptr)
+  if (rc /= 0) then                                ! handle_error_pnetcdf, io_pnetcdf.F:43-54: a message and error_status = 1
+    error_status = 1                               ! (on the rank that failed: a tile that does not fit is that rank's own finding)
+    pm = pomgpu_last_error(pom_ctx)                ! names the file and the cause
+    if (c_associated(pm)) then
+      call c_f_pointer(pm, msg, (/512/))
+      n = 0
+      do while (n < 511)
+        if (msg(n+1) == c_null_char) exit
+        n = n + 1
+      end do
+      write(*,'(/i4,''] Error: read_restart_pnetcdf: '',511a1)') my_task, msg(1:n)
+    end if
+    return
+  end if
+  rc = pomgpu_get_con(pom_ctx, c_loc(alpha))       ! time0, time, cont_bry
+  if (rc /= 0) error_status = 1
+  call pomgpu_download_state
 end subroutine

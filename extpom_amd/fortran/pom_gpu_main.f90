@@ -47,6 +47,11 @@ program pom_gpu_main
 
   call pomgpu_host_init(0)
   call pomgpu_upload_state
+  if (nread_rst /= 0) then                   ! initialize.f:39, for a host without PnetCDF: <wrk_pth>in/<read_rst_file>
+    my_task = 0; master_task = 0
+    i_global(1) = 1; j_global(1) = 1         ! one tile: the patch starts at the grid's first cell
+    call read_restart_pnetcdf
+  end if
   do n = 1, nrec
     rc = pomgpu_set_restore_record(pom_ctx, int(n, c_int), c_loc(tr(1,1,1,n)), c_loc(sr(1,1,1,n)))
   end do
@@ -98,4 +103,6 @@ subroutine bcast0d_mpi(work, from)
   implicit none
   double precision work
   integer from
+end subroutine
+subroutine pomgpu_barrier_mpi               ! pom_gpu_io.f90's barrier between ranks: one task, nothing to wait for
 end subroutine

@@ -91,6 +91,7 @@ program pom_gpu_mpi_main
   if (rc == 0) read(env, *) device
   call pomgpu_host_init(device)
   call pomgpu_upload_state                       ! before the ranks are connected: the wide-halo mode sizes its extended tile by isplit
+  if (nread_rst /= 0) call read_restart_pnetcdf   ! initialize.f:39, for a host without PnetCDF: <wrk_pth>in/<read_rst_file>
   if (nranks > 1) call pomgpu_host_connect_mpi
   do n = 1, nrec
     rc = pomgpu_set_restore_record(pom_ctx, int(n, c_int), c_loc(tr(1,1,1,n)), c_loc(sr(1,1,1,n)))

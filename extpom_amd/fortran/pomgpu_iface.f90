@@ -86,6 +86,12 @@ module pomgpu_iface
     integer(c_int) function pomgpu_write_restart(ctx, path, meta) bind(C, name='pomgpu_write_restart')
       import; type(c_ptr), value :: ctx, path; type(pomgpu_file_meta) :: meta
     end function
+    type(c_ptr) function pomgpu_last_error(ctx) bind(C, name='pomgpu_last_error')   ! a NUL-terminated text of at most 511 characters
+      import; type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function pomgpu_read_restart(ctx, path, meta, time0_out, iint_out) bind(C, name='pomgpu_read_restart')
+      import; type(c_ptr), value :: ctx, path, time0_out, iint_out; type(pomgpu_file_meta) :: meta   ! the two outputs may be c_null_ptr
+    end function
     integer(c_int) function pomgpu_domain_stats(ctx, out, sums_only) bind(C, name='pomgpu_domain_stats')
       import; type(c_ptr), value :: ctx; real(c_double) :: out(8); integer(c_int), value :: sums_only
     end function

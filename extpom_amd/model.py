@@ -221,6 +221,17 @@ class PomGpu:
         fn = self.L.pomgpu_write_output if kind == "output" else self.L.pomgpu_write_restart
         self._chk(fn(self.h, str(path).encode(), ctypes.byref(m)), "write_" + kind)
 
+    def read_restart(self, path, im_global=None, jm_global=None):
+        """read_restart_pnetcdf (io_pnetcdf.F:2420-2768) without PnetCDF: this tile's patch of the 37 restart fields from a classic
+        NetCDF file straight into the device mirrors, d and dt formed from them, time0 = time = the file's time (and cont_bry, if it
+        was non-zero, the file's iint).  Returns (time0, iint_in_file); self.st.con is refreshed, the arrays are NOT downloaded."""
+        st = self.st
+        m = _lib.FileMeta(b"", b"", im_global or st.im, jm_global or st.jm, st.i_off + 1, st.j_off + 1, 0, None)
+        t0, ii = ctypes.c_double(), ctypes.c_double()
+        self._chk(self.L.pomgpu_read_restart(self.h, str(path).encode(), ctypes.byref(m), ctypes.byref(t0), ctypes.byref(ii)), "read_restart")
+        self.get_con()
+        return t0.value, ii.value
+
     def io_wait(self):
         """join the host thread that is writing the last output / restart file (sync, the next write and close do it too)"""
         self._chk(self.L.pomgpu_io_wait(self.h), "io_wait")

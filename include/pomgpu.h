@@ -267,6 +267,20 @@ typedef struct pomgpu_file_meta {
 int pomgpu_io_wait(pomgpu_ctx *ctx);
 int pomgpu_write_output(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta);    /* write_output_pnetcdf */
 int pomgpu_write_restart(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta);   /* write_restart_pnetcdf */
+/* read_restart_pnetcdf (io_pnetcdf.F:2420-2768) without PnetCDF: the 18 2-D and 19 3-D variables of the restart file are found BY
+ * NAME in a classic NetCDF file (CDF-1 or CDF-2; order, extra variables, attributes and dimension names do not matter), and the
+ * tile's (im,jm) patch at (i0,j0) of each lands in X(1:im,1:jm[,1:kb]) of its mirror -- cells beyond (im,jm) of a trimmed tile and
+ * every other array keep what they held; then d = h + el, dt = h + et over the same cells, blkcon time0 = time = the file's `time`,
+ * and cont_bry = int(the file's `iint`) if cont_bry was non-zero at the call.  *time0_out / *iint_out (either may be NULL) return the
+ * two scalars.  Of `meta` only im_global, jm_global, i0, j0 are used.  Synchronous: the state is complete when the call returns; a
+ * file this context is still writing is joined first, and whatever the library keeps lazily is completed before mirrors are
+ * overwritten.  The host only reads raw big-endian runs into pinned buffers and copies them over; the byte reversal and the scatter
+ * into the mirrors are a kernel (in the fp32-storage variants it rounds the 3-D arrays as an upload does).
+ * Refused with POMGPU_EINVAL, error_status = 1 and the cause in pomgpu_last_error, BEFORE any mirror is written: a variable that is
+ * absent, not NC_DOUBLE, a record variable or of other dimension lengths than (kb, jm_global, im_global) / (jm_global, im_global);
+ * a file shorter than a variable's begin + size; any other magic (CDF-5, HDF5); a tile that does not fit the global grid.  An I/O
+ * error half way leaves the state unspecified (error_status = 1). */
+int pomgpu_read_restart(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta, double *time0_out, double *iint_out);   /* read_restart_pnetcdf */
 
 /* One internal step for the current blkcon.iint: get_time, [surface_forcing, lateral_bc -- once the host has
  * supplied forcing / lateral records, see below; skipped otherwise: constant forcing], lateral_viscosity,
