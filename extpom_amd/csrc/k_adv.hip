@@ -685,11 +685,13 @@ __device__ __forceinline__ void c_dens(const KP &P, const int i, const int j, co
 // ---------------------------------------------------------------------------------------------
 // realvertvl -- solver.f:2024-2067.  The zero-gradient edge copies (:2057-2060) become a clamped
 // source index; the mask (:2062-2064) is applied on store.
-__device__ __forceinline__ void c_realvertvl(const KP &P, const int i, const int j, const int k);
-__global__ void k_realvertvl(KP P) {
-  MARCH3(c_realvertvl(P, i, j, k))
+// etf_is_et: the launch that forms a wr left pending (pomgpu_ctx::wr_pending) runs after etf may have been rewritten by the next
+// step's external mode; et holds the bits etf had at :534 ("et = etf", advance.f:527) until the next mode_internal ends.
+__device__ __forceinline__ void c_realvertvl(const KP &P, const int i, const int j, const int k, const int etf_is_et);
+__global__ void k_realvertvl(KP P, int etf_is_et) {
+  MARCH3(c_realvertvl(P, i, j, k, etf_is_et))
 }
-__device__ __forceinline__ void c_realvertvl(const KP &P, const int i, const int j, const int k) {
+__device__ __forceinline__ void c_realvertvl(const KP &P, const int i, const int j, const int k, const int etf_is_et) {
   double v = 0.;
   if (k <= P.kbm1 && i <= P.im && j <= P.jm) {
     const int a = (P.W && i == 1) ? 2 : ((P.E && i == P.im) ? P.imm1 : i);
@@ -705,7 +707,7 @@ __device__ __forceinline__ void c_realvertvl(const KP &P, const int i, const int
       v = 0.5 * (w_(a, b, k) + w_(a, b, k + 1)) +
           0.5 * (u_(a + 1, b, k) * (TPS(a + 1, b) - tc) * dxr + u_(a, b, k) * (tc - TPS(a - 1, b)) * dxl +
                  v_(a, b + 1, k) * (TPS(a, b + 1) - tc) * dyt + v_(a, b, k) * (tc - TPS(a, b - 1)) * dyb) +
-          (1.0 + zzk) * (F2(etf, a, b) - F2(etb, a, b)) / P.dti2;
+          (1.0 + zzk) * ((etf_is_et ? F2(et, a, b) : F2(etf, a, b)) - F2(etb, a, b)) / P.dti2;
 #undef TPS
     }
     v = F2(fsm, i, j) * v;
@@ -723,7 +725,7 @@ __device__ __forceinline__ LevR realvertvl_load(const KP &P, int a, int b, int k
   L.w_n = w_(a, b, k + 1); L.u_c = u_(a, b, k); L.u_e = u_(a + 1, b, k); L.v_c = v_(a, b, k); L.v_n = v_(a, b + 1, k);
   return L;
 }
-__global__ void __launch_bounds__(256) k_realvertvl_col(KP P) {
+__global__ void __launch_bounds__(256) k_realvertvl_col(KP P, int etf_is_et) {
   const int i = TID_I, j = TID_J;
   if (i > P.iml || j > P.jml) return;
   const bool act = (i <= P.im && j <= P.jm);
@@ -737,7 +739,7 @@ __global__ void __launch_bounds__(256) k_realvertvl_col(KP P) {
   const double dt_c = dt_(a, b), dt_e = dt_(a + 1, b), dt_w = dt_(a - 1, b), dt_n = dt_(a, b + 1), dt_s = dt_(a, b - 1);
   const double et_c = F2(et, a, b), et_e = F2(et, a + 1, b), et_w = F2(et, a - 1, b), et_n = F2(et, a, b + 1), et_s = F2(et, a, b - 1);
   const double dxr = K2(R2DXSX, a + 1, b), dxl = K2(R2DXSX, a, b), dyt = K2(R2DYSY, a, b + 1), dyb = K2(R2DYSY, a, b);
-  const double detf = F2(etf, a, b) - F2(etb, a, b);
+  const double detf = (etf_is_et ? et_c : F2(etf, a, b)) - F2(etb, a, b);
   const double m = F2(fsm, i, j);
   double w_k = w_(a, b, 1);
   LevR c = realvertvl_load(P, a, b, 1), nxt = c;
@@ -905,7 +907,7 @@ void launch_restore(pomgpu_ctx *c, double fold, double fnew) { LAUNCH(c, k_resto
 void launch_restore_shift(pomgpu_ctx *c) { LAUNCH(c, k_restore_shift, gridm(c->P), blk2(), c->P); }
 void launch_restore_load(pomgpu_ctx *c, const double *tr, const double *sr, double tau) { LAUNCH(c, k_restore_load, gridm(c->P), blk2(), c->P, tr, sr, tau); }
 void launch_dens(pomgpu_ctx *c, const double *si, const double *ti, double *rhoo) { LAUNCH(c, k_dens, gridm(c->P), blk2(), c->P, si, ti, rhoo); }
-void launch_realvertvl(pomgpu_ctx *c) {
-  if (SW(c, REALVERTVL_CELLS)) LAUNCH(c, k_realvertvl, gridm(c->P), blk2(), c->P);
-  else LAUNCHN(c, "k_realvertvl_col", k_realvertvl_col, grid2(c->P), blk2(), c->P);
+void launch_realvertvl(pomgpu_ctx *c, int etf_is_et) {
+  if (SW(c, REALVERTVL_CELLS)) LAUNCH(c, k_realvertvl, gridm(c->P), blk2(), c->P, etf_is_et);
+  else LAUNCHN(c, "k_realvertvl_col", k_realvertvl_col, grid2(c->P), blk2(), c->P, etf_is_et);
 }

@@ -239,9 +239,25 @@ static void side_begin(pomgpu_ctx *c);
 static void side_end(pomgpu_ctx *c, hipEvent_t ev);
 static int rim_side(pomgpu_ctx *c);
 static void early_invalidate(pomgpu_ctx *c);
+// wr of the last completed step, if mode_internal left it pending (one tile).  Valid anywhere between the end of one mode_internal
+// and the 3-D part of the next: nothing in lateral_viscosity, mode_interaction, mode_external, surface_forcing or lateral_bc writes
+// w, u, v, dt, et or etb, and et holds the bits etf had when the reference calls realvertvl (advance.f:525-534) -- etf itself is
+// rewritten by the next step's last external substeps (:298-314), so the kernel reads et in its place.
+void pomgpu_wr_materialize(pomgpu_ctx *c) {
+  if (!c->wr_pending) return;
+  c->wr_pending = 0;
+  (void)hipSetDevice(c->device);
+  if (!(c->flags & POMGPU_CTX_2D)) launch_realvertvl(c, 1);
+}
+// may mode_internal leave wr to whoever asks for it?  Only where forming it needs no message round (a round is collective and cannot
+// happen on one rank's demand) and every read of the mirrors goes through the library
+static bool wr_on_demand(const pomgpu_ctx *c) {
+  return !c->exch && !c->tp.on && !c->wide.on && !c->parent && !(c->flags & POMGPU_CTX_2D) && !c->wr_eager && !SW(c, WR_NODEFER);
+}
 static void restore_materialize(pomgpu_ctx *c) {
   side_join(c);                                               // whoever asks for materialised state also waits for the side stream
   rho_materialize(c);
+  pomgpu_wr_materialize(c);
   if (!c->rst_pending) return;
   c->rst_pending = 0;
   launch_restore_fields(c, c->rst_fold, c->rst_fnew);
@@ -456,6 +472,7 @@ extern "C" int pomgpu_sync(pomgpu_ctx *c) {
 // ---- state transfer ----------------------------------------------------------------------------
 extern "C" int pomgpu_set_con(pomgpu_ctx *c, const pom_blkcon *con, int lramp) {
   if (!c || !con) return POMGPU_EINVAL;
+  if (c->wr_pending && con->dti2 != c->P.dti2) pomgpu_wr_materialize(c);   // the pending wr is the old dti2's
   c->con = *con;
   c->lramp = lramp;
   sync_scalars(c);
@@ -587,12 +604,15 @@ extern "C" int pomgpu_download_3d(pomgpu_ctx *c, int s, double *h) {
 extern "C" double *pomgpu_device_2d(pomgpu_ctx *c, int s) {
   if (!c || s < 0 || s >= POM_NBLK2D) return NULL;
   ext_canonical(c);
+  pomgpu_wr_materialize(c);                                   // a pending wr reads et, etb, dt: the caller may write them through the address it gets
+  c->wr_eager = 1;
   c->areas_checked = 0;                                       // the caller may write through the address it gets
   return SLOT2(c, s);
 }
 extern "C" double *pomgpu_device_3d(pomgpu_ctx *c, int s) {
   if (!c || s < 0 || s >= POM_NBLK3D) return NULL;
   restore_materialize(c);
+  c->wr_eager = 1;                                            // reads of wr (and writes of w, u, v) the library no longer sees: realvertvl ends every step from now on
   c->dev3_handed = 1;                                         // pomgpu_tune_placement would leave this address dangling: it refuses from now on (pomgpu.h)
   return SLOT3(c, s);
 }
@@ -617,6 +637,7 @@ extern "C" int pomgpu_set_restore_record(pomgpu_ctx *c, int n, const double *tr,
 extern "C" int pomgpu_set_exchange(pomgpu_ctx *c, pomgpu_exchange_fn fn, void *user) {
   if (c && fn) { F32_REFUSE(c, "set_exchange"); }
   if (!c) return POMGPU_EINVAL;
+  if (fn) pomgpu_wr_materialize(c);                           // while forming it still needs no message round
   c->exch = fn;
   c->exch_user = user;
   return POMGPU_OK;
@@ -1014,7 +1035,11 @@ static int wide_early_start(pomgpu_ctx *c);
 extern "C" int pomgpu_lateral_viscosity(pomgpu_ctx *c) {
   NEED_HOT(c);
   const int rc = wide_early_start(c);
-  return rc ? rc : lateral_viscosity(c, 0);
+  // rho's round trip stays a flag as in pomgpu_advance (same condition): k_profq of the pomgpu_mode_internal that follows applies it to
+  // what it loads and dens rewrites rho; a caller that does anything else first gets it stored (rho_materialize: every NEED, the next call of this)
+  const pom_blkcon &k0 = c->con;
+  const int defer_rt = k0.mode == 3 && (k0.iint != 1 || k0.time0 != 0.) && !SW(c, RHO_ROUNDTRIP);
+  return rc ? rc : lateral_viscosity(c, 0, defer_rt);
 }
 static int wide_begin(pomgpu_ctx *c);
 static int mode_interaction(pomgpu_ctx *c, int sums_done) {   // advance.f:144-202
@@ -1752,6 +1777,10 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
     c->wr_deferred = 1;                                       // :534 and solver.f:2055 beside the next step's external substeps
     return POMGPU_OK;
   }
+  // one tile: wr is a diagnostic for the output file that no routine of the step reads; it stays a flag until somebody looks at the
+  // mirrors (pomgpu_wr_materialize) -- in a run of steps nobody does, and the next step's end simply sets the flag again
+  if (wr_on_demand(c)) { c->wr_pending = 1; return POMGPU_OK; }
+  c->wr_pending = 0;
   rim_wait_r8(c);                                             // realvertvl reads u, v of the eastern / northern ghost line
   launch_realvertvl(c);                                       // :534
   // solver.f:2055 on the side stream: the round runs beside check_velocity and the next step's lateral_viscosity; the next
@@ -1761,8 +1790,12 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
   return POMGPU_OK;
 }
 extern "C" int pomgpu_mode_internal(pomgpu_ctx *c) { return mode_internal(c, 0); }
+// Reads vaf alone (k_reduce.hip), a blk2d array outside the external mode's two generations: it needs the extended tile's 2-D state
+// back and the side stream joined, not the lazily kept 3-D arrays (rho's round trip, the restore fields, wr) -- a host that steps
+// routine by routine calls this after every mode_internal (advance.f:57) and would otherwise pay for all three every step
 extern "C" int pomgpu_check_velocity(pomgpu_ctx *c, double *vamax, int *imax, int *jmax) {   // advance.f:611-641
-  NEED(c);
+  NEED_HOT(c);
+  side_join(c);
   launch_check_velocity(c);
   double out[3];
   HIPCHK(c, hipMemcpyAsync(out, c->d_vel, sizeof out, hipMemcpyDeviceToHost, c->stream));
@@ -2167,6 +2200,7 @@ extern "C" int pomgpu_proft(pomgpu_ctx *c, const double *f, const double *wfsurf
 }
 extern "C" int pomgpu_vertvl(pomgpu_ctx *c) { NEED(c); launch_vertvl(c, 0); return POMGPU_OK; }
 extern "C" int pomgpu_realvertvl(pomgpu_ctx *c) {
+  if (c) c->wr_pending = 0;                                   // this call overwrites wr, from etf as the reference does
   NEED(c);
   launch_realvertvl(c);
   xch(c, 1, D3(c, wr), c->P.kbm1);

@@ -647,6 +647,11 @@ struct pomgpu_ctx {
   int rho_rt_pending;
   int rst_pending;           // trstr/srstr/taurstr of the last step exist only as (rst_fold, rst_fnew) weights
   double rst_fold, rst_fnew;
+  // wr of the last step has not been formed (one tile, no exchange of any kind: mode_internal ends without realvertvl).  wr is a
+  // diagnostic nobody on the hot path reads; its operands w, u, v, dt, et, etb keep their bits until the next mode_internal's 3-D part,
+  // and et holds what etf held (advance.f:527), so whoever looks at the mirrors first gets it from launch_realvertvl(c, 1)
+  int wr_pending;
+  int wr_eager;              // pomgpu_device_2d / _3d has handed out an address: reads and writes the library cannot see -- wr at the end of every step from then on
   double *d_vel;             // device: vamax, then (imax,jmax) as two doubles' worth of ints
   int *d_err;                // device error flag
   int *d_areas;              // device flag: art, aru, arv equal their defining formulas on dx, dy (k_check_areas); areas_checked: it is current
@@ -803,7 +808,7 @@ void launch_restore(pomgpu_ctx *c, double fold, double fnew);
 void launch_restore_shift(pomgpu_ctx *c);
 void launch_restore_load(pomgpu_ctx *c, const double *tr, const double *sr, double tau);
 void launch_dens(pomgpu_ctx *c, const double *si, const double *ti, double *rhoo);
-void launch_realvertvl(pomgpu_ctx *c);
+void launch_realvertvl(pomgpu_ctx *c, int etf_is_et = 0);   // etf_is_et: read et where solver.f:2052 reads etf (a pending wr, pomgpu_ctx::wr_pending)
 // k_vert.hip
 void launch_baropg(pomgpu_ctx *c, int sum2d);
 void launch_baropg_mcc(pomgpu_ctx *c, int sum2d);
@@ -841,6 +846,7 @@ int pomgpu_tp_rccl(pomgpu_ctx *c, const void *id128, int rank, int nranks, const
 void pomgpu_tp_free(pomgpu_ctx *c);
 int pomgpu_tp_reserve(pomgpu_ctx *c, const size_t *need);                       // grow the staging buffers
 int pomgpu_tp_reserve2(pomgpu_ctx *c, const size_t *need);                      // ... those of the side stream
+void pomgpu_wr_materialize(pomgpu_ctx *c);                                      // a pending wr formed now (pomgpu_api.hip); part of pomgpu_materialize
 int pomgpu_materialize(pomgpu_ctx *c);                                          // every lazily kept array up to date in the mirrors (pomgpu_api.hip)
 void pomgpu_mirrors_written(pomgpu_ctx *c);                                     // the restart reader has written blk2d / blk3d mirrors on the device: what pomgpu_upload_2d / _3d invalidate (pomgpu_api.hip)
 int pomgpu_side_stream(pomgpu_ctx *c);                                          // create the side stream and its events (pomgpu_api.hip); 1 = there

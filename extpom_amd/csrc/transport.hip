@@ -286,6 +286,7 @@ int pomgpu_tp_setup(pomgpu_ctx *c, const int *nbr8) {
   if ((nbr8[0] < 0) != (P.W != 0) || (nbr8[1] < 0) != (P.E != 0) || (nbr8[2] < 0) != (P.S != 0) || (nbr8[3] < 0) != (P.N != 0))
     return pomgpu_fail(c, POMGPU_EINVAL, "transport: W E S N neighbours disagree with the tile's pomgpu_dims");
   for (int d = 0; d < 8; d++) T.nbr[d] = nbr8[d];
+  pomgpu_wr_materialize(c);                                   // a wr left pending on one tile: formed while that still needs no message round
   size_t need[8];
   const size_t len[8] = {(size_t)P.jm, (size_t)P.jm, (size_t)P.im, (size_t)P.im, 1, 1, 1, 1};
   for (int d = 0; d < 8; d++) need[d] = 8 * (size_t)P.kb * len[d];

@@ -83,7 +83,9 @@ int pomgpu_bind_host(pomgpu_ctx *ctx, const double *host_blk2d, const double *ho
  * arrays dimensioned (im,jm,kb).  Copied to the device. */
 int pomgpu_set_restore_record(pomgpu_ctx *ctx, int n, const double *tr, const double *sr);
 /* Device address of a mirror (for halo exchange by the caller, e.g. RCCL send/recv).  An address of a 3-D array stays valid until
- * pomgpu_destroy -- pomgpu_tune_placement, which moves those arrays, refuses once one has been handed out. */
+ * pomgpu_destroy -- pomgpu_tune_placement, which moves those arrays, refuses once one has been handed out.  Through an address the
+ * caller reads and writes behind the library's back: a pending wr (see pomgpu_run) is formed before the address is returned, and from
+ * then on the context forms wr at the end of every step. */
 double *pomgpu_device_2d(pomgpu_ctx *ctx, int slot2d);
 double *pomgpu_device_3d(pomgpu_ctx *ctx, int slot3d);
 
@@ -239,7 +241,9 @@ int pomgpu_mode_interaction(pomgpu_ctx *ctx);    /* advance.f:144-202 */
  * the context is marked failed: error_status = 1 and the next entry point / pomgpu_get_con reports it. */
 int pomgpu_mode_external(pomgpu_ctx *ctx);
 int pomgpu_mode_internal(pomgpu_ctx *ctx);       /* advance.f:356-537 */
-/* advance.f:611-641; any of the out pointers may be NULL.  Synchronises the stream. */
+/* advance.f:611-641; any of the out pointers may be NULL.  Synchronises the stream.  Reads vaf alone: unlike the other entry points
+ * outside pomgpu_advance it does NOT bring the lazily kept 3-D arrays (wr, rho's round trip, trstr / srstr / taurstr) up to date, so a
+ * host that calls it after every pomgpu_mode_internal, as advance.f:57 does, pays for none of them. */
 int pomgpu_check_velocity(pomgpu_ctx *ctx, double *vamax, int *imax, int *jmax);
 /* domain_stats (advance.f:644-756), the sums behind print_section, reduced on the device (deterministic
  * tree; no state download).  out[8] = vtot, atot, mtot, stot, tavg, savg, eavg, ekin in the reference's
@@ -291,7 +295,16 @@ int pomgpu_advance(pomgpu_ctx *ctx);
  * (pomgpu_rccl_init / pomgpu_transport_side_agree) every step but the last of the call leaves realvertvl (solver.f:2024-2067) and the
  * exchange of wr (:2055) to the step that follows: they run on the second stream beside that step's external substeps -- wr has
  * no reader on the hot path.  The last step of the call does both at once, so after the call the state is complete.  Like every
- * call that posts message rounds, every rank makes it with the same nsteps. */
+ * call that posts message rounds, every rank makes it with the same nsteps.
+ * wr ON ONE TILE (a context without exchange hook, transport or wide-halo mode): wr is a diagnostic that no routine of the step reads,
+ * so pomgpu_mode_internal -- called directly, by pomgpu_advance or by pomgpu_run -- ends without realvertvl and only notes that wr is
+ * due.  wr is "current" in the sense of every other lazily kept array: whatever looks at the mirrors or overwrites them from outside
+ * the step -- pomgpu_download*, pomgpu_upload*, pomgpu_device_2d / _3d, the two file writers, pomgpu_read_restart,
+ * pomgpu_tune_placement, pomgpu_domain_stats, every stand-alone kernel entry point below, a pomgpu_set_con that changes dti2 -- first
+ * forms the wr of the last completed step, bit for bit what realvertvl at the end of that step would have stored (between two
+ * mode_internal nothing writes w, u, v, dt, et, etb, and et holds what etf held, advance.f:525-534).  Steps that follow each other
+ * unobserved never form it.  pomgpu_realvertvl itself reads etf as the reference does and replaces whatever was due.
+ * POMGPU_WR_NODEFER restores realvertvl at the end of every step. */
 int pomgpu_run(pomgpu_ctx *ctx, int nsteps);
 
 /* Where the 3-D arrays live (no counterpart in the reference; optional).  The same kernels on the same bytes run up to 6 %
