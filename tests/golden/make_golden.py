@@ -2,7 +2,7 @@
 (oracle/_ref/libpomref_65x49x21.so, built from the unmodified sources by oracle/build_ref.sh) on
 the inputs of extpom_amd.cases.  Run from the repo root in a container that has /root/reference:
 
-    oracle/build_ref.sh 65 49 21 && oracle/build_ref.sh 256 192 50 && python tests/golden/make_golden.py [kb50 | kb50long NAME | forced | refcheck | archipelago]
+    oracle/build_ref.sh 65 49 21 && oracle/build_ref.sh 256 192 50 && python tests/golden/make_golden.py [kb50 | kb50long NAME | forced | refcheck | archipelago | constants]
 
 The fixture holds, per configuration and checkpoint step, the SHA-256 of every restart-list field
 (the prognostic state, reference io_pnetcdf.F:1724-1886) exactly as the reference left it in its
@@ -206,6 +206,51 @@ def generate_archipelago():
     generate(256, 192, 50, CONFIGS_ARCHIPELAGO_KB50, {}, "archipelago_256x192x50")
 
 
+# The run constants off their defaults (tests/off_default.py): `make_golden.py constants` writes off_default_constants_65x49x21.json,
+# state_digests of the reference's WHOLE state (every COMMON array, bdry, blkcon) under the full off-default set -- archipelago after
+# steps 1, 2, 3, 6, 12, seamount after 1, 3, 6, the set crossed with four namelist branches after 4 -- and, after 4 steps of
+# archipelago, under every entry of SINGLES.  "base" is the reference's state after 4 steps at the DEFAULT constants; the first record
+# of every run holds what differs from it and a later record what differs from the one before (off_default.expand_records rebuilds them).
+def generate_constants():
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import off_default as od
+    from oracle.refharness import state_digests
+
+    def run(case, consts, steps, **extra):
+        a = od.constants_case(case, 65, 49, 21, ref_finish_initial, consts, **extra)
+        lib = RefLib(65, 49, 21)
+        lib.put(a)
+        rec = {}
+        for n in range(1, max(steps) + 1):
+            lib.con["iint"][0] = n
+            lib.advance()
+            if n in steps:
+                lib.get(a)
+                rec[n] = state_digests(a)
+        return rec
+
+    base = run("archipelago", {}, (4,))[4]
+    runs = {}
+    for case, steps in od.GOLDEN_STEPS.items():
+        runs["all/" + case] = run(case, od.FULL, steps)
+    for name, nml in od.BRANCHES.items():
+        runs["all/archipelago/" + name] = run("archipelago", od.FULL, (4,), **nml)
+    for name, consts in od.SINGLES.items():
+        runs["single/" + name] = run("archipelago", consts, (4,))
+        print(name, "done", flush=True)
+    out = {"grid": [65, 49, 21], "base": base, "runs": {}}
+    for name, rec in runs.items():
+        prev, out["runs"][name] = base, {}
+        for n in sorted(rec):
+            out["runs"][name][str(n)] = _delta(prev, rec[n])
+            prev = rec[n]
+    assert od.expand_records(out) == runs
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(here, od.GOLDEN + ".json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True, separators=(",", ":"))
+    print("constants done", flush=True)
+
+
 def generate_refcheck():
     import ctypes
     from extpom_amd.cases import make_forcing_records, make_lateral_records
@@ -268,6 +313,8 @@ def generate_refcheck():
 
 
 def main():
+    if "constants" in sys.argv[1:]:
+        return generate_constants()
     if "archipelago" in sys.argv[1:]:
         return generate_archipelago()
     if "refcheck" in sys.argv[1:]:

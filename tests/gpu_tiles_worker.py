@@ -29,6 +29,7 @@ def worker(rank, world, split, port, out, nml):
     nml = dict(nml)
     mode = nml.pop("_exchange", "hook")
     case = nml.pop("_case", "island")
+    constants = nml.pop("_constants", None)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -38,33 +39,43 @@ def worker(rank, world, split, port, out, nml):
     nx, ny = {"x": (2, 1), "y": (1, 2), "xy": (2, 2), "y4": (1, 4)}[split]
     iml, jml = decomp.local_size(IM, JM, nx, ny)
     tile = decomp.make_tile(rank, IM, JM, iml, jml, n_proc=world)
-    st = make_case(case, IM, JM, KB, tile=tile, dte=6.0, isplit=ISPLIT, **nml)
     # kernels and torch's pack/unpack must share ONE stream; torch's default stream has handle 0, which
     # the C ABI reads as "create your own", so make a real stream current and hand that over
     ts = torch.cuda.Stream()
     torch.cuda.set_stream(ts)
-    g = PomGpu(st, device=dev, stream=ts.cuda_stream)
-    if mode == "hook":
-        halo = DeviceHalo(g, tile, torch.device("cuda", 0), staged=True)
-        g.set_order_exchange(Halo(tile, staged=True).device_order_hook(torch.device("cuda", 0)))   # baropg_mcc (npg = 2)
-    else:                                        # the library serves the exchange points itself (pomgpu_set_transport)
-        from extpom_amd.halo import StagedMover, connect_rccl
-        if mode == "rccl":
-            assert connect_rccl(g, tile, rank, world), "the RCCL transport could not connect the ranks"
-        else:
-            from extpom_amd.halo import dist_allmin
-            g.set_transport(tile, StagedMover(g, tile, torch.device("cuda", 0)), agree=dist_allmin())
-        if mode in ("wide", "rccl"):
-            tiles = [decomp.make_tile(r, IM, JM, iml, jml, n_proc=world) for r in range(world)]
-            assert g.set_wide_external(True, min(t.im for t in tiles), min(t.jm for t in tiles))
+    made = {}
 
-    def dens(s, a, b, c):
-        g.upload(s); g.call("dens", a, b, c); g.download(s)
+    def finish(st):
+        g = made["g"] = PomGpu(st, device=dev, stream=ts.cuda_stream)
+        if mode == "hook":
+            made["halo"] = DeviceHalo(g, tile, torch.device("cuda", 0), staged=True)
+            g.set_order_exchange(Halo(tile, staged=True).device_order_hook(torch.device("cuda", 0)))   # baropg_mcc (npg = 2)
+        else:                                        # the library serves the exchange points itself (pomgpu_set_transport)
+            from extpom_amd.halo import StagedMover, connect_rccl
+            if mode == "rccl":
+                assert connect_rccl(g, tile, rank, world), "the RCCL transport could not connect the ranks"
+            else:
+                from extpom_amd.halo import dist_allmin
+                g.set_transport(tile, StagedMover(g, tile, torch.device("cuda", 0)), agree=dist_allmin())
+            if mode in ("wide", "rccl"):
+                tiles = [decomp.make_tile(r, IM, JM, iml, jml, n_proc=world) for r in range(world)]
+                assert g.set_wide_external(True, min(t.im for t in tiles), min(t.jm for t in tiles))
 
-    def baropg(s):
-        g.upload(s); g.call("baropg_mcc" if int(s.npg) == 2 else "baropg"); g.download(s)
+        def dens(s, a, b, c):
+            g.upload(s); g.call("dens", a, b, c); g.download(s)
 
-    finish_initial(st, dens, baropg)
+        def baropg(s):
+            g.upload(s); g.call("baropg_mcc" if int(s.npg) == 2 else "baropg"); g.download(s)
+
+        finish_initial(st, dens, baropg)
+
+    if constants == "off":                       # every run constant off its default (tests/off_default.py)
+        import off_default
+        st = off_default.off_default_case(case, IM, JM, KB, finish, tile=tile, isplit=ISPLIT, **nml)
+    else:
+        st = make_case(case, IM, JM, KB, tile=tile, dte=6.0, isplit=ISPLIT, **nml)
+        finish(st)
+    g, halo = made["g"], made.get("halo")
     g.upload(st)
     g.prof_begin()
     g.run(STEPS)
@@ -84,15 +95,19 @@ def worker(rank, world, split, port, out, nml):
     dist.destroy_process_group()
 
 
-def main(split, nml, exchange="hook", case="island"):
+def main(split, nml, exchange="hook", case="island", constants=None):
     import tempfile
     from oracle.pyoracle import OracleTile, oracle_finish_initial
     out = tempfile.mkdtemp()
     port = 29700 + (os.getpid() % 200)
     world = 4 if split in ("xy", "y4") else 2
-    mp.spawn(worker, args=(world, split, port, out, dict(nml, _exchange=exchange, _case=case)), nprocs=world, join=True)
-    g = make_case(case, IM, JM, KB, dte=6.0, isplit=ISPLIT, **nml)
-    oracle_finish_initial(g)
+    mp.spawn(worker, args=(world, split, port, out, dict(nml, _exchange=exchange, _case=case, _constants=constants)), nprocs=world, join=True)
+    if constants == "off":
+        import off_default
+        g = off_default.off_default_case(case, IM, JM, KB, oracle_finish_initial, isplit=ISPLIT, **nml)
+    else:
+        g = make_case(case, IM, JM, KB, dte=6.0, isplit=ISPLIT, **nml)
+        oracle_finish_initial(g)
     OracleTile(g).run(STEPS)
     bad = []
     for r in range(world):
@@ -130,4 +145,5 @@ def main(split, nml, exchange="hook", case="island"):
 if __name__ == "__main__":
     main(sys.argv[1] if len(sys.argv) > 1 else "x", dict(npg=2) if "npg2" in sys.argv[2:] else {},
          "rccl" if "rccl" in sys.argv[2:] else ("wide" if "wide" in sys.argv[2:] else ("transport" if "transport" in sys.argv[2:] else "hook")),
-         next((a[5:] for a in sys.argv[2:] if a.startswith("case=")), "island"))       # case=archipelago: land on the seams, curved grid
+         next((a[5:] for a in sys.argv[2:] if a.startswith("case=")), "island"),        # case=archipelago: land on the seams, curved grid
+         next((a[10:] for a in sys.argv[2:] if a.startswith("constants=")), None))      # constants=off: tests/off_default.py

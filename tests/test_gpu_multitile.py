@@ -144,6 +144,18 @@ def test_archipelago_tiles_on_one_gpu_match_single_tile_oracle(args):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("args", [["xy"], ["xy", "transport"], ["xy", "wide"]], ids="-".join)
+def test_off_default_constants_on_archipelago_tiles(args):
+    """every run constant off its default (tests/off_default.py: four different rf*, both biases, alpha, the ramp ...) on 2 x 2 tiles of
+    97x61x16 with the per-point hooks, the library exchange and the wide-halo external mode: the tile-edge kernels state the filter, alpha
+    and the boundary radiation on their own, and an edge factor applied on a side that has a neighbour shows.  Owned cells equal the
+    single-tile oracle under the same constants bit for bit"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "gpu_tiles_worker.py")] + args + ["constants=off", "case=archipelago"], capture_output=True,
+                       text=True, timeout=900)
+    assert r.returncode == 0 and "TILES-OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+@pytest.mark.gpu
 def test_archipelago_whole_row_tiles():
     """1 x 4 whole-row tiles (72x150x12), wide-halo mode: the two inner tiles extended on both sides, land in their rims"""
     env = dict(os.environ, POM_TILES_GRID="72x150x12")

@@ -398,3 +398,133 @@ def _trimmed_tile(case):
     for n in BLK3D:
         if n not in SCRATCH:
             assert same_bits(a.field(n), b.field(n)[:, :49, :65]), n
+
+
+# ---- the run constants off their defaults (tests/off_default.py).  Every test above runs at horcon = tprni = smoth = 0.1, rfe = rfw = rfn =
+# rfs = 1, tbias = sbias = 0, ntp = 2: a kernel that reads P.horcon for P.tprni, P.rfe on the western edge, the wrong Jerlov column or no
+# bias at all is bit-identical to the oracle in all of them (DESIGN.md section 3 lists the mutants that only the tests below see).
+def _lockstep(a, b, steps, every=True):
+    """oracle on a, emulated kernels on b, compared after every step (or after the last only): non-scratch arrays and bdry"""
+    ot = OracleTile(a)
+    g = PomGpu(b, libpath=EMU)
+    for n in range(1, steps + 1):
+        ot.run(1)
+        g.run(1)
+        if every or n == steps:
+            g.download()
+            assert not diff(a, b) and same_bits(a.bdry, b.bdry), f"step {n}: {diff(a, b)}"
+            assert a.iint == b.iint == n
+    return ot, g
+
+
+@pytest.mark.parametrize("im,jm,kb,steps", [(65, 49, 21, 8), (66, 50, 21, 4), (128, 12, 21, 4), (64, 48, 70, 3)])
+def test_off_default_constants_steps(im, jm, kb, steps):
+    """every constant moved at once on the fourth case: the one-column and the two-columns-per-lane kernels, the register-resident and
+    (kb = 70) the work-vector column kernels, the latter with their own copy of the Jerlov table"""
+    import off_default as od
+    a = od.off_default_case("archipelago", im, jm, kb, oracle_finish_initial)
+    b = a.copy()
+    ot, g = _lockstep(a, b, steps)
+    assert g.check_velocity() == ot.vamax
+    assert b.rfw == 0.8 and b.sbias == 1.0 and b.ntp == 4 and 0.0 < a.ramp == b.ramp < 1.0
+
+
+def _branches():
+    import off_default as od
+    return list(od.BRANCHES.items())
+
+
+@pytest.mark.parametrize("name,nml", _branches(), ids=[b[0] for b in _branches()])
+def test_off_default_constants_namelist_branches(name, nml):
+    """the off-default set crossed with mode = 2, mode = 4, npg = 2 + nadv = 1 (advt1 has its own tprni, baropg_mcc its own grav and ramp)
+    and nitera = 2 + sw = 0.8 (the general advt2 path): the records the reference's digests hold for the device, on the emulated kernels"""
+    import off_default as od
+    a = od.off_default_case("archipelago", 65, 49, 21, oracle_finish_initial, **nml)
+    _lockstep(a, a.copy(), 4)
+
+
+@pytest.mark.parametrize("switches", SWITCH_SETS)
+def test_off_default_constants_general_kernels(monkeypatch, switches):
+    """the general kernels behind the fast paths (the four switch sets, at their grids) under the off-default set"""
+    import off_default as od
+    for v in switches:
+        monkeypatch.setenv(v, "3" if v == "POMGPU_COL_STRIP" else "1")
+    im, jm = (200, 30) if "POMGPU_COL_STRIP" in switches else (65, 49)
+    a = od.off_default_case("archipelago", im, jm, 21, oracle_finish_initial)
+    _lockstep(a, a.copy(), 3)
+
+
+def test_off_default_constants_marching_external_substep(monkeypatch):
+    """k_ext_march forced onto a small grid: its own statement of the filter, alpha and the boundary radiation"""
+    import off_default as od
+    monkeypatch.setenv("POMGPU_EXT_MARCH", "1")
+    monkeypatch.setenv("POMGPU_EXT_ROWS", "6")
+    a = od.off_default_case("archipelago", 70, 45, 11, oracle_finish_initial, isplit=10)
+    _lockstep(a, a.copy(), 3)
+
+
+def _single_names():
+    import off_default as od
+    return list(od.SINGLES)
+
+
+@pytest.mark.parametrize("name", _single_names())
+def test_single_constant_steps(name):
+    """one constant moved alone, 4 steps (tests/test_oracle_vs_reference.py asserts that each entry changes the prognostic state);
+    ispadv = 2, 4: the host's iext % ispadv logic and the non-fused substep; vmaxl: error_status = 1 and the run goes on"""
+    import off_default as od
+    a = od.constants_case("archipelago", 65, 49, 21, oracle_finish_initial, od.SINGLES[name])
+    b = a.copy()
+    ot, g = _lockstep(a, b, 4, every=False)
+    assert g.check_velocity() == ot.vamax
+    assert a.error_status == b.error_status == (1 if name == "vmaxl" else 0)
+
+
+LIVE_CON = dict(grav=9.81, kappa=0.41, rhoref=1027.0, horcon=0.2, tprni=0.25, umol=2e-5, smoth=0.08, alpha=0.225, nbct=4, nbcs=3, ntp=5,
+                ispadv=3, tbias=2.0, sbias=1.0, rfe=0.9, rfw=0.8, rfn=0.7, rfs=0.6)
+
+
+def test_constants_changed_on_a_live_context():
+    """pomgpu_set_con moves the constants after two steps at the defaults: the kernels' copy (KP, sync_scalars) and the host's
+    decisions (nbct, nbcs, ispadv) follow at once; three more steps, bit for bit throughout"""
+    a = make_case("archipelago", 65, 49, 21, dte=6.0, isplit=30, nbct=2)
+    oracle_finish_initial(a)
+    b = a.copy()
+    ot, g = _lockstep(a, b, 2)
+    g.set_con(**LIVE_CON)
+    for k, v in LIVE_CON.items():
+        setattr(a, k, v)
+    assert a.con.tobytes() == b.con.tobytes()
+    for n in range(3, 6):
+        ot.run(1)
+        g.run(1)
+        g.download()
+        assert not diff(a, b) and same_bits(a.bdry, b.bdry), f"step {n}: {diff(a, b)}"
+    assert a.con.tobytes() == b.con.tobytes() and b.ntp == 5 and b.ispadv == 3
+
+
+_WARM_OFF_DEFAULT = []
+
+
+def _warm_off_default():
+    """the off-default state of archipelago after three steps of the oracle, computed once"""
+    import off_default as od
+    if not _WARM_OFF_DEFAULT:
+        a = od.off_default_case("archipelago", 65, 49, 21, oracle_finish_initial)
+        OracleTile(a).run(3)
+        a.iint, a.iext = 4, 7
+        _WARM_OFF_DEFAULT.append(a)
+    return _WARM_OFF_DEFAULT[0].copy()
+
+
+@pytest.mark.parametrize("name,fields,ints", ROUTINES_ARCHIPELAGO, ids=[f"{r[0]}{''.join(map(str, r[2]))}" for r in ROUTINES_ARCHIPELAGO])
+def test_routine_bit_identical_off_default(name, fields, ints):
+    """each routine alone on the warm off-default state: where a run above differs, this names the routine"""
+    a = _warm_off_default()
+    b = a.copy()
+    ot = OracleTile(a)
+    ot.call(name, *[ot.a3(f) for f in fields], *[ctypes.c_int(i) for i in ints])
+    g = PomGpu(b, libpath=EMU)
+    g.call(name, *fields, *ints)
+    g.download()
+    assert not diff(a, b) and same_bits(a.bdry, b.bdry), f"{name}: {diff(a, b)}"

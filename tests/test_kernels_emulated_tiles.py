@@ -168,7 +168,10 @@ def main_rounds_saved(steps):
 
 
 def run_tiles(nx, ny, nml, single_round=False, library_exchange=False, wide=False, grid=None, isplit=10, case="island", steps=None,
-              by_routine=False, records=False, dte=6.0, side_fail_rank=None, side_rounds=None, rank_switches=None, errors=None):
+              by_routine=False, records=False, dte=6.0, side_fail_rank=None, side_rounds=None, rank_switches=None, errors=None,
+              pre=None, post=None):
+    """pre(st) / post(st): applied to every tile's state just before / just after finish_initial (constants that initialisation reads, such
+    as small, and constants that it resets, such as rfe)"""
     world = nx * ny
     IMg, JMg = grid or (IM, JM)
     iml, jml = decomp.local_size(IMg, JMg, nx, ny)
@@ -207,7 +210,11 @@ def run_tiles(nx, ny, nml, single_round=False, library_exchange=False, wide=Fals
             def baropg(s):
                 g.upload(s); g.call("baropg_mcc" if int(s.npg) == 2 else "baropg"); g.download(s)
 
+            if pre:
+                pre(st)
             finish_initial(st, dens, baropg)
+            if post:
+                post(st)
             if records:                              # file forcing: wind / heat / surface and lateral_bc records (cases.py)
                 from extpom_amd.cases import make_forcing_records, make_lateral_records
                 make_forcing_records(st, 4)
@@ -274,10 +281,14 @@ def test_tiles_match_single_tile_oracle_archipelago(nx, ny, nml, single_round):
     compare_with_single_tile(out, nml, case="archipelago")
 
 
-def compare_with_single_tile(out, nml, grid=None, isplit=10, case="island", steps=None, min_rounds=20, ghosts=False):
+def compare_with_single_tile(out, nml, grid=None, isplit=10, case="island", steps=None, min_rounds=20, ghosts=False, pre=None, post=None):
     IMg, JMg = grid or (IM, JM)
     g = make_case(case, IMg, JMg, KB, dte=6.0, isplit=isplit, **nml)
+    if pre:
+        pre(g)
     oracle_finish_initial(g)
+    if post:
+        post(g)
     OracleTile(g).run(steps or STEPS)
     bad = []
     for r, (tile, st, count) in out.items():
@@ -514,3 +525,23 @@ def test_wide_halo_mode_in_the_other_modes(nml):
     step), two Smolarkiewicz iterations (the general advt2 path with its own exchanges) -- 2x2 seamount tiles"""
     out = run_tiles(2, 2, nml, library_exchange=True, wide=True, grid=WIDE_GRID, isplit=WIDE_ISPLIT, case="seamount")
     compare_with_single_tile(out, nml, grid=WIDE_GRID, isplit=WIDE_ISPLIT, case="seamount", min_rounds=1)
+
+
+@pytest.mark.parametrize("nx,ny,kw", [(2, 2, dict()), (3, 2, dict(library_exchange=True)), (2, 2, dict(library_exchange=True, wide=True, grid=WIDE_GRID, isplit=WIDE_ISPLIT))],
+                         ids=["2x2-hooks", "3x2-library", "2x2-wide"])
+def test_off_default_constants_on_tiles(nx, ny, kw):
+    """every run constant off its default (tests/off_default.py) on tiles of the fourth case, with the per-point hooks, the library exchange and
+    the wide-halo external mode: the tile-edge kernels (k_bc.hip, k_tile.hip) have their own copies of the filter, alpha and the boundary
+    radiation, and with four DIFFERENT rf* a tile that applies an edge factor on a side where it has a neighbour shows up"""
+    import off_default as od
+    nml, small, post_values = od.split(od.FULL)
+
+    def pre(st):
+        st.small = small
+
+    post = lambda st: od.apply_post(st, post_values)
+    out = run_tiles(nx, ny, nml, case="archipelago", pre=pre, post=post, **kw)
+    cmp_kw = {k: v for k, v in kw.items() if k in ("grid", "isplit")}
+    compare_with_single_tile(out, nml, case="archipelago", pre=pre, post=post, min_rounds=2 if kw.get("wide") else 20, **cmp_kw)
+    for tile, st, _ in out.values():
+        assert st.rfs == 0.6 and st.small == small and st.lramp and 0.0 < st.ramp < 1.0

@@ -167,3 +167,74 @@ def test_ramped_forcing_bit_identical(ref):
         ot.run(1)
     (n, want), = _steps(rec)
     assert n == 6 and 0.0 < b.ramp < 1.0 and not _diff(b, want), _diff(b, want)
+
+
+# ---- the run constants off their defaults (tests/off_default.py; tests/golden/off_default_constants_65x49x21.json holds the reference's
+# side, `make_golden.py constants`): at the defaults horcon = tprni = smoth, the four rf* are 1 and the biases 0, so an oracle that
+# reads one for another would agree with the reference in every test above
+@pytest.fixture(scope="module")
+def ref_constants():
+    import off_default
+    return off_default.golden_records()
+
+
+def _off_default_runs():
+    import off_default as od
+    return ([("all/" + case, case, {}) for case in od.GOLDEN_STEPS] + [("all/archipelago/" + b, "archipelago", nml) for b, nml in od.BRANCHES.items()])
+
+
+@pytest.mark.parametrize("run,case,nml", _off_default_runs(), ids=[r[0] for r in _off_default_runs()])
+def test_off_default_constants_bit_identical(ref_constants, run, case, nml):
+    """every constant moved at once: archipelago after 1, 2, 3, 6, 12 steps, seamount after 1, 3, 6, four namelist branches after 4 --
+    all arrays, bdry and every blkcon member"""
+    import off_default as od
+    want = ref_constants[run]
+    assert sorted(want) == list(od.GOLDEN_STEPS[case] if not nml else (4,))
+    b = od.off_default_case(case, 65, 49, 21, oracle_finish_initial, **nml)
+    ot = OracleTile(b)
+    done = 0
+    for n in sorted(want):
+        ot.run(n - done)
+        done = n
+        assert not _diff(b, want[n]), f"{run}: step {n}: {_diff(b, want[n])}"
+    assert b.rfe == 0.9 and b.tbias == 2.0 and b.ntp == 4 and 0.0 < b.ramp < 1.0
+
+
+_BASELINES = {}
+
+
+def _baseline(consts):
+    """the oracle after 4 steps of archipelago at the default constants (for an ntp entry: at that entry's nbct), computed once"""
+    import off_default as od
+    nml = od.baseline_of(consts)
+    key = json.dumps(nml, sort_keys=True)
+    if key not in _BASELINES:
+        a = od.constants_case("archipelago", 65, 49, 21, oracle_finish_initial, nml)
+        OracleTile(a).run(4)
+        _BASELINES[key] = a
+    return _BASELINES[key]
+
+
+def _single_names():
+    import off_default as od
+    return list(od.SINGLES)
+
+
+@pytest.mark.parametrize("name", _single_names())
+def test_single_constant_bit_identical_and_live(ref_constants, name):
+    """one constant moved alone, 4 steps of archipelago: the reference's bits -- and NOT the bits of the default-constant run in at
+    least one prognostic field, without which the entry would test nothing (vmaxl: see below)"""
+    import off_default as od
+    from extpom_amd.layout import PROGNOSTIC
+    consts = od.SINGLES[name]
+    (n, want), = ref_constants["single/" + name].items()
+    b = od.constants_case("archipelago", 65, 49, 21, oracle_finish_initial, consts)
+    OracleTile(b).run(4)
+    assert n == 4 and not _diff(b, want), f"{name}: {_diff(b, want)}"
+    base = _baseline(consts)
+    moved = [f for f in PROGNOSTIC if b.field(f).tobytes() != base.field(f).tobytes()]
+    if name == "vmaxl":
+        # check_velocity (advance.f:611-641) compares and reports; no array depends on vmaxl.  What it moves is error_status.
+        assert not moved and b.error_status == 1 and base.error_status == 0
+    else:
+        assert moved, f"{name}: the constant leaves every prognostic field as the defaults do"
