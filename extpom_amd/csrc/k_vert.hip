@@ -1366,8 +1366,13 @@ __global__ void k_advv_profv(KP P, int do_adv, int do_prof) {
 // is the neighbour lane's (halo-lane wavefronts);  V = 1: profv, (i,j-1) needs a second load per level.
 // Phase A loads the whole column into the future ee/gg registers, phase B is the forward
 // elimination (solver.f:1712-1745 / :1810-1843), phase C the bottom value and back substitution.
-template <int KBT, int V>
-static __device__ __forceinline__ void d_profuv_reg(const KP &P, const bool store_tps) {
+// FUSE = 1 (k_profuv_filter_reg2): on the interior (5 <= i <= im-3, 5 <= j <= jm-3) the finished column stays in registers and the
+// Asselin filter of d_uv_filter_reg (advance.f:469-514) runs from them: u = uf and the new ub are stored, uf is not; on the
+// frame -- the cells whose old u, ub, uf bcondorl(3) still reads, and those it writes -- uf is stored as with FUSE = 0 and u, ub are
+// left alone (k_uv_filter_rim filters them behind bcondorl(3)).  Other workgroups, and the other component on blockIdx.z, rewrite the
+// ub, vb that the bottom friction reads from neighbour columns: ubk, vbk are level kbm1 of ub, vb as k_uvb_bottom saved them.
+template <int KBT, int V, int FUSE = 0>
+static __device__ __forceinline__ void d_profuv_reg(const KP &P, const bool store_tps, const double *ubk = nullptr, const double *vbk = nullptr) {
   const int j = TID_J;
   if (j > P.jm) return;
   int i0, lane = 1;
@@ -1412,10 +1417,14 @@ static __device__ __forceinline__ void d_profuv_reg(const KP &P, const bool stor
   const double m = V ? F2(dvm, i, j) : F2(dum, i, j);
   const double cb2 = F2(cbc, i, j) + F2(cbc, in_, jn_);
   double tps;
-  if (V) tps = 0.5 * cb2 * sqrt(sq(.25 * (F3(ub, i, j, kbm1) + F3(ub, i + 1, j, kbm1) + F3(ub, i, js, kbm1) + F3(ub, i + 1, js, kbm1))) +
-                                sq(F3(vb, i, j, kbm1)));
-  else tps = 0.5 * cb2 * sqrt(sq(F3(ub, i, j, kbm1)) +
-                              sq(.25 * (F3(vb, i, j, kbm1) + F3(vb, i, j + 1, kbm1) + F3(vb, iw, j, kbm1) + F3(vb, iw, j + 1, kbm1))));
+#define UBK(i, j) (FUSE ? G2(ubk, i, j) : (double)F3(ub, i, j, kbm1))
+#define VBK(i, j) (FUSE ? G2(vbk, i, j) : (double)F3(vb, i, j, kbm1))
+  if (V) tps = 0.5 * cb2 * sqrt(sq(.25 * (UBK(i, j) + UBK(i + 1, j) + UBK(i, js) + UBK(i + 1, js))) +
+                                sq(VBK(i, j)));
+  else tps = 0.5 * cb2 * sqrt(sq(UBK(i, j)) +
+                              sq(.25 * (VBK(i, j) + VBK(i, j + 1) + VBK(iw, j) + VBK(iw, j + 1))));
+#undef UBK
+#undef VBK
   SCHED_FENCE();
 #pragma unroll
   for (int k = 1; k <= KBT; k++) {
@@ -1460,14 +1469,73 @@ static __device__ __forceinline__ void d_profuv_reg(const KP &P, const bool stor
   const double c = -P.dti2 * (km_last + P.umol) / (F1(dz, kbm1) * F1(dzz, kbm2) * dh * dh);
   double x = (c * g_last - rhs_b) / (tps * P.dti2 / (-F1(dz, kbm1) * dh) - 1. - (e_last - 1.) * c);
   x = x * m;
-  G3(f, i, j, kbm1) = x;
-  if (V) F2(wvbot, i, j) = -tps * x; else F2(wubot, i, j) = -tps * x;
+  if (!FUSE) {
+    G3(f, i, j, kbm1) = x;
+    if (V) F2(wvbot, i, j) = -tps * x; else F2(wubot, i, j) = -tps * x;
 #pragma unroll
-  for (int ki = KBT - 2; ki >= 1; ki--) {
-    const double xn = (ee[ki - 1] * x + gg[ki - 1]) * m;
-    if (ki <= kbm2) { x = xn; PLANE(f, ki, col) = x; }
+    for (int ki = KBT - 2; ki >= 1; ki--) {
+      const double xn = (ee[ki - 1] * x + gg[ki - 1]) * m;
+      if (ki <= kbm2) { x = xn; PLANE(f, ki, col) = x; }
+    }
+    if (store_tps) F2(tps, i, j) = tps;
+  } else {
+    // no load or store below sits in a branch: a lane's accesses go to its interior offset or to its frame offset, the other of the
+    // two lies outside every descriptor (BOFF_NONE); levels past kbm1 (KBT > kb) repeat level kbm1's access with level kbm1's value
+    if (V) F2(wvbot, i, j) = -tps * x; else F2(wubot, i, j) = -tps * x;
+    const bool inner = (i >= 5 && i <= P.im - 3 && j >= 5 && j <= P.jm - 3);
+    const unsigned o_in = inner ? col : BOFF_NONE, o_fr = inner ? BOFF_NONE : col;
+    const unsigned lvb = LVB;
+    const BufA bf = BUF3(f), bb = BUF3(P.b3 + (size_t)(V ? P3_vb : P3_ub) * P.a3), bc = BUF3(P.b3 + (size_t)(V ? P3_v : P3_u) * P.a3);
+#define LVK(k) ((unsigned)(KC(k) - 1) * lvb)
+    // back substitution: x(ki) takes the register its ee[ki-1] has just left (rounded to the storage type, as the unfused filter
+    // reads it back), the old u(ki) is requested into gg[ki-1]
+#pragma unroll
+    for (int ki = KBT - 1; ki >= 1; ki--) {
+      if (ki <= KBT - 2) {
+        const double xn = (ee[ki - 1] * x + gg[ki - 1]) * m;
+        x = (ki <= kbm2) ? xn : x;
+      }
+      bst(bf, o_fr, LVK(ki), x);
+      ee[ki - 1] = (double)(pomgpu_st)x;
+      gg[ki - 1] = bld(bc, o_in, LVK(ki));
+    }
+    constexpr int CH = 8, NL = KBT - 1, NCH = (NL + CH - 1) / CH;
+    double t0[CH], t1[CH];
+#pragma unroll
+    for (int q = 0; q < CH; q++) t0[q] = bld(bb, o_in, LVK(q + 1));
+    const double c_kb = bld(bc, o_in, (unsigned)(kb - 1) * lvb), f_kb = bld(bf, o_in, (unsigned)(kb - 1) * lvb);
+    double su = 0.;
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++) {
+      if (ch + 1 < NCH) {
+#pragma unroll
+        for (int q = 0; q < CH; q++) {
+          const double y = bld(bb, o_in, LVK((ch + 1) * CH + q + 1));
+          if (ch & 1) t0[q] = y; else t1[q] = y;
+        }
+      }
+      SCHED_FENCE();
+#pragma unroll
+      for (int q = 0; q < CH; q++) {
+        const int k = ch * CH + q + 1;
+        if (k <= NL) {
+          const double uf = ee[k - 1];
+          const double d = uf + ((ch & 1) ? t1[q] : t0[q]) - 2. * gg[k - 1];                // advance.f:473-474 / :495-496
+          ee[k - 1] = d;
+          const double sn = su + d * F1(dz, KC(k));
+          su = (k <= kbm1) ? sn : su;
+          bst(bc, o_in, LVK(k), uf);                                                        // :489 / :511
+        }
+      }
+      SCHED_FENCE();
+    }
+#pragma unroll
+    for (int k = 1; k <= NL; k++) bst(bb, o_in, LVK(k), gg[k - 1] + .5 * P.smoth * (ee[k - 1] - su));   // :484-488 / :506-510
+    bst(bb, o_in, (unsigned)(kb - 1) * lvb, c_kb);
+    bst(bc, o_in, (unsigned)(kb - 1) * lvb, f_kb);
+    if (store_tps) F2(tps, i, j) = inner ? su : tps;
+#undef LVK
   }
-  if (store_tps) F2(tps, i, j) = tps;
 #undef KC
 #undef KCB
 #undef PLANE
@@ -1481,6 +1549,27 @@ template <int KBT>
 __global__ void __launch_bounds__(64 * ROWS_PROFUV) k_profuv_reg2(KP P) {
   if (blockIdx.z == 0) d_profuv_reg<KBT, 0>(P, false);
   else d_profuv_reg<KBT, 1>(P, true);
+}
+
+// profu, profv and, on the interior, the filter and time rotation of u, v (advance.f:461-462 + :469-514) as one grid: k_profuv_reg2's
+// mapping, one wave per SIMD.  uf, vf of the interior are not stored: they stay a flag (pomgpu_ctx::uvf_pending) until somebody looks.
+template <int KBT>
+__global__ void __launch_bounds__(64 * ROWS_PROFUV) k_profuv_filter_reg2(KP P, const double *ubk, const double *vbk) {
+  if (blockIdx.z == 0) d_profuv_reg<KBT, 0, 1>(P, false, ubk, vbk);
+  else d_profuv_reg<KBT, 1, 1>(P, true, ubk, vbk);
+}
+// level kbm1 of ub, vb into two planes of doubles, for the bottom friction of k_profuv_filter_reg2
+__global__ void k_uvb_bottom(KP P, double *ubk, double *vbk) {
+  const int i = TID_I, j = TID_J;
+  if (i > P.iml || j > P.jml) return;
+  G2(ubk, i, j) = F3(ub, i, j, P.kbm1);
+  G2(vbk, i, j) = F3(vb, i, j, P.kbm1);
+}
+// u -> uf, v -> vf on the interior k_profuv_filter_reg2 filtered, levels 1..kbm1: what the unfused pair leaves there
+__global__ void k_uvf_copy(KP P, double *dst, const double *src) {
+  const int i = TID_I + 4, j = TID_J + 4, k = TID_K;
+  if (i > P.im - 3 || j > P.jm - 3 || k > P.kbm1) return;
+  G3(dst, i, j, k) = G3(src, i, j, k);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1616,6 +1705,59 @@ __global__ void __launch_bounds__(64 * ROWS_UVF) k_uv_filter_reg2(KP P, int own)
   else d_uv_filter_reg<KBT, 1>(P, own);
 }
 
+// The filter on the frame k_profuv_filter_reg2 left out (columns 1..4, im-2..im and rows 1..4, jm-2..jm), behind bcondorl(3), from the
+// stored uf, vf: d_uv_filter_reg's arithmetic, one thread per column and component, the column read twice in chunks of eight levels.
+// blockIdx.y: 0 = the west and east columns, eight neighbouring lanes on the eight columns 1..4, im-2..im (the eighth idle) of one row;
+// 1..7 = the rows 1..4, jm-2..jm between them.  blockIdx.z: the component.
+template <int V>
+static __device__ __forceinline__ void d_uv_filter_rim(const KP &P) {
+  const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x), line = (int)blockIdx.y;
+  int i, j;
+  if (line == 0) {
+    const int il = t & 7;
+    j = (t >> 3) + 1;
+    if (il == 7 || j > P.jm) return;
+    i = il < 4 ? il + 1 : P.im - 6 + il;
+  } else {
+    i = t + 5;
+    if (i > P.im - 3) return;
+    j = line <= 4 ? line : P.jm - 7 + line;
+  }
+  const double *f = P.b3 + (size_t)(V ? P3_vf : P3_uf) * P.a3;
+  double *b = P.b3 + (size_t)(V ? P3_vb : P3_ub) * P.a3, *c = P.b3 + (size_t)(V ? P3_v : P3_u) * P.a3;
+  const int kb = P.kb, kbm1 = P.kbm1;
+  constexpr int CH = 8;
+  double xf[CH], xb[CH], xc[CH];
+#define KC(k) ((k) < kbm1 ? (k) : kbm1)
+  double su = 0.;
+  for (int k0 = 1; k0 <= kbm1; k0 += CH) {
+#pragma unroll
+    for (int q = 0; q < CH; q++) { xf[q] = G3(f, i, j, KC(k0 + q)); xb[q] = G3(b, i, j, KC(k0 + q)); xc[q] = G3(c, i, j, KC(k0 + q)); }
+#pragma unroll
+    for (int q = 0; q < CH; q++)
+      if (k0 + q <= kbm1) su = su + (xf[q] + xb[q] - 2. * xc[q]) * F1(dz, k0 + q);          // advance.f:473-474 / :495-496
+  }
+  for (int k0 = 1; k0 <= kbm1; k0 += CH) {
+#pragma unroll
+    for (int q = 0; q < CH; q++) { xf[q] = G3(f, i, j, KC(k0 + q)); xb[q] = G3(b, i, j, KC(k0 + q)); xc[q] = G3(c, i, j, KC(k0 + q)); }
+#pragma unroll
+    for (int q = 0; q < CH; q++)
+      if (k0 + q <= kbm1) {
+        G3(b, i, j, k0 + q) = xc[q] + .5 * P.smoth * ((xf[q] + xb[q] - 2. * xc[q]) - su);   // :484-488 / :506-510
+        G3(c, i, j, k0 + q) = xf[q];                                                        // :489 / :511
+      }
+  }
+  const double c_kb = G3(c, i, j, kb), f_kb = G3(f, i, j, kb);
+  G3(b, i, j, kb) = c_kb;
+  G3(c, i, j, kb) = f_kb;
+  if (V) F2(tps, i, j) = su;
+#undef KC
+}
+__global__ void k_uv_filter_rim(KP P) {
+  if (blockIdx.z == 0) d_uv_filter_rim<0>(P);
+  else d_uv_filter_rim<1>(P);
+}
+
 // ---- launchers --------------------------------------------------------------------------------
 static inline dim3 colblk() { return dim3(64, 2, 1); }
 static inline dim3 rowblk(int rows) { return dim3(64, rows, 1); }
@@ -1742,6 +1884,34 @@ int launch_profuv_reg(pomgpu_ctx *c) {
   else if (kb <= 56) launch_profuv_reg_t<56>(c);
   else launch_profuv_reg_t<64>(c);
   return 1;
+}
+// the fused tail of one tile (pomgpu_api.hip: uv_fused): the snapshot of ub, vb at kbm1, then profu, profv with the interior's filter
+template <int KBT> static void launch_profuv_filter_reg_t(pomgpu_ctx *c, double *ubk, double *vbk) {
+  const KP &P = c->P;
+  LAUNCH(c, k_uvb_bottom, grid2(P), blk2(), c->P, ubk, vbk);
+  LAUNCHN(c, "k_profuv_filter_reg2", (k_profuv_filter_reg2<KBT>), dim3((P.iml + 61) / 62, (P.jml + ROWS_PROFUV - 1) / ROWS_PROFUV, 2), rowblk(ROWS_PROFUV), c->P,
+          (const double *)ubk, (const double *)vbk);
+}
+void launch_profuv_filter_reg(pomgpu_ctx *c, double *ubk, double *vbk) {   // the caller has checked kb (6..64)
+  const int kb = c->P.kb;
+  if (kb <= 24) launch_profuv_filter_reg_t<24>(c, ubk, vbk);
+  else if (kb <= 32) launch_profuv_filter_reg_t<32>(c, ubk, vbk);
+  else if (kb <= 40) launch_profuv_filter_reg_t<40>(c, ubk, vbk);
+  else if (kb <= 44) launch_profuv_filter_reg_t<44>(c, ubk, vbk);
+  else if (kb <= 50) launch_profuv_filter_reg_t<50>(c, ubk, vbk);
+  else if (kb <= 56) launch_profuv_filter_reg_t<56>(c, ubk, vbk);
+  else launch_profuv_filter_reg_t<64>(c, ubk, vbk);
+}
+void launch_uv_filter_rim(pomgpu_ctx *c) {
+  const KP &P = c->P;
+  const int len = 8 * P.jm > P.im - 7 ? 8 * P.jm : P.im - 7;
+  LAUNCH(c, k_uv_filter_rim, dim3((len + 63) / 64, 8, 2), dim3(64, 1, 1), c->P);
+}
+void launch_uvf_copy(pomgpu_ctx *c) {                          // a pending uf, vf (pomgpu_ctx::uvf_pending): one launch per component
+  const KP &P = c->P;
+  const dim3 g((P.im - 7 + 63) / 64, (P.jm - 7 + 3) / 4, P.kbm1);
+  LAUNCH(c, k_uvf_copy, g, blk2(), c->P, P.b3 + (size_t)P3_uf * P.a3, (const double *)(P.b3 + (size_t)P3_u * P.a3));
+  LAUNCH(c, k_uvf_copy, g, blk2(), c->P, P.b3 + (size_t)P3_vf * P.a3, (const double *)(P.b3 + (size_t)P3_v * P.a3));
 }
 template <int KBT> static void launch_uv_filter_reg_t(pomgpu_ctx *c, int own) {
   if (!SW(c, NO_TWIN)) { LAUNCHN(c, "k_uv_filter_reg2", (k_uv_filter_reg2<KBT>), twin(rowgrid(c->P, ROWS_UVF)), rowblk(ROWS_UVF), c->P, own); return; }

@@ -254,10 +254,23 @@ void pomgpu_wr_materialize(pomgpu_ctx *c) {
 static bool wr_on_demand(const pomgpu_ctx *c) {
   return !c->exch && !c->tp.on && !c->wide.on && !c->parent && !(c->flags & POMGPU_CTX_2D) && !c->wr_eager && !SW(c, WR_NODEFER);
 }
+// may mode_internal end in k_profuv_filter_reg2 and leave the interior of uf, vf pending?  One tile whose mirrors only the library reads
+// (as for wr), a grid with an interior, and the register kernels' range of kb
+static bool uv_fused(const pomgpu_ctx *c) {
+  const KP &P = c->P;
+  return !c->exch && !c->tp.on && !c->wide.on && !c->parent && !(c->flags & POMGPU_CTX_2D) && !c->wr_eager && P.kb >= 6 && P.kb <= 64 &&
+         P.im >= 8 && P.jm >= 8 && !SW(c, THOMAS_SCRATCH) && !SW(c, NO_TWIN) && !SW(c, UV_NOFUSE);
+}
+static void uvf_materialize(pomgpu_ctx *c) {
+  if (!c->uvf_pending) return;
+  c->uvf_pending = 0;
+  launch_uvf_copy(c);
+}
 static void restore_materialize(pomgpu_ctx *c) {
   side_join(c);                                               // whoever asks for materialised state also waits for the side stream
   rho_materialize(c);
   pomgpu_wr_materialize(c);
+  uvf_materialize(c);
   if (!c->rst_pending) return;
   c->rst_pending = 0;
   launch_restore_fields(c, c->rst_fold, c->rst_fnew);
@@ -346,6 +359,7 @@ static int ctx_create(pomgpu_ctx **out, const pomgpu_dims *d, int device, void *
   alloc(&P.bd, nbd);
   for (int n = 0; n < POMGPU_NSCR3 && !only2d; n++) alloc(&P.s3[n], P.n3);
   for (int n = 0; n < POMGPU_NSCR2; n++) alloc(&P.s2[n], P.n2);
+  for (int n = 0; n < 2 && !only2d; n++) alloc(&c->uvb_bot[n], P.n2);
   for (int n = 0; n < POMGPU_NCOEF2; n++) alloc(&P.c2[n], P.n2);
   alloc(&c->alt2[0], (size_t)POMGPU_NGEN * P.n2);              // ONE block: a kernel reaches the whole set through one buffer descriptor (k_ext_march2)
   for (int n = 1; n < POMGPU_NGEN && ok; n++) c->alt2[n] = c->alt2[0] + (size_t)n * P.n2;
@@ -399,6 +413,7 @@ extern "C" void pomgpu_destroy(pomgpu_ctx *c) {
   (void)hipFree(P.b1); (void)hipFree(P.b2); (void)hipFree(P.b3); (void)hipFree(P.bd);
   for (int n = 0; n < POMGPU_NSCR3; n++) (void)hipFree(P.s3[n]);
   for (int n = 0; n < POMGPU_NSCR2; n++) (void)hipFree(P.s2[n]);
+  (void)hipFree(c->uvb_bot[0]); (void)hipFree(c->uvb_bot[1]);
   for (int n = 0; n < POMGPU_NCOEF2; n++) (void)hipFree(P.c2[n]);
   (void)hipFree(c->alt2[0]); (void)hipFree(c->alt3[0]);         // one block each
   (void)hipFree(P.m8);
@@ -1617,6 +1632,7 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
   rim_wait_r2(c);                                             // advx, advy, aam: ghost cells from the side stream (advq, advt2 read aam's)
   rim_wait_r8(c);                                             // (a step whose lateral_viscosity did not run: nothing else has waited)
   if ((k.iint != 1 || k.time0 != 0.) && k.mode != 2) {
+    c->uvf_pending = 0;                                       // u, v change now and advq rewrites uf, vf whole: nobody has asked for the copy
     launch_int_uvmean(c);                                     // :365-393
     launch_vertvl(c, 1);                                      // :396-398
     // :400 exchange3d_mpi(w): nothing reads w's ghost cells before advt / advu (advq takes w at the cell's own
@@ -1726,9 +1742,11 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
       }
     }
     rim_wait_rq(c);                                           // profu / profv average km with the neighbour line's
+    const bool fuse = uv_fused(c);                            // :461-462 and the interior of :469-514 in one kernel (one tile)
     if (c->P.kb >= 6 && c->P.kb <= 64 && !SW(c, THOMAS_SCRATCH)) {
       launch_advuv_col(c);                                    // :459-460 advu, advv in one pass
-      launch_profuv_reg(c);                                   // :461-462 profu, profv with register-resident elimination vectors
+      if (fuse) launch_profuv_filter_reg(c, c->uvb_bot[0], c->uvb_bot[1]);
+      else launch_profuv_reg(c);                              // :461-462 profu, profv with register-resident elimination vectors
     } else {
       launch_advu_profu(c, 1, 1);                             // :459-462
       launch_advv_profv(c, 1, 1);
@@ -1757,7 +1775,8 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
     } else {
       if (lib_x) xch(c, 4, D2(c, wubot), 1, D2(c, wvbot), 1, D3(c, uf), P.kbm1, D3(c, vf), P.kbm1);   // solver.f:1777,1874 + :466-467
       else xch(c, 2, D3(c, uf), P.kbm1, D3(c, vf), P.kbm1);   // :466-467
-      launch_uv_filter(c);                                    // :469-514
+      if (fuse) { launch_uv_filter_rim(c); c->uvf_pending = 1; }   // :469-514 on the frame; the interior's uf, vf stay a flag
+      else launch_uv_filter(c);                               // :469-514
       if (lib_x && !SW(c, UV_FULL_EXCHANGE)) {
         // :516-521 exchange all kb levels of ub, u, uf, vb, v, vf.  For u, uf, v, vf the levels 1..kbm1 are redundant: uf, vf
         // were exchanged at :466-467 and not written since, and u = uf, v = vf are copies.  What is not valid in a ghost

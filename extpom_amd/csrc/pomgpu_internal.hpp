@@ -512,7 +512,7 @@ static inline dim3 grid2_halo(const KP &P) { return dim3((P.iml + 61) / 62, (P.j
   X(PROFQ_NOPACE) X(COL_STRIP) X(BAND_BYTES) X(PAD3) X(IO_SYNC) X(ADVCT_SPLIT) X(ADVQ_EXCHANGE) X(PROD_FULL) X(QFILTER_SPLIT) \
   X(UV_FULL_EXCHANGE) X(NO_OVERLAP) X(NO_SIDE_COMM) X(WR_MAIN) X(WIDE_W) X(WIDE_FULL) X(DEBUG_ALLOC) X(TEST_SPLIT_FAIL_RANK)  \
   X(EDGE_SPLIT) X(WR_NODEFER) X(EXT_RING_FIRST) X(TUNE_FORCE) X(NO_TWIN) X(RIM_MAIN) X(RIM_RESULTS_MAIN) X(SUM2D_OFF) X(ADVCT_ROWS4) X(ADVCT_ROWS8) \
-  X(IO_CHUNK_KB)
+  X(IO_CHUNK_KB) X(UV_NOFUSE)
 enum pomgpu_sw {
 #define POMGPU_SW_(name) SW_##name,
   POMGPU_SWITCHES(POMGPU_SW_)
@@ -651,6 +651,12 @@ struct pomgpu_ctx {
   // diagnostic nobody on the hot path reads; its operands w, u, v, dt, et, etb keep their bits until the next mode_internal's 3-D part,
   // and et holds what etf held (advance.f:527), so whoever looks at the mirrors first gets it from launch_realvertvl(c, 1)
   int wr_pending;
+  // uf, vf of the interior (5 <= i <= im-3, 5 <= j <= jm-3, levels 1..kbm1) have not been stored: k_profuv_filter_reg2 kept the column in
+  // registers for the filter, and what the reference leaves there is a copy of u, v.  Nothing on the hot path reads uf, vf before the next
+  // mode_internal's advq rewrites them whole; whoever looks at the mirrors first gets the copy (restore_materialize).  Valid until the
+  // 3-D part of the next mode_internal changes u, v, which drops the flag.
+  int uvf_pending;
+  double *uvb_bot[2];        // level kbm1 of ub, vb as they were before that kernel: its bottom friction reads neighbour columns others rewrite
   int wr_eager;              // pomgpu_device_2d / _3d has handed out an address: reads and writes the library cannot see -- wr at the end of every step from then on
   double *d_vel;             // device: vamax, then (imax,jmax) as two doubles' worth of ints
   int *d_err;                // device error flag
@@ -760,6 +766,9 @@ void launch_advt2x2_col(pomgpu_ctx *c, const double *tb, const double *t, const 
 void launch_advq2_col(pomgpu_ctx *c, const double *q, const double *qb, double *qf, const double *ql, const double *qlb, double *qlf, int zero_else);
 void launch_advuv_col(pomgpu_ctx *c);
 int launch_profuv_reg(pomgpu_ctx *c);   // 0 when kb is outside the instantiated range
+void launch_profuv_filter_reg(pomgpu_ctx *c, double *ubk, double *vbk);   // k_uvb_bottom + k_profuv_filter_reg2 (kb in 6..64); ubk, vbk: two planes of n2 doubles
+void launch_uv_filter_rim(pomgpu_ctx *c);   // the filter on the frame the fused kernel leaves out (im, jm >= 8)
+void launch_uvf_copy(pomgpu_ctx *c);        // u -> uf, v -> vf on that kernel's interior, levels 1..kbm1
 void launch_advave_m2a(pomgpu_ctx *c);
 void launch_advave_m2b(pomgpu_ctx *c);
 void launch_vint(pomgpu_ctx *c, int only_aam, int ghost = 0);   // ghost: +1 = every cell but the ghost lines (aam2d only), -1 = the ghost lines alone

@@ -242,7 +242,8 @@ int pomgpu_mode_interaction(pomgpu_ctx *ctx);    /* advance.f:144-202 */
 int pomgpu_mode_external(pomgpu_ctx *ctx);
 int pomgpu_mode_internal(pomgpu_ctx *ctx);       /* advance.f:356-537 */
 /* advance.f:611-641; any of the out pointers may be NULL.  Synchronises the stream.  Reads vaf alone: unlike the other entry points
- * outside pomgpu_advance it does NOT bring the lazily kept 3-D arrays (wr, rho's round trip, trstr / srstr / taurstr) up to date, so a
+ * outside pomgpu_advance it does NOT bring the lazily kept 3-D arrays (wr, rho's round trip, trstr / srstr / taurstr, the interior of
+ * uf / vf) up to date, so a
  * host that calls it after every pomgpu_mode_internal, as advance.f:57 does, pays for none of them. */
 int pomgpu_check_velocity(pomgpu_ctx *ctx, double *vamax, int *imax, int *jmax);
 /* domain_stats (advance.f:644-756), the sums behind print_section, reduced on the device (deterministic
@@ -304,7 +305,12 @@ int pomgpu_advance(pomgpu_ctx *ctx);
  * forms the wr of the last completed step, bit for bit what realvertvl at the end of that step would have stored (between two
  * mode_internal nothing writes w, u, v, dt, et, etb, and et holds what etf held, advance.f:525-534).  Steps that follow each other
  * unobserved never form it.  pomgpu_realvertvl itself reads etf as the reference does and replaces whatever was due.
- * POMGPU_WR_NODEFER restores realvertvl at the end of every step. */
+ * POMGPU_WR_NODEFER restores realvertvl at the end of every step.
+ * uf, vf ON ONE TILE (the same kind of context, kb in 6..64, im and jm >= 8, no address handed out by pomgpu_device_2d / _3d): profu,
+ * profv and the filter of advance.f:469-514 are one kernel on the interior (5 <= i <= im-3, 5 <= j <= jm-3), which leaves the step with
+ * u = uf, v = vf there without storing uf, vf (levels 1..kbm1).  Nothing in the step reads them before the next advq rewrites both
+ * arrays whole, so the copy u -> uf, v -> vf is kept lazily like wr: the same callers as above (all but pomgpu_set_con) make it first,
+ * and the next pomgpu_mode_internal that runs its 3-D part drops it.  POMGPU_UV_NOFUSE keeps the two kernels apart. */
 int pomgpu_run(pomgpu_ctx *ctx, int nsteps);
 
 /* Where the 3-D arrays live (no counterpart in the reference; optional).  The same kernels on the same bytes run up to 6 %

@@ -21,6 +21,8 @@ ROWS = {   # kernel as the profile names it -> (reference lines,
     "k_advct_col": ("a2", "`solver.f:201-408`", "k_advct_col"),
     "k_uv_filter_reg2": ("a19", "`advance.f:469-514`", "k_uv_filter_reg"),
     "k_profuv_reg2": ("a18", "`solver.f:1686-1877`", "k_profuv_reg"),
+    "k_profuv_filter_reg2": ("a18 + a19 (interior)", "`solver.f:1686-1877`, `advance.f:469-514`", "k_profuv_filter_reg2"),
+    "k_uv_filter_rim": ("a19 (frame)", "`advance.f:469-514`", "k_uv_filter_rim"),
     "k_proft_reg2": ("a14 x 2", "`solver.f:1541-1683`", "k_proft_reg"),
     "k_baropg": ("a3", "`solver.f:848-940`", "k_baropg_rs"),
     "k_int_uvmean_reg2": ("a7", "`advance.f:365-393`", "k_int_uvmean_reg"),
@@ -28,7 +30,7 @@ ROWS = {   # kernel as the profile names it -> (reference lines,
     "k_vertvl": ("a8", "`solver.f:1970-2021`", "k_vertvl_rs"),
     "k_aam_pair": ("a1", "`advance.f:122-137`", "k_aam_pair"),
 }
-PASSES = dict(bench.KERNEL_PASSES, k_uv_filter_reg2=10, k_profuv_reg2=6, k_proft_reg2=6, k_int_uvmean_reg2=4, k_baropg=4, k_vertvl=3)
+PASSES = dict(bench.KERNEL_PASSES, k_uv_filter_reg2=10, k_profuv_reg2=6, k_profuv_filter_reg2=12, k_uv_filter_rim=0, k_proft_reg2=6, k_int_uvmean_reg2=4, k_baropg=4, k_vertvl=3)
 TWIN = {"k_uv_filter_reg2", "k_profuv_reg2", "k_proft_reg2", "k_int_uvmean_reg2"}   # traffic.json holds one launch of the pair (older name): x 2
 
 line = json.load(open(sys.argv[1]))
@@ -42,6 +44,9 @@ for k, (rows, ref, tname) in ROWS.items():
     if k not in ms:
         continue
     p = PASSES[k]
+    if not p:                                                 # an edge-line kernel: no full-array pass to set its time against
+        print(f"| `{k}` | {rows} | {ref} | lines | {ms[k]:.2f} | -- | -- |")
+        continue
     alg = p * 8.0 * cells
     frac = alg / (ms[k] * 1e-3) / 1e9 / bench.HBM_PEAK_GBS
     rec = tj.get(f"basin2048/1/{k}") or tj.get(f"basin2048/1/{tname}")
