@@ -1,5 +1,6 @@
 // cdf_out.hip -- the library's file I/O unit: the output and restart files of the reference WITHOUT PnetCDF, written and (the
-// restart file) read back.  Writing is host code plus device-to-host copies; reading has the one kernel of this file, k_cdf_unpack.
+// restart file) read back, and the forcing files read record by record.  Writing is host code plus device-to-host copies; reading has the
+// kernels of this file: k_cdf_unpack (restart), k_frc_unpack, k_lat_unpack, k_rst_unpack (forcing).
 // io_pnetcdf.F writes NetCDF "64-bit offset" files
 // (nf_64bit_offset = CDF-2) through the parallel library: write_output_pnetcdf (:57-410) and
 // write_restart_pnetcdf (:1661-2083).  The classic format is simple enough to emit directly: a header (dimensions,
@@ -355,7 +356,7 @@ extern "C" int pomgpu_write_restart(pomgpu_ctx *c, const char *path, const pomgp
 // above and may hold its variables in another order.  Everything is checked before the first mirror is written.
 namespace {
 struct RVar { std::string name; std::vector<uint32_t> dimids; uint32_t type = 0; uint64_t begin = 0; };
-struct RHeader { std::vector<uint64_t> dimlen; std::vector<RVar> vars; };
+struct RHeader { std::vector<uint64_t> dimlen; std::vector<RVar> vars; uint32_t numrecs = 0; };   // numrecs: records written so far (the forcing files)
 struct Cur {                                                    // big-endian cursor over the bytes read so far
   const unsigned char *p; size_t n, at = 0; bool shortfall = false;
   bool need(size_t k) { if (at + k > n) { shortfall = true; return false; } return true; }
@@ -391,7 +392,7 @@ int parse_header(const unsigned char *buf, size_t n, RHeader &H, std::string &wh
   }
   const bool wide = buf[3] == 2;
   c.at = 4;
-  (void)c.u32();                                                // numrecs
+  H.numrecs = c.u32();
   uint32_t tag = c.u32(), cnt = c.u32();
   if (c.shortfall) return 1;
   H.dimlen.clear(); H.vars.clear();
@@ -618,5 +619,467 @@ extern "C" int pomgpu_read_restart(pomgpu_ctx *c, const char *path, const pomgpu
   if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, POMGPU_EHIP, "read_restart: %s: synchronise failed", path);
   if (time0_out) *time0_out = sc[1];
   if (iint_out) *iint_out = sc[0];
+  return POMGPU_OK;
+}
+
+// ---- forcing records from the files (pomgpu_set_forcing_files) ---------------------------------------------------------------------
+// read_wind_pnetcdf, read_heat_pnetcdf, read_surface_pnetcdf (io_pnetcdf.F:2912-2998, :3110-3224), read_boundary_conditions_pnetcdf
+// (:3393-3621) and read_restore_ts_interior_pnetcdf (:3275-3333) without PnetCDF.  The host names the files once; the schedule code of
+// pomgpu_api.hip (frc_read, lat_read, restore_prepare) asks for record n when the step needs it, and the fetch below puts it where
+// the setter of the same record would have put it: the tile's band of raw big-endian values with pread into a pinned buffer, one copy
+// to the device on the stream the step is being enqueued on, and a kernel that swaps bytes, widens, converts units, tapers the wind
+// and scatters.  Nothing here waits for the device but the reuse of a pinned buffer (an event per buffer).
+namespace {
+struct FVar {                                                   // one variable a reader asks for, as the header describes it
+  const char *name;
+  uint32_t type = 0;                                            // 5 = NC_FLOAT, 6 = NC_DOUBLE
+  bool rec = false;                                             // its first dimension is the unlimited one
+  uint64_t begin = 0, stride = 0, slab = 0;                     // record n at begin + (n-1) * stride; slab: bytes of one record of this variable
+  uint64_t nfixed = 0;                                          // records along a fixed first dimension
+  unsigned esize() const { return type == 5 ? 4u : 8u; }
+};
+struct FSource {
+  int fd = -1;
+  std::string path;
+  uint64_t fsize = 0;
+  uint32_t numrecs = 0;
+  std::vector<FVar> v;
+};
+struct FFiles {
+  FSource s[3];                                                 // sfrc, lbry, clim
+  int im_global = 0, jm_global = 0, i0 = 1, j0 = 1;
+  unsigned char *pin[2] = {NULL, NULL}, *stage = NULL;          // two pinned buffers and the device buffer their copies land in
+  size_t cap = 0;                                               // bytes of each
+#ifndef POMGPU_EMU
+  hipEvent_t ev[2] = {NULL, NULL};                              // the copy out of pin[b] has completed
+  int used[2] = {0, 0};
+#endif
+  int b = 0;
+};
+const char *const FF_WHAT[3] = {"sfrc", "lbry", "clim"};
+const char *const FF_SFRC[6] = {"sustr", "svstr", "shflux", "swrad", "SST", "SSS"};
+const char *const FF_LBRY[10] = {"zeta.east", "zeta.south", "u.east", "v.east", "temp.east", "salt.east", "u.south", "v.south", "temp.south", "salt.south"};
+const char *const FF_CLIM[2] = {"Tclim", "Sclim"};
+
+template <class T> struct CdfRaw;
+template <> struct CdfRaw<float> {
+  static __device__ __forceinline__ double get(const void *p, size_t q) {
+    const unsigned u = __builtin_bswap32(((const unsigned *)p)[q]);
+    float x;
+    __builtin_memcpy(&x, &u, 4);
+    return (double)x;                                           // exact, what get_vara_double does with an NC_FLOAT variable
+  }
+};
+template <> struct CdfRaw<double> {
+  static __device__ __forceinline__ double get(const void *p, size_t q) {
+    const unsigned long long u = __builtin_bswap64(((const unsigned long long *)p)[q]);
+    double x;
+    __builtin_memcpy(&x, &u, 8);
+    return x;
+  }
+};
+}  // namespace
+
+// the reader's unit conversion, in its own order and with its own literals
+__device__ __forceinline__ double frc_convert(int kind, double x, double rhoref) {
+  if (kind == 0) return -x / 1025.;                             // io_pnetcdf.F:2963-2964
+  if (kind == 1) return -x / rhoref / 3986.;                    // :3163-3164
+  return x;
+}
+// The wind taper (:2966-2995) of the cell (i,j), whose converted value is x; m = dum for wu, dvm for wv.  The interior, the four edge
+// lines and the four corners have a formula each; the corners see raw values because no statement before theirs writes them.  Row jm
+// of the columns 2..imm1 is formed from ROW 1 as the statement before has left it (":2971 wu(2:imm1,jm) = wu(2:imm1,1)/3.d0*..."), so
+// the caller hands that lane x1 = the converted value of (i,1) and the lane redoes row 1's statement itself.
+__device__ __forceinline__ double frc_taper(const KP &P, const double *m, int i, int j, double x, double x1) {
+  const int im = P.im, jm = P.jm;
+  const bool iin = i >= 2 && i <= im - 1, jin = j >= 2 && j <= jm - 1;
+  if (iin && jin) return .25 * x * (G2(m, i, j + 1) + G2(m, i, j - 1) + G2(m, i + 1, j) + G2(m, i - 1, j));
+  if (iin && j == 1) return x / 3. * (G2(m, i, 2) + G2(m, i - 1, 1) + G2(m, i + 1, 1));
+  if (iin) {                                                    // j == jm
+    const double r1 = x1 / 3. * (G2(m, i, 2) + G2(m, i - 1, 1) + G2(m, i + 1, 1));
+    return r1 / 3. * (G2(m, i, jm - 1) + G2(m, i - 1, jm) + G2(m, i + 1, jm));
+  }
+  if (jin && i == 1) return x / 3. * (G2(m, 2, j) + G2(m, 1, j - 1) + G2(m, 1, j + 1));
+  if (jin) return x / 3. * (G2(m, im - 1, j) + G2(m, im, j - 1) + G2(m, im, j + 1));   // i == im
+  if (i == 1 && j == 1) return .5 * x * (G2(m, 1, 2) + G2(m, 2, 1));
+  if (j == 1) return .5 * x * (G2(m, im, 2) + G2(m, im - 1, 1));
+  if (i == im) return .5 * x * (G2(m, im, jm - 1) + G2(m, im - 1, jm));
+  return .5 * x * (G2(m, 1, jm - 1) + G2(m, 2, jm));
+}
+// One record of wind (kind 0), heat (1) or surface (2): the tile's band of rows of one or two variables (raw bytes at sa, sb -- sb NULL:
+// the second field is not wanted -- `pitch` values per row, the tile's first column at i0) into the (im,jm) records da, db that
+// pomgpu_set_forcing_record fills.  Thread mapping of k_cdf_unpack: threadIdx.x runs along i.
+template <class TA, class TB>
+__global__ void k_frc_unpack(KP P, int kind, double *da, double *db, const void *sa, const void *sb, int pitch, int i0) {
+  const int i = TID_I, j = TID_J;
+  if (i > P.im || j > P.jm) return;
+  const size_t q = (size_t)(j - 1) * (size_t)pitch + (size_t)(i0 + i - 1), q1 = (size_t)(i0 + i - 1);
+  const size_t r = (size_t)(j - 1) * P.im + (size_t)(i - 1);
+  const bool top = kind == 0 && j == P.jm;                          // the only lanes that need their column's row-1 value
+  double a = frc_convert(kind, CdfRaw<TA>::get(sa, q), P.rhoref);
+  if (kind == 0) a = frc_taper(P, A2(dum), i, j, a, top ? frc_convert(0, CdfRaw<TA>::get(sa, q1), P.rhoref) : 0.);
+  da[r] = a;
+  if (!sb) return;
+  double b = frc_convert(kind, CdfRaw<TB>::get(sb, q), P.rhoref);
+  if (kind == 0) b = frc_taper(P, A2(dvm), i, j, b, top ? frc_convert(0, CdfRaw<TB>::get(sb, q1), P.rhoref) : 0.);
+  db[r] = b;
+}
+// One record of read_boundary_conditions_pnetcdf (:3426-3614) into the 20 concatenated arrays pomgpu_set_lateral_record fills (the order
+// of the reader's arguments; k_lateral's phase 0 consumes them).  One thread per edge point, as in k_lateral.  From the file, compact
+// (the tile's jm or im values per level): src[0] zeta.east, [1] zeta.south, [2..5] u v temp salt .east, [6..9] u v temp salt .south;
+// f32 bit q: that variable is NC_FLOAT.  t_w s_w / t_n s_n: line i = 1 / j = jm of tclim, sclim; u_w v_w u_n v_n: zero; everything
+// beyond jm / im: zero, but in the elevations, which the reader leaves as they are there -- as it leaves elw, eln everywhere.
+struct LatSrc { const void *p[10]; unsigned f32; };
+__device__ __forceinline__ double lat_raw(const LatSrc &s, int q, size_t at) { return (s.f32 >> q) & 1u ? CdfRaw<float>::get(s.p[q], at) : CdfRaw<double>::get(s.p[q], at); }
+__global__ void k_lat_unpack(KP P, double *rec, LatSrc s) {
+  const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int kb = P.kb, jml = P.jml, iml = P.iml;
+  if (t >= jml + iml) return;
+  const size_t njk = (size_t)jml * kb, nik = (size_t)iml * kb;
+  double *e = rec + 8 * njk + 8 * nik;                            // elw ele (jml each), eln els (iml each)
+  if (t < jml) {
+    const int a = t + 1;
+    const bool in = a <= P.jm;
+    for (int k = 1; k <= kb; k++) {
+      const size_t o = (size_t)(k - 1) * jml + (a - 1), f = (size_t)(k - 1) * P.jm + (a - 1);
+      rec[o] = in ? (double)F3(tclim, 1, a, k) : 0.;
+      rec[njk + o] = in ? (double)F3(sclim, 1, a, k) : 0.;
+      rec[2 * njk + o] = 0.;
+      rec[3 * njk + o] = 0.;
+      rec[4 * njk + o] = in ? lat_raw(s, 4, f) : 0.;
+      rec[5 * njk + o] = in ? lat_raw(s, 5, f) : 0.;
+      rec[6 * njk + o] = in ? lat_raw(s, 2, f) : 0.;
+      rec[7 * njk + o] = in ? lat_raw(s, 3, f) : 0.;
+    }
+    e[a - 1] = BD1(elw, a);
+    e[jml + a - 1] = in ? lat_raw(s, 0, (size_t)(a - 1)) : BD1(ele, a);
+  } else {
+    const int a = t - jml + 1;
+    const bool in = a <= P.im;
+    double *r = rec + 8 * njk;
+    for (int k = 1; k <= kb; k++) {
+      const size_t o = (size_t)(k - 1) * iml + (a - 1), f = (size_t)(k - 1) * P.im + (a - 1);
+      r[o] = in ? (double)F3(tclim, a, P.jm, k) : 0.;
+      r[nik + o] = in ? (double)F3(sclim, a, P.jm, k) : 0.;
+      r[2 * nik + o] = 0.;
+      r[3 * nik + o] = 0.;
+      r[4 * nik + o] = in ? lat_raw(s, 8, f) : 0.;
+      r[5 * nik + o] = in ? lat_raw(s, 9, f) : 0.;
+      r[6 * nik + o] = in ? lat_raw(s, 7, f) : 0.;
+      r[7 * nik + o] = in ? lat_raw(s, 6, f) : 0.;
+    }
+    e[2 * (size_t)jml + a - 1] = BD1(eln, a);
+    e[2 * (size_t)jml + iml + a - 1] = in ? lat_raw(s, 1, (size_t)(a - 1)) : BD1(els, a);
+  }
+}
+// Levels k0 .. k0+gridDim.z-1 of Tclim or Sclim (bands of `rows` rows, `pitch` values per row) into the (im,jm,kb) record
+// pomgpu_set_restore_record fills; k_restore_load rounds it into the fp32-storage variants' mirrors as it does the setter's.
+template <class T>
+__global__ void k_rst_unpack(double *dst, const void *src, int im, int jm, int rows, int pitch, int i0, int k0) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x), j = (int)(blockIdx.y * blockDim.y + threadIdx.y), k = (int)blockIdx.z;
+  if (i >= im || j >= jm) return;
+  dst[((size_t)(k0 + k) * jm + j) * im + i] = CdfRaw<T>::get(src, ((size_t)k * rows + j) * (size_t)pitch + (size_t)(i0 + i));
+}
+
+static FFiles *FF(pomgpu_ctx *c) { return (FFiles *)c->frc_files; }
+int pomgpu_ff_has(pomgpu_ctx *c, int src) { return c->frc_files && FF(c)->s[src].fd >= 0; }
+void pomgpu_ff_free(pomgpu_ctx *c) {
+  FFiles *F = FF(c);
+  if (!F) return;
+  for (FSource &s : F->s) if (s.fd >= 0) (void)close(s.fd);
+#ifndef POMGPU_EMU
+  for (int b = 0; b < 2; b++) { if (F->ev[b]) (void)hipEventDestroy(F->ev[b]); if (F->pin[b]) (void)hipHostFree(F->pin[b]); }
+  if (F->stage) (void)hipFree(F->stage);
+#else
+  if (F->pin[0]) (void)hipFree(F->pin[0]);
+#endif
+  delete F;
+  c->frc_files = NULL;
+}
+// the header of `fd`, whole: 0 = parsed, -1 = refused (why: `what`)
+static int ff_header(int fd, uint64_t fsize, RHeader &H, std::string &what) {
+  std::vector<unsigned char> hb;
+  int rc = 1;
+  for (size_t want = 1 << 16; rc == 1; want *= 4) {
+    const size_t n = (size_t)(want < fsize ? want : fsize);
+    hb.resize(n);
+    if (n && pread_all(fd, hb.data(), n, 0)) { what = "I/O error (header)"; return -1; }
+    rc = parse_header(hb.data(), n, H, what);
+    if (rc == 1 && n == fsize) { what = fsize ? "the file ends inside its header" : "the file is empty"; rc = -1; }
+  }
+  return rc;
+}
+// One source's variables against what its reader asks for: `want[q]` = the dimension lengths after the record dimension; min_rec: records a
+// fixed first dimension must at least have.  Empty string = accepted, S.v filled.
+static std::string ff_check(const RHeader &H, FSource &S, const char *const *names, const std::vector<std::vector<uint64_t>> &want, uint64_t min_rec) {
+  // bytes of one record of the file: the record variables' per-record sizes, each from its dimensions, padded to 4 bytes (a lone record
+  // variable is not padded); vsize is not trusted (it saturates)
+  uint64_t recsize = 0, lone = 0;
+  int nrecvar = 0;
+  for (const RVar &v : H.vars) {
+    if (v.dimids.empty() || H.dimlen[v.dimids[0]] != 0) continue;
+    if (v.type < 1 || v.type > 6) return "variable " + v.name + " has the unknown NetCDF type " + std::to_string(v.type);
+    uint64_t n = NC_TYPE_BYTES[v.type];
+    for (size_t d = 1; d < v.dimids.size(); d++) if (__builtin_mul_overflow(n, H.dimlen[v.dimids[d]], &n)) return "variable " + v.name + " is larger than 2^64 bytes";
+    recsize += (n + 3) & ~(uint64_t)3;
+    lone = n;
+    nrecvar++;
+  }
+  if (nrecvar == 1) recsize = lone;
+  S.v.clear();
+  S.numrecs = H.numrecs;
+  for (size_t q = 0; q < want.size(); q++) {
+    const char *name = names[q];
+    const RVar *v = NULL;
+    for (const RVar &x : H.vars) if (x.name == name) { v = &x; break; }
+    if (!v) return std::string("variable ") + name + " is absent";
+    if (v->type != 5 && v->type != 6) return std::string("variable ") + name + " has NetCDF type " + std::to_string(v->type) + ", neither NC_FLOAT (5) nor NC_DOUBLE (6)";
+    bool same = v->dimids.size() == want[q].size() + 1;
+    for (size_t d = 1; same && d < v->dimids.size(); d++) if (H.dimlen[v->dimids[d]] != want[q][d - 1]) same = false;
+    if (same && H.dimlen[v->dimids[0]] != 0 && H.dimlen[v->dimids[0]] < min_rec) same = false;
+    if (!same) {
+      std::string w = min_rec > 1 ? "(>= " + std::to_string(min_rec) : std::string("(records");
+      for (uint64_t len : want[q]) w += ", " + std::to_string(len);
+      return std::string("variable ") + name + " has the dimension lengths " + lengths_of(H, *v) + ", wanted " + w + ")";
+    }
+    FVar f;
+    f.name = name; f.type = v->type; f.begin = v->begin;
+    f.slab = f.esize();
+    for (uint64_t len : want[q]) f.slab *= len;
+    f.rec = H.dimlen[v->dimids[0]] == 0;
+    f.stride = f.rec ? recsize : f.slab;
+    f.nfixed = f.rec ? 0 : H.dimlen[v->dimids[0]];
+    const uint64_t nrec = f.rec ? (uint64_t)H.numrecs : f.nfixed;
+    if (f.rec && H.numrecs == 0xffffffffu) { S.v.push_back(f); continue; }   // "streaming": the length is known at the fetch alone
+    if (f.begin > S.fsize || (nrec && ((nrec - 1) > (S.fsize - f.begin) / (f.stride ? f.stride : 1) || (nrec - 1) * f.stride + f.slab > S.fsize - f.begin)))
+      return std::string("variable ") + name + " (" + std::to_string(nrec) + " records of " + std::to_string(f.slab) + " bytes from " + std::to_string(f.begin) +
+             ") reaches beyond the file's " + std::to_string(S.fsize) + " bytes: a truncated file";
+    S.v.push_back(f);
+  }
+  if (min_rec > 1 && S.v[0].rec && H.numrecs < min_rec) return std::string("variable ") + names[0] + " has " + std::to_string(H.numrecs) + " records, wanted >= " + std::to_string(min_rec);
+  return std::string();
+}
+
+extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const char *lbry, const char *clim, const pomgpu_file_meta *m) {
+  if (!c || !m) return POMGPU_EINVAL;
+  (void)hipSetDevice(c->device);
+  const KP &P = c->P;
+  if (m->i0 < 1 || m->j0 < 1 || m->i0 + P.im - 1 > m->im_global || m->j0 + P.jm - 1 > m->jm_global)
+    return fail(c, POMGPU_EINVAL, "set_forcing_files: the tile (%d..%d, %d..%d) does not fit the global grid %d x %d", m->i0, m->i0 + P.im - 1, m->j0,
+                m->j0 + P.jm - 1, m->im_global, m->jm_global);
+  if (P.im < 3 || P.jm < 3) return fail(c, POMGPU_EINVAL, "set_forcing_files: the wind taper needs a tile of at least 3 x 3 cells");
+  FFiles *old = FF(c);
+  if (old && (old->im_global != m->im_global || old->jm_global != m->jm_global || old->i0 != m->i0 || old->j0 != m->j0))
+    return fail(c, POMGPU_EINVAL, "set_forcing_files: files are registered under another global grid or tile origin");
+  const uint64_t img = (uint64_t)m->im_global, jmg = (uint64_t)m->jm_global, kb = (uint64_t)P.kb;
+  const char *paths[3] = {sfrc, lbry, clim};
+  FSource fresh[3];
+  auto drop = [&]() { for (FSource &s : fresh) if (s.fd >= 0) (void)close(s.fd); };
+  for (int q = 0; q < 3; q++) {                                 // every file is opened and checked before anything is kept
+    if (!paths[q]) continue;
+    FSource &S = fresh[q];
+    S.path = paths[q];
+    S.fd = open(paths[q], O_RDONLY);
+    if (S.fd < 0) { drop(); return fail(c, POMGPU_EINVAL, "set_forcing_files: cannot open %s", paths[q]); }
+    struct stat sb;
+    if (fstat(S.fd, &sb)) { drop(); return fail(c, POMGPU_EINVAL, "set_forcing_files: cannot stat %s", paths[q]); }
+    S.fsize = (uint64_t)sb.st_size;
+    RHeader H;
+    std::string what;
+    if (ff_header(S.fd, S.fsize, H, what) < 0) { drop(); return fail(c, POMGPU_EINVAL, "set_forcing_files: %s is not a %s file this library reads: %s", paths[q], FF_WHAT[q], what.c_str()); }
+    std::string why;
+    if (q == 0) why = ff_check(H, S, FF_SFRC, std::vector<std::vector<uint64_t>>(6, {jmg, img}), 1);
+    else if (q == 1) why = ff_check(H, S, FF_LBRY, {{jmg}, {img}, {kb, jmg}, {kb, jmg}, {kb, jmg}, {kb, jmg}, {kb, img}, {kb, img}, {kb, img}, {kb, img}}, 1);
+    else why = ff_check(H, S, FF_CLIM, {{kb, jmg, img}, {kb, jmg, img}}, 12);
+    if (!why.empty()) { drop(); return fail(c, POMGPU_EINVAL, "set_forcing_files: %s: %s", paths[q], why.c_str()); }
+  }
+  // ---- accepted: the buffers every fetch uses, sized once (no allocation inside a step) ----
+  FFiles *F = old ? old : new FFiles();
+  const size_t band2 = (size_t)P.jm * (size_t)img * 8;           // one level's band of rows at the file's full width, doubles
+  size_t run = (SW(c, IO_CHUNK_KB) && SWV(c, IO_CHUNK_KB) > 0 ? (size_t)SWV(c, IO_CHUNK_KB) << 10 : (size_t)64 << 20);
+  if (run < band2) run = band2;
+  if (run > band2 * (size_t)P.kb) run = band2 * (size_t)P.kb;
+  size_t need = 2 * band2;                                        // sfrc: two variables' bands
+  const size_t lat = 8 * ((size_t)P.jm + P.im) + 4 * 8 * (size_t)P.kb * ((size_t)P.jm + P.im);
+  if (need < lat) need = lat;
+  if (need < run) need = run;
+  int bad = 0;
+  if (F->cap < need) {
+    if (hipStreamSynchronize(c->stream) != hipSuccess) bad = 1;   // (a second registration: earlier fetches may still be copying)
+#ifndef POMGPU_EMU
+    for (int b = 0; b < 2; b++) { if (F->pin[b]) (void)hipHostFree(F->pin[b]); F->pin[b] = NULL; F->used[b] = 0; }
+    if (F->stage) (void)hipFree(F->stage);
+    F->stage = NULL;
+    if (hipHostMalloc((void **)&F->pin[0], need, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void **)&F->pin[1], need, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc((void **)&F->stage, need) != hipSuccess) bad = 1;
+    for (int b = 0; b < 2 && !bad; b++) if (!F->ev[b] && hipEventCreateWithFlags(&F->ev[b], hipEventDisableTiming) != hipSuccess) bad = 1;
+#else
+    if (F->pin[0]) (void)hipFree(F->pin[0]);
+    if (hipMalloc((void **)&F->pin[0], need) != hipSuccess) bad = 1;
+    F->stage = F->pin[0];                                         // host emulation: one buffer, no copy
+#endif
+    F->cap = bad ? 0 : need;
+  }
+  // the slots the setters would have allocated on their first call
+  const size_t rec2 = sizeof(double) * (size_t)P.im * P.jm, rec3 = rec2 * (size_t)P.kb;
+  const size_t latrec = sizeof(double) * (8 * (size_t)P.jml * P.kb + 8 * (size_t)P.iml * P.kb + 2 * (size_t)P.jml + 2 * (size_t)P.iml);
+  if (!bad && paths[0])
+    for (int k = 0; k < 3; k++) for (int sl = 0; sl < 4; sl++) for (int f = 0; f < 2; f++)
+      if (!c->frc_dev[k][sl][f] && hipMalloc((void **)&c->frc_dev[k][sl][f], rec2) != hipSuccess) bad = 1;
+  if (!bad && paths[1]) for (int sl = 0; sl < 4; sl++) if (!c->lat_dev[sl] && hipMalloc((void **)&c->lat_dev[sl], latrec) != hipSuccess) bad = 1;
+  if (!bad && paths[2] && !c->rec_t[0] && (hipMalloc((void **)&c->rec_t[0], rec3) != hipSuccess || hipMalloc((void **)&c->rec_s[0], rec3) != hipSuccess)) bad = 1;
+  c->frc_files = F;
+  if (bad) {
+    drop();
+    (void)hipGetLastError();
+    if (!old) pomgpu_ff_free(c);
+    return fail(c, POMGPU_ENOMEM, "set_forcing_files: no memory for the read buffers (%zu bytes, twice pinned)", need);
+  }
+  F->im_global = m->im_global; F->jm_global = m->jm_global; F->i0 = m->i0; F->j0 = m->j0;
+  for (int q = 0; q < 3; q++) {
+    if (!paths[q]) continue;
+    if (F->s[q].fd >= 0) (void)close(F->s[q].fd);
+    F->s[q] = fresh[q];
+    if (q == 0) { for (int k = 0; k < 3; k++) for (int sl = 0; sl < 4; sl++) c->frc_n[k][sl] = 0; c->frc_on = 1; }   // records the setters left are not the file's
+    if (q == 1) { for (int sl = 0; sl < 4; sl++) c->lat_n[sl] = 0; c->lat_on = 1; }
+  }
+  return POMGPU_OK;
+}
+
+// Is record n (1-based) of every variable in `which` inside the file?  A record beyond numrecs or the file's end gets ONE second look
+// (the file may have grown); then the step fails, before anything is written.
+static int ff_have(pomgpu_ctx *c, FSource &S, const char *who, int n, std::initializer_list<int> which) {
+  for (int pass = 0; pass < 2; pass++) {
+    bool ok = n >= 1;
+    for (int q : which) {
+      const FVar &f = S.v[q];
+      const uint64_t nrec = f.rec ? (uint64_t)S.numrecs : f.nfixed;
+      if (!ok || (uint64_t)n > nrec) { ok = false; break; }
+      if (f.begin > S.fsize || (uint64_t)(n - 1) > (S.fsize - f.begin) / (f.stride ? f.stride : 1) || (uint64_t)(n - 1) * f.stride + f.slab > S.fsize - f.begin) { ok = false; break; }
+    }
+    if (ok) return POMGPU_OK;
+    if (pass == 1 || n < 1) break;
+    unsigned char h8[8];
+    struct stat sb;
+    if (fstat(S.fd, &sb) || pread_all(S.fd, h8, 8, 0)) break;
+    S.fsize = (uint64_t)sb.st_size;
+    S.numrecs = ((uint32_t)h8[4] << 24) | ((uint32_t)h8[5] << 16) | ((uint32_t)h8[6] << 8) | (uint32_t)h8[7];
+  }
+  return fail(c, POMGPU_EINVAL, "%s: record %d is not in %s (%u records, %llu bytes)", who, n, S.path.c_str(), (unsigned)S.numrecs, (unsigned long long)S.fsize);
+}
+// a pinned buffer free for the next run's preads / its bytes on their way to the device, in stream order behind the kernels that read the last run
+static unsigned char *ff_buffer(FFiles *F) {
+#ifndef POMGPU_EMU
+  if (F->used[F->b] && hipEventSynchronize(F->ev[F->b]) != hipSuccess) return NULL;
+#endif
+  return F->pin[F->b];
+}
+static int ff_send(pomgpu_ctx *c, FFiles *F, size_t bytes) {
+#ifndef POMGPU_EMU
+  if (hipMemcpyAsync(F->stage, F->pin[F->b], bytes, hipMemcpyHostToDevice, c->cur) != hipSuccess || hipEventRecord(F->ev[F->b], c->cur) != hipSuccess) return 1;
+  F->used[F->b] = 1;
+  F->b ^= 1;
+#else
+  (void)c; (void)bytes;
+#endif
+  return 0;
+}
+static int ff_io_error(pomgpu_ctx *c, const char *who, int n, const FSource &S, int hip) {
+  if (hip) (void)hipGetLastError();
+  return fail(c, hip ? POMGPU_EHIP : POMGPU_EINVAL, hip ? "%s: a HIP call failed while reading record %d of %s" : "%s: I/O error reading record %d of %s", who, n, S.path.c_str());
+}
+
+// record n of wind (kind 0), heat (1), surface (2) into the slot pomgpu_set_forcing_record(kind, n, ...) fills
+int pomgpu_ff_fetch_surface(pomgpu_ctx *c, int kind, int n) {
+  FFiles *F = FF(c);
+  FSource &S = F->s[0];
+  const KP &P = c->P;
+  static const char *const who[3] = {"wind", "heat", "surface"};
+  const int va = 2 * kind, vb = 2 * kind + 1, nvar = kind == 2 ? 1 : 2;   // SSS is read by the reference and dropped (bounds_forcing.f:978-979): not read here
+  int rc = kind == 2 ? ff_have(c, S, who[kind], n, {va}) : ff_have(c, S, who[kind], n, {va, vb});
+  if (rc) return rc;
+  const int sl = n % 4;
+  unsigned char *pin = ff_buffer(F);
+  if (!pin) return ff_io_error(c, who[kind], n, S, 1);
+  const size_t half = (size_t)P.jm * (size_t)F->im_global * 8;   // where the second variable's band starts (8-byte aligned whatever the types)
+  for (int q = 0; q < nvar; q++) {
+    const FVar &f = S.v[q ? vb : va];
+    const uint64_t at = f.begin + (uint64_t)(n - 1) * f.stride + (uint64_t)(F->j0 - 1) * (uint64_t)F->im_global * f.esize();
+    if (pread_all(S.fd, pin + q * half, (size_t)P.jm * (size_t)F->im_global * f.esize(), at)) return ff_io_error(c, who[kind], n, S, 0);
+  }
+  if (ff_send(c, F, nvar == 2 ? 2 * half : half)) return ff_io_error(c, who[kind], n, S, 1);
+  double *da = c->frc_dev[kind][sl][0], *db = c->frc_dev[kind][sl][1];
+  const void *sa = F->stage, *sb = nvar == 2 ? (const void *)(F->stage + half) : NULL;
+  const bool fa = S.v[va].type == 5, fb = nvar == 2 && S.v[vb].type == 5;
+  const int pitch = F->im_global, i0 = F->i0 - 1;
+  if (fa && fb) LAUNCHN(c, "k_frc_unpack", (k_frc_unpack<float, float>), grid2(P), blk2(), P, kind, da, db, sa, sb, pitch, i0);
+  else if (fa) LAUNCHN(c, "k_frc_unpack", (k_frc_unpack<float, double>), grid2(P), blk2(), P, kind, da, db, sa, sb, pitch, i0);
+  else if (fb) LAUNCHN(c, "k_frc_unpack", (k_frc_unpack<double, float>), grid2(P), blk2(), P, kind, da, db, sa, sb, pitch, i0);
+  else LAUNCHN(c, "k_frc_unpack", (k_frc_unpack<double, double>), grid2(P), blk2(), P, kind, da, db, sa, sb, pitch, i0);
+  c->frc_n[kind][sl] = n;
+  return POMGPU_OK;
+}
+// record n of the lateral file into the slot pomgpu_set_lateral_record(n, ...) fills
+int pomgpu_ff_fetch_lateral(pomgpu_ctx *c, int n) {
+  FFiles *F = FF(c);
+  FSource &S = F->s[1];
+  const KP &P = c->P;
+  int rc = ff_have(c, S, "lateral_bc", n, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9});
+  if (rc) return rc;
+  const int sl = n % 4;
+  unsigned char *pin = ff_buffer(F);
+  if (!pin) return ff_io_error(c, "lateral_bc", n, S, 1);
+  LatSrc src;
+  src.f32 = 0;
+  size_t at = 0, off[10];
+  for (int q = 0; q < 10; q++) {
+    const FVar &f = S.v[q];
+    const bool east = q == 0 || (q >= 2 && q <= 5);              // along j: the tile's jm values from j0; else im values from i0
+    const int nlev = q < 2 ? 1 : P.kb;
+    const uint64_t glen = east ? (uint64_t)F->jm_global : (uint64_t)F->im_global, first = (uint64_t)((east ? F->j0 : F->i0) - 1);
+    const size_t len = (size_t)(east ? P.jm : P.im) * f.esize();
+    const uint64_t base = f.begin + (uint64_t)(n - 1) * f.stride + first * f.esize();
+    off[q] = at;
+    if ((uint64_t)(east ? P.jm : P.im) == glen) { if (pread_all(S.fd, pin + at, len * nlev, base)) return ff_io_error(c, "lateral_bc", n, S, 0); }
+    else for (int k = 0; k < nlev; k++) if (pread_all(S.fd, pin + at + (size_t)k * len, len, base + (uint64_t)k * glen * f.esize())) return ff_io_error(c, "lateral_bc", n, S, 0);
+    at += (len * nlev + 7) & ~(size_t)7;
+    if (f.type == 5) src.f32 |= 1u << q;
+  }
+  if (ff_send(c, F, at)) return ff_io_error(c, "lateral_bc", n, S, 1);
+  for (int q = 0; q < 10; q++) src.p[q] = F->stage + off[q];
+  const int nt = P.jml + P.iml;
+  LAUNCH(c, k_lat_unpack, dim3((unsigned)((nt + 63) / 64), 1, 1), dim3(64, 1, 1), P, c->lat_dev[sl], src);
+  c->lat_n[sl] = n;
+  return POMGPU_OK;
+}
+// Tclim, Sclim of month mod(n+9,12)+1 (io_pnetcdf.F:3316) into rec_t[0], rec_s[0], the (im,jm,kb) records k_restore_load reads
+int pomgpu_ff_fetch_restore(pomgpu_ctx *c, int n) {
+  FFiles *F = FF(c);
+  FSource &S = F->s[2];
+  const KP &P = c->P;
+  if (n < 1) return fail(c, POMGPU_EINVAL, "restore_interior: record %d", n);
+  const int month = (n + 9) % 12 + 1;
+  int rc = ff_have(c, S, "restore_interior", month, {0, 1});
+  if (rc) return rc;
+  const uint64_t img = (uint64_t)F->im_global, jmg = (uint64_t)F->jm_global;
+  const size_t band = (size_t)P.jm * (size_t)img;                // values of one level's band
+  const bool whole_rows = (uint64_t)P.jm == jmg;
+  for (int q = 0; q < 2; q++) {
+    const FVar &f = S.v[q];
+    const int lev_per_run = (int)(F->cap / (band * f.esize())) < P.kb ? (int)(F->cap / (band * f.esize())) : P.kb;
+    double *dst = q ? c->rec_s[0] : c->rec_t[0];
+    for (int k0 = 0; k0 < P.kb; k0 += lev_per_run) {
+      const int nl = P.kb - k0 < lev_per_run ? P.kb - k0 : lev_per_run;
+      unsigned char *pin = ff_buffer(F);
+      if (!pin) return ff_io_error(c, "restore_interior", n, S, 1);
+      const uint64_t first = f.begin + (uint64_t)(month - 1) * f.stride + (((uint64_t)k0 * jmg + (uint64_t)(F->j0 - 1)) * img) * f.esize();
+      if (whole_rows) { if (pread_all(S.fd, pin, (size_t)nl * band * f.esize(), first)) return ff_io_error(c, "restore_interior", n, S, 0); }
+      else for (int k = 0; k < nl; k++) if (pread_all(S.fd, pin + (size_t)k * band * f.esize(), band * f.esize(), first + (uint64_t)k * jmg * img * f.esize())) return ff_io_error(c, "restore_interior", n, S, 0);
+      if (ff_send(c, F, (size_t)nl * band * f.esize())) return ff_io_error(c, "restore_interior", n, S, 1);
+      const dim3 grid((unsigned)((P.im + 63) / 64), (unsigned)((P.jm + 3) / 4), (unsigned)nl);
+      if (f.type == 5) LAUNCHN(c, "k_rst_unpack", k_rst_unpack<float>, grid, blk2(), dst, (const void *)F->stage, P.im, P.jm, P.jm, (int)img, F->i0 - 1, k0);
+      else LAUNCHN(c, "k_rst_unpack", k_rst_unpack<double>, grid, blk2(), dst, (const void *)F->stage, P.im, P.jm, P.jm, (int)img, F->i0 - 1, k0);
+    }
+  }
   return POMGPU_OK;
 }

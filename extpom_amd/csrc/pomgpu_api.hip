@@ -403,6 +403,7 @@ extern "C" void pomgpu_destroy(pomgpu_ctx *c) {
                     "before pomgpu_destroy to get its status\n");
   wide_free(c);
   pomgpu_tp_free(c);
+  pomgpu_ff_free(c);
   KP &P = c->P;
   (void)hipFree(P.r1);
   if (c->tune_block) {                                        // pomgpu_tune_placement: blk3d and the scratch arrays are pieces of one allocation
@@ -639,6 +640,7 @@ extern "C" int pomgpu_bind_host(pomgpu_ctx *c, const double *h2, const double *h
 }
 extern "C" int pomgpu_set_restore_record(pomgpu_ctx *c, int n, const double *tr, const double *sr) {
   if (!c || n < 1 || n > POMGPU_MAXREC || !tr || !sr) return POMGPU_EINVAL;
+  if (pomgpu_ff_has(c, 2)) return fail(c, POMGPU_EINVAL, "set_restore_record: the restore records come from a file (pomgpu_set_forcing_files)");
   const size_t cnt = (size_t)c->P.im * c->P.jm * c->P.kb;
   if (!c->rec_t[n]) {
     HIPCHK(c, hipMalloc((void **)&c->rec_t[n], cnt * sizeof(double)));
@@ -847,6 +849,13 @@ static int restore_prepare(pomgpu_ctx *c, double *fold_out, double *fnew_out) { 
   const int irst = (int)(trst * 86400. / k.dti);
   const int ntime = (int)(k.time / trst);
   auto load = [&](int n) -> int {
+    if (pomgpu_ff_has(c, 2)) {                                  // read_restore_ts_interior_pnetcdf(n, ...) from the file
+      const int rc = pomgpu_ff_fetch_restore(c, n);
+      if (rc) return rc;
+      launch_restore_load(c, c->rec_t[0], c->rec_s[0], 1. / trst);
+      c->tau_known[1] = 1; c->tau_val[1] = 1. / trst;
+      return POMGPU_OK;
+    }
     if (n < 1 || n > POMGPU_MAXREC || !c->rec_t[n])
       return fail(c, POMGPU_EINVAL, "restore_interior: record %d was not supplied (pomgpu_set_restore_record)", n);
     launch_restore_load(c, c->rec_t[n], c->rec_s[n], 1. / trst);
@@ -1834,6 +1843,7 @@ extern "C" int pomgpu_check_velocity(pomgpu_ctx *c, double *vamax, int *imax, in
 extern "C" int pomgpu_set_forcing_record(pomgpu_ctx *c, int kind, int n, const double *a, const double *b) {
   NEED(c);
   if (kind < 0 || kind > 2 || n < 1 || !a || !b) return fail(c, POMGPU_EINVAL, "set_forcing_record: kind 0..2, n >= 1, two (im,jm) fields");
+  if (pomgpu_ff_has(c, 0)) return fail(c, POMGPU_EINVAL, "set_forcing_record: the surface records come from a file (pomgpu_set_forcing_files)");
   const int sl = n % 4;
   const size_t bytes = sizeof(double) * (size_t)c->P.im * c->P.jm;
   for (int f = 0; f < 2; f++) {
@@ -1847,7 +1857,8 @@ extern "C" int pomgpu_set_forcing_record(pomgpu_ctx *c, int kind, int n, const d
 }
 static int frc_read(pomgpu_ctx *c, int kind, int n, double *xf, double *yf) {   // what read_*_pnetcdf(n, ...) delivers
   const int sl = ((n % 4) + 4) % 4;
-  if (n < 1 || c->frc_n[kind][sl] != n)
+  if (pomgpu_ff_has(c, 0)) { const int rc = pomgpu_ff_fetch_surface(c, kind, n); if (rc) return rc; }   // the file's record n, into the slot the setter fills
+  else if (n < 1 || c->frc_n[kind][sl] != n)
     return fail(c, POMGPU_EINVAL, "%s: record %d was not supplied (pomgpu_set_forcing_record)", kind == 0 ? "wind" : kind == 1 ? "heat" : "surface", n);
   launch_frc_load(c, c->frc_dev[kind][sl][0], c->frc_dev[kind][sl][1], xf, yf);
   return POMGPU_OK;
@@ -1895,6 +1906,7 @@ extern "C" int pomgpu_surface_forcing(pomgpu_ctx *c) {        // advance.f:77-93
 extern "C" int pomgpu_set_lateral_record(pomgpu_ctx *c, int n, const double *const *a) {
   NEED(c);
   if (n < 1 || !a) return fail(c, POMGPU_EINVAL, "set_lateral_record: n >= 1 and 20 arrays");
+  if (pomgpu_ff_has(c, 1)) return fail(c, POMGPU_EINVAL, "set_lateral_record: the lateral records come from a file (pomgpu_set_forcing_files)");
   const KP &P = c->P;
   const size_t njk = (size_t)P.jml * P.kb, nik = (size_t)P.iml * P.kb;
   const size_t total = 8 * njk + 8 * nik + 2 * (size_t)P.jml + 2 * (size_t)P.iml;
@@ -1914,7 +1926,8 @@ extern "C" int pomgpu_set_lateral_record(pomgpu_ctx *c, int n, const double *con
 }
 static int lat_read(pomgpu_ctx *c, int n) {
   const int sl = ((n % 4) + 4) % 4;
-  if (n < 1 || c->lat_n[sl] != n) return fail(c, POMGPU_EINVAL, "lateral_bc: record %d was not supplied (pomgpu_set_lateral_record)", n);
+  if (pomgpu_ff_has(c, 1)) { const int rc = pomgpu_ff_fetch_lateral(c, n); if (rc) return rc; }
+  else if (n < 1 || c->lat_n[sl] != n) return fail(c, POMGPU_EINVAL, "lateral_bc: record %d was not supplied (pomgpu_set_lateral_record)", n);
   launch_lat(c, 0, c->lat_dev[sl], 0., 0.);
   return POMGPU_OK;
 }

@@ -681,6 +681,7 @@ struct pomgpu_ctx {
   unsigned ext_bar_base;     // the counter's value when the next k_ext_loop starts (every workgroup arrives once per barrier)
   int ext_loop_off;          // a k_ext_loop launch of this context gave up at its barrier: the substeps run as launches of their own from then on
   void *io_job;              // the output / restart file being written behind the model's back (cdf_out.hip), NULL = none
+  void *frc_files;           // pomgpu_set_forcing_files: the open forcing files and their read buffers (cdf_out.hip), NULL = none
   int launch_err;            // first hipError_t a kernel launch returned (0 = none); reported by the next sync / get_con
   char err[512];
 };
@@ -861,6 +862,12 @@ void pomgpu_mirrors_written(pomgpu_ctx *c);                                     
 int pomgpu_side_stream(pomgpu_ctx *c);                                          // create the side stream and its events (pomgpu_api.hip); 1 = there
 int pomgpu_tp_side_ok(pomgpu_ctx *c);                                           // can rounds run on the side stream (second communicator / callback mover)?
 int pomgpu_tp_move_side(pomgpu_ctx *c, const size_t *scount, const size_t *rcount);   // send2 / recv2, on c->side
+// cdf_out.hip: forcing records from the files pomgpu_set_forcing_files named (src 0 = sfrc, 1 = lbry, 2 = clim)
+int pomgpu_ff_has(pomgpu_ctx *c, int src);
+int pomgpu_ff_fetch_surface(pomgpu_ctx *c, int kind, int n);                    // record n of kind 0..2 into frc_dev[kind][n % 4], frc_n set
+int pomgpu_ff_fetch_lateral(pomgpu_ctx *c, int n);                              // record n into lat_dev[n % 4], lat_n set
+int pomgpu_ff_fetch_restore(pomgpu_ctx *c, int n);                              // month mod(n+9,12)+1 into rec_t[0], rec_s[0]
+void pomgpu_ff_free(pomgpu_ctx *c);
 // k_reduce.hip
 void launch_check_velocity(pomgpu_ctx *c);
 void launch_domain_stats(pomgpu_ctx *c, double *out_dev);

@@ -3,8 +3,10 @@
 ! (the reference would read them through PnetCDF, which this image lacks), read pom.nml like
 ! read_input (initialize.f:71-74,173-198), then
 !     do iint=1,nsteps: advance
-! where `advance_hot` is the reference's sequence (advance.f:6-59) minus file forcing / print /
-! output, and every routine it calls is a pom_gpu_host.f90 wrapper -> C ABI -> HIP kernels.
+! where `advance_hot` is the reference's sequence (advance.f:6-59) minus print / output, and every
+! routine it calls is a pom_gpu_host.f90 wrapper -> C ABI -> HIP kernels.  File forcing: the input
+! files <wrk_pth>in/<netcdf_file>.sfrc.nc / .lbry.nc / .clim.nc that exist are read by the library
+! itself (pom_gpu_forcing_files.f90); without them the forcing is constant.
 ! Writes the final blocks back for checking against the oracle (tests/test_fortran_host.py).
 !
 ! usage: pom_gpu_main <state.in> <state.out>     (pom.nml in the working directory)
@@ -47,14 +49,15 @@ program pom_gpu_main
 
   call pomgpu_host_init(0)
   call pomgpu_upload_state
-  if (nread_rst /= 0) then                   ! initialize.f:39, for a host without PnetCDF: <wrk_pth>in/<read_rst_file>
-    my_task = 0; master_task = 0
-    i_global(1) = 1; j_global(1) = 1         ! one tile: the patch starts at the grid's first cell
-    call read_restart_pnetcdf
+  my_task = 0; master_task = 0
+  i_global(1) = 1; j_global(1) = 1           ! one tile: the patch starts at the grid's first cell
+  if (nread_rst /= 0) call read_restart_pnetcdf   ! initialize.f:39, for a host without PnetCDF: <wrk_pth>in/<read_rst_file>
+  call pomgpu_open_forcing_files(pom_frc_sfrc, pom_frc_lbry, pom_frc_clim)
+  if (.not. pom_frc_clim) then                   ! (with a clim file restore_interior's records are the file's)
+    do n = 1, nrec
+      rc = pomgpu_set_restore_record(pom_ctx, int(n, c_int), c_loc(tr(1,1,1,n)), c_loc(sr(1,1,1,n)))
+    end do
   end if
-  do n = 1, nrec
-    rc = pomgpu_set_restore_record(pom_ctx, int(n, c_int), c_loc(tr(1,1,1,n)), c_loc(sr(1,1,1,n)))
-  end do
   do n = 1, nsteps                           ! pom.f:17-19
     iint = iint + 1
     call advance_hot
@@ -72,8 +75,9 @@ program pom_gpu_main
   call pomgpu_destroy(pom_ctx)
 end program
 
-! advance.f:6-59 without surface_forcing / lateral_bc (file readers), print_section and output
+! advance.f:6-59 without print_section and output; surface_forcing (advance.f:77-93) / lateral_bc where the library has the file
 subroutine advance_hot
+  use pomgpu_iface, only: pom_frc_sfrc, pom_frc_lbry
   implicit none
   include 'pom.h'
   time=dti*float(iint)/86400.d0+time0        ! get_time, advance.f:62-75
@@ -84,6 +88,12 @@ subroutine advance_hot
   else
     ramp=1.d0
   endif
+  if (pom_frc_sfrc) then
+    call wind
+    call heat
+    call surface
+  end if
+  if (pom_frc_lbry) call lateral_bc
   call lateral_viscosity
   call mode_interaction
   do iext=1,isplit

@@ -8,6 +8,8 @@ module pomgpu_iface
     integer(c_int) :: im, jm, kb, im_local, jm_local, n_west, n_east, n_south, n_north
   end type
   type(c_ptr), save :: pom_ctx = c_null_ptr
+  ! which forcing files the library reads itself (set by pomgpu_open_forcing_files' caller; pom_gpu_main's advance_hot looks at them)
+  logical, save :: pom_frc_sfrc = .false., pom_frc_lbry = .false., pom_frc_clim = .false.
   type, bind(C) :: pomgpu_file_meta               ! include/pomgpu.h
     type(c_ptr) :: title, time_start
     integer(c_int) :: im_global, jm_global, i0, j0, create
@@ -76,6 +78,9 @@ module pomgpu_iface
     end function
     integer(c_int) function pomgpu_set_lateral_record(ctx, n, arrays) bind(C, name='pomgpu_set_lateral_record')
       import; type(c_ptr), value :: ctx; integer(c_int), value :: n; type(c_ptr) :: arrays(20)
+    end function
+    integer(c_int) function pomgpu_set_forcing_files(ctx, sfrc, lbry, clim, meta) bind(C, name='pomgpu_set_forcing_files')
+      import; type(c_ptr), value :: ctx, sfrc, lbry, clim; type(pomgpu_file_meta) :: meta   ! any path may be c_null_ptr
     end function
     integer(c_int) function pomgpu_io_wait(ctx) bind(C, name='pomgpu_io_wait')
       import; type(c_ptr), value :: ctx

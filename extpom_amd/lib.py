@@ -94,6 +94,7 @@ _SIGS = {
     "pomgpu_write_output": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
     "pomgpu_write_restart": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
     "pomgpu_read_restart": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "pomgpu_set_forcing_files": (_I, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
     "pomgpu_domain_stats": (_I, [_P, ctypes.POINTER(ctypes.c_double), _I]),
     "pomgpu_advq": (_I, [_P, _P, _P, _P]),
     "pomgpu_advt1": (_I, [_P, _P, _P, _P, _P]),

@@ -232,6 +232,15 @@ class PomGpu:
         self.get_con()
         return t0.value, ii.value
 
+    def set_forcing_files(self, sfrc=None, lbry=None, clim=None, im_global=None, jm_global=None):
+        """pomgpu_set_forcing_files: from now on wind / heat / surface (sfrc), lateral_bc (lbry) and restore_interior (clim) take the
+        records their schedule asks for from these classic NetCDF files, on the device; None leaves a source as it is.  This tile's
+        patch starts at (i_off+1, j_off+1) of the global grid, as in read_restart."""
+        st = self.st
+        m = _lib.FileMeta(b"", b"", im_global or st.im, jm_global or st.jm, st.i_off + 1, st.j_off + 1, 0, None)
+        enc = lambda p: None if p is None else str(p).encode()
+        self._chk(self.L.pomgpu_set_forcing_files(self.h, enc(sfrc), enc(lbry), enc(clim), ctypes.byref(m)), "set_forcing_files")
+
     def io_wait(self):
         """join the host thread that is writing the last output / restart file (sync, the next write and close do it too)"""
         self._chk(self.L.pomgpu_io_wait(self.h), "io_wait")

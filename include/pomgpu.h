@@ -80,7 +80,8 @@ int pomgpu_get_con(pomgpu_ctx *ctx, pom_blkcon *con);
 int pomgpu_bind_host(pomgpu_ctx *ctx, const double *host_blk2d, const double *host_blk3d);
 /* Relaxation targets that the reference's restore_interior reads through
  * read_restore_ts_interior_pnetcdf(n,kb,tr,sr) (bounds_forcing.f:1040,1060): record n (1-based),
- * arrays dimensioned (im,jm,kb).  Copied to the device. */
+ * arrays dimensioned (im,jm,kb).  Copied to the device.  Refused (POMGPU_EINVAL) once the records come from a file
+ * (pomgpu_set_forcing_files). */
 int pomgpu_set_restore_record(pomgpu_ctx *ctx, int n, const double *tr, const double *sr);
 /* Device address of a mirror (for halo exchange by the caller, e.g. RCCL send/recv).  An address of a 3-D array stays valid until
  * pomgpu_destroy -- pomgpu_tune_placement, which moves those arrays, refuses once one has been handed out.  Through an address the
@@ -110,11 +111,13 @@ int pomgpu_set_order_exchange(pomgpu_ctx *ctx, pomgpu_order_fn fn, void *user);
 
 /* ---- surface forcing on the device (bounds_forcing.f:871-983, called from advance.f:77-93) ---------------
  * wind and heat keep two records (…b, …f members of blk2d) and interpolate linearly in time; surface sets the
- * SST without interpolation.  The readers stay the host's (read_wind_pnetcdf, read_heat_pnetcdf,
+ * SST without interpolation.  The records come from the files named with pomgpu_set_forcing_files (below), or -- a source without a
+ * file -- from the host's readers (read_wind_pnetcdf, read_heat_pnetcdf,
  * read_surface_pnetcdf: io_pnetcdf.F:2912,3110,3170): the host hands the library the pair of (im,jm) fields
  * of record n -- kind 0 = wind (wu, wv), 1 = heat (shf, swr), 2 = surface (sst, sss) -- before the step whose
  * wind / heat / surface call asks for it; the last four records per kind are kept.  pomgpu_get_time must have
- * set the step's time.  A record that was not supplied: error_status = 1, POMGPU_EINVAL. */
+ * set the step's time.  A record that was not supplied: error_status = 1, POMGPU_EINVAL.  Refused (POMGPU_EINVAL) once the
+ * surface records come from a file. */
 int pomgpu_set_forcing_record(pomgpu_ctx *ctx, int kind, int n, const double *a, const double *b);
 int pomgpu_wind(pomgpu_ctx *ctx);              /* bounds_forcing.f:871-912 */
 int pomgpu_heat(pomgpu_ctx *ctx);              /* bounds_forcing.f:915-960 */
@@ -125,7 +128,8 @@ int pomgpu_surface_forcing(pomgpu_ctx *ctx);   /* advance.f:77-93: wind, heat, s
  * interpolate pattern on the open-boundary arrays of `bdry`, plus the depth integrals uab?f, vab?f, uabe, uabw,
  * vabn, vabs.  The host's reader (read_boundary_conditions_pnetcdf, io_pnetcdf.F:3393) fills 20 arrays: tbwf sbwf
  * ubwf vbwf tbef sbef ubef vbef tbnf sbnf vbnf ubnf tbsf sbsf vbsf ubsf elw ele eln els -- hand them over in this
- * order, each in the shape of the bdry member it lands in ((jm_local,kb), (im_local,kb), (jm_local), (im_local)). */
+ * order, each in the shape of the bdry member it lands in ((jm_local,kb), (im_local,kb), (jm_local), (im_local)).  Refused
+ * (POMGPU_EINVAL) once the lateral records come from a file (pomgpu_set_forcing_files). */
 int pomgpu_set_lateral_record(pomgpu_ctx *ctx, int n, const double *const *arrays20);
 int pomgpu_lateral_bc(pomgpu_ctx *ctx);
 
@@ -287,10 +291,30 @@ int pomgpu_write_restart(pomgpu_ctx *ctx, const char *path, const pomgpu_file_me
  * error half way leaves the state unspecified (error_status = 1). */
 int pomgpu_read_restart(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta, double *time0_out, double *iint_out);   /* read_restart_pnetcdf */
 
-/* One internal step for the current blkcon.iint: get_time, [surface_forcing, lateral_bc -- once the host has
- * supplied forcing / lateral records, see below; skipped otherwise: constant forcing], lateral_viscosity,
+/* The forcing files without PnetCDF: read_wind_pnetcdf, read_heat_pnetcdf, read_surface_pnetcdf (io_pnetcdf.F:2912-3224),
+ * read_boundary_conditions_pnetcdf (:3393-3621), read_restore_ts_interior_pnetcdf (:3275-3333).  The host names the files once --
+ * sfrc: <...>.sfrc.nc (sustr svstr shflux swrad SST SSS), lbry: <...>.lbry.nc (zeta u v temp salt, each .east and .south), clim:
+ * <...>.clim.nc (Tclim Sclim); any of them may be NULL: that source stays as it is (records by setter, or constant forcing) -- and from
+ * then on pomgpu_wind / _heat / _surface, pomgpu_lateral_bc and restore_interior take record n (restore: month mod(n+9,12)+1) from the
+ * file when their own schedule asks for it: the tile's rows with pread into one of two pinned buffers, one copy and one kernel on the
+ * stream, which swaps bytes, widens NC_FLOAT, converts units (wind -x/1025., heat -x/rhoref/3986.), tapers the wind against the tile's
+ * dum / dvm (:2966-2995) and builds the lateral record (t_w s_w t_n s_n from tclim sclim, u_w v_w u_n v_n zero, elw eln untouched).  The
+ * host is held up for the preads alone.  A registered sfrc / lbry file makes pomgpu_advance / pomgpu_run call surface_forcing /
+ * lateral_bc; the setters of a source that has a file are refused.  Of `meta` only im_global, jm_global, i0, j0 are used; every rank of a
+ * decomposition names the same files with its own i0, j0 -- not collective, no message round.
+ * The call opens each file and checks its header: classic NetCDF (CDF-1 or CDF-2), every variable found BY NAME, NC_FLOAT or NC_DOUBLE,
+ * the record number as the slowest dimension (the unlimited one, or a fixed one), then (jm_global, im_global) in sfrc; (jm_global),
+ * (im_global), (kb, jm_global), (kb, im_global) in lbry; (kb, jm_global, im_global) with at least 12 records in clim.  Anything else
+ * -- and a file shorter than the records its header counts, a tile outside the global grid -- is refused with POMGPU_EINVAL,
+ * error_status = 1 and the cause in pomgpu_last_error; nothing is registered then and no mirror or record slot changes.  At a fetch, a
+ * record beyond the file's count or end (looked at once more: the file may have grown) fails that step the same way, before the record
+ * slot is written. */
+int pomgpu_set_forcing_files(pomgpu_ctx *ctx, const char *sfrc, const char *lbry, const char *clim, const pomgpu_file_meta *meta);
+
+/* One internal step for the current blkcon.iint: get_time, [surface_forcing, lateral_bc -- once the host has named
+ * forcing files or supplied forcing / lateral records, see above; skipped otherwise: constant forcing], lateral_viscosity,
  * mode_interaction, isplit x mode_external, mode_internal, check_velocity (advance.f:6-59 minus print and
- * output, which stay on the host).  Does not synchronise. */
+ * output, which stay on the host).  Does not synchronise: a record fetched from a file holds the host for its preads only. */
 int pomgpu_advance(pomgpu_ctx *ctx);
 /* nsteps x { iint = iint+1; advance }  (pom.f:17-19).  Does not synchronise.  On several tiles with the second stream agreed
  * (pomgpu_rccl_init / pomgpu_transport_side_agree) every step but the last of the call leaves realvertvl (solver.f:2024-2067) and the
