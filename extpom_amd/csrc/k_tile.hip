@@ -245,7 +245,8 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
 // face coefficient are read once for both -- 12.5 array passes instead of 2 x 9.5.
 struct QFields { const double *q[2], *qb[2]; double *qf[2]; };
 // operands of a level, shared through the workgroup's LDS slab in this order: q[0..NF-1], qb[0..NF-1], aam, v; own row only: u, w
-template <int NF> struct LevQa { pomgpu_ct c[2 * NF + 2], o[2], h[ROWSHARE_SLOTS(2 * NF + 2)]; };
+// (NO = 1: the kernel forms w itself, see WF below, and only u remains)
+template <int NF, int NO = 2> struct LevQa { pomgpu_ct c[2 * NF + 2], o[NO], h[ROWSHARE_SLOTS(2 * NF + 2)]; };
 struct CoefQ { pomgpu_ct dts, hs, msk, ds_num; InvDc den; };
 __device__ __forceinline__ CoefQ coefq_x(const KP &P, int i, int j) {
   CoefQ c; c.dts = K2(DTSX, i, j); c.hs = K2(HSX, i, j); c.msk = F2(dum, i, j); c.den = inv_of(CT(K2(DXSX, i, j))); c.ds_num = K2(DYSX, i, j); return c;
@@ -261,9 +262,20 @@ __device__ __forceinline__ pomgpu_ct advq_face(const CoefQ &c, pomgpu_ct q_hi, p
   return CT(.5) * c.ds_num * x;
 }
 // loop discipline and row sharing as in k_advt2_col
-template <int NF>
+//
+// WF: the kernel forms w on its way down instead of loading it -- vertvl (solver.f:1970-2021) with the fsm mask of bcondorl(5), as
+// k_vertvl_rs (k_vert.hip) runs it in front of this kernel in mode_internal.  That routine is a running sum down the same levels on
+// the same lanes, over operands this march already holds: u of the own row on all 64 lanes (the east neighbour's is one lane away), v
+// and v(i,j+1) from the slab, and the previous level's copies of them.  Iteration L forms w(L) from level L-1's u_e, u, v_n, v, stores
+// it where the kernel used to load it, and multiplies the STORED value -- masked on levels 1..kbm1, rounded to the storage type --
+// with q(L): what the unfused kernel reads back.  The chain is fp64 (vertvl is fp64 in the fp32-storage build too) with
+// k_vertvl_rs's expressions in k_vertvl_rs's order; nobody reads a neighbour column's w here, so no workgroup waits for another.
+// Rim columns get vertvl's tail (w = w * fsm on levels 1..kbm1) after the loop.  The fp32-arithmetic variant, whose stencil kernels
+// hold no fp64 arithmetic, does not instantiate WF and keeps the vertvl launch (POMGPU_W_FUSE).
+template <int NF, bool WF = false>
 __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int zero_else) {
   constexpr int NS = 2 * NF + 2, NH = ROWSHARE_SLOTS(NS), AM = 2 * NF, VV = 2 * NF + 1;
+  typedef LevQa<NF, WF ? 1 : 2> Lev;
   HALO_XCD_DECODE_R(LDS_ROWS)
   const int r = WAVE_UNIFORM((int)threadIdx.y), j0w = j - r;
   const bool jrow = j <= P.jml;
@@ -293,26 +305,45 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
   const unsigned oc = BOFF2(i, jc), lvb = LVB;
   // interior columns get the new value, every other owned column a zero (zero_else) or nothing
   const unsigned ost = in ? oc : ((zero_else && icol) ? oc : BOFF_NONE);
+  const unsigned ostw = in ? oc : BOFF_NONE;                // w: interior columns only, as k_vertvl_rs stores it
 #ifndef POMGPU_EMU
   __shared__ pomgpu_ct slab[2][NS][ROWSHARE_ROWS][64];
 #else
   const unsigned os = BOFF2(i, js), on = BOFF2(i, jn);
 #endif
-  auto load = [&](LevQa<NF> &L, int k) {
+  // WF: vertvl's column constants and start value (k_vertvl_rs: the same expressions in the same order)
+  double vv_cw = 0., vv_ce = 0., vv_cs = 0., vv_cn = 0., vv_det = 0., vv_m = 0., wk = 0.;
+  InvD vv_area; vv_area.b = vv_area.y = 0.;
+  if constexpr (WF) {
+    vv_m = F2(fsm, i, jc);
+    const double dyc = F2(dy, i, jc), dtc = F2(dt, i, jc), dxc = F2(dx, i, jc);
+    const double dyw = halo_w(dyc, [&] { return F2(dy, iw, jc); }), dtw = halo_w(dtc, [&] { return F2(dt, iw, jc); });
+    const double dye = halo_e(dyc, [&] { return F2(dy, ie, jc); }), dte = halo_e(dtc, [&] { return F2(dt, ie, jc); });
+    vv_cw = .25 * (dyc + dyw) * (dtc + dtw);
+    vv_ce = .25 * (dye + dyc) * (dte + dtc);
+    vv_cs = .25 * (dxc + F2(dx, i, js)) * (dtc + F2(dt, i, js));
+    vv_cn = .25 * (F2(dx, i, jn) + dxc) * (F2(dt, i, jn) + dtc);
+    vv_area = inv_of(dxc * dyc);
+    vv_det = (F2(etf, i, jc) - F2(etb, i, jc)) / P.dti2;
+    wk = 0.5 * (F2(vfluxb, i, jc) + F2(vfluxf, i, jc));                                      // :2004
+  }
+  auto load = [&](Lev &L, int k) {
     const unsigned lv = (unsigned)WAVE_UNIFORM(k - 1) * lvb;
 #pragma unroll
     for (int x = 0; x < NS; x++) L.c[x] = bldc(bs[x], oc, lv);
-    L.o[0] = bldc(bo[0], oc, lv); L.o[1] = bldc(bo[1], oc, lv);
+    L.o[0] = bldc(bo[0], oc, lv);
+    if constexpr (!WF) L.o[1] = bldc(bo[1], oc, lv);
 #pragma unroll
     for (int q = 0; q < NH; q++) L.h[q] = bldc(bh[q], S.hoff[q], lv);
   };
   pomgpu_ct u_m = 0., v_m = 0., vn_m = 0., am_m = 0., ams_m = 0., amn_m = 0.;   // u, v, v(j+1), aam (c, s, n) of level L-1
   pomgpu_ct am_w_prv = 0.;                    // aam(i-1,j,L-1) as seen by this lane
+  pomgpu_ct ue_m = 0.;                        // WF: u(i+1,j,L-1)
   pomgpu_ct wq_pp[NF], wq_p[NF];              // w*q of levels L-2 and L-1
   pomgpu_ct xe_p[NF], xw_p[NF], yn_p[NF], ys_p[NF], qb_p[NF];   // faces and qb of level L-1, waiting for w(L)*q(L)
 #pragma unroll
   for (int f = 0; f < NF; f++) wq_pp[f] = wq_p[f] = xe_p[f] = xw_p[f] = yn_p[f] = ys_p[f] = qb_p[f] = 0.;
-  auto step = [&](const int L, const int par, const LevQa<NF> &cur, LevQa<NF> &nxt) {
+  auto step = [&](const int L, const int par, const Lev &cur, Lev &nxt) {
     load(nxt, L + 1 <= kb ? L + 1 : kb);                    // the last iterations re-request level kb
     NbrT<NS> nb;
 #ifndef POMGPU_EMU
@@ -328,9 +359,22 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
 #pragma unroll
     for (int x = 0; x < NS; x++) { nb.s[x] = bldc(bs[x], os, lvc); nb.n[x] = bldc(bs[x], on, lvc); }
 #endif
-    const pomgpu_ct am_c = cur.c[AM], v_c = cur.c[VV], u_c = cur.o[0], w_c = cur.o[1];
+    const pomgpu_ct am_c = cur.c[AM], v_c = cur.c[VV], u_c = cur.o[0];
     const pomgpu_ct am_s = nb.s[AM], am_n = nb.n[AM], v_n = nb.n[VV];
     const pomgpu_ct am_w = halo_w(am_c, [&] { return F3(aam, iw, jc, L); });
+    pomgpu_ct w_c, ue_c = 0.;
+    if constexpr (WF) {
+      ue_c = halo_e(u_c, [&] { return F3(u, ie, jc, L); });
+      // w(L) from level L-1 (solver.f:2006-2014); selects, no branch: iteration 1 keeps the start value.  The running sum is never masked
+      const double wn = wk + F1(dz, L >= 2 ? L - 1 : 1) *
+                             (divi(vv_ce * (double)ue_m - vv_cw * (double)u_m + vv_cn * (double)vn_m - vv_cs * (double)v_m, vv_area) + vv_det);
+      wk = L >= 2 ? wn : wk;
+      const double wst = L <= kbm1 ? wk * vv_m : wk;        // bcondorl(5)'s mask on levels 1..kbm1
+      bst(bo[1], ostw, (unsigned)WAVE_UNIFORM(L - 1) * lvb, wst);
+      w_c = CT((pomgpu_st)wst);                             // what the unfused kernel loads: the stored value
+    } else {
+      w_c = cur.o[1];
+    }
     const int k = L - 1;                                    // level completed in this iteration
     InvDc dz2; dz2.b = dz2.y = 0.;
     if (k >= 2 && k <= kbm1) { dz2.b = CT(F1(dz, k)) + CT(F1(dz, k - 1)); dz2.y = CT(1.0) / dz2.b; }
@@ -367,9 +411,10 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
       xe_p[f] = xe_c; xw_p[f] = xw_c; yn_p[f] = yn_c; ys_p[f] = ys_c;
     }
     am_w_prv = am_w;
+    if constexpr (WF) ue_m = ue_c;
     u_m = u_c; v_m = v_c; vn_m = v_n; am_m = am_c; ams_m = am_s; amn_m = am_n;
   };
-  LevQa<NF> ra, rb;
+  Lev ra, rb;
   load(ra, 1);
   rb = ra;
   for (int L = 1; L <= kb; L += 2) {
@@ -379,6 +424,10 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
   if (icol && zero_else) {
 #pragma unroll
     for (int f = 0; f < NF; f++) G3(A.qf[f], i, jc, kb) = 0.;
+  }
+  if constexpr (WF) {                                       // rim columns: the mask of bcondorl(5) alone (k_vertvl_rs's tail).  After the loop, as in k_advt2_col
+    if (icol && !in && i0 <= P.im && jc <= P.jm)
+      for (int k = 1; k <= kbm1; k++) F3(w, i, jc, k) = F3(w, i, jc, k) * vv_m;
   }
 }
 
@@ -810,6 +859,14 @@ void launch_advq2_col(pomgpu_ctx *c, const double *q, const double *qb, double *
   QFields A; A.q[0] = q; A.qb[0] = qb; A.qf[0] = qf; A.q[1] = ql; A.qb[1] = qlb; A.qf[1] = qlf;
   LAUNCHN(c, "k_advq2_col", (k_advq_col<2>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A, zero_else);
 }
+// the same pass with vertvl (mask of bcondorl(5) included) inside its march: w is written, not read (mode_internal on one tile).
+// Not in the fp32-arithmetic variant (POMGPU_W_FUSE, pomgpu_internal.hpp)
+#if POMGPU_W_FUSE
+void launch_advq2w_col(pomgpu_ctx *c, const double *q, const double *qb, double *qf, const double *ql, const double *qlb, double *qlf, int zero_else) {
+  QFields A; A.q[0] = q; A.qb[0] = qb; A.qf[0] = qf; A.q[1] = ql; A.qb[1] = qlb; A.qf[1] = qlf;
+  LAUNCHN(c, "k_advq2_col", (k_advq_col<2, true>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A, zero_else);
+}
+#endif
 void launch_advct_col(pomgpu_ctx *c, int sum2d) {
   // low tiles (a tile of an 8- or 4-tile split of 2048x1536): 4-row workgroups, two per compute unit
   const bool rows4 = SW(c, ADVCT_ROWS4) || (!SW(c, ADVCT_ROWS8) && c->P.jml <= 400 && c->exch);

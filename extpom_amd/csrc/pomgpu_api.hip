@@ -261,6 +261,14 @@ static bool uv_fused(const pomgpu_ctx *c) {
   return !c->exch && !c->tp.on && !c->wide.on && !c->parent && !(c->flags & POMGPU_CTX_2D) && !c->wr_eager && P.kb >= 6 && P.kb <= 64 &&
          P.im >= 8 && P.jm >= 8 && !SW(c, THOMAS_SCRATCH) && !SW(c, NO_TWIN) && !SW(c, UV_NOFUSE);
 }
+// may mode_internal form w inside the q2 / q2l advection march (k_advq_col<2, true>) instead of launching vertvl in front of it?  One
+// tile with no exchange of any kind (on tiles w has a message round of its own, Rw, between the two kernels) and the one-pass q2 / q2l
+// path.  No lazy state comes with it: w is in memory, final, when the kernel ends.  The fp32-arithmetic variant has no such kernel
+// (POMGPU_W_FUSE) and keeps the pair
+static bool w_fused(const pomgpu_ctx *c) {
+  return POMGPU_W_FUSE && !c->exch && !c->tp.on && !c->wide.on && !(c->flags & POMGPU_CTX_2D) && !SW(c, ADVQ_SINGLE) && !SW(c, ADVQ_EXCHANGE) &&
+         !SW(c, VERTVL_CELLS) && !SW(c, W_NOFUSE);
+}
 static void uvf_materialize(pomgpu_ctx *c) {
   if (!c->uvf_pending) return;
   c->uvf_pending = 0;
@@ -1643,7 +1651,8 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
   if ((k.iint != 1 || k.time0 != 0.) && k.mode != 2) {
     c->uvf_pending = 0;                                       // u, v change now and advq rewrites uf, vf whole: nobody has asked for the copy
     launch_int_uvmean(c);                                     // :365-393
-    launch_vertvl(c, 1);                                      // :396-398
+    const bool wf = w_fused(c);                               // :396-398 inside advq's march below
+    if (!wf) launch_vertvl(c, 1);                             // :396-398
     // :400 exchange3d_mpi(w): nothing reads w's ghost cells before advt / advu (advq takes w at the cell's own
     // column only), so on tiles it travels with profq's bottom-boundary exchange below -- one round less
     const bool lib_x = c->tp.on && c->exch;                   // the library's own exchange: rounds may be merged
@@ -1669,6 +1678,10 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
       if (SW(c, ADVQ_SINGLE)) {
         launch_advq_col(c, D3(c, q2), D3(c, q2b), D3(c, uf), 1);
         launch_advq_col(c, D3(c, q2l), D3(c, q2lb), D3(c, vf), 1);
+#if POMGPU_W_FUSE
+      } else if (wf) {
+        launch_advq2w_col(c, D3(c, q2), D3(c, q2b), D3(c, uf), D3(c, q2l), D3(c, q2lb), D3(c, vf), 1);  // ... and w, formed on the way down
+#endif
       } else {
         launch_advq2_col(c, D3(c, q2), D3(c, q2b), D3(c, uf), D3(c, q2l), D3(c, q2lb), D3(c, vf), 1);   // q2 and q2l in one pass
       }

@@ -91,6 +91,14 @@ typedef float pomgpu_ct;
 typedef double pomgpu_ct;
 #endif
 #define CT(x) ((pomgpu_ct)(x))
+// w formed inside the q2 / q2l march (k_advq_col<2, true>, k_tile.hip) brings vertvl's fp64 running sum into a stencil kernel.  The
+// fp32-arithmetic variant keeps its stencil kernels free of fp64 arithmetic, so it has no such kernel and mode_internal keeps the
+// vertvl launch there; the product and the fp32-storage build have it.
+#ifdef POMGPU_COMPUTE_F32
+#define POMGPU_W_FUSE 0
+#else
+#define POMGPU_W_FUSE 1
+#endif
 #ifdef POMGPU_STORE_F32
 struct Ref3 {
   pomgpu_st *p;
@@ -512,7 +520,7 @@ static inline dim3 grid2_halo(const KP &P) { return dim3((P.iml + 61) / 62, (P.j
   X(PROFQ_NOPACE) X(COL_STRIP) X(BAND_BYTES) X(PAD3) X(IO_SYNC) X(ADVCT_SPLIT) X(ADVQ_EXCHANGE) X(PROD_FULL) X(QFILTER_SPLIT) \
   X(UV_FULL_EXCHANGE) X(NO_OVERLAP) X(NO_SIDE_COMM) X(WR_MAIN) X(WIDE_W) X(WIDE_FULL) X(DEBUG_ALLOC) X(TEST_SPLIT_FAIL_RANK)  \
   X(EDGE_SPLIT) X(WR_NODEFER) X(EXT_RING_FIRST) X(TUNE_FORCE) X(NO_TWIN) X(RIM_MAIN) X(RIM_RESULTS_MAIN) X(SUM2D_OFF) X(ADVCT_ROWS4) X(ADVCT_ROWS8) \
-  X(IO_CHUNK_KB) X(UV_NOFUSE)
+  X(IO_CHUNK_KB) X(UV_NOFUSE) X(W_NOFUSE)
 enum pomgpu_sw {
 #define POMGPU_SW_(name) SW_##name,
   POMGPU_SWITCHES(POMGPU_SW_)
@@ -765,6 +773,9 @@ void launch_advct_fix2d(pomgpu_ctx *c, int west, int south);
 void launch_advt2x2_col(pomgpu_ctx *c, const double *tb, const double *t, const double *tc, double *tf, const double *sb, const double *s_,
                         const double *sc, double *sf);
 void launch_advq2_col(pomgpu_ctx *c, const double *q, const double *qb, double *qf, const double *ql, const double *qlb, double *qlf, int zero_else);
+#if POMGPU_W_FUSE
+void launch_advq2w_col(pomgpu_ctx *c, const double *q, const double *qb, double *qf, const double *ql, const double *qlb, double *qlf, int zero_else);
+#endif
 void launch_advuv_col(pomgpu_ctx *c);
 int launch_profuv_reg(pomgpu_ctx *c);   // 0 when kb is outside the instantiated range
 void launch_profuv_filter_reg(pomgpu_ctx *c, double *ubk, double *vbk);   // k_uvb_bottom + k_profuv_filter_reg2 (kb in 6..64); ubk, vbk: two planes of n2 doubles

@@ -17,7 +17,7 @@ ROWS = {   # kernel as the profile names it -> (reference lines,
     "k_ts_update": ("a15 + a16 + restore", "`advance.f:444-454`, `solver.f:1162-1209`", "k_ts_update"),
     "k_advt2x2_col": ("a13 x 2", "`solver.f:577-731`", "k_advt2_col"),
     "k_advuv_col": ("a17", "`solver.f:734-845`", "k_advuv_col"),
-    "k_advq2_col": ("a9 x 2", "`solver.f:411-477`", "k_advq_col"),
+    "k_advq2_col": ("a8 + a9 x 2 (one tile: w formed in the march; a9 x 2 beside `k_vertvl` otherwise)", "`solver.f:411-477`, `:1970-2021`", "k_advq_col"),
     "k_advct_col": ("a2", "`solver.f:201-408`", "k_advct_col"),
     "k_uv_filter_reg2": ("a19", "`advance.f:469-514`", "k_uv_filter_reg"),
     "k_profuv_reg2": ("a18", "`solver.f:1686-1877`", "k_profuv_reg"),
@@ -27,7 +27,7 @@ ROWS = {   # kernel as the profile names it -> (reference lines,
     "k_baropg": ("a3", "`solver.f:848-940`", "k_baropg_rs"),
     "k_int_uvmean_reg2": ("a7", "`advance.f:365-393`", "k_int_uvmean_reg"),
     "k_realvertvl_col": ("a20", "`solver.f:2024-2067`", "k_realvertvl_col"),
-    "k_vertvl": ("a8", "`solver.f:1970-2021`", "k_vertvl_rs"),
+    "k_vertvl": ("a8 (tiles, `POMGPU_W_NOFUSE`: absent from a one-tile step)", "`solver.f:1970-2021`", "k_vertvl_rs"),
     "k_aam_pair": ("a1", "`advance.f:122-137`", "k_aam_pair"),
 }
 PASSES = dict(bench.KERNEL_PASSES, k_uv_filter_reg2=10, k_profuv_reg2=6, k_profuv_filter_reg2=12, k_uv_filter_rim=0, k_proft_reg2=6, k_int_uvmean_reg2=4, k_baropg=4, k_vertvl=3)
