@@ -4,6 +4,9 @@
 // not over the field; the whole-field mask multiplies that end each branch are fused into the
 // Asselin-filter passes that follow (k_adv.hip).
 //
+// u, v are read through uvm_ld (pomgpu_internal.hpp): while KP::uvm is set (mode_internal on one tile) they still lack the depth-mean
+// correction of advance.f:365-393 in memory and get it as they are loaded -- levels 1..kbm1, so not bcond(6)'s level kb.
+//
 // Corner precedence: the reference sweeps east/west inside its j-loop and then south/north inside
 // its i-loop, so at a corner cell the south/north value wins; the east/west lines therefore skip
 // the corner cells that a physical south/north edge also owns.
@@ -25,7 +28,7 @@ __global__ void k_bcond4_edges(KP P) {
   const bool vert = (k != 1 && k != P.kbm1);
   double u1, wm, tv, sv;
   if (line == 1) {          // east
-    u1 = 2. * F3(u, P.im, j, k) * P.dti / (F2(dx, P.im, j) + F2(dx, P.imm1, j));
+    u1 = 2. * uvm_ld<0>(P, P.im, j, k) * P.dti / (F2(dx, P.im, j) + F2(dx, P.imm1, j));
     if (u1 <= 0.) {
       tv = F3(t, P.im, j, k) - u1 * (BDJ(tbe, j, k) - F3(t, P.im, j, k));
       sv = F3(s, P.im, j, k) - u1 * (BDJ(sbe, j, k) - F3(s, P.im, j, k));
@@ -39,7 +42,7 @@ __global__ void k_bcond4_edges(KP P) {
       }
     }
   } else if (line == 0) {   // west
-    u1 = 2. * F3(u, 2, j, k) * P.dti / (F2(dx, 1, j) + F2(dx, 2, j));
+    u1 = 2. * uvm_ld<0>(P, 2, j, k) * P.dti / (F2(dx, 1, j) + F2(dx, 2, j));
     if (u1 >= 0.) {
       tv = F3(t, 1, j, k) - u1 * (F3(t, 1, j, k) - BDJ(tbw, j, k));
       sv = F3(s, 1, j, k) - u1 * (F3(s, 1, j, k) - BDJ(sbw, j, k));
@@ -53,7 +56,7 @@ __global__ void k_bcond4_edges(KP P) {
       }
     }
   } else if (line == 2) {   // south
-    u1 = 2. * F3(v, i, 2, k) * P.dti / (F2(dy, i, 1) + F2(dy, i, 2));
+    u1 = 2. * uvm_ld<1>(P, i, 2, k) * P.dti / (F2(dy, i, 1) + F2(dy, i, 2));
     if (u1 >= 0.) {
       tv = F3(t, i, 1, k) - u1 * (F3(t, i, 1, k) - BDI(tbs, i, k));
       sv = F3(s, i, 1, k) - u1 * (F3(s, i, 1, k) - BDI(sbs, i, k));
@@ -67,7 +70,7 @@ __global__ void k_bcond4_edges(KP P) {
       }
     }
   } else {                  // north
-    u1 = 2. * F3(v, i, P.jm, k) * P.dti / (F2(dy, i, P.jm) + F2(dy, i, P.jmm1));
+    u1 = 2. * uvm_ld<1>(P, i, P.jm, k) * P.dti / (F2(dy, i, P.jm) + F2(dy, i, P.jmm1));
     if (u1 <= 0.) {
       tv = F3(t, i, P.jm, k) - u1 * (BDI(tbn, i, k) - F3(t, i, P.jm, k));
       sv = F3(s, i, P.jm, k) - u1 * (BDI(sbn, i, k) - F3(s, i, P.jm, k));
@@ -93,7 +96,7 @@ __global__ void k_bcond6_edges(KP P) {
   if (k > P.kb) return;
   double u1, qv, lv;
   if (line == 0) {
-    u1 = 2. * F3(u, 2, j, k) * P.dti / (F2(dx, 1, j) + F2(dx, 2, j));
+    u1 = 2. * uvm_ld<0>(P, 2, j, k) * P.dti / (F2(dx, 1, j) + F2(dx, 2, j));
     if (u1 >= 0.) {
       qv = F3(q2, 1, j, k) - u1 * (F3(q2, 1, j, k) - P.small_);
       lv = F3(q2l, 1, j, k) - u1 * (F3(q2l, 1, j, k) - P.small_);
@@ -102,7 +105,7 @@ __global__ void k_bcond6_edges(KP P) {
       lv = F3(q2l, 1, j, k) - u1 * (F3(q2l, 2, j, k) - F3(q2l, 1, j, k));
     }
   } else if (line == 1) {
-    u1 = 2. * F3(u, P.im, j, k) * P.dti / (F2(dx, P.im, j) + F2(dx, P.imm1, j));
+    u1 = 2. * uvm_ld<0>(P, P.im, j, k) * P.dti / (F2(dx, P.im, j) + F2(dx, P.imm1, j));
     if (u1 <= 0.) {
       qv = F3(q2, P.im, j, k) - u1 * (P.small_ - F3(q2, P.im, j, k));
       lv = F3(q2l, P.im, j, k) - u1 * (P.small_ - F3(q2l, P.im, j, k));
@@ -111,7 +114,7 @@ __global__ void k_bcond6_edges(KP P) {
       lv = F3(q2l, P.im, j, k) - u1 * (F3(q2l, P.im, j, k) - F3(q2l, P.imm1, j, k));
     }
   } else if (line == 2) {
-    u1 = 2. * F3(v, i, 2, k) * P.dti / (F2(dy, i, 1) + F2(dy, i, 2));
+    u1 = 2. * uvm_ld<1>(P, i, 2, k) * P.dti / (F2(dy, i, 1) + F2(dy, i, 2));
     if (u1 >= 0.) {
       qv = F3(q2, i, 1, k) - u1 * (F3(q2, i, 1, k) - P.small_);
       lv = F3(q2l, i, 1, k) - u1 * (F3(q2l, i, 1, k) - P.small_);
@@ -120,7 +123,7 @@ __global__ void k_bcond6_edges(KP P) {
       lv = F3(q2l, i, 1, k) - u1 * (F3(q2l, i, 2, k) - F3(q2l, i, 1, k));
     }
   } else {
-    u1 = 2. * F3(v, i, P.jm, k) * P.dti / (F2(dy, i, P.jm) + F2(dy, i, P.jmm1));
+    u1 = 2. * uvm_ld<1>(P, i, P.jm, k) * P.dti / (F2(dy, i, P.jm) + F2(dy, i, P.jmm1));
     if (u1 <= 0.) {
       qv = F3(q2, i, P.jm, k) - u1 * (P.small_ - F3(q2, i, P.jm, k));
       lv = F3(q2l, i, P.jm, k) - u1 * (P.small_ - F3(q2l, i, P.jm, k));
@@ -155,19 +158,19 @@ __global__ void k_bcondorl3(KP P) {
   const bool jin = (j >= 2 && j <= P.jmm1), iin = (i >= 2 && i <= P.imm1);
   double uf = F3(uf, i, j, k), vf = F3(vf, i, j, k);
   if (P.E && jin && i == P.im) {                                                            // :425-434
-    uf = orl(F3(ub, P.im - 1, j, k), F3(uf, P.im - 1, j, k), F3(u, P.im - 2, j, k), F3(ub, P.im, j, k), F3(u, P.im - 1, j, k));
+    uf = orl(F3(ub, P.im - 1, j, k), F3(uf, P.im - 1, j, k), uvm_ld<0>(P, P.im - 2, j, k), F3(ub, P.im, j, k), uvm_ld<0>(P, P.im - 1, j, k));
     vf = 0.;
   }
   if (P.W && jin && (i == 1 || i == 2)) {                                                   // :437-447
-    uf = orl(F3(ub, 3, j, k), F3(uf, 3, j, k), F3(u, 4, j, k), F3(ub, 2, j, k), F3(u, 3, j, k));
+    uf = orl(F3(ub, 3, j, k), F3(uf, 3, j, k), uvm_ld<0>(P, 4, j, k), F3(ub, 2, j, k), uvm_ld<0>(P, 3, j, k));
     if (i == 1) vf = 0.;
   }
   if (P.S && iin && (j == 1 || j == 2)) {                                                   // :452-462
-    vf = orl(F3(vb, i, 3, k), F3(vf, i, 3, k), F3(v, i, 4, k), F3(vb, i, 2, k), F3(v, i, 3, k));
+    vf = orl(F3(vb, i, 3, k), F3(vf, i, 3, k), uvm_ld<1>(P, i, 4, k), F3(vb, i, 2, k), uvm_ld<1>(P, i, 3, k));
     if (j == 1) uf = 0.;
   }
   if (P.N && iin && j == P.jm) {                                                            // :465-474
-    vf = orl(F3(vb, i, P.jm - 1, k), F3(vf, i, P.jm - 1, k), F3(v, i, P.jm - 2, k), F3(vb, i, P.jm, k), F3(v, i, P.jm - 1, k));
+    vf = orl(F3(vb, i, P.jm - 1, k), F3(vf, i, P.jm - 1, k), uvm_ld<1>(P, i, P.jm - 2, k), F3(vb, i, P.jm, k), uvm_ld<1>(P, i, P.jm - 1, k));
     uf = 0.;
   }
   F3(uf, i, j, k) = uf * F2(dum, i, j);

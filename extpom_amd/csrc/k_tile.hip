@@ -45,11 +45,23 @@ __global__ void k_coef_dt(KP P) {
   K2(DTSY, i, j) = F2(dt, i, j) + F2(dt, i, js);
   K2(DT4, i, j) = F2(dt, i, j) + F2(dt, iw, j) + F2(dt, i, js) + F2(dt, iw, js);
 }
-__global__ void k_coef_eta(KP P) {
+// uvm: also the depth means advance.f:375-392 gives u, v (C2_UCOR, C2_VCOR; utf, vtf are final once the external mode is done), with
+// the reference's division; UVM_MARK where it corrects nothing: i = 1 for u, j = 1 for v, and beyond (im, jm)
+__global__ void k_coef_eta(KP P, int uvm) {
   const int i = TID_I, j = TID_J;
   if (i > P.iml || j > P.jml) return;
   K2(HEA, i, j) = (F2(h, i, j) + F2(etb, i, j)) * F2(art, i, j);
   K2(HFA, i, j) = (F2(h, i, j) + F2(etf, i, j)) * F2(art, i, j);
+  if (uvm) {
+    const unsigned long long mb = UVM_MARK;
+    double mark;
+    __builtin_memcpy(&mark, &mb, sizeof mark);
+    const int iw = i > 1 ? i - 1 : 1, js = j > 1 ? j - 1 : 1;
+    const double cu = (F2(utb, i, j) + F2(utf, i, j)) / (F2(dt, i, j) + F2(dt, iw, j));     // advance.f:375-382
+    const double cv = (F2(vtb, i, j) + F2(vtf, i, j)) / (F2(dt, i, j) + F2(dt, i, js));     // :385-392
+    K2(UCOR, i, j) = (i >= 2 && i <= P.im && j <= P.jm) ? cu : mark;
+    K2(VCOR, i, j) = (j >= 2 && j <= P.jm && i <= P.im) ? cv : mark;
+  }
 }
 
 // ---- advt2, nitera == 1 -- solver.f:577-731 with smol_adif's mask (:1898-1900) --------------------
@@ -107,7 +119,10 @@ __device__ __forceinline__ FaceT advt2_face(const pomgpu_ct tprni, const CoefT &
 //   * dz(k) comes through the constant address space (scalar load) -- as a vector load it queued behind the batch;
 //   * buffer addressing: no vector instruction computes an address; two register sets alternate as current / next
 //     level (no copies); divisors that are fixed along the column are inverted once (divi).
-template <int NF>
+// UM: u, v in memory still lack the depth-mean correction of advance.f:365-393 (KP::uvm, uvm_fix in pomgpu_internal.hpp): applied to
+// u of the own column and to v before it enters the slab -- the own row's with the lane's coefficients, the share of a row outside the
+// workgroup with that row's; the east face travels through the lane shift as before.  Every level this kernel loads is <= kbm1.
+template <int NF, bool UM = false>
 __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
   constexpr int NS = 2 * NF + 2, NH = ROWSHARE_SLOTS(NS), AM = 2 * NF, VV = 2 * NF + 1;
   HALO_XCD_DECODE_R(LDS_ROWS)                                           // a workgroup outside the grid leaves as a whole
@@ -138,6 +153,10 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
   const RowShare<NS> S = rowshare_setup<NS>(P, r, j, j0w, i);
 #pragma unroll
   for (int q = 0; q < NH; q++) bh[q] = BUF3(rowshare_pick<NS>(ps, S.hop[q]));
+  const UvmC mu = UM ? uvm_of<0>(P, i, jc) : uvm_none(), mv = UM ? uvm_of<1>(P, i, jc) : uvm_none();
+  UvmC mh[NH];
+#pragma unroll
+  for (int q = 0; q < NH; q++) mh[q] = UM ? rowshare_uvm<1, NS, LDS_ROWS>(P, S, q, VV, j0w, i) : uvm_none();
   const unsigned oc = BOFF2(i, jc), lvb = LVB;
   const unsigned ost = in ? oc : BOFF_NONE;
 #ifndef POMGPU_EMU
@@ -167,11 +186,12 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
   auto step = [&](const int L, const int par, const LevT<NF> &cur, LevT<NF> &nxt) {
     load(nxt, (unsigned)(L < kbm1 ? L : kbm1 - 1) * lvb);     // the last iterations re-request level kbm1
     NbrT<NS> nb;
+    const pomgpu_ct v_c = uvm_fix(cur.c[VV], mv);
 #ifndef POMGPU_EMU
 #pragma unroll
-    for (int x = 0; x < NS; x++) slab[par][x][r + 1][lane] = cur.c[x];
+    for (int x = 0; x < NS; x++) slab[par][x][r + 1][lane] = x == VV ? v_c : cur.c[x];
 #pragma unroll
-    for (int q = 0; q < NH; q++) slab[par][S.hop[q]][S.hrow[q]][lane] = cur.h[q];
+    for (int q = 0; q < NH; q++) slab[par][S.hop[q]][S.hrow[q]][lane] = uvm_fix(cur.h[q], mh[q]);
     __syncthreads();
 #pragma unroll
     for (int x = 0; x < NS; x++) { nb.s[x] = slab[par][x][S.ss][lane]; nb.n[x] = slab[par][x][S.sn][lane]; }
@@ -179,8 +199,9 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
     const unsigned lvc = (unsigned)((L <= kbm1 ? L : kbm1) - 1) * lvb;
 #pragma unroll
     for (int x = 0; x < NS; x++) { nb.s[x] = bldc(bs[x], os, lvc); nb.n[x] = bldc(bs[x], on, lvc); }
+    nb.s[VV] = uvm_fix(nb.s[VV], uvm_of<1>(P, i, js)); nb.n[VV] = uvm_fix(nb.n[VV], uvm_of<1>(P, i, jn));
 #endif
-    const pomgpu_ct am_c = cur.c[AM], u_c = cur.o[0], w_c = cur.o[1];
+    const pomgpu_ct am_c = cur.c[AM], u_c = uvm_fix(cur.o[0], mu), w_c = cur.o[1];
     const pomgpu_ct am_w = halo_w(am_c, [&] { return F3(aam, iw, jc, L); });
     InvDc dzk; dzk.b = dzk.y = 0.;
     if (L >= 2) { dzk.b = F1(dz, L - 1); dzk.y = R1(dz, L - 1); }
@@ -194,13 +215,13 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
         const pomgpu_ct fc_w = halo_w(fc_c, [&] { return G3(A.fcl[f], iw, jc, L); });
         const FaceT xw = advt2_face(tprni, cw, u_c, fb_c, fb_w, fc_c, fc_w, am_c, am_w);
         auto east = [&] {                                   // emulation only: the east face from memory
-          return advt2_face(tprni, coef_x(P, ie, jc), F3(u, ie, jc, L), G3(A.fb[f], ie, jc, L), fb_c, G3(A.fcl[f], ie, jc, L), fc_c,
+          return advt2_face(tprni, coef_x(P, ie, jc), uvm_ld<0>(P, ie, jc, L), G3(A.fb[f], ie, jc, L), fb_c, G3(A.fcl[f], ie, jc, L), fc_c,
                             F3(aam, ie, jc, L), am_c);
         };
         FaceT xe;
         xe.adv = halo_e(xw.adv, [&] { return east().adv; });
         xe.dif = halo_e(xw.dif, [&] { return east().dif; });
-        const FaceT ys = advt2_face(tprni, cs, cur.c[VV], fb_c, nb.s[f], fc_c, nb.s[NF + f], am_c, nb.s[AM]);
+        const FaceT ys = advt2_face(tprni, cs, v_c, fb_c, nb.s[f], fc_c, nb.s[NF + f], am_c, nb.s[AM]);
         const FaceT yn = advt2_face(tprni, cn, nb.n[VV], nb.n[f], fb_c, nb.n[NF + f], fc_c, nb.n[AM], am_c);
         s_adv = xe.adv - xw.adv + yn.adv - ys.adv;                                            // solver.f:670-671
         s_dif = xe.dif - xw.dif + yn.dif - ys.dif;                                            // :721-722
@@ -272,7 +293,9 @@ __device__ __forceinline__ pomgpu_ct advq_face(const CoefQ &c, pomgpu_ct q_hi, p
 // k_vertvl_rs's expressions in k_vertvl_rs's order; nobody reads a neighbour column's w here, so no workgroup waits for another.
 // Rim columns get vertvl's tail (w = w * fsm on levels 1..kbm1) after the loop.  The fp32-arithmetic variant, whose stencil kernels
 // hold no fp64 arithmetic, does not instantiate WF and keeps the vertvl launch (POMGPU_W_FUSE).
-template <int NF, bool WF = false>
+// UM: as in k_advt2_col -- u, v corrected as they are loaded (levels 1..kbm1), w formed from the corrected values as vertvl follows
+// advance.f:365-393
+template <int NF, bool WF = false, bool UM = false>
 __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int zero_else) {
   constexpr int NS = 2 * NF + 2, NH = ROWSHARE_SLOTS(NS), AM = 2 * NF, VV = 2 * NF + 1;
   typedef LevQa<NF, WF ? 1 : 2> Lev;
@@ -302,6 +325,10 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
   const RowShare<NS> S = rowshare_setup<NS>(P, r, j, j0w, i);
 #pragma unroll
   for (int q = 0; q < NH; q++) bh[q] = BUF3(rowshare_pick<NS>(ps, S.hop[q]));
+  const UvmC mu = UM ? uvm_of<0>(P, i, jc) : uvm_none(), mv = UM ? uvm_of<1>(P, i, jc) : uvm_none();
+  UvmC mh[NH];
+#pragma unroll
+  for (int q = 0; q < NH; q++) mh[q] = UM ? rowshare_uvm<1, NS, LDS_ROWS>(P, S, q, VV, j0w, i) : uvm_none();
   const unsigned oc = BOFF2(i, jc), lvb = LVB;
   // interior columns get the new value, every other owned column a zero (zero_else) or nothing
   const unsigned ost = in ? oc : ((zero_else && icol) ? oc : BOFF_NONE);
@@ -346,11 +373,13 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
   auto step = [&](const int L, const int par, const Lev &cur, Lev &nxt) {
     load(nxt, L + 1 <= kb ? L + 1 : kb);                    // the last iterations re-request level kb
     NbrT<NS> nb;
+    const bool lcor = L <= kbm1;                            // level kb of u, v is never corrected
+    const pomgpu_ct v_c = uvm_fix(cur.c[VV], mv, lcor), u_c = uvm_fix(cur.o[0], mu, lcor);
 #ifndef POMGPU_EMU
 #pragma unroll
-    for (int x = 0; x < NS; x++) slab[par][x][r + 1][lane] = cur.c[x];
+    for (int x = 0; x < NS; x++) slab[par][x][r + 1][lane] = x == VV ? v_c : cur.c[x];
 #pragma unroll
-    for (int q = 0; q < NH; q++) slab[par][S.hop[q]][S.hrow[q]][lane] = cur.h[q];
+    for (int q = 0; q < NH; q++) slab[par][S.hop[q]][S.hrow[q]][lane] = uvm_fix(cur.h[q], mh[q], lcor);
     __syncthreads();
 #pragma unroll
     for (int x = 0; x < NS; x++) { nb.s[x] = slab[par][x][S.ss][lane]; nb.n[x] = slab[par][x][S.sn][lane]; }
@@ -358,13 +387,14 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
     const unsigned lvc = (unsigned)((L <= kb ? L : kb) - 1) * lvb;
 #pragma unroll
     for (int x = 0; x < NS; x++) { nb.s[x] = bldc(bs[x], os, lvc); nb.n[x] = bldc(bs[x], on, lvc); }
+    nb.s[VV] = uvm_fix(nb.s[VV], uvm_of<1>(P, i, js), lcor); nb.n[VV] = uvm_fix(nb.n[VV], uvm_of<1>(P, i, jn), lcor);
 #endif
-    const pomgpu_ct am_c = cur.c[AM], v_c = cur.c[VV], u_c = cur.o[0];
+    const pomgpu_ct am_c = cur.c[AM];
     const pomgpu_ct am_s = nb.s[AM], am_n = nb.n[AM], v_n = nb.n[VV];
     const pomgpu_ct am_w = halo_w(am_c, [&] { return F3(aam, iw, jc, L); });
     pomgpu_ct w_c, ue_c = 0.;
     if constexpr (WF) {
-      ue_c = halo_e(u_c, [&] { return F3(u, ie, jc, L); });
+      ue_c = halo_e(u_c, [&] { return uvm_ld<0>(P, ie, jc, L); });
       // w(L) from level L-1 (solver.f:2006-2014); selects, no branch: iteration 1 keeps the start value.  The running sum is never masked
       const double wn = wk + F1(dz, L >= 2 ? L - 1 : 1) *
                              (divi(vv_ce * (double)ue_m - vv_cw * (double)u_m + vv_cn * (double)vn_m - vv_cs * (double)v_m, vv_area) + vv_det);
@@ -388,7 +418,7 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
         const pomgpu_ct xw = advq_face(cw, q_c, q_w, u_c, u_m, am_c, am_w, am_m, am_w_prv, qb_c, qb_w);
         xw_c = xw;
         xe_c = halo_e(xw, [&] {                             // emulation only: the east face from memory
-          return advq_face(coefq_x(P, ie, jc), G3(A.q[f], ie, jc, L), q_c, F3(u, ie, jc, L), F3(u, ie, jc, L - 1), F3(aam, ie, jc, L), am_c,
+          return advq_face(coefq_x(P, ie, jc), G3(A.q[f], ie, jc, L), q_c, uvm_ld<0>(P, ie, jc, L), uvm_ld<0>(P, ie, jc, L - 1), F3(aam, ie, jc, L), am_c,
                            F3(aam, ie, jc, L - 1), am_m, G3(A.qb[f], ie, jc, L), qb_c);
         });
         ys_c = advq_face(cs, q_c, nb.s[f], v_c, v_m, am_c, am_s, am_m, ams_m, qb_c, nb.s[NF + f]);
@@ -525,6 +555,8 @@ __global__ void k_advct_fix(KP P, const double *from_w, const double *from_s) {
 // sum2d: also leave the vertical integrals adx2d, ady2d of advance.f:152-168 (k_vint) -- the column is here anyway
 // Operands of a level, all five shared through the workgroup's LDS slab (rows j-1, j, j+1): u, v, ub, vb, aam.
 // Loop discipline and row sharing as in k_advt2_col.
+// sum2d bit 1 (one tile): also leave su = sum_k u(k)*dz(k), sv = sum_k v(k)*dz(k) of every owned column (C2_USUM, C2_VSUM), the sums
+// advance.f:365-372 forms at the head of mode_internal -- nothing writes u, v between here and there -- in that loop's order, fp64
 // ROWS rows per workgroup: 8 (LDS_ROWS) on large grids; 4 on low tiles, where a launch is only three or four rounds of workgroups and two
 // workgroups per compute unit leave the last round fuller (launch_advct_col)
 template <int ROWS> struct LevCaT { pomgpu_ct c[5], h[(2 * 5 + ROWS - 1) / ROWS]; };
@@ -551,6 +583,9 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
   const bool in = out && iin && jrow;
   const int kb = P.kb, kbm1 = P.kbm1;
   double ax2 = 0., ay2 = 0.;                                // the vertical sums stay fp64 in every build: they feed the external mode
+#if POMGPU_UVM_ONLOAD
+  double su2 = 0., sv2 = 0.;
+#endif
   // column-resident coefficients
   const pomgpu_ct dtsx_c = K2(DTSX, i, jc), dtsx_s = K2(DTSX, i, js);
   const pomgpu_ct dtsx_e = halo_e(dtsx_c, [&] { return K2(DTSX, ie, jc); });
@@ -672,6 +707,10 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
     const double dzk = F1(dz, k);
     ax2 = ax2 + ax * dzk;
     ay2 = ay2 + ay * dzk;
+#if POMGPU_UVM_ONLOAD
+    su2 = su2 + (double)u_c * dzk;                                                             // advance.f:365-372
+    sv2 = sv2 + (double)v_c * dzk;
+#endif
   };
   LevCa ra, rb;
 #ifdef POMGPU_EMU
@@ -685,6 +724,14 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
   }
 #ifdef POMGPU_EMU
   }
+#if POMGPU_UVM_ONLOAD
+  else {                                                    // a rim row's sums: the march above does not run there in the emulation
+    for (int k = 1; k <= kbm1; k++) { su2 = su2 + (double)F3(u, i, jc, k) * F1(dz, k); sv2 = sv2 + (double)F3(v, i, jc, k) * F1(dz, k); }
+  }
+#endif
+#endif
+#if POMGPU_UVM_ONLOAD
+  if (out && (sum2d & 2)) { K2(USUM, i, jc) = su2; K2(VSUM, i, jc) = sv2; }
 #endif
   if (out) {
     if (jrow) {
@@ -692,7 +739,7 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
     } else {                                                // rim rows: advx = advy = 0 (solver.f:211,:317)
       for (int k = 1; k <= kb; k++) { F3(advx, i, jc, k) = 0.; F3(advy, i, jc, k) = 0.; }
     }
-    if (sum2d) { F2(adx2d, i, jc) = jrow ? ax2 : 0.; F2(ady2d, i, jc) = jrow ? ay2 : 0.; }
+    if (sum2d & 1) { F2(adx2d, i, jc) = jrow ? ax2 : 0.; F2(ady2d, i, jc) = jrow ? ay2 : 0.; }
   }
 #ifdef POMGPU_WGTIME
   __syncthreads();
@@ -721,6 +768,9 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
 struct LevUV { pomgpu_ct c[3], h[ROWSHARE_SLOTS(3)], ub, vb, advx, advy, drhox, drhoy; };
 // Same loop discipline as k_advt2_col: one batch of loads per level, issued a whole iteration ahead and never inside a
 // branch, stores of lanes without an output column aimed outside the buffer, buffer addressing, two register sets.
+// UM: as in k_advt2_col -- u, v corrected as they are loaded and before they enter a slab (levels 1..kbm1; the last iteration loads
+// level kb, which nothing uses); a halo job may carry u or v: it takes that component's coefficients of the row it loads
+template <bool UM>
 __global__ void __launch_bounds__(64 * LDS_ROWS) k_advuv_col(KP P) {
   constexpr int NS = 3, NH = ROWSHARE_SLOTS(NS), W = 0, U = 1, V = 2;
   HALO_XCD_DECODE_R(LDS_ROWS)
@@ -761,6 +811,11 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advuv_col(KP P) {
   const RowShare<NS> S = rowshare_setup<NS>(P, r, j, j0w, i);
 #pragma unroll
   for (int q = 0; q < NH; q++) bh[q] = BUF3(rowshare_pick<NS>(ps, S.hop[q]));
+  const UvmC mu = UM ? uvm_of<0>(P, i, jc) : uvm_none(), mv = UM ? uvm_of<1>(P, i, jc) : uvm_none();
+  UvmC mh[NH];
+#pragma unroll
+  for (int q = 0; q < NH; q++)
+    mh[q] = !UM ? uvm_none() : (S.hop[q] == U ? rowshare_uvm<0, NS, LDS_ROWS>(P, S, q, U, j0w, i) : rowshare_uvm<1, NS, LDS_ROWS>(P, S, q, V, j0w, i));
   const unsigned oc = BOFF2(i, jc), lvb = LVB;
   const unsigned ost = out ? oc : BOFF_NONE;
 #ifndef POMGPU_EMU
@@ -777,12 +832,13 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advuv_col(KP P) {
     L.ub = bldc(bub, oc, lv);  L.vb = bldc(bvb, oc, lv);
     L.advx = bldc(bax, oc, lv); L.advy = bldc(bay, oc, lv); L.drhox = bldc(bdx, oc, lv); L.drhoy = bldc(bdy, oc, lv);
   };
-  auto park = [&](const pomgpu_ct (&cv)[3], const pomgpu_ct (&hv)[NH], const int sl) {
+  // lcor: the level being parked is one of 1..kbm1.  u_o, v_o: the own column's corrected values, as they went into the slab
+  auto park = [&](const pomgpu_ct (&cv)[3], const pomgpu_ct (&hv)[NH], const int sl, const bool lcor, pomgpu_ct &u_o, pomgpu_ct &v_o) {
+    u_o = uvm_fix(cv[U], mu, lcor); v_o = uvm_fix(cv[V], mv, lcor);
 #ifndef POMGPU_EMU
+    slab[sl][W][r + 1][lane] = cv[W]; slab[sl][U][r + 1][lane] = u_o; slab[sl][V][r + 1][lane] = v_o;
 #pragma unroll
-    for (int x = 0; x < NS; x++) slab[sl][x][r + 1][lane] = cv[x];
-#pragma unroll
-    for (int q = 0; q < NH; q++) slab[sl][S.hop[q]][S.hrow[q]][lane] = hv[q];
+    for (int q = 0; q < NH; q++) slab[sl][S.hop[q]][S.hrow[q]][lane] = uvm_fix(hv[q], mh[q], lcor);
 #endif
   };
   // level 1 of u, v (and w, unused) into slab 0: what the first iteration reads as its "level k" neighbours
@@ -793,26 +849,27 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advuv_col(KP P) {
     for (int x = 0; x < NS; x++) c1[x] = bldc(bs[x], oc, 0u);
 #pragma unroll
     for (int q = 0; q < NH; q++) h1[q] = bldc(bh[q], S.hoff[q], 0u);
-    park(c1, h1, 0);
-    u_k = c1[U]; v_k = c1[V];
+    park(c1, h1, 0, true, u_k, v_k);
   }
   pomgpu_ct fu_k = 0., fv_k = 0.;                              // vertical fluxes at level k (0 at the surface)
   auto step = [&](const int k, const int sl, const LevUV &c, LevUV &nxt) {   // sl = k % 3: the slab of level k+1
     load(nxt, k + 1 <= kbm1 ? k + 1 : kbm1);                // in flight during this iteration (the last one re-requests level kbm1)
-    park(c.c, c.h, sl);
+    pomgpu_ct u_c, v_c;                                     // level k+1
+    park(c.c, c.h, sl, k + 1 <= kbm1, u_c, v_c);
     const int slm = sl == 0 ? 2 : sl - 1;                   // the slab of level k
 #ifndef POMGPU_EMU
     __syncthreads();
     const pomgpu_ct w_s = slab[sl][W][S.ss][lane], u_s = slab[slm][U][S.ss][lane], v_n = slab[slm][V][S.sn][lane];
 #else
-    const pomgpu_ct w_s = bldc(bs[W], os, (unsigned)k * lvb), u_s = bldc(bs[U], os, (unsigned)(k - 1) * lvb), v_n = bldc(bs[V], on, (unsigned)(k - 1) * lvb);
+    const pomgpu_ct w_s = bldc(bs[W], os, (unsigned)k * lvb), u_s = uvm_fix(bldc(bs[U], os, (unsigned)(k - 1) * lvb), uvm_of<0>(P, i, js)),
+                    v_n = uvm_fix(bldc(bs[V], on, (unsigned)(k - 1) * lvb), uvm_of<1>(P, i, jn));
 #endif
-    const pomgpu_ct w_c = c.c[W], u_c = c.c[U], v_c = c.c[V];   // level k+1
+    const pomgpu_ct w_c = c.c[W];
     const pomgpu_ct w_w = halo_w(w_c, [&] { return F3(w, iw, jc, k + 1); });
     const pomgpu_ct tc = cd_c * (v_n + v_k);                                                // cor*dt*(v(i,j+1,k)+v(i,j,k))
-    const pomgpu_ct tw = halo_w(tc, [&] { return F2(cor, iw, jc) * F2(dt, iw, jc) * (F3(v, iw, jn, k) + F3(v, iw, jc, k)); });
-    const pomgpu_ct u_e = halo_e(u_k, [&] { return F3(u, ie, jc, k); });
-    const pomgpu_ct u_se = halo_e(u_s, [&] { return F3(u, ie, js, k); });
+    const pomgpu_ct tw = halo_w(tc, [&] { return F2(cor, iw, jc) * F2(dt, iw, jc) * (uvm_ld<1>(P, iw, jn, k) + uvm_ld<1>(P, iw, jc, k)); });
+    const pomgpu_ct u_e = halo_e(u_k, [&] { return uvm_ld<0>(P, ie, jc, k); });
+    const pomgpu_ct u_se = halo_e(u_s, [&] { return uvm_ld<0>(P, ie, js, k); });
     // vertical fluxes at level k+1 (:744-751, :801-808); zero below kbm1, and where the column has no west / south neighbour
     pomgpu_ct fu_n = 0., fv_n = 0.;
     if (k + 1 <= kbm1) {
@@ -850,7 +907,7 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advuv_col(KP P) {
 // ---- launchers ------------------------------------------------------------------------------------
 void launch_coef_static(pomgpu_ctx *c) { LAUNCH(c, k_coef_static, grid2(c->P), blk2(), c->P); }
 void launch_coef_dt(pomgpu_ctx *c) { LAUNCH(c, k_coef_dt, grid2(c->P), blk2(), c->P); }
-void launch_coef_eta(pomgpu_ctx *c) { LAUNCH(c, k_coef_eta, grid2(c->P), blk2(), c->P); }
+void launch_coef_eta(pomgpu_ctx *c, int uvm) { LAUNCH(c, k_coef_eta, grid2(c->P), blk2(), c->P, uvm); }
 void launch_advq_col(pomgpu_ctx *c, const double *q, const double *qb, double *qf, int zero_else) {
   QFields A; A.q[0] = A.q[1] = q; A.qb[0] = A.qb[1] = qb; A.qf[0] = A.qf[1] = qf;
   LAUNCHN(c, "k_advq_col", (k_advq_col<1>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A, zero_else);
@@ -864,12 +921,16 @@ void launch_advq2_col(pomgpu_ctx *c, const double *q, const double *qb, double *
 #if POMGPU_W_FUSE
 void launch_advq2w_col(pomgpu_ctx *c, const double *q, const double *qb, double *qf, const double *ql, const double *qlb, double *qlf, int zero_else) {
   QFields A; A.q[0] = q; A.qb[0] = qb; A.qf[0] = qf; A.q[1] = ql; A.qb[1] = qlb; A.qf[1] = qlf;
+#if POMGPU_UVM_ONLOAD
+  if (c->P.uvm) { LAUNCHN(c, "k_advq2_col", (k_advq_col<2, true, true>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A, zero_else); return; }
+#endif
   LAUNCHN(c, "k_advq2_col", (k_advq_col<2, true>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A, zero_else);
 }
 #endif
 void launch_advct_col(pomgpu_ctx *c, int sum2d) {
   // low tiles (a tile of an 8- or 4-tile split of 2048x1536): 4-row workgroups, two per compute unit
   const bool rows4 = SW(c, ADVCT_ROWS4) || (!SW(c, ADVCT_ROWS8) && c->P.jml <= 400 && c->exch);
+  sum2d = (sum2d ? 1 : 0) | (POMGPU_UVM_ONLOAD && !c->exch && !c->tp.on && !c->wide.on && !(c->flags & POMGPU_CTX_2D) ? 2 : 0);   // bit 1: the depth sums of u, v (one tile)
   if (rows4) LAUNCHN(c, "k_advct_col", (k_advct_col<4>), grid1_halo_r(c->P, 4), blk_col_r(4), c->P, sum2d);
   else LAUNCHN(c, "k_advct_col", (k_advct_col<LDS_ROWS>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, sum2d);
 }
@@ -905,7 +966,12 @@ void launch_advct_fix(pomgpu_ctx *c, const double *from_w, const double *from_s)
   const int len = P.im > P.jm ? P.im : P.jm;
   LAUNCH(c, k_advct_fix, dim3((len + 63) / 64, P.kbm1, 1), dim3(64, 1, 1), c->P, from_w, from_s);
 }
-void launch_advuv_col(pomgpu_ctx *c) { LAUNCH(c, k_advuv_col, grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P); }
+void launch_advuv_col(pomgpu_ctx *c) {
+#if POMGPU_UVM_ONLOAD
+  if (c->P.uvm) { LAUNCHN(c, "k_advuv_col", (k_advuv_col<true>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P); return; }
+#endif
+  LAUNCHN(c, "k_advuv_col", (k_advuv_col<false>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P);
+}
 void launch_advt2_rows(pomgpu_ctx *c, const double *fb, const double *f, const double *fc, double *ff) {
   {
     TFields A; A.fb[0] = A.fb[1] = fb; A.f[0] = A.f[1] = f; A.fcl[0] = A.fcl[1] = fc; A.ff[0] = A.ff[1] = ff;
@@ -915,5 +981,8 @@ void launch_advt2_rows(pomgpu_ctx *c, const double *fb, const double *f, const d
 void launch_advt2x2_col(pomgpu_ctx *c, const double *tb, const double *t, const double *tc, double *tf, const double *sb, const double *s_,
                         const double *sc, double *sf) {
   TFields A; A.fb[0] = tb; A.f[0] = t; A.fcl[0] = tc; A.ff[0] = tf; A.fb[1] = sb; A.f[1] = s_; A.fcl[1] = sc; A.ff[1] = sf;
+#if POMGPU_UVM_ONLOAD
+  if (c->P.uvm) { LAUNCHN(c, "k_advt2x2_col", (k_advt2_col<2, true>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A); return; }
+#endif
   LAUNCHN(c, "k_advt2x2_col", (k_advt2_col<2>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A);
 }

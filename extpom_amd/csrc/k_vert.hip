@@ -587,6 +587,18 @@ __global__ void __launch_bounds__(64 * ROWS) k_profq(KP P, int rho_rt_pace, int 
   const int ie = i < P.iml ? i + 1 : i, jn = j < P.jml ? j + 1 : j;
   const double hij = h_(i, j);
   const InvD dhk = inv_of(dh * P.kappa);
+  // KP::uvm (one tile): u, v in memory still lack the depth-mean correction of advance.f:365-393; the production term takes the loaded
+  // values corrected with the coefficients of the column each comes from (uvm_fix, pomgpu_internal.hpp)
+  // Only the columns 2..imm1 x 2..jmm1 (pin) use them, and there the reference corrects all four: no per-lane mark to test, the
+  // select is on KP::uvm alone (wave-uniform)
+  UvmC m_uc = uvm_none(), m_ue = uvm_none(), m_vc = uvm_none(), m_vn = uvm_none();
+#if POMGPU_UVM_ONLOAD
+  if (FP == 1 && P.uvm) {                                   // one tile only (FP = 2: tiles keep the pass)
+    m_uc.s = K2(USUM, i, j); m_uc.c = K2(UCOR, i, j); m_ue.s = K2(USUM, ie, j); m_ue.c = K2(UCOR, ie, j);
+    m_vc.s = K2(VSUM, i, j); m_vc.c = K2(VCOR, i, j); m_vn.s = K2(VSUM, i, jn); m_vn.c = K2(VCOR, i, jn);
+    m_uc.on = m_ue.on = m_vc.on = m_vn.on = true;
+  }
+#endif
   // buffers and per-lane offsets
   // descriptors are formed where they are used (uniform pointer -> scalar registers); kept as named values they were
   // carried through the loops in vector registers (too many for the scalar file) at the price of a waterfall loop per load
@@ -616,8 +628,14 @@ __global__ void __launch_bounds__(64 * ROWS) k_profq(KP P, int rho_rt_pace, int 
   const unsigned o_pr = (FP == 0 || (FP == 2 && !pin)) ? oc : BOFF_NONE;
   const unsigned o_rm = rho_rt ? oc : BOFF_NONE;            // rmean is requested only where it is used (outside the buffer: no traffic)
   // boundary values of the two solves -- :1296-1297, :1417-1425
+  // (the peeled walk forms them where it holds their operand, two column-resident values less: vbot at level kbm1 from that level's
+  // q2, ufbot from the level kb it loads last -- the walk down stores neither q2 nor level kb of uf)
+#ifdef PROFQ_OLDWALK
   const double vbot = P.kappa * (1 + F1(z, kbm1)) * dh * F3(q2, i, j, kbm1);
   const double ufbot = F3(uf, i, j, kb);
+#else
+  double ufbot;
+#endif
   double e1p = 0., g1p = P.cb_profq * utau2;    // ee1, gg1 of level k-1 (level 1: the surface boundary value)
   double e2p = 0., g2p = 0.;                    // ee2, gg2 of level k-1
   double ccm = 0., rhom = 0.;                   // sound speed and density of level k-1
@@ -646,7 +664,7 @@ __global__ void __launch_bounds__(64 * ROWS) k_profq(KP P, int rho_rt_pace, int 
     double q2b = cur.q2b;
     double l, gh = 0.;
     double uck = 0., uek = 0., vck = 0., vnk = 0., bg = 0.;
-    if (pin && k <= kbm1) { uck = cur.uc; uek = cur.ue; vck = cur.vc; vnk = cur.vn; }
+    if (pin && k <= kbm1) { uck = uvm_fix(cur.uc, m_uc); uek = uvm_fix(cur.ue, m_ue); vck = uvm_fix(cur.vc, m_vc); vnk = uvm_fix(cur.vn, m_vn); }
     double q2lb = 0.;
     if (mid) {
       q2b = fabs(q2b);                                                                      // :1325-1326
@@ -781,7 +799,10 @@ __global__ void __launch_bounds__(64 * ROWS) k_profq(KP P, int rho_rt_pace, int 
     double q2b = cur.q2b;
     double l, gh = 0.;
     double uck = 0., uek = 0., vck = 0., vnk = 0., bg = 0.;
-    if (PH != PH_KB) { uck = pin ? cur.uc : 0.; uek = pin ? cur.ue : 0.; vck = pin ? cur.vc : 0.; vnk = pin ? cur.vn : 0.; }
+    if (PH != PH_KB) {
+      uck = pin ? uvm_fix(cur.uc, m_uc) : 0.; uek = pin ? uvm_fix(cur.ue, m_ue) : 0.;
+      vck = pin ? uvm_fix(cur.vc, m_vc) : 0.; vnk = pin ? uvm_fix(cur.vn, m_vn) : 0.;
+    }
     double q2lb = 0.;
     if (mid) {
       q2b = fabs(q2b);                                                                      // :1325-1326
@@ -822,7 +843,7 @@ __global__ void __launch_bounds__(64 * ROWS) k_profq(KP P, int rho_rt_pace, int 
         e2p = 0.;
         g2p = -P.kappa * F1(z, 2) * dh * cur.q2;
       } else {
-        const double rhs = (PH == PH_KBM1) ? vbot : cur.vf;
+        const double rhs = (PH == PH_KBM1) ? P.kappa * (1 + F1(z, kbm1)) * dh * cur.q2 : cur.vf;
         const double g2 = 1. / (a + c * (1. - e2p) - (P.dti2 * dtef2 + 1.));
         e2p = a * g2;
         g2p = (P.dti2 * (-pr * l * e1) + c * g2p - rhs) * g2;
@@ -908,6 +929,7 @@ __global__ void __launch_bounds__(64 * ROWS) k_profq(KP P, int rho_rt_pace, int 
     if (pace) PACE_BARRIER();
     step(integral_constant<int, PH_KBM1>(), kbm1, ra, rb);
     step(integral_constant<int, PH_KB>(), kb, rb, ra);
+    ufbot = rb.uf;                                          // uf(i,j,kb)
   }
 #endif
   // ---- back substitution -- :1406-1413, :1448-1455, abs :1467-1468; with the fused filter one level of k_q_filter rides
@@ -1504,6 +1526,13 @@ static __device__ __forceinline__ void d_profuv_reg(const KP &P, const bool stor
 #pragma unroll
     for (int q = 0; q < CH; q++) t0[q] = bld(bb, o_in, LVK(q + 1));
     const double c_kb = bld(bc, o_in, (unsigned)(kb - 1) * lvb), f_kb = bld(bf, o_in, (unsigned)(kb - 1) * lvb);
+    // KP::uvm: the old u(ki) still lacks advance.f:365-393.  Every column filtered here (i, j >= 5) is one the reference corrects: no
+    // mark to test, the select is wave-uniform.  Requested behind the fence: nothing of it is live during the solve above
+    SCHED_FENCE();
+    UvmC mc = uvm_none();
+#if POMGPU_UVM_ONLOAD
+    if (P.uvm) { mc.s = V ? K2(VSUM, i, j) : K2(USUM, i, j); mc.c = V ? K2(VCOR, i, j) : K2(UCOR, i, j); mc.on = true; }
+#endif
     double su = 0.;
 #pragma unroll
     for (int ch = 0; ch < NCH; ch++) {
@@ -1520,6 +1549,7 @@ static __device__ __forceinline__ void d_profuv_reg(const KP &P, const bool stor
         const int k = ch * CH + q + 1;
         if (k <= NL) {
           const double uf = ee[k - 1];
+          gg[k - 1] = uvm_fix(gg[k - 1], mc);
           const double d = uf + ((ch & 1) ? t1[q] : t0[q]) - 2. * gg[k - 1];                // advance.f:473-474 / :495-496
           ee[k - 1] = d;
           const double sn = su + d * F1(dz, KC(k));
@@ -1728,11 +1758,14 @@ static __device__ __forceinline__ void d_uv_filter_rim(const KP &P) {
   const int kb = P.kb, kbm1 = P.kbm1;
   constexpr int CH = 8;
   double xf[CH], xb[CH], xc[CH];
+  const UvmC mc = uvm_of<V>(P, i, j);                         // KP::uvm: the old u, v of levels 1..kbm1 lack advance.f:365-393
 #define KC(k) ((k) < kbm1 ? (k) : kbm1)
   double su = 0.;
   for (int k0 = 1; k0 <= kbm1; k0 += CH) {
 #pragma unroll
     for (int q = 0; q < CH; q++) { xf[q] = G3(f, i, j, KC(k0 + q)); xb[q] = G3(b, i, j, KC(k0 + q)); xc[q] = G3(c, i, j, KC(k0 + q)); }
+#pragma unroll
+    for (int q = 0; q < CH; q++) xc[q] = uvm_fix(xc[q], mc);
 #pragma unroll
     for (int q = 0; q < CH; q++)
       if (k0 + q <= kbm1) su = su + (xf[q] + xb[q] - 2. * xc[q]) * F1(dz, k0 + q);          // advance.f:473-474 / :495-496
@@ -1740,6 +1773,8 @@ static __device__ __forceinline__ void d_uv_filter_rim(const KP &P) {
   for (int k0 = 1; k0 <= kbm1; k0 += CH) {
 #pragma unroll
     for (int q = 0; q < CH; q++) { xf[q] = G3(f, i, j, KC(k0 + q)); xb[q] = G3(b, i, j, KC(k0 + q)); xc[q] = G3(c, i, j, KC(k0 + q)); }
+#pragma unroll
+    for (int q = 0; q < CH; q++) xc[q] = uvm_fix(xc[q], mc);
 #pragma unroll
     for (int q = 0; q < CH; q++)
       if (k0 + q <= kbm1) {

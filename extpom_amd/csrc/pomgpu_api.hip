@@ -269,12 +269,24 @@ static bool w_fused(const pomgpu_ctx *c) {
   return POMGPU_W_FUSE && !c->exch && !c->tp.on && !c->wide.on && !(c->flags & POMGPU_CTX_2D) && !SW(c, ADVQ_SINGLE) && !SW(c, ADVQ_EXCHANGE) &&
          !SW(c, VERTVL_CELLS) && !SW(c, W_NOFUSE);
 }
+// may mode_internal leave u, v raw in memory and have every kernel between the external mode and the velocity filter apply the
+// depth-mean correction (advance.f:365-393) to what it loads, instead of launching k_int_uvmean?  Where all those kernels are the ones
+// that know how (uvm_fix, pomgpu_internal.hpp): the fused q2 / q2l march that also forms w, the one-pass tracer advection or none
+// (mode 4), k_advuv_col and the fused profu / profv / filter tail -- and where k_advct_col has left the depth sums of the u, v that
+// are in memory now (uvm_valid).  POMGPU_UVMEAN_PASS (read here, at launch time) keeps the pass.  No lazy state survives the step: the
+// filter that ends the 3-D body overwrites u, v.  The fp32-arithmetic variant keeps the pass at build time (POMGPU_UVM_ONLOAD)
+static bool uvm_onload(const pomgpu_ctx *c) {
+  const pom_blkcon &k = c->con;
+  return POMGPU_UVM_ONLOAD && w_fused(c) && uv_fused(c) && c->uvm_valid && !SW(c, UVMEAN_PASS) &&
+         (k.mode == 4 || (k.nadv == 2 && c->P.nitera == 1 && !SW(c, ADVT2_SINGLE)));
+}
 static void uvf_materialize(pomgpu_ctx *c) {
   if (!c->uvf_pending) return;
   c->uvf_pending = 0;
   launch_uvf_copy(c);
 }
 static void restore_materialize(pomgpu_ctx *c) {
+  c->uvm_valid = 0;                                           // whoever asks for materialised state may write u, v next (uploads, handed-out addresses, stand-alone entry points)
   side_join(c);                                               // whoever asks for materialised state also waits for the side stream
   rho_materialize(c);
   pomgpu_wr_materialize(c);
@@ -736,7 +748,11 @@ static void seq_advave(pomgpu_ctx *c) {                       // solver.f:6-198
 }
 static void seq_advct(pomgpu_ctx *c, int sum2d = 0, int defer_xch = 0) {   // solver.f:201-408
   KP &P = c->P;
-  if (!c->exch) { launch_advct_col(c, sum2d); return; }       // one tile: nothing to exchange, fluxes stay in registers
+  if (!c->exch) {                                             // one tile: nothing to exchange, fluxes stay in registers
+    launch_advct_col(c, sum2d);
+    c->uvm_valid = POMGPU_UVM_ONLOAD && !c->tp.on && !c->wide.on && !(c->flags & POMGPU_CTX_2D);   // ... and the depth sums of u, v are left for mode_internal
+    return;
+  }
   if (c->tp.on && !SW(c, ADVCT_SPLIT)) {            // tiles, the library's own exchange: see k_advct_edge
     pomgpu_transport &T = c->tp;
     const size_t ne = 2 * (size_t)P.kbm1 * P.jm, nn = 2 * (size_t)P.kbm1 * P.im;
@@ -1004,6 +1020,7 @@ int pomgpu_materialize(pomgpu_ctx *c) {
 // pomgpu_read_restart (cdf_out.hip) has written 2-D and 3-D mirrors with its own kernel: what pomgpu_upload_2d invalidates for
 // those slots (none of them is a mask or a taurstr array; upload_3d invalidates nothing else)
 void pomgpu_mirrors_written(pomgpu_ctx *c) {
+  c->uvm_valid = 0;                                           // u, v are the file's now
   c->wide.static_done = 0;
   early_invalidate(c);
   refresh_coefs(c);
@@ -1650,7 +1667,11 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
   rim_wait_r8(c);                                             // (a step whose lateral_viscosity did not run: nothing else has waited)
   if ((k.iint != 1 || k.time0 != 0.) && k.mode != 2) {
     c->uvf_pending = 0;                                       // u, v change now and advq rewrites uf, vf whole: nobody has asked for the copy
-    launch_int_uvmean(c);                                     // :365-393
+    // :365-393 as a pass over u, v -- or applied by every kernel below to what it loads of them, u, v staying raw in memory until the
+    // filter overwrites them (uvm_onload; KP::uvm tells the kernels, and is down again when this function returns)
+    struct UvmScope { pomgpu_ctx *c; ~UvmScope() { c->P.uvm = 0; c->uvm_valid = 0; } } uvm_scope{c};
+    P.uvm = uvm_onload(c) ? 1 : 0;
+    if (!P.uvm) launch_int_uvmean(c);                         // :365-393
     const bool wf = w_fused(c);                               // :396-398 inside advq's march below
     if (!wf) launch_vertvl(c, 1);                             // :396-398
     // :400 exchange3d_mpi(w): nothing reads w's ghost cells before advt / advu (advq takes w at the cell's own
@@ -1669,7 +1690,7 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
     }
     else if (!lib_x) xch(c, 1, D3(c, w), P.kb);
     // :403-409 (uf = vf = 0 is folded into the advq step kernels)
-    launch_coef_eta(c);                                       // etb/etf are final once the external mode is done
+    launch_coef_eta(c, P.uvm);                                // etb/etf are final once the external mode is done (and utf, vtf: the means u, v are corrected to)
     // advq's exchange of xflux, yflux (solver.f:458-459) hands a tile the neighbour's xflux(2,j) as its
     // xflux(im,j): the same formula on the same operands the tile holds in its own ghost cells (q, qb, u, dt, aam
     // have all been exchanged), i.e. the value it computes itself.  The fused flux+step kernel therefore serves

@@ -18,7 +18,7 @@
 #endif
 #define POMGPU_NSCR3 8     // 3-D scratch arrays (the reference's automatic arrays that survive fusion)
 #define POMGPU_NSCR2 8     // 2-D scratch arrays
-#define POMGPU_NCOEF2 24   // derived 2-D coefficient arrays
+#define POMGPU_NCOEF2 25   // derived 2-D coefficient arrays
 #define POMGPU_MAXREC 8
 #define POMGPU_KBMAX 128   // per-column private arrays in the tridiagonal kernels
 #define POMGPU_CTX_2D 1
@@ -56,6 +56,9 @@ struct KP {
   // the three 0/1 masks of a cell in one byte (bit 0 fsm, 1 dum, 2 dvm), k_coef_static: the fused external substep
   // reads 2 bytes instead of 4 doubles per cell; (double)bit * x is the reference's mask multiply, bit for bit
   unsigned char *m8;
+  // 1 while u, v in memory still lack the depth-mean correction of advance.f:365-393 and every kernel that loads them applies it
+  // (uvm_fix below; mode_internal on one tile, between the external mode and the velocity filter).  0 everywhere else
+  int uvm;
 };
 enum pomgpu_x2 { X2_ua, X2_va, X2_d, X2_el, X2_elb, X2_uab, X2_vab };
 
@@ -98,6 +101,13 @@ typedef double pomgpu_ct;
 #define POMGPU_W_FUSE 0
 #else
 #define POMGPU_W_FUSE 1
+#endif
+// The depth-mean correction of u, v (advance.f:365-393) applied to what a kernel loads instead of stored by a pass of its own (uvm_fix
+// below) is fp64 arithmetic inside the stencil kernels: the fp32-arithmetic variant keeps the pass (k_int_uvmean), as it keeps vertvl.
+#ifdef POMGPU_COMPUTE_F32
+#define POMGPU_UVM_ONLOAD 0
+#else
+#define POMGPU_UVM_ONLOAD 1
 #endif
 #ifdef POMGPU_STORE_F32
 struct Ref3 {
@@ -162,10 +172,51 @@ enum pomgpu_coef2 {
   C2_CVA, C2_CVB,      // dy(i+1,j)-dy(i-1,j), dx(i,j+1)-dx(i,j-1)            (static; curvature terms)
   C2_R2DXSX, C2_R2DYSY,// 2.0/DXSX, 2.0/DYSY                                  (static; realvertvl's dxl/dyb)
   C2_RDX, C2_RDY,      // RN(1/dx), RN(1/dy): the reciprocals divi() needs         (static; k_aam_pair's four divisions per cell)
+  C2_USUM, C2_VSUM,    // sum_k u(k)*dz(k), sum_k v(k)*dz(k) of the u, v in memory (k_advct_col; pomgpu_ctx::uvm_valid says whether they still are)
+  C2_UCOR, C2_VCOR,    // (utb+utf)/(dt(i,j)+dt(i-1,j)), (vtb+vtf)/(dt(i,j)+dt(i,j-1)) or UVM_MARK (k_coef_eta, mode_internal)
   C2__count
 };
 static_assert(C2__count <= POMGPU_NCOEF2, "raise POMGPU_NCOEF2");
 #define K2(name, i, j) P.c2[C2_##name][IX2(i, j)]
+
+// ---- the depth-mean correction of u, v on load (advance.f:365-393 without its pass) ----------------------------------------------
+// The reference makes the depth mean of u equal (utb+utf)/(dt(i,j)+dt(i-1,j)): u(k) = (u(k) - su) + cu on levels 1..kbm1 of the columns
+// i >= 2, v alike on j >= 2.  While KP::uvm is set, u and v in memory are still raw and every kernel that reads them applies these two
+// operations to the loaded value, with the sums (C2_USUM, C2_VSUM) and means (C2_UCOR, C2_VCOR) of the column it loaded -- and rounds
+// to the storage type, which is what the pass stored.  A column the reference leaves alone carries UVM_MARK in place of its mean: the
+// correction is a select there, not (x - 0) + 0, which would turn -0.0 into +0.0.  The mark is a NaN no division delivers.
+#define UVM_MARK 0x7ff8c0de5eed0001ULL
+struct UvmC { double s, c; bool on; };
+__device__ __forceinline__ UvmC uvm_none() { UvmC m; m.s = 0.; m.c = 0.; m.on = false; return m; }
+// the coefficients of column (i,j) for component V (0: u, 1: v); nothing while the correction is not pending
+template <int V> __device__ __forceinline__ UvmC uvm_of(const KP &P, int i, int j) {
+  UvmC m = uvm_none();
+#if POMGPU_UVM_ONLOAD
+  if (P.uvm) {
+    m.s = V ? K2(VSUM, i, j) : K2(USUM, i, j);
+    m.c = V ? K2(VCOR, i, j) : K2(UCOR, i, j);
+    unsigned long long b;
+    __builtin_memcpy(&b, &m.c, sizeof b);
+    m.on = b != UVM_MARK;
+  }
+#endif
+  return m;
+}
+// lev: the value belongs to a level 1..kbm1 (level kb is never corrected)
+__device__ __forceinline__ double uvm_fix(double x, const UvmC &m, bool lev = true) {
+#if POMGPU_UVM_ONLOAD
+  const double y = (double)(pomgpu_st)((x - m.s) + m.c);
+  return (m.on && lev) ? y : x;
+#else
+  return x;
+#endif
+}
+__device__ __forceinline__ float uvm_fix(float x, const UvmC &, bool = true) { return x; }   // the fp32-arithmetic variant: never pending
+// u(i,j,k) / v(i,j,k) as the pass would have left it, straight from memory (edge kernels, emulation fallbacks)
+template <int V> __device__ __forceinline__ double uvm_ld(const KP &P, int i, int j, int k) {
+  const double x = V ? (double)F3(v, i, j, k) : (double)F3(u, i, j, k);
+  return uvm_fix(x, uvm_of<V>(P, i, j), k <= P.kbm1);
+}
 
 // Neighbour-lane access for stencils along i.  A wavefront owns 64 consecutive i of one row; the
 // value its western / eastern neighbour lane holds replaces a second global load of the same word.
@@ -380,6 +431,13 @@ template <int NS, int ROWS = LDS_ROWS> __device__ __forceinline__ RowShare<NS, R
   }
   return S;
 }
+// the depth-mean coefficients (uvm_of) of halo job q, if it loads shared operand `op` (component V of u, v): those of the column and
+// ROW it loads from -- south of the workgroup's first row or north of its last, not the wavefront's own.  Wave-uniform branches
+template <int V, int NS, int ROWS> __device__ __forceinline__ UvmC rowshare_uvm(const KP &P, const RowShare<NS, ROWS> &S, int q, int op, int j0w, int i) {
+  if (S.hop[q] != op || S.hrow[q] == ROWS + 2) return uvm_none();
+  const int jsouth = j0w > 1 ? j0w - 1 : 1, jnorth = j0w + ROWS <= P.jml ? j0w + ROWS : P.jml;
+  return uvm_of<V>(P, i, S.hrow[q] == 0 ? jsouth : jnorth);
+}
 // the array a halo job reads: chosen by a wavefront-uniform index; the pointer is pinned to scalar registers so that the
 // descriptor built from it is one (a descriptor in vector registers costs a waterfall loop around every load)
 template <int NS> __device__ __forceinline__ const double *rowshare_pick(const double *const (&b)[NS], int op) {
@@ -520,7 +578,7 @@ static inline dim3 grid2_halo(const KP &P) { return dim3((P.iml + 61) / 62, (P.j
   X(PROFQ_NOPACE) X(COL_STRIP) X(BAND_BYTES) X(PAD3) X(IO_SYNC) X(ADVCT_SPLIT) X(ADVQ_EXCHANGE) X(PROD_FULL) X(QFILTER_SPLIT) \
   X(UV_FULL_EXCHANGE) X(NO_OVERLAP) X(NO_SIDE_COMM) X(WR_MAIN) X(WIDE_W) X(WIDE_FULL) X(DEBUG_ALLOC) X(TEST_SPLIT_FAIL_RANK)  \
   X(EDGE_SPLIT) X(WR_NODEFER) X(EXT_RING_FIRST) X(TUNE_FORCE) X(NO_TWIN) X(RIM_MAIN) X(RIM_RESULTS_MAIN) X(SUM2D_OFF) X(ADVCT_ROWS4) X(ADVCT_ROWS8) \
-  X(IO_CHUNK_KB) X(UV_NOFUSE) X(W_NOFUSE)
+  X(IO_CHUNK_KB) X(UV_NOFUSE) X(W_NOFUSE) X(UVMEAN_PASS)
 enum pomgpu_sw {
 #define POMGPU_SW_(name) SW_##name,
   POMGPU_SWITCHES(POMGPU_SW_)
@@ -664,6 +722,10 @@ struct pomgpu_ctx {
   // mode_internal's advq rewrites them whole; whoever looks at the mirrors first gets the copy (restore_materialize).  Valid until the
   // 3-D part of the next mode_internal changes u, v, which drops the flag.
   int uvf_pending;
+  // C2_USUM, C2_VSUM are the depth sums of the u, v now in memory: k_advct_col has left them (lateral_viscosity) and nothing has written
+  // u, v since.  Dropped by everything that may write them from outside the step (restore_materialize: uploads, downloads, handed-out
+  // addresses, the stand-alone entry points; the restart reader) and by mode_internal itself, whose filter rewrites u, v.
+  int uvm_valid;
   double *uvb_bot[2];        // level kbm1 of ub, vb as they were before that kernel: its bottom friction reads neighbour columns others rewrite
   int wr_eager;              // pomgpu_device_2d / _3d has handed out an address: reads and writes the library cannot see -- wr at the end of every step from then on
   double *d_vel;             // device: vamax, then (imax,jmax) as two doubles' worth of ints
@@ -847,7 +909,7 @@ void launch_uv_filter(pomgpu_ctx *c, int own = 0);   // own: the ghost lines are
 // k_tile.hip
 void launch_coef_static(pomgpu_ctx *c);
 void launch_coef_dt(pomgpu_ctx *c);
-void launch_coef_eta(pomgpu_ctx *c);
+void launch_coef_eta(pomgpu_ctx *c, int uvm = 0);   // uvm: C2_UCOR, C2_VCOR as well (mode_internal)
 void launch_advt2_rows(pomgpu_ctx *c, const double *fb, const double *f, const double *fc, double *ff);
 void launch_advq_col(pomgpu_ctx *c, const double *q, const double *qb, double *qf, int zero_else);
 // k_bc.hip
