@@ -1179,13 +1179,100 @@ template <int KBT, int SW>
 __global__ void __launch_bounds__(64 * ROWS_PROFT) k_proft_reg(KP P, double *f, const double *wfsurf, const double *fsurf, int nbc) {
   d_proft_reg<KBT, SW>(P, f, wfsurf, fsurf, nbc);
 }
-// T and S (advance.f:439-440: two calls that share nothing but kh) as ONE grid, the tracer on blockIdx.z: on a tile of an 8-GPU split a
-// launch is three to four rounds of workgroups whose last round is mostly empty -- one launch pays for that once, not twice
+// T and S (advance.f:439-440) as ONE grid, the tracer on blockIdx.z: on a tile of an 8-GPU split a launch is three to four rounds of
+// workgroups whose last round is mostly empty -- one launch pays for that once, not twice.  The two halves share no value: each reads kh
+// and forms the matrix's coefficients for itself (k_proft_ts_reg below forms them once).  Kept for the surface conditions the one-lane
+// kernel does not serve and behind POMGPU_PROFT_TWIN.
 struct ProftArgs { double *f; const double *wfsurf, *fsurf; int nbc; };
 template <int KBT, int SW>
 __global__ void __launch_bounds__(64 * ROWS_PROFT) k_proft_reg2(KP P, ProftArgs a0, ProftArgs a1) {
   if (blockIdx.z == 0) d_proft_reg<KBT, SW>(P, a0.f, a0.wfsurf, a0.fsurf, a0.nbc);
   else d_proft_reg<KBT, SW>(P, a1.f, a1.wfsurf, a1.fsurf, a1.nbc);
+}
+
+// T and S in ONE LANE.  The two solves have the same matrix: a(k), c(k), the reciprocal 1/(a + c*(1 - ee(k-1)) - 1), ee(k) and the
+// bottom denominator c(kbm1)*(1 - ee(kbm2)) - 1 depend on kh, dz, dzz, dh and ee(1) only (solver.f:1589-1598, :1650-1661, :1666-1669),
+// and ee(1) only on whether nbc is 1, 2 (a flux condition) or 3, 4 (a prescribed surface value, :1617-1648).  Two fp64 divisions and a
+// reciprocal per level are formed once instead of once per tracer, kh is read once (5 array passes instead of 6), and a lane has
+// 3*kb loads in flight instead of 2*kb -- at one wave per SIMD, where no sibling wave hides either the arithmetic or the latency.
+// Three vectors in registers: ee, and gg of each tracer (its right-hand side, its level 1, its bottom value and its back substitution
+// are its own).  Every expression is d_proft_reg's, token for token; a shared value is the one both halves of the twin computed.
+// The launcher guarantees (aT.nbc <= 2) == (aS.nbc <= 2).  No short-wave term: nbc 1 or 3 on both tracers (launch_proft2).
+template <int KBT>
+static __device__ __forceinline__ void d_proft_ts_reg(const KP &P, const ProftArgs &aT, const ProftArgs &aS) {
+  COL2
+  if (i > P.im || j > P.jm) return;
+  double ee[KBT], ggT[KBT], ggS[KBT];
+  const int kbm1 = P.kbm1, kbm2 = P.kbm2;
+#define KC(k) ((k) < kbm1 ? (k) : kbm1)                       /* clamp a level index into the column */
+  // ---- phase A: all loads, level by level
+#pragma unroll
+  for (int k = 2; k <= KBT - 1; k++) {
+    ee[k - 1] = F3(kh, i, j, KC(k));
+    if (k <= KBT - 2) {
+      ggT[k - 1] = G3(aT.f, i, j, KC(k));
+      ggS[k - 1] = G3(aS.f, i, j, KC(k));
+    }
+  }
+  const double fT_1 = G3(aT.f, i, j, 1), fT_kbm1 = G3(aT.f, i, j, kbm1);
+  const double fS_1 = G3(aS.f, i, j, 1), fS_kbm1 = G3(aS.f, i, j, kbm1);
+  const double dh = h_(i, j) + F2(etf, i, j);
+  const double wfsT = G2(aT.wfsurf, i, j), fsT = G2(aT.fsurf, i, j);
+  const double wfsS = G2(aS.wfsurf, i, j), fsS = G2(aS.fsurf, i, j);
+  SCHED_FENCE();
+  // ---- phase B: forward elimination
+#define ACOEF(k, khn) (-P.dti2 * ((khn) + P.umol) / (F1(dz, KC(k)) * F1(dzz, KC(k)) * dh * dh))       /* khn = kh(k+1) */
+#define CCOEF(k, khk) (-P.dti2 * ((khk) + P.umol) / (F1(dz, KC(k)) * F1(dzz, KC((k)-1)) * dh * dh))   /* khk = kh(k)   */
+  const double a1 = ACOEF(1, ee[1]);
+  const double a1m = a1 - 1.;
+  ee[0] = (aT.nbc <= 2) ? a1 / a1m : 0.;
+  {
+    const double g = P.dti2 * wfsT / (F1(dz, 1) * dh) - fT_1;
+    ggT[0] = (aT.nbc == 1) ? g / a1m : fsT;
+  }
+  {
+    const double g = P.dti2 * wfsS / (F1(dz, 1) * dh) - fS_1;
+    ggS[0] = (aS.nbc == 1) ? g / a1m : fsS;
+  }
+  double e_last = ee[0], gT_last = ggT[0], gS_last = ggS[0], kh_last = ee[1];   // ee, gg of level kbm2; kh of level kbm1
+#pragma unroll
+  for (int k = 2; k <= KBT - 2; k++) {
+    const double a = ACOEF(k, ee[k]), c = CCOEF(k, ee[k - 1]);
+    const bool fin = (k == kbm2);
+    kh_last = fin ? ee[k] : kh_last;
+    const double g = 1. / (a + c * (1. - ee[k - 2]) - 1.);
+    ee[k - 1] = a * g;
+    ggT[k - 1] = (c * ggT[k - 2] - ggT[k - 1] + 0.) * g;
+    ggS[k - 1] = (c * ggS[k - 2] - ggS[k - 1] + 0.) * g;
+    e_last = fin ? ee[k - 1] : e_last;
+    gT_last = fin ? ggT[k - 1] : gT_last;
+    gS_last = fin ? ggS[k - 1] : gS_last;
+  }
+  // ---- phase C: bottom values and back substitution
+  {
+    const double c = CCOEF(kbm1, kh_last);
+    const double den = c * (1. - e_last) - 1.;
+    double xT = (c * gT_last - fT_kbm1 + 0.) / den;
+    double xS = (c * gS_last - fS_kbm1 + 0.) / den;
+    G3(aT.f, i, j, kbm1) = xT;
+    G3(aS.f, i, j, kbm1) = xS;
+#pragma unroll
+    for (int ki = KBT - 2; ki >= 1; ki--) {
+      const double xnT = (ee[ki - 1] * xT + ggT[ki - 1]);
+      const double xnS = (ee[ki - 1] * xS + ggS[ki - 1]);
+      if (ki <= kbm2) {
+        xT = xnT; G3(aT.f, i, j, ki) = xT;
+        xS = xnS; G3(aS.f, i, j, ki) = xS;
+      }
+    }
+  }
+#undef KC
+#undef ACOEF
+#undef CCOEF
+}
+template <int KBT>
+__global__ void __launch_bounds__(64 * ROWS_PROFT) k_proft_ts_reg(KP P, ProftArgs aT, ProftArgs aS) {
+  d_proft_ts_reg<KBT>(P, aT, aS);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1878,9 +1965,24 @@ void launch_proft(pomgpu_ctx *c, double *f, const double *wfsurf, const double *
   else launch_proft_reg<64>(c, f, wfsurf, fsurf, nbc);
 }
 // proft for T and S in one launch (advance.f:439-440); 0 = not applicable (no register kernel for this kb, or the two tracers' surface
-// conditions differ in whether the short-wave term is compiled in): the caller launches them one by one
+// conditions differ in whether the short-wave term is compiled in): the caller launches them one by one.
+// Both tracers in one lane (k_proft_ts_reg) where they have the same matrix -- the same class of surface condition, flux (nbc 1, 2) or
+// value (3, 4) -- and the instantiation exists: without the short-wave term (nbc 1 or 3 on both; with it even the twin's two vectors
+// spill), KBT up to PROFT_TS_KBMAX (three vectors of 64 levels do not fit the 512 registers of a wave).  Otherwise, and under
+// POMGPU_PROFT_TWIN, the twin.  Either runs under the profile name k_proft_reg2; the one-lane kernel also counts proft_ts_lane.
+#define PROFT_TS_KBMAX 56
 template <int KBT>
-static void launch_proft2_reg(pomgpu_ctx *c, const ProftArgs &a0, const ProftArgs &a1, int sw) {
+static void launch_proft2_reg(pomgpu_ctx *c, const ProftArgs &a0, const ProftArgs &a1, int sw, int lane) {
+  if constexpr (KBT <= PROFT_TS_KBMAX) {
+    if (lane) {
+      if (c->prof_on) {
+        const int s = pomgpu_prof_slot(c, "proft_ts_lane");    // a count without events: which path the k_proft_reg2 of this profile was
+        if (s >= 0) (c->parent ? c->parent : c)->prof[s].launches++;
+      }
+      LAUNCHN(c, "k_proft_reg2", (k_proft_ts_reg<KBT>), rowgrid(c->P, ROWS_PROFT), rowblk(ROWS_PROFT), c->P, a0, a1);
+      return;
+    }
+  }
   if (sw) LAUNCHN(c, "k_proft_reg2", (k_proft_reg2<KBT, 1>), twin(rowgrid(c->P, ROWS_PROFT)), rowblk(ROWS_PROFT), c->P, a0, a1);
   else LAUNCHN(c, "k_proft_reg2", (k_proft_reg2<KBT, 0>), twin(rowgrid(c->P, ROWS_PROFT)), rowblk(ROWS_PROFT), c->P, a0, a1);
 }
@@ -1888,13 +1990,14 @@ int launch_proft2(pomgpu_ctx *c, double *f0, const double *wfsurf0, const double
   const int kb = c->P.kb, sw0 = (nbc0 == 2 || nbc0 == 4), sw1 = (nbc1 == 2 || nbc1 == 4);
   if (SW(c, NO_TWIN) || SW(c, THOMAS_SCRATCH) || kb > 64 || kb < 6 || sw0 != sw1) return 0;
   const ProftArgs a0 = {f0, wfsurf0, fsurf0, nbc0}, a1 = {f1, wfsurf1, fsurf1, nbc1};
-  if (kb <= 24) launch_proft2_reg<24>(c, a0, a1, sw0);
-  else if (kb <= 32) launch_proft2_reg<32>(c, a0, a1, sw0);
-  else if (kb <= 40) launch_proft2_reg<40>(c, a0, a1, sw0);
-  else if (kb <= 44) launch_proft2_reg<44>(c, a0, a1, sw0);
-  else if (kb <= 50) launch_proft2_reg<50>(c, a0, a1, sw0);
-  else if (kb <= 56) launch_proft2_reg<56>(c, a0, a1, sw0);
-  else launch_proft2_reg<64>(c, a0, a1, sw0);
+  const int lane = !SW(c, PROFT_TWIN) && !sw0 && (nbc0 <= 2) == (nbc1 <= 2);
+  if (kb <= 24) launch_proft2_reg<24>(c, a0, a1, sw0, lane);
+  else if (kb <= 32) launch_proft2_reg<32>(c, a0, a1, sw0, lane);
+  else if (kb <= 40) launch_proft2_reg<40>(c, a0, a1, sw0, lane);
+  else if (kb <= 44) launch_proft2_reg<44>(c, a0, a1, sw0, lane);
+  else if (kb <= 50) launch_proft2_reg<50>(c, a0, a1, sw0, lane);
+  else if (kb <= 56) launch_proft2_reg<56>(c, a0, a1, sw0, lane);
+  else launch_proft2_reg<64>(c, a0, a1, sw0, lane);
   return 1;
 }
 void launch_advu_profu(pomgpu_ctx *c, int do_adv, int do_prof) { LAUNCH(c, k_advu_profu, colgrid(c->P), colblk(), c->P, do_adv, do_prof); }

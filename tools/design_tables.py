@@ -23,14 +23,14 @@ ROWS = {   # kernel as the profile names it -> (reference lines,
     "k_profuv_reg2": ("a18", "`solver.f:1686-1877`", "k_profuv_reg"),
     "k_profuv_filter_reg2": ("a18 + a19 (interior)", "`solver.f:1686-1877`, `advance.f:469-514`", "k_profuv_filter_reg2"),
     "k_uv_filter_rim": ("a19 (frame)", "`advance.f:469-514`", "k_uv_filter_rim"),
-    "k_proft_reg2": ("a14 x 2", "`solver.f:1541-1683`", "k_proft_reg"),
+    "k_proft_reg2": ("a14 x 2 (T and S in one lane, `kh` read once; 6 passes as the twin)", "`solver.f:1541-1683`", "k_proft_reg"),
     "k_baropg": ("a3", "`solver.f:848-940`", "k_baropg_rs"),
     "k_int_uvmean_reg2": ("a7 (tiles, `POMGPU_UVMEAN_PASS`: absent from a one-tile step, whose kernels correct u, v as they load them)", "`advance.f:365-393`", "k_int_uvmean_reg"),
     "k_realvertvl_col": ("a20", "`solver.f:2024-2067`", "k_realvertvl_col"),
     "k_vertvl": ("a8 (tiles, `POMGPU_W_NOFUSE`: absent from a one-tile step)", "`solver.f:1970-2021`", "k_vertvl_rs"),
     "k_aam_pair": ("a1", "`advance.f:122-137`", "k_aam_pair"),
 }
-PASSES = dict(bench.KERNEL_PASSES, k_uv_filter_reg2=10, k_profuv_reg2=6, k_profuv_filter_reg2=12, k_uv_filter_rim=0, k_proft_reg2=6, k_int_uvmean_reg2=4, k_baropg=4, k_vertvl=3)
+PASSES = dict(bench.KERNEL_PASSES, k_uv_filter_reg2=10, k_profuv_reg2=6, k_profuv_filter_reg2=12, k_uv_filter_rim=0, k_proft_reg2=5, k_int_uvmean_reg2=4, k_baropg=4, k_vertvl=3)
 TWIN = {"k_uv_filter_reg2", "k_profuv_reg2", "k_proft_reg2", "k_int_uvmean_reg2"}   # traffic.json holds one launch of the pair (older name): x 2
 
 line = json.load(open(sys.argv[1]))
