@@ -1083,3 +1083,433 @@ int pomgpu_ff_fetch_restore(pomgpu_ctx *c, int n) {
   }
   return POMGPU_OK;
 }
+
+// ---- a cold start from the reference's input files (pomgpu_cold_start) ---------------------------------------------------------------
+// initialize.f:24-36 after read_input: initialize_arrays, read_grid (read_grid_pnetcdf io_pnetcdf.F:2085-2263, initialize.f:317-389),
+// initial_conditions (read_initial_ts_pnetcdf :2771-2842, read_clim_ts_pnetcdf :2845-2909, initialize.f:392-463), update_initial
+// (:466-521) and bottom_friction (:524-544) without PnetCDF.  The headers go through parse_header / ff_check; the data path is the
+// restart reader's (raw big-endian bands through two pinned buffers, one staging buffer, kernels behind each copy on a copy stream).
+// What needs sin or log (cor, cbc) is formed on the host with libm from the band while it sits in the pinned buffer; dz, dzz likewise.
+namespace {
+struct CVar { uint32_t type = 0; uint64_t begin = 0; unsigned es = 0; };   // a fixed-size variable of the grid file
+struct CPlane { const char *name; int slot; };
+const CPlane CS_PLANES[13] = {{"dx", P2_dx}, {"dy", P2_dy}, {"lon_rho", P2_east_e}, {"lat_rho", P2_north_e}, {"lon_u", P2_east_u}, {"lat_u", P2_north_u},
+                              {"lon_v", P2_east_v}, {"lat_v", P2_north_v}, {"lon_psi", P2_east_c}, {"lat_psi", P2_north_c}, {"angle", P2_rot}, {"h", P2_h},
+                              {"fsm", P2_fsm}};
+const char *const CS_INIT[2] = {"T", "S"};
+const unsigned CS_REAL = (1u << 5) | (1u << 6), CS_MASK = CS_REAL | (1u << 1) | (1u << 3) | (1u << 4);   // NC_FLOAT NC_DOUBLE / also NC_BYTE NC_SHORT NC_INT
+// value q of a raw big-endian array of NetCDF type `type` on the host (the kernels' cold_raw below)
+double host_raw(unsigned type, const void *p, size_t q) {
+  if (type == 6) { uint64_t u; memcpy(&u, (const char *)p + q * 8, 8); u = __builtin_bswap64(u); double x; memcpy(&x, &u, 8); return x; }
+  if (type == 5) { uint32_t u; memcpy(&u, (const char *)p + q * 4, 4); u = __builtin_bswap32(u); float x; memcpy(&x, &u, 4); return (double)x; }
+  if (type == 4) { uint32_t u; memcpy(&u, (const char *)p + q * 4, 4); return (double)(int32_t)__builtin_bswap32(u); }
+  if (type == 3) { const unsigned char *b = (const unsigned char *)p + q * 2; return (double)(int16_t)(uint16_t)((b[0] << 8) | b[1]); }
+  return (double)((const signed char *)p)[q];
+}
+// `name` as a variable of the lengths `want` (at_least: one dimension of at least want[0]), of a type in `types`, no record variable, inside the file
+std::string cold_fixed(const RHeader &H, uint64_t fsize, const char *name, const std::vector<uint64_t> &want, bool at_least, unsigned types, CVar &out) {
+  const RVar *v = NULL;
+  for (const RVar &x : H.vars) if (x.name == name) { v = &x; break; }
+  if (!v) return std::string("variable ") + name + " is absent";
+  if (v->type > 6 || !((types >> v->type) & 1u))
+    return std::string("variable ") + name + " has NetCDF type " + std::to_string(v->type) + (types == CS_REAL ? ", neither NC_FLOAT (5) nor NC_DOUBLE (6)" : ", none of NC_BYTE (1), NC_SHORT (3), NC_INT (4), NC_FLOAT (5), NC_DOUBLE (6)");
+  uint64_t count = 1;
+  bool same = v->dimids.size() == want.size();
+  for (size_t d = 0; d < v->dimids.size(); d++) {
+    const uint64_t len = H.dimlen[v->dimids[d]];
+    if (len == 0) return std::string("variable ") + name + " is a record variable (unlimited dimension)";
+    if (__builtin_mul_overflow(count, len, &count)) count = UINT64_MAX / 8;
+    if (same && (at_least ? len < want[d] : len != want[d])) same = false;
+  }
+  if (!same) {
+    std::string w = at_least ? "(>= " : "(";
+    for (size_t d = 0; d < want.size(); d++) w += (d ? ", " : "") + std::to_string(want[d]);
+    return std::string("variable ") + name + " has the dimension lengths " + lengths_of(H, *v) + ", wanted " + w + ")";
+  }
+  out.type = v->type; out.begin = v->begin; out.es = NC_TYPE_BYTES[v->type];
+  if (v->begin > fsize || count * out.es > fsize - v->begin)
+    return std::string("variable ") + name + " (" + std::to_string(count * out.es) + " bytes at " + std::to_string(v->begin) + ") reaches beyond the file's " + std::to_string(fsize) + " bytes";
+  return std::string();
+}
+}  // namespace
+
+__device__ __forceinline__ double cold_raw(unsigned type, const void *p, size_t q) {
+  if (type == 6) return CdfRaw<double>::get(p, q);
+  if (type == 5) return CdfRaw<float>::get(p, q);
+  if (type == 4) return (double)(int)__builtin_bswap32(((const unsigned *)p)[q]);
+  if (type == 3) { const unsigned char *b = (const unsigned char *)p + q * 2; return (double)(short)(unsigned short)((b[0] << 8) | b[1]); }
+  return (double)((const signed char *)p)[q];
+}
+// the readers' defaults over the whole padded arrays (io_pnetcdf.F:2159-2171; the others and fsm are zero already)
+__global__ void k_cold_defaults(KP P) {
+  const int i = TID_I, j = TID_J;
+  if (i > P.iml || j > P.jml) return;
+  F2(dx, i, j) = 1.;
+  F2(dy, i, j) = 1.;
+  F2(h, i, j) = 1.;
+}
+// One plane of the grid file.  Thread mapping of k_cdf_unpack over the tile's WINDOW: the band holds wj more rows below the tile's first
+// and the lanes reach wi more columns to its west (a tile with a south / west neighbour; 0 or 1).  The tile's part lands in
+// X(1:im, 1:jm); `win` (dx, dy, fsm; else NULL) keeps window and tile as (0:im, 0:jm) for k_cold_grid2d, line 0 being the window's.
+__global__ void k_cold_plane(double *dst, double *win, const void *src, unsigned type, int im, int jm, int iml, int wi, int wj, int pitch, int c0) {
+  const int a = (int)(blockIdx.x * blockDim.x + threadIdx.x), b = (int)(blockIdx.y * blockDim.y + threadIdx.y);
+  if (a >= im + wi || b >= jm + wj) return;
+  const double x = cold_raw(type, src, (size_t)b * (size_t)pitch + (size_t)(c0 + a));
+  const int i = a - wi + 1, j = b - wj + 1;                       // 1-based in the tile; 0: the window line
+  if (i >= 1 && j >= 1) dst[(size_t)(j - 1) * iml + (i - 1)] = x;
+  if (win) win[(size_t)j * (im + 1) + i] = x;
+}
+// read_grid's 2-D fields (initialize.f:361-384, io_pnetcdf.F:2243-2254, parallel_mpi.f:496), one lane per cell.  art, d, dt are
+// whole-array statements and cover the padding; the rest covers (1:im, 1:jm).  aru, arv: the loop's formula wherever its operands
+// exist -- the window supplies column 0 / row 0 of a tile with a neighbour there, which is what exchange2d_mpi brings from the owner --
+// and on global column 1, then global row 1, the copy of the line next to it (:373-381), i.e. the formula of that line.
+#define WN(p, ii, jj) (p)[(size_t)(jj) * (size_t)(P.im + 1) + (size_t)(ii)]
+__global__ void k_cold_grid2d(KP P, const double *wdx, const double *wdy, const double *wfsm, int wi, int wj, double *cfl) {
+  const int i = TID_I, j = TID_J;
+  if (i > P.iml || j > P.jml) return;
+  const double dxc = F2(dx, i, j), dyc = F2(dy, i, j), hc = F2(h, i, j);
+  F2(art, i, j) = dxc * dyc;
+  F2(d, i, j) = hc + F2(el, i, j);
+  F2(dt, i, j) = hc + F2(et, i, j);
+  if (i > P.im || j > P.jm) return;
+  const int ie = (i == 1 && !wi) ? 2 : i, je = (j == 1 && !wj) ? 2 : j;
+  F2(aru, i, j) = .25 * (WN(wdx, ie, je) + WN(wdx, ie - 1, je)) * (WN(wdy, ie, je) + WN(wdy, ie - 1, je));
+  F2(arv, i, j) = .25 * (WN(wdx, ie, je) + WN(wdx, ie, je - 1)) * (WN(wdy, ie, je) + WN(wdy, ie, je - 1));
+  const double fs = WN(wfsm, i, j);
+  const bool west = i > 1 || wi, south = j > 1 || wj;            // is there a cell behind this one?
+  F2(dum, i, j) = (west && WN(wfsm, i - 1, j) == 0. && fs != 0.) ? 0. : fs;
+  F2(dvm, i, j) = (south && WN(wfsm, i, j - 1) == 0. && fs != 0.) ? 0. : fs;
+  cfl[IX2(i, j)] = .5 / sqrt(1. / (dxc * dxc) + 1. / (dyc * dyc)) / sqrt(P.grav * (hc + P.small_)) * fs;
+}
+#undef WN
+// minval(cfl, cfl > 0) (parallel_mpi.f:499) over (1:im, 1:jm): one workgroup, k_reduce.hip's tree (a strided share per lane, the
+// wavefront shuffle tree, four partials through LDS), no atomics.  min is exact, so the shape does not show in the result.  The host
+// emulation, which has no lanes to shuffle between, scans the plane in the launcher instead
+#ifndef POMGPU_EMU
+__global__ void __launch_bounds__(256) k_cold_cflmin(KP P, const double *cfl, double *out) {
+  __shared__ double part[4];
+  double m = __DBL_MAX__;                                        // minval of nothing: huge()
+  const long long total = (long long)P.im * P.jm;
+  for (long long n = threadIdx.x; n < total; n += blockDim.x) {
+    const double x = cfl[IX2((int)(n % P.im) + 1, (int)(n / P.im) + 1)];
+    if (x > 0. && x < m) m = x;
+  }
+  for (int off = 32; off > 0; off >>= 1) { const double y = __shfl_down(m, off, 64); if (y < m) m = y; }
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) { for (int w = 1; w < 4; w++) if (part[w] < m) m = part[w]; out[0] = m; }
+}
+#endif
+// Levels k0+1 .. k0+gridDim.z (all <= kbm1) of T (which = 0) or S (1), read from the staging buffer once: tb and t (sb and s) get the
+// same bits -- rounded to the storage type as an upload rounds -- tsurf (ssurf) level 1, and the boundary arrays their lines
+// (initialize.f:437-438, :447-460, :497-498)
+template <class T>
+__global__ void k_cold_ts(KP P, int which, const void *src, int rows, int pitch, int c0, int k0) {
+  const int i = TID_I, j = TID_J, k = k0 + (int)blockIdx.z + 1;
+  if (i > P.im || j > P.jm) return;
+  const double x = (double)(pomgpu_st)CdfRaw<T>::get(src, ((size_t)blockIdx.z * rows + (size_t)(j - 1)) * (size_t)pitch + (size_t)(c0 + i - 1));
+  if (which == 0) {
+    F3(tb, i, j, k) = x; F3(t, i, j, k) = x;
+    if (k == 1) F2(tsurf, i, j) = x;
+    if (i == P.im) BDJ(tbe, j, k) = x;
+    if (i == 1) BDJ(tbw, j, k) = x;
+    if (j == P.jm) BDI(tbn, i, k) = x;
+    if (j == 1) BDI(tbs, i, k) = x;
+  } else {
+    F3(sb, i, j, k) = x; F3(s, i, j, k) = x;
+    if (k == 1) F2(ssurf, i, j) = x;
+    if (i == P.im) BDJ(sbe, j, k) = x;
+    if (i == 1) BDJ(sbw, j, k) = x;
+    if (j == P.jm) BDI(sbn, i, k) = x;
+    if (j == 1) BDI(sbs, i, k) = x;
+  }
+}
+// k_cdf_unpack for either real type: gridDim.z levels of Tclim / Sclim into the mirror (dst: the first of those levels)
+template <class T>
+__global__ void k_cold_vol(pomgpu_st *dst, const void *src, int im, int jm, int iml, size_t n2, int rows, int pitch, int c0) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x), j = (int)(blockIdx.y * blockDim.y + threadIdx.y), k = (int)blockIdx.z;
+  if (i >= im || j >= jm) return;
+  dst[(size_t)k * n2 + (size_t)j * iml + i] = (pomgpu_st)CdfRaw<T>::get(src, ((size_t)k * rows + j) * (size_t)pitch + (size_t)(c0 + i));
+}
+// update_initial (initialize.f:472-500) on a state whose uab, vab, elb, etb, vfluxf, ub, vb are zero: store only, the column's levels
+// in the thread.  ua va el et etf, w(:,:,1), u v are whole-array copies of those zeros; l .. aam cover (1:im, 1:jm) and all kb levels,
+// each value formed in fp64 from dt(i,j) and rounded by the store alone; a lane outside aims its stores outside the descriptor.
+// d = h+el, dt = h+et (:477-478) repeat what k_cold_grid2d has stored.  0.1 is a REAL(4) literal (:484); q2 = q2b, q2l = q2lb (:495-496)
+__global__ void k_cold_update(KP P, double aam_init, double sqrt_small) {
+  const int i = TID_I, j = TID_J;
+  if (i > P.iml || j > P.jml) return;
+  const unsigned o = BOFF2(i, j), oa = (i <= P.im && j <= P.jm) ? o : BOFF_NONE;
+  const double lc = (double)0.1f * F2(dt, i, j), q2bc = P.small_, q2lbc = lc * q2bc, khc = lc * sqrt_small;
+  F2(ua, i, j) = 0.; F2(va, i, j) = 0.; F2(el, i, j) = 0.; F2(et, i, j) = 0.; F2(etf, i, j) = 0.;
+  const BufA bl = BUF3(A3(l)), bq2b = BUF3(A3(q2b)), bq2lb = BUF3(A3(q2lb)), bkh = BUF3(A3(kh)), bkm = BUF3(A3(km)), bkq = BUF3(A3(kq)),
+             baam = BUF3(A3(aam)), bq2 = BUF3(A3(q2)), bq2l = BUF3(A3(q2l)), bu = BUF3(A3(u)), bv = BUF3(A3(v)), bw = BUF3(A3(w));
+  bst(bw, o, 0u, 0.);
+  unsigned so = 0u;
+  for (int k = 1; k <= P.kb; k++) {
+    bst(bl, oa, so, lc); bst(bq2b, oa, so, q2bc); bst(bq2lb, oa, so, q2lbc);
+    bst(bkh, oa, so, khc); bst(bkm, oa, so, khc); bst(bkq, oa, so, khc); bst(baam, oa, so, aam_init);
+    bst(bq2, oa, so, q2bc); bst(bq2l, oa, so, q2lbc);
+    bst(bu, o, so, 0.); bst(bv, o, so, 0.);
+    so += LVB;
+  }
+}
+// drx2d, dry2d (initialize.f:511-518): running sums, from zero, of drhox, drhoy AS STORED (baropg has rounded them to the storage type)
+// times dz(k), k ascending
+__global__ void k_cold_drsum(KP P) {
+  const int i = TID_I, j = TID_J;
+  const bool act = i <= P.im && j <= P.jm;
+  const unsigned o = act ? BOFF2(i, j) : BOFF_NONE;
+  const BufA bx = BUF3(A3(drhox)), by = BUF3(A3(drhoy));
+  double sx = 0., sy = 0.;
+  unsigned so = 0u;
+  for (int k = 1; k <= P.kbm1; k++) {
+    const double dzk = F1(dz, k);
+    sx = sx + bld(bx, o, so) * dzk;
+    sy = sy + bld(by, o, so) * dzk;
+    so += LVB;
+  }
+  if (act) { F2(drx2d, i, j) = sx; F2(dry2d, i, j) = sy; }
+}
+static void cold_update_initial(pomgpu_ctx *c) { LAUNCH(c, k_cold_update, grid2(c->P), blk2(), c->P, c->con.aam_init, sqrt(c->con.small)); }
+static void cold_sums(pomgpu_ctx *c) { LAUNCH(c, k_cold_drsum, grid2(c->P), blk2(), c->P); }
+
+extern "C" int pomgpu_cold_start(pomgpu_ctx *c, const char *grid, const char *init, const char *clim, const pomgpu_file_meta *m, pomgpu_cold_info *info) {
+  if (!c || !grid || !init || !clim || !m) return POMGPU_EINVAL;
+  (void)hipSetDevice(c->device);
+  { const int rcw = pomgpu_io_wait(c); if (rcw) return rcw; }  // a file this context is still writing
+  const KP &P = c->P;
+  if (c->flags & POMGPU_CTX_2D) return fail(c, POMGPU_EINVAL, "cold_start: not on a 2-D context");
+  const int wi = P.W ? 0 : 1, wj = P.S ? 0 : 1;                // one more column / row on the low side of a tile with a neighbour there
+  if (m->i0 - wi < 1 || m->j0 - wj < 1 || m->i0 + P.im - 1 > m->im_global || m->j0 + P.jm - 1 > m->jm_global)
+    return fail(c, POMGPU_EINVAL, "cold_start: %s: the tile (%d..%d, %d..%d)%s does not fit the global grid %d x %d", grid, m->i0, m->i0 + P.im - 1, m->j0,
+                m->j0 + P.jm - 1, wi || wj ? " with its window line towards the west / south neighbour" : "", m->im_global, m->jm_global);
+  if (c->con.npg != 1 && c->con.npg != 2) return fail(c, POMGPU_EINVAL, "cold_start: invalid value for npg (%d)", c->con.npg);
+  const uint64_t img = (uint64_t)m->im_global, jmg = (uint64_t)m->jm_global, kb = (uint64_t)P.kb;
+  const char *paths[3] = {grid, init, clim};
+  static const char *const kind[3] = {"grid", "init", "clim"};
+  FSource F[3];
+  RHeader H[3];
+  auto drop = [&]() { for (FSource &s : F) if (s.fd >= 0) (void)close(s.fd); };
+  for (int q = 0; q < 3; q++) {
+    F[q].path = paths[q];
+    F[q].fd = open(paths[q], O_RDONLY);
+    if (F[q].fd < 0) { drop(); return fail(c, POMGPU_EINVAL, "cold_start: cannot open %s", paths[q]); }
+    struct stat sb;
+    if (fstat(F[q].fd, &sb)) { drop(); return fail(c, POMGPU_EINVAL, "cold_start: cannot stat %s", paths[q]); }
+    F[q].fsize = (uint64_t)sb.st_size;
+    std::string what;
+    if (ff_header(F[q].fd, F[q].fsize, H[q], what) < 0) { drop(); return fail(c, POMGPU_EINVAL, "cold_start: %s is not a %s file this library reads: %s", paths[q], kind[q], what.c_str()); }
+  }
+  auto refuse = [&](int q, const std::string &why) { drop(); return fail(c, POMGPU_EINVAL, "cold_start: %s: %s", paths[q], why.c_str()); };
+  // grid
+  CVar vz, vzz, vp[13];
+  {
+    std::string why = cold_fixed(H[0], F[0].fsize, "z", {kb}, true, CS_REAL, vz);
+    if (why.empty()) why = cold_fixed(H[0], F[0].fsize, "zz", {kb}, true, CS_REAL, vzz);
+    for (int q = 0; q < 13 && why.empty(); q++) why = cold_fixed(H[0], F[0].fsize, CS_PLANES[q].name, {jmg, img}, false, q == 12 ? CS_MASK : CS_REAL, vp[q]);
+    if (!why.empty()) return refuse(0, why);
+  }
+  // init: record 1, levels 1..kb-1 of T, S
+  uint64_t nlev[2] = {kb - 1, kb - 1};
+  {
+    bool unlimited = false, level = false;
+    for (uint64_t len : H[1].dimlen) if (len == 0) unlimited = true;
+    for (const RVar &v : H[1].vars) {
+      if (v.name == "Level") level = true;
+      for (int q = 0; q < 2; q++) if (v.name == CS_INIT[q] && v.dimids.size() == 4) nlev[q] = H[1].dimlen[v.dimids[1]];
+    }
+    if (!unlimited) return refuse(1, "the file has no unlimited dimension");
+    if (!level) return refuse(1, "variable Level is absent");
+    std::string why = ff_check(H[1], F[1], CS_INIT, {{nlev[0], jmg, img}, {nlev[1], jmg, img}}, 1);
+    for (int q = 0; q < 2 && why.empty(); q++) {
+      if (nlev[q] < kb - 1) why = std::string("variable ") + CS_INIT[q] + " has " + std::to_string(nlev[q]) + " levels, wanted >= " + std::to_string(kb - 1);
+      else if (!F[1].v[q].rec) why = std::string("variable ") + CS_INIT[q] + " is not a record variable";
+    }
+    if (why.empty() && (F[1].numrecs < 1 || F[1].numrecs == 0xffffffffu)) why = "the file holds no complete record (numrecs " + std::to_string(F[1].numrecs) + ")";
+    if (!why.empty()) return refuse(1, why);
+  }
+  // clim: record 10 (initialize.f:407), the forcing reader's layout check
+  {
+    std::string why = ff_check(H[2], F[2], FF_CLIM, {{kb, jmg, img}, {kb, jmg, img}}, 10);
+    if (why.empty() && F[2].v[0].rec && F[2].numrecs == 0xffffffffu) why = "the record count is unknown (a file still being written)";
+    if (!why.empty()) return refuse(2, why);
+  }
+  // the reference stops where cor(im/2, jm/2) is zero (initialize.f:354-355): looked at before anything changes
+  const double deg2rad = c->con.pi / 180.;
+  auto cor_of = [&](double lat) { return 2. * 7.29e-5 * sin(lat * deg2rad); };
+  const CVar &vlat = vp[3], &vh = vp[11];
+  double cor_mid = 0.;
+  {
+    unsigned char raw[8];
+    const uint64_t cell = (uint64_t)(m->j0 - 1 + P.jm / 2 - 1) * img + (uint64_t)(m->i0 - 1 + P.im / 2 - 1);
+    if (pread_all(F[0].fd, raw, vlat.es, vlat.begin + cell * vlat.es)) return refuse(0, "I/O error (lat_rho)");
+    cor_mid = cor_of(host_raw(vlat.type, raw, 0));
+    if (cor_mid == 0.) return refuse(0, "Coriolis problem: cor(im/2, jm/2) of this tile is zero (lat_rho = " + std::to_string(host_raw(vlat.type, raw, 0)) + ")");
+  }
+  // masks are 0 or 1 (the kernels fold repeated mask multiplies; pomgpu_upload checks the same): the tile's window of fsm, read ahead
+  {
+    const CVar &vf = vp[12];
+    std::vector<unsigned char> row((size_t)(P.im + wi) * vf.es);
+    for (int j = 0; j < P.jm + wj; j++) {
+      const uint64_t cell = (uint64_t)(m->j0 - 1 - wj + j) * img + (uint64_t)(m->i0 - 1 - wi);
+      if (pread_all(F[0].fd, row.data(), row.size(), vf.begin + cell * vf.es)) return refuse(0, "I/O error (fsm)");
+      for (int i = 0; i < P.im + wi; i++) {
+        const double x = host_raw(vf.type, row.data(), (size_t)i);
+        if (x != 0. && x != 1.)
+          return refuse(0, "variable fsm holds " + std::to_string(x) + " at global (" + std::to_string(m->i0 - wi + i) + ", " + std::to_string(m->j0 - wj + j) + "), neither 0 nor 1");
+      }
+    }
+  }
+  // ---- from here on the state changes ----
+  { const int rcm = pomgpu_materialize(c); if (rcm) { drop(); return rcm; } }
+  int bad = 0;
+  const size_t nbd = P.bdoff[PB__count - 1] + (size_t)P.iml * P.kb;
+  std::vector<double> b1((size_t)POM_NBLK1D * P.kb, 0.), hcor(P.n2, 0.), hcbc(P.n2, 0.);
+  {                                                            // z, zz; dz, dzz (initialize.f:331-336)
+    std::vector<unsigned char> raw((size_t)P.kb * 8);
+    for (int q = 0; q < 2 && !bad; q++) {
+      const CVar &v = q ? vzz : vz;
+      if (pread_all(F[0].fd, raw.data(), (size_t)P.kb * v.es, v.begin)) { bad = 1; break; }
+      double *x = b1.data() + (size_t)(q ? P1_zz : P1_z) * P.kb, *dx = b1.data() + (size_t)(q ? P1_dzz : P1_dz) * P.kb;
+      for (int k = 0; k < P.kb; k++) x[k] = host_raw(v.type, raw.data(), (size_t)k);
+      for (int k = 0; k < P.kb - 1; k++) dx[k] = x[k] - x[k + 1];
+      dx[P.kb - 1] = 0.;
+    }
+  }
+  // the COMMON blocks as they are at program start and as initialize_arrays leaves them, then the readers' defaults
+  if (!bad && (hipMemsetAsync(P.b2, 0, sizeof(double) * POM_NBLK2D * P.n2, c->stream) != hipSuccess || hipMemsetAsync(P.bd, 0, sizeof(double) * nbd, c->stream) != hipSuccess ||
+               hipMemcpyAsync(P.b1, b1.data(), sizeof(double) * b1.size(), hipMemcpyHostToDevice, c->stream) != hipSuccess)) bad = 2;
+  for (int n = 0; n < POM_NBLK3D && !bad; n++) if (hipMemsetAsync(P.b3 + (size_t)n * P.a3, 0, sizeof(double) * P.n3, c->stream) != hipSuccess) bad = 2;
+  if (!bad) LAUNCH(c, k_cold_defaults, grid2(P), blk2(), P);
+  // the buffers of the restart reader's loop, for this call only; a run is whole levels of the tile's band of rows at the file's full width
+  const size_t band2 = (size_t)(P.jm + wj) * (size_t)img * 8, band3 = (size_t)P.jm * (size_t)img * 8;
+  size_t cap = SW(c, IO_CHUNK_KB) && SWV(c, IO_CHUNK_KB) > 0 ? (size_t)SWV(c, IO_CHUNK_KB) << 10 : (size_t)64 << 20;   // bytes per buffer
+  if (cap > band3 * (size_t)P.kb) cap = band3 * (size_t)P.kb;
+  if (cap < band2) cap = band2;
+  const size_t nwin = (size_t)(P.im + 1) * (size_t)(P.jm + 1);
+  unsigned char *pin[2] = {NULL, NULL}, *stage = NULL;
+  double *win = NULL;                                            // dx, dy, fsm over the window
+  if (!bad && hipMalloc((void **)&win, 3 * nwin * sizeof(double)) != hipSuccess) bad = 2;
+#ifdef POMGPU_EMU
+  if (!bad && hipMalloc((void **)&pin[0], cap) != hipSuccess) bad = 2;
+  stage = pin[0];
+  hipStream_t rs = c->stream;
+#else
+  hipStream_t rs = NULL;
+  hipEvent_t ev[2] = {NULL, NULL};                              // the copy out of pin[b] has completed
+  if (!bad && (hipHostMalloc((void **)&pin[0], cap, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void **)&pin[1], cap, hipHostMallocDefault) != hipSuccess ||
+               hipMalloc((void **)&stage, cap) != hipSuccess || hipStreamCreateWithFlags(&rs, hipStreamNonBlocking) != hipSuccess ||
+               hipEventCreateWithFlags(&ev[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ev[1], hipEventDisableTiming) != hipSuccess))
+    bad = 2;
+  int used[2] = {0, 0};
+#endif
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !bad) bad = 2;   // the zeroes precede the first store of the copy stream
+  const hipStream_t cur0 = c->cur;
+  c->cur = rs;
+  int b = 0;
+  // nl bands of `bytes` each, `stride` bytes apart in the file, into the free pinned buffer and on their way to the staging buffer
+  auto fetch = [&](int fd, uint64_t first, size_t bytes, uint64_t stride, int nl) {
+#ifndef POMGPU_EMU
+    if (used[b] && hipEventSynchronize(ev[b]) != hipSuccess) { bad = 2; return; }
+#endif
+    if (stride == bytes) { if (pread_all(fd, pin[b], (size_t)nl * bytes, first)) bad = 1; }
+    else for (int k = 0; k < nl && !bad; k++) if (pread_all(fd, pin[b] + (size_t)k * bytes, bytes, first + (uint64_t)k * stride)) bad = 1;
+#ifndef POMGPU_EMU
+    if (!bad && (hipMemcpyAsync(stage, pin[b], (size_t)nl * bytes, hipMemcpyHostToDevice, rs) != hipSuccess || hipEventRecord(ev[b], rs) != hipSuccess)) bad = 2;
+    if (!bad) used[b] = 1;
+#endif
+  };
+  auto flip = [&]() {
+#ifndef POMGPU_EMU
+    b ^= 1;
+#endif
+  };
+  const int c0 = m->i0 - 1 - wi;                                 // the file column (0-based) of the window's first
+  for (int q = 0; q < 13 && !bad; q++) {                         // the planes of the grid file, rows j0-wj .. j0+jm-1
+    const CVar &v = vp[q];
+    const size_t bytes = (size_t)(P.jm + wj) * (size_t)img * v.es;
+    fetch(F[0].fd, v.begin + (uint64_t)(m->j0 - 1 - wj) * img * v.es, bytes, bytes, 1);
+    if (bad) break;
+    if (&v == &vlat || &v == &vh) {                              // cor (initialize.f:349) and cbc (:536-540) on the host, from the band in the pinned buffer
+      const double zk = 1. + b1[(size_t)P1_zz * P.kb + (P.kbm1 - 1)];
+      for (int j = 0; j < P.jm; j++)
+        for (int i = 0; i < P.im; i++) {
+          const double x = host_raw(v.type, pin[b], (size_t)(j + wj) * (size_t)img + (size_t)(m->i0 - 1 + i));
+          if (&v == &vlat) hcor[(size_t)j * P.iml + i] = cor_of(x);
+          else {
+            const double t = c->con.kappa / log(zk * x / c->con.z0b), cb = t * t;
+            hcbc[(size_t)j * P.iml + i] = fmin(c->con.cbcmax, fmax(c->con.cbcmin, cb));
+          }
+        }
+    }
+    double *w = q == 0 ? win : (q == 1 ? win + nwin : (q == 12 ? win + 2 * nwin : NULL));
+    LAUNCH(c, k_cold_plane, dim3((unsigned)((P.im + wi + 63) / 64), (unsigned)((P.jm + wj + 3) / 4), 1), blk2(), P.b2 + (size_t)CS_PLANES[q].slot * P.n2, w, (const void *)stage,
+           (unsigned)v.type, P.im, P.jm, P.iml, wi, wj, (int)img, c0);
+    flip();
+  }
+  for (int q = 0; q < 4 && !bad; q++) {                          // T, S (record 1, levels 1..kbm1), Tclim, Sclim (record 10, kb levels)
+    const bool ini = q < 2;
+    const FVar &f = ini ? F[1].v[q] : F[2].v[q - 2];
+    const int nlv = ini ? P.kbm1 : P.kb;
+    const size_t bytes = (size_t)P.jm * (size_t)img * f.esize();
+    const uint64_t stride = jmg * img * f.esize();
+    const uint64_t base = f.begin + (ini ? 0 : 9 * f.stride) + (uint64_t)(m->j0 - 1) * img * f.esize();
+    int per = (int)(cap / bytes);
+    if (per > nlv) per = nlv;
+    for (int k0 = 0; k0 < nlv && !bad; k0 += per) {
+      const int nl = nlv - k0 < per ? nlv - k0 : per;
+      fetch(ini ? F[1].fd : F[2].fd, base + (uint64_t)k0 * stride, bytes, stride, nl);
+      if (bad) break;
+      const dim3 g((unsigned)((P.im + 63) / 64), (unsigned)((P.jm + 3) / 4), (unsigned)nl);
+      if (ini) {
+        if (f.type == 5) LAUNCHN(c, "k_cold_ts", k_cold_ts<float>, g, blk2(), P, q, (const void *)stage, P.jm, (int)img, m->i0 - 1, k0);
+        else LAUNCHN(c, "k_cold_ts", k_cold_ts<double>, g, blk2(), P, q, (const void *)stage, P.jm, (int)img, m->i0 - 1, k0);
+      } else {
+        pomgpu_st *dst = (pomgpu_st *)(P.b3 + (size_t)(q == 2 ? P3_tclim : P3_sclim) * P.a3) + (size_t)k0 * P.n2;
+        if (f.type == 5) LAUNCHN(c, "k_cold_vol", k_cold_vol<float>, g, blk2(), dst, (const void *)stage, P.im, P.jm, P.iml, P.n2, P.jm, (int)img, m->i0 - 1);
+        else LAUNCHN(c, "k_cold_vol", k_cold_vol<double>, g, blk2(), dst, (const void *)stage, P.im, P.jm, P.iml, P.n2, P.jm, (int)img, m->i0 - 1);
+      }
+      flip();
+    }
+  }
+  c->cur = cur0;
+  if (hipStreamSynchronize(rs) != hipSuccess && !bad) bad = 2;
+#ifndef POMGPU_EMU
+  if (ev[0]) (void)hipEventDestroy(ev[0]);
+  if (ev[1]) (void)hipEventDestroy(ev[1]);
+  if (rs) (void)hipStreamDestroy(rs);
+  if (pin[0]) (void)hipHostFree(pin[0]);
+  if (pin[1]) (void)hipHostFree(pin[1]);
+  if (stage) (void)hipFree(stage);
+#else
+  (void)hipFree(pin[0]);
+#endif
+  drop();
+  // ---- the files are on the device: what read_grid, initial_conditions, update_initial and bottom_friction derive ----
+  double cflmin = __DBL_MAX__;
+  if (!bad && !c->launch_err) {
+    pom_blkcon con = c->con;
+    con.period = (2. * con.pi) / fabs(cor_mid) / 86400.;         // initialize.f:357, from THIS tile's midpoint
+    con.rfe = con.rfw = con.rfn = con.rfs = 1.;                  // :442-445
+    (void)pomgpu_set_con(c, &con, c->lramp);
+    if (hipMemcpyAsync(P.b2 + (size_t)P2_cor * P.n2, hcor.data(), sizeof(double) * P.n2, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(P.b2 + (size_t)P2_cbc * P.n2, hcbc.data(), sizeof(double) * P.n2, hipMemcpyHostToDevice, c->stream) != hipSuccess) bad = 2;
+    double *cfl = P.s2[7];
+    LAUNCH(c, k_cold_grid2d, grid2(P), blk2(), P, (const double *)win, (const double *)(win + nwin), (const double *)(win + 2 * nwin), wi, wj, cfl);
+#ifndef POMGPU_EMU
+    LAUNCH(c, k_cold_cflmin, dim3(1), dim3(256), P, (const double *)cfl, c->d_stats);
+    if (hipMemcpyAsync(&cflmin, c->d_stats, sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) bad = 2;
+#else
+    for (int j = 1; j <= P.jm; j++) for (int i = 1; i <= P.im; i++) { const double x = cfl[IX2(i, j)]; if (x > 0. && x < cflmin) cflmin = x; }
+#endif
+    pomgpu_cold_tail(c, cold_update_initial, cold_sums);
+  }
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !bad) bad = 2;
+  if (win) (void)hipFree(win);
+  if (bad || c->launch_err) {
+    if (bad == 2) (void)hipGetLastError();
+    return fail(c, bad == 1 ? POMGPU_EINVAL : POMGPU_EHIP, bad == 1 ? "cold_start: I/O error on %s, %s or %s (the state is unspecified)" : "cold_start: a HIP call failed while reading %s, %s or %s (the state is unspecified)", grid, init, clim);
+  }
+  if (info) { info->cflmin = cflmin; info->period = c->con.period; }
+  return POMGPU_OK;
+}

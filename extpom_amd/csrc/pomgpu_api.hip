@@ -1025,6 +1025,18 @@ void pomgpu_mirrors_written(pomgpu_ctx *c) {
   early_invalidate(c);
   refresh_coefs(c);
 }
+// pomgpu_cold_start (cdf_out.hip) has filled the grid, tb sb t s and tclim sclim: the rest of initial_conditions and update_initial
+// (initialize.f:416-425, :472-518) in the reference's order, with the launchers the stand-alone entry points use; the two kernels of
+// cdf_out.hip come in as functions.  Then what pomgpu_upload of all blocks invalidates.  The caller has vetted npg
+void pomgpu_cold_tail(pomgpu_ctx *c, void (*update_initial)(pomgpu_ctx *), void (*sums)(pomgpu_ctx *)) {
+  launch_dens(c, D3(c, sclim), D3(c, tclim), D3(c, rmean));
+  launch_dens(c, D3(c, sb), D3(c, tb), D3(c, rho));
+  update_initial(c);
+  if (c->con.npg == 2) seq_baropg_mcc(c); else seq_baropg(c);
+  sums(c);
+  c->tau_known[0] = c->tau_known[1] = 0;                       // taurstrb, taurstrf are zero arrays now, not the library's value
+  pomgpu_mirrors_written(c);
+}
 extern "C" int pomgpu_get_time(pomgpu_ctx *c) {               // advance.f:62-75
   NEED_HOT(c);
   pom_blkcon &k = c->con;

@@ -932,6 +932,7 @@ int pomgpu_tp_reserve2(pomgpu_ctx *c, const size_t *need);                      
 void pomgpu_wr_materialize(pomgpu_ctx *c);                                      // a pending wr formed now (pomgpu_api.hip); part of pomgpu_materialize
 int pomgpu_materialize(pomgpu_ctx *c);                                          // every lazily kept array up to date in the mirrors (pomgpu_api.hip)
 void pomgpu_mirrors_written(pomgpu_ctx *c);                                     // the restart reader has written blk2d / blk3d mirrors on the device: what pomgpu_upload_2d / _3d invalidate (pomgpu_api.hip)
+void pomgpu_cold_tail(pomgpu_ctx *c, void (*update_initial)(pomgpu_ctx *), void (*sums)(pomgpu_ctx *));   // pomgpu_cold_start's 3-D tail in the reference's order (pomgpu_api.hip): dens twice, update_initial, baropg by npg, drx2d dry2d; then what pomgpu_upload invalidates
 int pomgpu_side_stream(pomgpu_ctx *c);                                          // create the side stream and its events (pomgpu_api.hip); 1 = there
 int pomgpu_tp_side_ok(pomgpu_ctx *c);                                           // can rounds run on the side stream (second communicator / callback mover)?
 int pomgpu_tp_move_side(pomgpu_ctx *c, const size_t *scount, const size_t *rcount);   // send2 / recv2, on c->side

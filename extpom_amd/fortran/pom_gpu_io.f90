@@ -3,6 +3,8 @@
 ! dimensions / variables / attributes) are written by the library straight from the device state
 ! (pomgpu_write_output / pomgpu_write_restart); every rank writes its patch, rank 0 creates the file first.
 ! read_restart_pnetcdf reads such a file (or one PnetCDF wrote) back into the device state and the COMMON blocks.
+! cold_start_files is initialize.f:24-36 (initialize_arrays, read_grid, initial_conditions, update_initial, bottom_friction) from the
+! reference's grid, init and clim files (pomgpu_cold_start).
 ! Link instead of the reference's two writers and its restart reader.  pomgpu_barrier_mpi is the integrator's one-liner
 ! (call mpi_barrier(pom_comm, ierr); nothing on a single rank): this file does not include mpif.h.
 subroutine write_output_pnetcdf
@@ -113,4 +115,60 @@ subroutine read_restart_pnetcdf
   rc = pomgpu_get_con(pom_ctx, c_loc(alpha))       ! time0, time, cont_bry
   if (rc /= 0) error_status = 1
   call pomgpu_download_state
+end subroutine
+
+! initialize.f:24-36 without PnetCDF: what initialize does between read_input and the restart reader -- initialize_arrays, read_grid,
+! initial_conditions, update_initial, bottom_friction -- on the device, from <wrk_pth>in/<netcdf_file>.grid.nc, .init.nc and .clim.nc
+! (the names of io_pnetcdf.F:2102, :2790, :2865).  Call it after read_input and pomgpu_upload_state (blkcon holds the run's constants;
+! the arrays may hold anything).  Every rank reads its own patch and one more column / row towards a west / south neighbour, so no
+! exchange is needed; afterwards the device state AND the COMMON blocks hold what the reference would have.  pom_cflmin is this rank's
+! cflmin: check_cflmin_mpi (parallel_mpi.f:501-512) reduces it with mpi_min and prints the warning; one rank prints it here.
+subroutine cold_start_files
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  type(pomgpu_file_meta) :: m
+  type(pomgpu_cold_info), target :: info
+  character(len=400) :: fname
+  character(kind=c_char, len=401), target :: cgrid, cinit, cclim
+  character(kind=c_char), pointer :: msg(:)
+  type(c_ptr) :: pm
+  integer(c_int) :: rc
+  integer :: n
+  write(fname, '(a,''in/'',a,''.grid.nc'')') trim(wrk_pth), trim(netcdf_file)
+  cgrid = trim(fname)//c_null_char
+  if (my_task == 0) write(*,'(/''reading file '',a)') trim(fname)
+  write(fname, '(a,''in/'',a,''.init.nc'')') trim(wrk_pth), trim(netcdf_file)
+  cinit = trim(fname)//c_null_char
+  if (my_task == 0) write(*,'(/''reading file '',a)') trim(fname)
+  write(fname, '(a,''in/'',a,''.clim.nc'')') trim(wrk_pth), trim(netcdf_file)
+  cclim = trim(fname)//c_null_char
+  if (my_task == 0) write(*,'(/''reading file '',a)') trim(fname)
+  call pomgpu_push_con                             ! read_input's constants
+  m%title = c_null_ptr; m%time_start = c_null_ptr; m%stats = c_null_ptr; m%create = 0
+  m%im_global = im_global; m%jm_global = jm_global
+  m%i0 = i_global(1); m%j0 = j_global(1)
+  rc = pomgpu_cold_start(pom_ctx, c_loc(cgrid), c_loc(cinit), c_loc(cclim), m, c_loc(info))
+  if (rc /= 0) then                                ! handle_error_pnetcdf, io_pnetcdf.F:43-54: a message and error_status = 1
+    error_status = 1
+    pm = pomgpu_last_error(pom_ctx)                ! names the file and the cause
+    if (c_associated(pm)) then
+      call c_f_pointer(pm, msg, (/512/))
+      n = 0
+      do while (n < 511)
+        if (msg(n+1) == c_null_char) exit
+        n = n + 1
+      end do
+      write(*,'(/i4,''] Error: cold_start_files: '',511a1)') my_task, msg(1:n)
+    end if
+    return
+  end if
+  rc = pomgpu_get_con(pom_ctx, c_loc(alpha))       ! period, rfe, rfw, rfn, rfs
+  if (rc /= 0) error_status = 1
+  call pomgpu_download_state
+  pom_cflmin = info%cflmin
+  if (n_proc == 1 .and. pom_cflmin < dte) then     ! parallel_mpi.f:504-511
+    write(*,'(/a,f5.2,a)') "[!] Specified timestep (", dte, ") is too large."
+    write(*,'(a,f5.2,a/)') "    You are strongly advised to make dte smaller than ", pom_cflmin, "."
+  end if
 end subroutine

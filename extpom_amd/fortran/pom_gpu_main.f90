@@ -9,7 +9,12 @@
 ! itself (pom_gpu_forcing_files.f90); without them the forcing is constant.
 ! Writes the final blocks back for checking against the oracle (tests/test_fortran_host.py).
 !
+! A cold start needs no dump: `--cold` sets read_input's constants (initialize.f:80-198), reads pom.nml and has cold_start_files
+! (pom_gpu_io.f90) do initialize.f:24-36 on the device from <wrk_pth>in/<netcdf_file>.grid.nc, .init.nc and .clim.nc; the restart
+! reader (nread_rst /= 0), the forcing files, the steps and the dump follow as ever.
+!
 ! usage: pom_gpu_main <state.in> <state.out>     (pom.nml in the working directory)
+!        pom_gpu_main --cold <state.out> <nsteps>
 program pom_gpu_main
   use pomgpu_iface
   implicit none
@@ -19,7 +24,8 @@ program pom_gpu_main
   integer :: nsteps, nrec, n, rc, n2, n3, nbd
   double precision :: vtot, atot, mtot, stot, tavg, savg, eavg, ekin
   double precision, allocatable, target :: tr(:,:,:,:), sr(:,:,:,:)
-  character(len=256) :: fin, fout
+  character(len=256) :: fin, fout, arg3
+  logical :: cold
 
   call get_command_argument(1, fin)
   call get_command_argument(2, fout)
@@ -27,30 +33,53 @@ program pom_gpu_main
   n3 = n2*kb
   nbd = 8*jm_local + 8*im_local + (12+12+6+6)*0   ! filled below
   nbd = 20*jm_local + 20*im_local + 18*jm_local*kb + 18*im_local*kb   ! bdry: 20 J, 20 I... see pom_layout.h
-  open(71, file=trim(fin), form='unformatted', access='stream', status='old')
-  read(71) im, jm, n_west, n_east, n_south, n_north, nsteps, nrec, nbd
+  cold = trim(fin) == '--cold'
+  if (cold) then                             ! one tile, the whole grid; read_input's constants (initialize.f:80-168)
+    call get_command_argument(3, arg3)
+    read(arg3, *) nsteps
+    im = im_local; jm = jm_local; nrec = 0
+    n_west = -1; n_east = -1; n_south = -1; n_north = -1
+    rhoref=1025.d0; tbias=0.d0; sbias=0.d0; grav=9.806d0; kappa=0.4d0; z0b=.01d0; cbcmin=.0025d0; cbcmax=1.d0
+    horcon=0.1d0; tprni=.1d0; umol=1.d-6; vmaxl=100.d0; slmax=2.d0; ntp=2; nbct=1; nbcs=1; ispadv=1; smoth=0.10d0
+    alpha=0.d0; aam_init=0.d0
+  else
+    open(71, file=trim(fin), form='unformatted', access='stream', status='old')
+    read(71) im, jm, n_west, n_east, n_south, n_north, nsteps, nrec, nbd
+    call blk_read(71, dz, 4*kb)                ! COMMON members are contiguous: read each block whole
+    call blk_read(71, aam2d, 73*n2)
+    call blk_read(71, aam, 40*n3)
+    call blk_read(71, ele, nbd)
+    call blk_read(71, alpha, 47)               ! blkcon: 376 bytes
+  end if
   imm1=im-1; imm2=im-2; jmm1=jm-1; jmm2=jm-2; kbm1=kb-1; kbm2=kb-2
-  call blk_read(71, dz, 4*kb)                ! COMMON members are contiguous: read each block whole
-  call blk_read(71, aam2d, 73*n2)
-  call blk_read(71, aam, 40*n3)
-  call blk_read(71, ele, nbd)
-  call blk_read(71, alpha, 47)               ! blkcon: 376 bytes
   allocate(tr(im,jm,kb,max(nrec,1)), sr(im,jm,kb,max(nrec,1)))
-  do n = 1, nrec
-    read(71) tr(:,:,:,n), sr(:,:,:,n)
-  end do
-  close(71)
+  if (.not. cold) then
+    do n = 1, nrec
+      read(71) tr(:,:,:,n), sr(:,:,:,n)
+    end do
+    close(71)
+  end if
   lramp = .false.
   open(73, file='pom.nml', status='old')
   read(73, nml=pom_nml)
   close(73)
   dti=dte*float(isplit); dte2=dte*2; dti2=dti*2
   ispi=1.d0/float(isplit); isp2i=1.d0/(2.d0*float(isplit))
+  if (cold) then                             ! the rest of read_input (initialize.f:178-198)
+    small=1.d-9; pi=atan(1.d0)*4.d0
+    iend=max0(nint(days*24.d0*3600.d0/dti),2)
+    iprint=nint(prtd1*24.d0*3600.d0/dti)
+    iswtch=nint(swtch*24.d0*3600.d0/dti)
+    irestart=nint(write_rst*24.d0*3600.d0/dti)
+    time0=0.d0; time=0.d0
+    if (nread_rst == 0) cont_bry = 0
+  end if
 
   call pomgpu_host_init(0)
   call pomgpu_upload_state
   my_task = 0; master_task = 0
   i_global(1) = 1; j_global(1) = 1           ! one tile: the patch starts at the grid's first cell
+  if (cold) call cold_start_files            ! initialize.f:24-36
   if (nread_rst /= 0) call read_restart_pnetcdf   ! initialize.f:39, for a host without PnetCDF: <wrk_pth>in/<read_rst_file>
   call pomgpu_open_forcing_files(pom_frc_sfrc, pom_frc_lbry, pom_frc_clim)
   if (.not. pom_frc_clim) then                   ! (with a clim file restore_interior's records are the file's)

@@ -15,6 +15,10 @@ module pomgpu_iface
     integer(c_int) :: im_global, jm_global, i0, j0, create
     type(c_ptr) :: stats
   end type
+  type, bind(C) :: pomgpu_cold_info               ! include/pomgpu.h
+    real(c_double) :: cflmin, period
+  end type
+  real(c_double), save :: pom_cflmin = 0.d0       ! this rank's cflmin of the last cold_start_files (check_cflmin_mpi reduces it over the ranks)
   interface
     integer(c_int) function pomgpu_create(ctx, dims, device, stream) bind(C, name='pomgpu_create')
       import; type(c_ptr) :: ctx; type(pomgpu_dims) :: dims; integer(c_int), value :: device; type(c_ptr), value :: stream
@@ -96,6 +100,9 @@ module pomgpu_iface
     end function
     integer(c_int) function pomgpu_read_restart(ctx, path, meta, time0_out, iint_out) bind(C, name='pomgpu_read_restart')
       import; type(c_ptr), value :: ctx, path, time0_out, iint_out; type(pomgpu_file_meta) :: meta   ! the two outputs may be c_null_ptr
+    end function
+    integer(c_int) function pomgpu_cold_start(ctx, grid, init, clim, meta, info) bind(C, name='pomgpu_cold_start')
+      import; type(c_ptr), value :: ctx, grid, init, clim, info; type(pomgpu_file_meta) :: meta   ! info may be c_null_ptr
     end function
     integer(c_int) function pomgpu_domain_stats(ctx, out, sums_only) bind(C, name='pomgpu_domain_stats')
       import; type(c_ptr), value :: ctx; real(c_double) :: out(8); integer(c_int), value :: sums_only

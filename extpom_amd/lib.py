@@ -28,6 +28,11 @@ class FileMeta(ctypes.Structure):
                 ("i0", ctypes.c_int), ("j0", ctypes.c_int), ("create", ctypes.c_int), ("stats", ctypes.POINTER(ctypes.c_double))]
 
 
+class ColdInfo(ctypes.Structure):
+    """pomgpu_cold_info (include/pomgpu.h)"""
+    _fields_ = [("cflmin", ctypes.c_double), ("period", ctypes.c_double)]
+
+
 class Dims(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in
                 ("im", "jm", "kb", "im_local", "jm_local", "n_west", "n_east", "n_south", "n_north")]
@@ -95,6 +100,7 @@ _SIGS = {
     "pomgpu_write_restart": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
     "pomgpu_read_restart": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "pomgpu_set_forcing_files": (_I, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
+    "pomgpu_cold_start": (_I, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(FileMeta), ctypes.POINTER(ColdInfo)]),
     "pomgpu_domain_stats": (_I, [_P, ctypes.POINTER(ctypes.c_double), _I]),
     "pomgpu_advq": (_I, [_P, _P, _P, _P]),
     "pomgpu_advt1": (_I, [_P, _P, _P, _P, _P]),

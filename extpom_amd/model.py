@@ -232,6 +232,20 @@ class PomGpu:
         self.get_con()
         return t0.value, ii.value
 
+    def cold_start(self, grid, init, clim, im_global=None, jm_global=None) -> dict:
+        """pomgpu_cold_start: initialize.f:24-36 after read_input (initialize_arrays, read_grid, initial_conditions, update_initial,
+        bottom_friction) from the reference's <...>.grid.nc, .init.nc and .clim.nc, on the device and without PnetCDF.  blkcon must
+        hold read_input's constants (this context's st.con does).  This tile's patch starts at (i_off+1, j_off+1) of the global grid,
+        as in read_restart.  Returns {"cflmin": the tile's minimum of cfl over cfl > 0, "period": from the tile's cor(im/2, jm/2)};
+        self.st.con is refreshed, NO array is downloaded (download() brings the state over)."""
+        st = self.st
+        m = _lib.FileMeta(b"", b"", im_global or st.im, jm_global or st.jm, st.i_off + 1, st.j_off + 1, 0, None)
+        info = _lib.ColdInfo()
+        self._chk(self.L.pomgpu_cold_start(self.h, str(grid).encode(), str(init).encode(), str(clim).encode(), ctypes.byref(m), ctypes.byref(info)),
+                  "cold_start")
+        self.get_con()
+        return {"cflmin": info.cflmin, "period": info.period}
+
     def set_forcing_files(self, sfrc=None, lbry=None, clim=None, im_global=None, jm_global=None):
         """pomgpu_set_forcing_files: from now on wind / heat / surface (sfrc), lateral_bc (lbry) and restore_interior (clim) take the
         records their schedule asks for from these classic NetCDF files, on the device; None leaves a source as it is.  This tile's

@@ -291,6 +291,39 @@ int pomgpu_write_restart(pomgpu_ctx *ctx, const char *path, const pomgpu_file_me
  * error half way leaves the state unspecified (error_status = 1). */
 int pomgpu_read_restart(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta, double *time0_out, double *iint_out);   /* read_restart_pnetcdf */
 
+/* A cold start without PnetCDF: what initialize (initialize.f:24-36) does after read_input -- initialize_arrays, read_grid,
+ * initial_conditions, update_initial, bottom_friction -- from the reference's three input files, on the device.
+ * grid: <...>.grid.nc (io_pnetcdf.F:2113-2156): z, zz (at least kb values) and dx dy lon_rho lat_rho lon_u lat_u lon_v lat_v lon_psi
+ * lat_psi angle h fsm as (jm_global, im_global); init: <...>.init.nc (:2800-2810): an unlimited dimension, a variable Level, and T, S as
+ * (record, Level >= kb-1, jm_global, im_global), of which record 1 and levels 1..kb-1 are read; clim: <...>.clim.nc (:2875-2878): Tclim,
+ * Sclim as (record, kb, jm_global, im_global) with at least 10 records, of which record 10 is read (initialize.f:407).  Classic NetCDF
+ * (CDF-1 or CDF-2), every variable found BY NAME, NC_FLOAT or NC_DOUBLE (fsm also NC_BYTE, NC_SHORT, NC_INT).
+ * Precondition: blkcon holds read_input's constants (pomgpu_set_con, or an upload of con alone).  Of `meta` only im_global, jm_global,
+ * i0, j0 are used; every rank of a decomposition names the same files with its own i0, j0 -- not collective: a tile with a west / south
+ * neighbour reads ONE more column / row on its low side and forms dum, dvm, aru, arv of its ghost line from it, where the reference
+ * exchanges them (io_pnetcdf.F:2255-2256, initialize.f:370-371).  baropg_mcc (npg = 2) posts its own order exchange as ever.
+ * The call completes what the library keeps lazily, joins a file still being written, ZEROES blk2d, blk3d and bdry (the COMMON blocks
+ * at program start), sets the readers' defaults (dx = dy = h = 1 over the padded arrays) and then fills the state as the reference does:
+ * dz dzz, cor, period (from THIS tile's cor(im/2, jm/2), as the reference computes it), art aru arv, dum dvm, d dt, tb sb t s (level
+ * kb stays +0.0: the reference copies an uninitialised automatic array there), tsurf ssurf, the eight boundary arrays tbe .. sbs,
+ * rfe = rfw = rfn = rfs = 1, tclim sclim, rmean and rho (dens), update_initial with baropg / baropg_mcc by npg, drx2d dry2d, cbc.
+ * cor and cbc (sin, log) and dz, dzz are formed on the host with libm; everything else is kernels behind the copies of raw big-endian
+ * bands (the restart reader's loop: POMGPU_IO_CHUNK_KB applies; the fp32-storage variants round 3-D arrays as an upload does).
+ * time, time0, iint, the record slots and a registration by pomgpu_set_forcing_files stay untouched.  Synchronous.
+ * info (may be NULL): cflmin = this tile's min of cfl over cfl > 0 (parallel_mpi.f:493-499; huge(), what minval gives, if there is none; the caller
+ * reduces over ranks and prints the warning) and period.
+ * Refused with POMGPU_EINVAL, error_status = 1 and file and cause in pomgpu_last_error, BEFORE any mirror, slot or blkcon member
+ * changes: another magic (CDF-5, HDF5), a missing or misshapen variable, a file shorter than begin + size, a tile outside the global
+ * grid, cor(im/2, jm/2) == 0 (the reference stops there, initialize.f:354-355), npg other than 1 or 2 (:506-508), a value of fsm in
+ * the tile's window other than 0 or 1 (the kernels fold mask multiplies; pomgpu_upload refuses the same).  An I/O error half
+ * way leaves the state unspecified (error_status = 1). */
+typedef struct pomgpu_cold_info {
+  double cflmin;
+  double period;
+} pomgpu_cold_info;
+int pomgpu_cold_start(pomgpu_ctx *ctx, const char *grid, const char *init, const char *clim, const pomgpu_file_meta *meta,
+                      pomgpu_cold_info *info);
+
 /* The forcing files without PnetCDF: read_wind_pnetcdf, read_heat_pnetcdf, read_surface_pnetcdf (io_pnetcdf.F:2912-3224),
  * read_boundary_conditions_pnetcdf (:3393-3621), read_restore_ts_interior_pnetcdf (:3275-3333).  The host names the files once --
  * sfrc: <...>.sfrc.nc (sustr svstr shflux swrad SST SSS), lbry: <...>.lbry.nc (zeta u v temp salt, each .east and .south), clim:
