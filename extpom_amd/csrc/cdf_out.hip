@@ -655,6 +655,11 @@ struct FFiles {
   int used[2] = {0, 0};
 #endif
   int b = 0;
+  // a clim file on z levels (pomgpu_set_z_inputs): its level count, the window lines towards the west, east, south, north neighbour, and
+  // one allocation: the window of one variable as doubles, ztosig's two work arrays, its table
+  int zks = 0, wi = 0, we = 0, wj = 0, wn = 0;
+  double *zdev = NULL;
+  size_t zwin = 0, zwork = 0;
 };
 const char *const FF_WHAT[3] = {"sfrc", "lbry", "clim"};
 const char *const FF_SFRC[6] = {"sustr", "svstr", "shflux", "swrad", "SST", "SSS"};
@@ -782,6 +787,10 @@ __global__ void k_rst_unpack(double *dst, const void *src, int im, int jm, int r
 }
 
 static FFiles *FF(pomgpu_ctx *c) { return (FFiles *)c->frc_files; }
+// ztosig for a clim file on z levels (defined with the kernel, further down)
+static std::string z_levels(const RHeader &H, const FSource &S, const char *name, std::vector<double> &zs);
+static void ztosig_table(const double *zs, int ks, double *tab);
+static void launch_ztosig_window(pomgpu_ctx *c, double *out, int record, const double *zsrc, const double *tab, double *wa, double *wb, int ks, int wi, int we, int wj, int wn);
 int pomgpu_ff_has(pomgpu_ctx *c, int src) { return c->frc_files && FF(c)->s[src].fd >= 0; }
 void pomgpu_ff_free(pomgpu_ctx *c) {
   FFiles *F = FF(c);
@@ -793,6 +802,7 @@ void pomgpu_ff_free(pomgpu_ctx *c) {
 #else
   if (F->pin[0]) (void)hipFree(F->pin[0]);
 #endif
+  if (F->zdev) (void)hipFree(F->zdev);
   delete F;
   c->frc_files = NULL;
 }
@@ -868,6 +878,13 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
     return fail(c, POMGPU_EINVAL, "set_forcing_files: the tile (%d..%d, %d..%d) does not fit the global grid %d x %d", m->i0, m->i0 + P.im - 1, m->j0,
                 m->j0 + P.jm - 1, m->im_global, m->jm_global);
   if (P.im < 3 || P.jm < 3) return fail(c, POMGPU_EINVAL, "set_forcing_files: the wind taper needs a tile of at least 3 x 3 cells");
+  // a clim file on z levels (pomgpu_set_z_inputs): ztosig's fill-in looks at all four neighbours, so the monthly fetch reads one more column / row
+  // towards every neighbour of the tile
+  const int zc = clim && c->z_clim, wi = zc && !P.W, we = zc && !P.E, wj = zc && !P.S, wn = zc && !P.N;
+  if (m->i0 - wi < 1 || m->j0 - wj < 1 || m->i0 + P.im - 1 + we > m->im_global || m->j0 + P.jm - 1 + wn > m->jm_global)
+    return fail(c, POMGPU_EINVAL, "set_forcing_files: %s: the tile (%d..%d, %d..%d) with its window lines towards every neighbour does not fit the global grid %d x %d", clim,
+                m->i0, m->i0 + P.im - 1, m->j0, m->j0 + P.jm - 1, m->im_global, m->jm_global);
+  std::vector<double> zlev;
   FFiles *old = FF(c);
   if (old && (old->im_global != m->im_global || old->jm_global != m->jm_global || old->i0 != m->i0 || old->j0 != m->j0))
     return fail(c, POMGPU_EINVAL, "set_forcing_files: files are registered under another global grid or tile origin");
@@ -890,15 +907,20 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
     std::string why;
     if (q == 0) why = ff_check(H, S, FF_SFRC, std::vector<std::vector<uint64_t>>(6, {jmg, img}), 1);
     else if (q == 1) why = ff_check(H, S, FF_LBRY, {{jmg}, {img}, {kb, jmg}, {kb, jmg}, {kb, jmg}, {kb, jmg}, {kb, img}, {kb, img}, {kb, img}, {kb, img}}, 1);
-    else why = ff_check(H, S, FF_CLIM, {{kb, jmg, img}, {kb, jmg, img}}, 12);
+    else {
+      if (zc) why = z_levels(H, S, "z", zlev);
+      const uint64_t kc = zc && why.empty() ? (uint64_t)zlev.size() : kb;
+      if (why.empty()) why = ff_check(H, S, FF_CLIM, {{kc, jmg, img}, {kc, jmg, img}}, 12);
+    }
     if (!why.empty()) { drop(); return fail(c, POMGPU_EINVAL, "set_forcing_files: %s: %s", paths[q], why.c_str()); }
   }
   // ---- accepted: the buffers every fetch uses, sized once (no allocation inside a step) ----
   FFiles *F = old ? old : new FFiles();
-  const size_t band2 = (size_t)P.jm * (size_t)img * 8;           // one level's band of rows at the file's full width, doubles
+  const size_t band2 = (size_t)(P.jm + wj + wn) * (size_t)img * 8;   // one level's band of rows (the window's, for a z-level clim file) at the file's full width, doubles
+  const size_t zks = zlev.size(), nlevmax = zks > (size_t)P.kb ? zks : (size_t)P.kb;
   size_t run = (SW(c, IO_CHUNK_KB) && SWV(c, IO_CHUNK_KB) > 0 ? (size_t)SWV(c, IO_CHUNK_KB) << 10 : (size_t)64 << 20);
   if (run < band2) run = band2;
-  if (run > band2 * (size_t)P.kb) run = band2 * (size_t)P.kb;
+  if (run > band2 * nlevmax) run = band2 * nlevmax;
   size_t need = 2 * band2;                                        // sfrc: two variables' bands
   const size_t lat = 8 * ((size_t)P.jm + P.im) + 4 * 8 * (size_t)P.kb * ((size_t)P.jm + P.im);
   if (need < lat) need = lat;
@@ -928,6 +950,27 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
       if (!c->frc_dev[k][sl][f] && hipMalloc((void **)&c->frc_dev[k][sl][f], rec2) != hipSuccess) bad = 1;
   if (!bad && paths[1]) for (int sl = 0; sl < 4; sl++) if (!c->lat_dev[sl] && hipMalloc((void **)&c->lat_dev[sl], latrec) != hipSuccess) bad = 1;
   if (!bad && paths[2] && !c->rec_t[0] && (hipMalloc((void **)&c->rec_t[0], rec3) != hipSuccess || hipMalloc((void **)&c->rec_s[0], rec3) != hipSuccess)) bad = 1;
+  // ztosig's buffers and table: allocated here, so that a step allocates nothing; an earlier registration keeps its own until these exist
+  const size_t zwin = zks * (size_t)(P.im + wi + we) * (size_t)(P.jm + wj + wn), zwork = zks * P.n2;
+  double *znew = NULL;
+  if (!bad && paths[2] && zks) {
+    std::vector<double> tab(4 * zks);
+    ztosig_table(zlev.data(), (int)zks, tab.data());
+    if (hipMalloc((void **)&znew, (zwin + 2 * zwork + 4 * zks) * sizeof(double)) != hipSuccess ||
+        hipMemcpyAsync(znew + zwin + 2 * zwork, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+      bad = 1;
+      if (znew) (void)hipFree(znew);
+      znew = NULL;
+    }
+  }
+  if (!bad && paths[2]) {
+    if (F->zdev && hipStreamSynchronize(c->stream) != hipSuccess) bad = 1;   // an earlier fetch may still be mapping out of the old buffers
+    if (F->zdev) (void)hipFree(F->zdev);
+    F->zdev = znew;
+    F->zks = (int)zks; F->wi = wi; F->we = we; F->wj = wj; F->wn = wn;
+    F->zwin = zwin; F->zwork = zwork;
+  }
   c->frc_files = F;
   if (bad) {
     drop();
@@ -1062,26 +1105,170 @@ int pomgpu_ff_fetch_restore(pomgpu_ctx *c, int n) {
   int rc = ff_have(c, S, "restore_interior", month, {0, 1});
   if (rc) return rc;
   const uint64_t img = (uint64_t)F->im_global, jmg = (uint64_t)F->jm_global;
-  const size_t band = (size_t)P.jm * (size_t)img;                // values of one level's band
-  const bool whole_rows = (uint64_t)P.jm == jmg;
+  // a z-level clim file: all zks levels over the tile's window into the window buffer, then ztosig into the record, in k_rst_unpack's place
+  const int onz = F->zks > 0, rows = P.jm + F->wj + F->wn, cols = P.im + F->wi + F->we, nlev = onz ? F->zks : P.kb;
+  const size_t band = (size_t)rows * (size_t)img;               // values of one level's band
+  const bool whole_rows = (uint64_t)rows == jmg;
   for (int q = 0; q < 2; q++) {
     const FVar &f = S.v[q];
-    const int lev_per_run = (int)(F->cap / (band * f.esize())) < P.kb ? (int)(F->cap / (band * f.esize())) : P.kb;
+    const int lev_per_run = (int)(F->cap / (band * f.esize())) < nlev ? (int)(F->cap / (band * f.esize())) : nlev;
     double *dst = q ? c->rec_s[0] : c->rec_t[0];
-    for (int k0 = 0; k0 < P.kb; k0 += lev_per_run) {
-      const int nl = P.kb - k0 < lev_per_run ? P.kb - k0 : lev_per_run;
+    for (int k0 = 0; k0 < nlev; k0 += lev_per_run) {
+      const int nl = nlev - k0 < lev_per_run ? nlev - k0 : lev_per_run;
       unsigned char *pin = ff_buffer(F);
       if (!pin) return ff_io_error(c, "restore_interior", n, S, 1);
-      const uint64_t first = f.begin + (uint64_t)(month - 1) * f.stride + (((uint64_t)k0 * jmg + (uint64_t)(F->j0 - 1)) * img) * f.esize();
+      const uint64_t first = f.begin + (uint64_t)(month - 1) * f.stride + (((uint64_t)k0 * jmg + (uint64_t)(F->j0 - 1 - F->wj)) * img) * f.esize();
       if (whole_rows) { if (pread_all(S.fd, pin, (size_t)nl * band * f.esize(), first)) return ff_io_error(c, "restore_interior", n, S, 0); }
       else for (int k = 0; k < nl; k++) if (pread_all(S.fd, pin + (size_t)k * band * f.esize(), band * f.esize(), first + (uint64_t)k * jmg * img * f.esize())) return ff_io_error(c, "restore_interior", n, S, 0);
       if (ff_send(c, F, (size_t)nl * band * f.esize())) return ff_io_error(c, "restore_interior", n, S, 1);
-      const dim3 grid((unsigned)((P.im + 63) / 64), (unsigned)((P.jm + 3) / 4), (unsigned)nl);
-      if (f.type == 5) LAUNCHN(c, "k_rst_unpack", k_rst_unpack<float>, grid, blk2(), dst, (const void *)F->stage, P.im, P.jm, P.jm, (int)img, F->i0 - 1, k0);
-      else LAUNCHN(c, "k_rst_unpack", k_rst_unpack<double>, grid, blk2(), dst, (const void *)F->stage, P.im, P.jm, P.jm, (int)img, F->i0 - 1, k0);
+      const dim3 grid((unsigned)((cols + 63) / 64), (unsigned)((rows + 3) / 4), (unsigned)nl);
+      double *to = onz ? F->zdev : dst;
+      if (f.type == 5) LAUNCHN(c, "k_rst_unpack", k_rst_unpack<float>, grid, blk2(), to, (const void *)F->stage, cols, rows, rows, (int)img, F->i0 - 1 - F->wi, k0);
+      else LAUNCHN(c, "k_rst_unpack", k_rst_unpack<double>, grid, blk2(), to, (const void *)F->stage, cols, rows, rows, (int)img, F->i0 - 1 - F->wi, k0);
     }
+    if (onz) launch_ztosig_window(c, dst, 1, F->zdev, F->zdev + F->zwin + 2 * F->zwork, F->zdev + F->zwin, F->zdev + F->zwin + F->zwork, F->zks, F->wi, F->we, F->wj, F->wn);
   }
   return POMGPU_OK;
+}
+
+// ---- ztosig: z-level T or S onto the sigma levels (initialize.f:547-595 with splinc :598-638 and splint :641-667) -----------------------
+// One column per lane, threadIdx.x -> i, the level loops in the thread.  ks goes up to splinc's nmax = 300, so the column's vectors do
+// not live in registers: tin (the filled-in source, splinc's y) and u / y2 are two work arrays of this call laid out like the source,
+// (i, j, k), so that a wavefront touches one contiguous row piece per level; a lane reads back only what it stored itself.  What
+// depends on zs alone -- sig, p and the decomposition's y2(i) = (sig-1.)/p (:613-615) -- comes in `tab` (zs, sig, p, y2, ks values each),
+// formed once per call by ztosig_table with the same fp64 expressions.
+//   fill-in (:564-572): from the RAW source only -- no lane reads what another has stored -- one level ahead of the decomposition, which
+//     needs y(i+1); amax1 is the REAL(4) intrinsic: the neighbour maximum reaches tin rounded to single; 0.01 is a REAL(4) literal
+//   natural spline (yp1 = ypn = 2.d30): y2(1) = u(1) = 0, qn = un = 0, the reference's order and association throughout
+//   splint: its bisection as written, on the table (a**3 = a*a*a, h**2 = h*h)
+// All kb levels are stored (level kb is an extrapolation), rounded once to the storage type.  Columns on the frame of (1:im, 1:jm) and
+// those with h <= 1.0 get the +0.0 of `t = 0.` (:558); k_ztosig_edges makes the copies of :589-592 after the exchange of :586.
+#define POMGPU_ZTOSIG_NMAX 300
+static void ztosig_table(const double *zs, int ks, double *tab) {
+  double *x = tab, *sg = tab + ks, *pp = tab + 2 * (size_t)ks, *d2 = tab + 3 * (size_t)ks;
+  for (int i = 0; i < ks; i++) { x[i] = zs[i]; sg[i] = 0.; pp[i] = 0.; d2[i] = 0.; }
+  for (int i = 1; i < ks - 1; i++) {
+    const double sig = (x[i] - x[i - 1]) / (x[i + 1] - x[i - 1]);
+    const double p = sig * d2[i - 1] + (double)2.f;
+    sg[i] = sig; pp[i] = p;
+    d2[i] = (sig - (double)1.f) / p;
+  }
+}
+// Where the source and the result live: the source as doubles, `sp` values per row and `sl` per level, the tile's cell (1,1) at `so`
+// (the stand-alone call: the tile's own array; the file readers: the tile's WINDOW, one more column / row towards every neighbour); the
+// result `op` values per row and `ol` per level (a mirror, or the (im,jm,kb) restore record).  Columns ilo..ihi x jlo..jhi are mapped
+// from their own source column.  fuse = 0: every other cell of (1:im, 1:jm) gets zero and the caller exchanges and copies the edges.
+// fuse = 1 (the file readers, which post no message round): the range reaches the ghost lines towards neighbours -- formed from the
+// window with the owner's arithmetic, which is what the exchange would bring -- and stops one line short of a physical edge, whose
+// cells map the column next to them across every physical edge they lie on: what the four copies leave there, corners included.
+struct ZtsGeo { int sp, op, ilo, ihi, jlo, jhi, fuse; size_t sl, so, ol; };
+template <class TO>
+__global__ void k_ztosig(KP P, TO *out, const double *src, const double *tab, double *wa, double *wb, int ks, ZtsGeo g) {
+  const int i = TID_I, j = TID_J;
+  if (i > P.im || j > P.jm) return;
+  const int is = i < g.ilo ? g.ilo : (i > g.ihi ? g.ihi : i), js = j < g.jlo ? g.jlo : (j > g.jhi ? g.jhi : j);
+  const double hc = F2(h, is, js);
+  TO *const oc = out + (size_t)(j - 1) * g.op + (size_t)(i - 1);
+  if ((!g.fuse && (is != i || js != j)) || !(hc > (double)1.f)) {
+    for (int k = 0; k < P.kb; k++) oc[(size_t)k * g.ol] = (TO)0.;
+    return;
+  }
+  const double *xs = tab, *sg = tab + ks, *pp = tab + 2 * (size_t)ks, *d2 = tab + 3 * (size_t)ks;
+  const size_t o = IX2(i, j), lv = P.n2;
+  const double *const sc = src + g.so + (size_t)(js - 1) * g.sp + (size_t)(is - 1);
+  const double miss = (double)0.01f;
+  auto raw = [&](int k) {                                       // tin(k) before the copy from above; k is 0-based
+    const double *s = sc + (size_t)k * g.sl;
+    double v = s[0];
+    if (xs[k] <= hc && v < miss) {
+      double m = s[-1];
+      m = s[1] > m ? s[1] : m;
+      m = s[-(ptrdiff_t)g.sp] > m ? s[-(ptrdiff_t)g.sp] : m;
+      m = s[g.sp] > m ? s[g.sp] : m;
+      v = (double)(float)m;
+    }
+    return v;
+  };
+  double y0 = raw(0), y1 = raw(1), up = 0.;
+  if (y1 < miss) y1 = y0;
+  wa[o] = y0;
+  wb[o] = 0.;
+  for (int n = 1; n < ks - 1; n++) {
+    double yn = raw(n + 1);
+    if (yn < miss) yn = y1;
+    const double u = ((double)6.f * ((yn - y1) / (xs[n + 1] - xs[n]) - (y1 - y0) / (xs[n] - xs[n - 1])) / (xs[n + 1] - xs[n - 1]) - sg[n] * up) / pp[n];
+    wa[(size_t)n * lv + o] = y1;
+    wb[(size_t)n * lv + o] = u;
+    up = u; y0 = y1; y1 = yn;
+  }
+  wa[(size_t)(ks - 1) * lv + o] = y1;
+  const double qn = (double)0.f, un = 0.;
+  double y2 = (un - qn * up) / (qn * d2[ks - 2] + (double)1.f);
+  wb[(size_t)(ks - 1) * lv + o] = y2;
+  for (int k = ks - 2; k >= 0; k--) {
+    y2 = d2[k] * y2 + wb[(size_t)k * lv + o];
+    wb[(size_t)k * lv + o] = y2;
+  }
+  for (int k = 1; k <= P.kb; k++) {
+    const double x = -F1(zz, k) * hc;
+    int klo = 1, khi = ks;
+    while (khi - klo > 1) {
+      const int kk = (khi + klo) / 2;
+      if (xs[kk - 1] > x) khi = kk; else klo = kk;
+    }
+    const double xl = xs[klo - 1], xh = xs[khi - 1], hh = xh - xl;
+    const double a = (xh - x) / hh, b = (x - xl) / hh;
+    const size_t ql = (size_t)(klo - 1) * lv + o, qh = (size_t)(khi - 1) * lv + o;
+    oc[(size_t)(k - 1) * g.ol] = (TO)(a * wa[ql] + b * wa[qh] + ((a * a * a - a) * wb[ql] + (b * b * b - b) * wb[qh]) * (hh * hh) / (double)6.f);
+  }
+}
+// The copies onto physical edges (:589-592: west, east, south, north).  One lane per frame cell and level; a cell takes the value the
+// sequence leaves there: the cell next to it across every physical edge it lies on -- never a cell this kernel writes, so the four
+// statements' order shows only in which cell a corner ends up with, and that is this one.
+__global__ void k_ztosig_edges(KP P, double *t) {
+  const int q = (int)(blockIdx.x * blockDim.x + threadIdx.x), k = (int)blockIdx.y + 1;
+  int i, j;
+  if (q < P.im) { i = q + 1; j = 1; }
+  else if (q < 2 * P.im) { i = q - P.im + 1; j = P.jm; }
+  else if (q < 2 * P.im + P.jm) { i = 1; j = q - 2 * P.im + 1; }
+  else if (q < 2 * (P.im + P.jm)) { i = P.im; j = q - 2 * P.im - P.jm + 1; }
+  else return;
+  const int is = (i == 1 && P.W) ? 2 : ((i == P.im && P.E) ? P.imm1 : i), js = (j == 1 && P.S) ? 2 : ((j == P.jm && P.N) ? P.jmm1 : j);
+  if (is != i || js != j) G3(t, i, j, k) = G3(t, is, js, k);
+}
+// the interior of ztosig into the mirror `t`; zs: ks host doubles (vetted), src: host (im_local, jm_local, ks).  Synchronous: the source
+// and the work arrays are this call's.  The caller exchanges t and calls launch_ztosig_edges
+int launch_ztosig(pomgpu_ctx *c, double *t, const double *zs, int ks, const double *src) {
+  const KP &P = c->P;
+  const size_t vol = (size_t)ks * P.n2;
+  std::vector<double> tab(4 * (size_t)ks);
+  ztosig_table(zs, ks, tab.data());
+  double *dev = NULL;                                            // source, tin, u / y2, table
+  if (hipMalloc((void **)&dev, (3 * vol + tab.size()) * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return POMGPU_ENOMEM; }
+  int rc = POMGPU_OK;
+  if (hipMemcpyAsync(dev, src, vol * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(dev + 3 * vol, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = POMGPU_EHIP;
+  const ZtsGeo g = {P.iml, P.iml, 2, P.imm1, 2, P.jmm1, 0, P.n2, 0, P.n2};
+  if (!rc) LAUNCHN(c, "k_ztosig", k_ztosig<pomgpu_st>, grid2(P), blk2(), P, (pomgpu_st *)t, (const double *)dev, (const double *)(dev + 3 * vol), dev + vol, dev + 2 * vol, ks, g);
+  if (hipStreamSynchronize(c->stream) != hipSuccess) rc = POMGPU_EHIP;
+  (void)hipFree(dev);
+  return rc;
+}
+void launch_ztosig_edges(pomgpu_ctx *c, double *t) {
+  const KP &P = c->P;
+  LAUNCH(c, k_ztosig_edges, dim3((unsigned)((2 * (P.im + P.jm) + 63) / 64), (unsigned)P.kb, 1), dim3(64, 1, 1), P, t);
+}
+// ztosig for the file readers: the source is the tile's window (wi, we, wj, wn: one more line towards the west, east, south, north
+// neighbour), every cell of (1:im, 1:jm) comes out of the one kernel (ZtsGeo, fuse = 1); enqueued on c->cur, no message round
+// record = 0: `out` is a mirror; 1: the (im, jm, kb) restore record, plain doubles in every build
+static void launch_ztosig_window(pomgpu_ctx *c, double *out, int record, const double *zsrc, const double *tab, double *wa, double *wb, int ks, int wi, int we, int wj, int wn) {
+  const KP &P = c->P;
+  const int wim = P.im + wi + we, wjm = P.jm + wj + wn;
+  ZtsGeo g = {wim, P.iml, wi ? 1 : 2, we ? P.im : P.imm1, wj ? 1 : 2, wn ? P.jm : P.jmm1, 1, (size_t)wim * wjm, (size_t)wj * wim + wi, P.n2};
+  if (record) {
+    g.op = P.im; g.ol = (size_t)P.im * P.jm;
+    LAUNCHN(c, "k_ztosig", k_ztosig<double>, grid2(P), blk2(), P, out, zsrc, tab, wa, wb, ks, g);
+  } else LAUNCHN(c, "k_ztosig", k_ztosig<pomgpu_st>, grid2(P), blk2(), P, (pomgpu_st *)out, zsrc, tab, wa, wb, ks, g);
 }
 
 // ---- a cold start from the reference's input files (pomgpu_cold_start) ---------------------------------------------------------------
@@ -1273,6 +1460,64 @@ __global__ void k_cold_drsum(KP P) {
 static void cold_update_initial(pomgpu_ctx *c) { LAUNCH(c, k_cold_update, grid2(c->P), blk2(), c->P, c->con.aam_init, sqrt(c->con.small)); }
 static void cold_sums(pomgpu_ctx *c) { LAUNCH(c, k_cold_drsum, grid2(c->P), blk2(), c->P); }
 
+// tb (which = 0) or sb (1) as ztosig has stored it, all kb levels, into what initialize.f:437-460 and update_initial's `t = tb` derive from
+// it: the bits k_cold_ts hands out, read back from the mirror (the fp32-storage variants: the rounded value)
+__global__ void k_cold_zts(KP P, int which) {
+  const int i = TID_I, j = TID_J, k = (int)blockIdx.z + 1;
+  if (i > P.im || j > P.jm) return;
+  if (which == 0) {
+    const double x = F3(tb, i, j, k);
+    F3(t, i, j, k) = x;
+    if (k == 1) F2(tsurf, i, j) = x;
+    if (k <= P.kbm1) {
+      if (i == P.im) BDJ(tbe, j, k) = x;
+      if (i == 1) BDJ(tbw, j, k) = x;
+      if (j == P.jm) BDI(tbn, i, k) = x;
+      if (j == 1) BDI(tbs, i, k) = x;
+    }
+  } else {
+    const double x = F3(sb, i, j, k);
+    F3(s, i, j, k) = x;
+    if (k == 1) F2(ssurf, i, j) = x;
+    if (k <= P.kbm1) {
+      if (i == P.im) BDJ(sbe, j, k) = x;
+      if (i == 1) BDJ(sbw, j, k) = x;
+      if (j == P.jm) BDI(sbn, i, k) = x;
+      if (j == 1) BDI(sbs, i, k) = x;
+    }
+  }
+}
+// the z levels of an init (`Level`) or clim (`z`) file: a 1-D NC_FLOAT / NC_DOUBLE variable of 2..300 finite, strictly increasing values
+static std::string z_levels(const RHeader &H, const FSource &S, const char *name, std::vector<double> &zs) {
+  const RVar *v = NULL;
+  for (const RVar &x : H.vars) if (x.name == name) { v = &x; break; }
+  if (!v) return std::string("variable ") + name + " (the z levels) is absent";
+  if (v->dimids.size() != 1) return std::string("variable ") + name + " has " + std::to_string(v->dimids.size()) + " dimensions, wanted the one of the z levels";
+  const uint64_t ks = H.dimlen[v->dimids[0]];
+  if (ks < 2 || ks > POMGPU_ZTOSIG_NMAX) return std::string("variable ") + name + " holds " + std::to_string(ks) + " z levels, wanted 2..300";
+  CVar cv;
+  std::string why = cold_fixed(H, S.fsize, name, {ks}, false, CS_REAL, cv);
+  if (!why.empty()) return why;
+  std::vector<unsigned char> raw((size_t)ks * cv.es);
+  if (pread_all(S.fd, raw.data(), raw.size(), cv.begin)) return std::string("I/O error (") + name + ")";
+  zs.resize((size_t)ks);
+  for (size_t k = 0; k < ks; k++) {
+    zs[k] = host_raw(cv.type, raw.data(), k);
+    if (!__builtin_isfinite(zs[k]) || (k && !(zs[k] > zs[k - 1])))
+      return std::string("variable ") + name + " is not finite and strictly increasing at level " + std::to_string(k + 1) + " (" + std::to_string(zs[k]) + ")";
+  }
+  return std::string();
+}
+
+extern "C" int pomgpu_set_z_inputs(pomgpu_ctx *c, int init_on_z, int clim_on_z) {
+  if (!c) return POMGPU_EINVAL;
+  if (pomgpu_ff_has(c, 2) && (clim_on_z != 0) != (c->z_clim != 0))
+    return fail(c, POMGPU_EINVAL, "set_z_inputs: a clim file is registered (pomgpu_set_forcing_files) as a %s file", c->z_clim ? "z-level" : "sigma-level");
+  c->z_init = init_on_z != 0;
+  c->z_clim = clim_on_z != 0;
+  return POMGPU_OK;
+}
+
 extern "C" int pomgpu_cold_start(pomgpu_ctx *c, const char *grid, const char *init, const char *clim, const pomgpu_file_meta *m, pomgpu_cold_info *info) {
   if (!c || !grid || !init || !clim || !m) return POMGPU_EINVAL;
   (void)hipSetDevice(c->device);
@@ -1280,9 +1525,13 @@ extern "C" int pomgpu_cold_start(pomgpu_ctx *c, const char *grid, const char *in
   const KP &P = c->P;
   if (c->flags & POMGPU_CTX_2D) return fail(c, POMGPU_EINVAL, "cold_start: not on a 2-D context");
   const int wi = P.W ? 0 : 1, wj = P.S ? 0 : 1;                // one more column / row on the low side of a tile with a neighbour there
-  if (m->i0 - wi < 1 || m->j0 - wj < 1 || m->i0 + P.im - 1 > m->im_global || m->j0 + P.jm - 1 > m->jm_global)
+  const int zin[2] = {c->z_init, c->z_clim};                   // pomgpu_set_z_inputs: T, S / Tclim, Sclim are on z levels and go through ztosig,
+  const int we = (zin[0] || zin[1]) && !P.E ? 1 : 0, wn = (zin[0] || zin[1]) && !P.N ? 1 : 0;   // whose fill-in looks at the neighbour on the high side too
+  if (m->i0 - wi < 1 || m->j0 - wj < 1 || m->i0 + P.im - 1 + we > m->im_global || m->j0 + P.jm - 1 + wn > m->jm_global)
     return fail(c, POMGPU_EINVAL, "cold_start: %s: the tile (%d..%d, %d..%d)%s does not fit the global grid %d x %d", grid, m->i0, m->i0 + P.im - 1, m->j0,
-                m->j0 + P.jm - 1, wi || wj ? " with its window line towards the west / south neighbour" : "", m->im_global, m->jm_global);
+                m->j0 + P.jm - 1, we || wn ? " with its window lines towards every neighbour" : (wi || wj ? " with its window line towards the west / south neighbour" : ""),
+                m->im_global, m->jm_global);
+  if ((zin[0] || zin[1]) && (P.im < 3 || P.jm < 3)) return fail(c, POMGPU_EINVAL, "cold_start: z-level input needs a tile of at least 3 x 3 cells");
   if (c->con.npg != 1 && c->con.npg != 2) return fail(c, POMGPU_EINVAL, "cold_start: invalid value for npg (%d)", c->con.npg);
   const uint64_t img = (uint64_t)m->im_global, jmg = (uint64_t)m->jm_global, kb = (uint64_t)P.kb;
   const char *paths[3] = {grid, init, clim};
@@ -1311,6 +1560,7 @@ extern "C" int pomgpu_cold_start(pomgpu_ctx *c, const char *grid, const char *in
   }
   // init: record 1, levels 1..kb-1 of T, S
   uint64_t nlev[2] = {kb - 1, kb - 1};
+  std::vector<double> zlev[2];                                  // the z levels of the init / clim file (pomgpu_set_z_inputs)
   {
     bool unlimited = false, level = false;
     for (uint64_t len : H[1].dimlen) if (len == 0) unlimited = true;
@@ -1320,9 +1570,11 @@ extern "C" int pomgpu_cold_start(pomgpu_ctx *c, const char *grid, const char *in
     }
     if (!unlimited) return refuse(1, "the file has no unlimited dimension");
     if (!level) return refuse(1, "variable Level is absent");
-    std::string why = ff_check(H[1], F[1], CS_INIT, {{nlev[0], jmg, img}, {nlev[1], jmg, img}}, 1);
+    std::string why = zin[0] ? z_levels(H[1], F[1], "Level", zlev[0]) : std::string();
+    if (zin[0] && why.empty()) nlev[0] = nlev[1] = (uint64_t)zlev[0].size();   // T, S must have Level's length, wherever they stand in the header
+    if (why.empty()) why = ff_check(H[1], F[1], CS_INIT, {{nlev[0], jmg, img}, {nlev[1], jmg, img}}, 1);
     for (int q = 0; q < 2 && why.empty(); q++) {
-      if (nlev[q] < kb - 1) why = std::string("variable ") + CS_INIT[q] + " has " + std::to_string(nlev[q]) + " levels, wanted >= " + std::to_string(kb - 1);
+      if (!zin[0] && nlev[q] < kb - 1) why = std::string("variable ") + CS_INIT[q] + " has " + std::to_string(nlev[q]) + " levels, wanted >= " + std::to_string(kb - 1);
       else if (!F[1].v[q].rec) why = std::string("variable ") + CS_INIT[q] + " is not a record variable";
     }
     if (why.empty() && (F[1].numrecs < 1 || F[1].numrecs == 0xffffffffu)) why = "the file holds no complete record (numrecs " + std::to_string(F[1].numrecs) + ")";
@@ -1330,7 +1582,9 @@ extern "C" int pomgpu_cold_start(pomgpu_ctx *c, const char *grid, const char *in
   }
   // clim: record 10 (initialize.f:407), the forcing reader's layout check
   {
-    std::string why = ff_check(H[2], F[2], FF_CLIM, {{kb, jmg, img}, {kb, jmg, img}}, 10);
+    std::string why = zin[1] ? z_levels(H[2], F[2], "z", zlev[1]) : std::string();
+    const uint64_t kc = zin[1] && why.empty() ? (uint64_t)zlev[1].size() : kb;
+    if (why.empty()) why = ff_check(H[2], F[2], FF_CLIM, {{kc, jmg, img}, {kc, jmg, img}}, 10);
     if (why.empty() && F[2].v[0].rec && F[2].numrecs == 0xffffffffu) why = "the record count is unknown (a file still being written)";
     if (!why.empty()) return refuse(2, why);
   }
@@ -1382,7 +1636,7 @@ extern "C" int pomgpu_cold_start(pomgpu_ctx *c, const char *grid, const char *in
   for (int n = 0; n < POM_NBLK3D && !bad; n++) if (hipMemsetAsync(P.b3 + (size_t)n * P.a3, 0, sizeof(double) * P.n3, c->stream) != hipSuccess) bad = 2;
   if (!bad) LAUNCH(c, k_cold_defaults, grid2(P), blk2(), P);
   // the buffers of the restart reader's loop, for this call only; a run is whole levels of the tile's band of rows at the file's full width
-  const size_t band2 = (size_t)(P.jm + wj) * (size_t)img * 8, band3 = (size_t)P.jm * (size_t)img * 8;
+  const size_t band2 = (size_t)(P.jm + wj + wn) * (size_t)img * 8, band3 = (size_t)P.jm * (size_t)img * 8;
   size_t cap = SW(c, IO_CHUNK_KB) && SWV(c, IO_CHUNK_KB) > 0 ? (size_t)SWV(c, IO_CHUNK_KB) << 10 : (size_t)64 << 20;   // bytes per buffer
   if (cap > band3 * (size_t)P.kb) cap = band3 * (size_t)P.kb;
   if (cap < band2) cap = band2;
@@ -1390,6 +1644,19 @@ extern "C" int pomgpu_cold_start(pomgpu_ctx *c, const char *grid, const char *in
   unsigned char *pin[2] = {NULL, NULL}, *stage = NULL;
   double *win = NULL;                                            // dx, dy, fsm over the window
   if (!bad && hipMalloc((void **)&win, 3 * nwin * sizeof(double)) != hipSuccess) bad = 2;
+  // z-level input: the window of one variable as doubles, ztosig's two work arrays and the table of either file (cdf_out.hip's end)
+  const int wim = P.im + wi + we, wjm = P.jm + wj + wn;
+  const size_t ksz[2] = {zlev[0].size(), zlev[1].size()}, ksmax = ksz[0] > ksz[1] ? ksz[0] : ksz[1];
+  const size_t zwin = ksmax * (size_t)wim * (size_t)wjm, zwork = ksmax * P.n2;
+  double *zdev = NULL;
+  std::vector<double> ztab[2];
+  if (!bad && ksmax && hipMalloc((void **)&zdev, (zwin + 2 * zwork + 8 * ksmax) * sizeof(double)) != hipSuccess) bad = 2;
+  for (int q = 0; q < 2 && !bad; q++) {
+    if (!ksz[q]) continue;
+    ztab[q].resize(4 * ksz[q]);
+    ztosig_table(zlev[q].data(), (int)ksz[q], ztab[q].data());
+    if (hipMemcpyAsync(zdev + zwin + 2 * zwork + (size_t)q * 4 * ksmax, ztab[q].data(), ztab[q].size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) bad = 2;
+  }
 #ifdef POMGPU_EMU
   if (!bad && hipMalloc((void **)&pin[0], cap) != hipSuccess) bad = 2;
   stage = pin[0];
@@ -1450,10 +1717,11 @@ extern "C" int pomgpu_cold_start(pomgpu_ctx *c, const char *grid, const char *in
   for (int q = 0; q < 4 && !bad; q++) {                          // T, S (record 1, levels 1..kbm1), Tclim, Sclim (record 10, kb levels)
     const bool ini = q < 2;
     const FVar &f = ini ? F[1].v[q] : F[2].v[q - 2];
-    const int nlv = ini ? P.kbm1 : P.kb;
-    const size_t bytes = (size_t)P.jm * (size_t)img * f.esize();
+    const int onz = zin[ini ? 0 : 1];                            // all ks levels over the window, then ztosig; else the sigma levels over the tile
+    const int zq = ini ? 0 : 1, nlv = onz ? (int)ksz[zq] : (ini ? P.kbm1 : P.kb), rows = onz ? wjm : P.jm;
+    const size_t bytes = (size_t)rows * (size_t)img * f.esize();
     const uint64_t stride = jmg * img * f.esize();
-    const uint64_t base = f.begin + (ini ? 0 : 9 * f.stride) + (uint64_t)(m->j0 - 1) * img * f.esize();
+    const uint64_t base = f.begin + (ini ? 0 : 9 * f.stride) + (uint64_t)(m->j0 - 1 - (onz ? wj : 0)) * img * f.esize();
     int per = (int)(cap / bytes);
     if (per > nlv) per = nlv;
     for (int k0 = 0; k0 < nlv && !bad; k0 += per) {
@@ -1461,7 +1729,11 @@ extern "C" int pomgpu_cold_start(pomgpu_ctx *c, const char *grid, const char *in
       fetch(ini ? F[1].fd : F[2].fd, base + (uint64_t)k0 * stride, bytes, stride, nl);
       if (bad) break;
       const dim3 g((unsigned)((P.im + 63) / 64), (unsigned)((P.jm + 3) / 4), (unsigned)nl);
-      if (ini) {
+      if (onz) {
+        const dim3 gw((unsigned)((wim + 63) / 64), (unsigned)((wjm + 3) / 4), (unsigned)nl);
+        if (f.type == 5) LAUNCHN(c, "k_rst_unpack", k_rst_unpack<float>, gw, blk2(), zdev, (const void *)stage, wim, wjm, wjm, (int)img, c0, k0);
+        else LAUNCHN(c, "k_rst_unpack", k_rst_unpack<double>, gw, blk2(), zdev, (const void *)stage, wim, wjm, wjm, (int)img, c0, k0);
+      } else if (ini) {
         if (f.type == 5) LAUNCHN(c, "k_cold_ts", k_cold_ts<float>, g, blk2(), P, q, (const void *)stage, P.jm, (int)img, m->i0 - 1, k0);
         else LAUNCHN(c, "k_cold_ts", k_cold_ts<double>, g, blk2(), P, q, (const void *)stage, P.jm, (int)img, m->i0 - 1, k0);
       } else {
@@ -1470,6 +1742,11 @@ extern "C" int pomgpu_cold_start(pomgpu_ctx *c, const char *grid, const char *in
         else LAUNCHN(c, "k_cold_vol", k_cold_vol<double>, g, blk2(), dst, (const void *)stage, P.im, P.jm, P.iml, P.n2, P.jm, (int)img, m->i0 - 1);
       }
       flip();
+    }
+    if (onz && !bad) {
+      double *t = P.b3 + (size_t)(q == 0 ? P3_tb : (q == 1 ? P3_sb : (q == 2 ? P3_tclim : P3_sclim))) * P.a3;
+      launch_ztosig_window(c, t, 0, zdev, zdev + zwin + 2 * zwork + (size_t)zq * 4 * ksmax, zdev + zwin, zdev + zwin + zwork, nlv, wi, we, wj, wn);
+      if (ini) LAUNCH(c, k_cold_zts, grid3(P, P.kb), blk2(), P, q);
     }
   }
   c->cur = cur0;
@@ -1506,6 +1783,7 @@ extern "C" int pomgpu_cold_start(pomgpu_ctx *c, const char *grid, const char *in
   }
   if (hipStreamSynchronize(c->stream) != hipSuccess && !bad) bad = 2;
   if (win) (void)hipFree(win);
+  if (zdev) (void)hipFree(zdev);
   if (bad || c->launch_err) {
     if (bad == 2) (void)hipGetLastError();
     return fail(c, bad == 1 ? POMGPU_EINVAL : POMGPU_EHIP, bad == 1 ? "cold_start: I/O error on %s, %s or %s (the state is unspecified)" : "cold_start: a HIP call failed while reading %s, %s or %s (the state is unspecified)", grid, init, clim);

@@ -2267,6 +2267,24 @@ extern "C" int pomgpu_dens(pomgpu_ctx *c, const double *si, const double *ti, co
   launch_dens(c, a, b, d);
   return POMGPU_OK;
 }
+// ztosig(zs,tb,zz,h,t,...) (initialize.f:547-595): zs and the z-level source are the caller's own arrays and come from the host; h, zz
+// are the mirrors', the neighbours the context's; t is a COMMON array like every array argument
+extern "C" int pomgpu_ztosig(pomgpu_ctx *c, const double *zs, int ks, const double *src, const double *t) {
+  NEED(c);
+  if (!zs || !src) return fail(c, POMGPU_EINVAL, "ztosig: zs and src must be given");
+  if (ks < 2 || ks > 300) return fail(c, POMGPU_EINVAL, "ztosig: ks = %d is outside 2..300 (splinc's nmax)", ks);
+  for (int k = 0; k < ks; k++)
+    if (!__builtin_isfinite(zs[k]) || (k && !(zs[k] > zs[k - 1])))
+      return fail(c, POMGPU_EINVAL, "ztosig: zs(%d) = %g is not finite or not above zs(%d): the levels must increase strictly", k + 1, zs[k], k);
+  if (c->P.im < 3 || c->P.jm < 3) return fail(c, POMGPU_EINVAL, "ztosig: the tile has no interior column");
+  double *d = dev3(c, t);
+  if (!d) return fail(c, POMGPU_EINVAL, "ztosig: t must be a blk3d array of the bound host block");
+  const int rc = launch_ztosig(c, d, zs, ks, src);
+  if (rc) return fail(c, rc, "ztosig: %s", rc == POMGPU_ENOMEM ? "no device memory for the source and the work arrays" : "a HIP call failed");
+  xch(c, 1, d, c->P.kb);                                      // :586
+  launch_ztosig_edges(c, d);                                  // :589-592
+  return POMGPU_OK;
+}
 extern "C" int pomgpu_profq(pomgpu_ctx *c) { NEED(c); seq_profq(c); return POMGPU_OK; }
 extern "C" int pomgpu_proft(pomgpu_ctx *c, const double *f, const double *wfsurf, const double *fsurf, int nbc) {
   NEED(c);

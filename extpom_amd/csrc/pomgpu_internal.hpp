@@ -751,6 +751,7 @@ struct pomgpu_ctx {
   unsigned ext_bar_base;     // the counter's value when the next k_ext_loop starts (every workgroup arrives once per barrier)
   int ext_loop_off;          // a k_ext_loop launch of this context gave up at its barrier: the substeps run as launches of their own from then on
   void *io_job;              // the output / restart file being written behind the model's back (cdf_out.hip), NULL = none
+  int z_init, z_clim;        // pomgpu_set_z_inputs: the init / clim file holds z levels and goes through ztosig (cdf_out.hip)
   void *frc_files;           // pomgpu_set_forcing_files: the open forcing files and their read buffers (cdf_out.hip), NULL = none
   int launch_err;            // first hipError_t a kernel launch returned (0 = none); reported by the next sync / get_con
   char err[512];
@@ -942,6 +943,11 @@ int pomgpu_ff_fetch_surface(pomgpu_ctx *c, int kind, int n);                    
 int pomgpu_ff_fetch_lateral(pomgpu_ctx *c, int n);                              // record n into lat_dev[n % 4], lat_n set
 int pomgpu_ff_fetch_restore(pomgpu_ctx *c, int n);                              // month mod(n+9,12)+1 into rec_t[0], rec_s[0]
 void pomgpu_ff_free(pomgpu_ctx *c);
+// cdf_out.hip: ztosig (initialize.f:547-595).  launch_ztosig: the interior columns of `t` from the host's zs (ks values) and z-level source
+// (im_local, jm_local, ks), every other cell of (1:im, 1:jm) zero; synchronous, 0 or a pomgpu_status.  launch_ztosig_edges: the copies onto
+// physical edges, after the exchange
+int launch_ztosig(pomgpu_ctx *c, double *t, const double *zs, int ks, const double *src);
+void launch_ztosig_edges(pomgpu_ctx *c, double *t);
 // k_reduce.hip
 void launch_check_velocity(pomgpu_ctx *c);
 void launch_domain_stats(pomgpu_ctx *c, double *out_dev);

@@ -69,7 +69,9 @@ subroutine pomgpu_open_forcing_files(have_sfrc, have_lbry, have_clim)
   m%title = c_null_ptr; m%time_start = c_null_ptr; m%stats = c_null_ptr; m%create = 0
   m%im_global = im_global; m%jm_global = jm_global
   m%i0 = i_global(1); m%j0 = j_global(1)
-  rc = pomgpu_set_forcing_files(pom_ctx, p(1), p(2), p(3), m)
+  rc = 0
+  if (have(3)) rc = pomgpu_set_z_inputs(pom_ctx, merge(1_c_int, 0_c_int, pom_init_on_z), merge(1_c_int, 0_c_int, pom_clim_on_z))   ! a z-level clim file: the months go through ztosig
+  if (rc == 0) rc = pomgpu_set_forcing_files(pom_ctx, p(1), p(2), p(3), m)
   if (rc /= 0) then                                ! handle_error_pnetcdf, io_pnetcdf.F:43-54: a message and error_status = 1
     error_status = 1
     have_sfrc = .false.; have_lbry = .false.; have_clim = .false.

@@ -121,7 +121,9 @@ end subroutine
 ! initial_conditions, update_initial, bottom_friction -- on the device, from <wrk_pth>in/<netcdf_file>.grid.nc, .init.nc and .clim.nc
 ! (the names of io_pnetcdf.F:2102, :2790, :2865).  Call it after read_input and pomgpu_upload_state (blkcon holds the run's constants;
 ! the arrays may hold anything).  Every rank reads its own patch and one more column / row towards a west / south neighbour, so no
-! exchange is needed; afterwards the device state AND the COMMON blocks hold what the reference would have.  pom_cflmin is this rank's
+! exchange is needed; afterwards the device state AND the COMMON blocks hold what the reference would have.  pom_init_on_z / pom_clim_on_z
+! (pomgpu_iface): T, S / Tclim, Sclim are on the z levels of `Level` / `z` and are mapped with ztosig, as the reference's commented calls
+! (initialize.f:410-422) would; a tile then reads one more line towards EVERY neighbour.  pom_cflmin is this rank's
 ! cflmin: check_cflmin_mpi (parallel_mpi.f:501-512) reduces it with mpi_min and prints the warning; one rank prints it here.
 subroutine cold_start_files
   use pomgpu_iface
@@ -148,7 +150,8 @@ subroutine cold_start_files
   m%title = c_null_ptr; m%time_start = c_null_ptr; m%stats = c_null_ptr; m%create = 0
   m%im_global = im_global; m%jm_global = jm_global
   m%i0 = i_global(1); m%j0 = j_global(1)
-  rc = pomgpu_cold_start(pom_ctx, c_loc(cgrid), c_loc(cinit), c_loc(cclim), m, c_loc(info))
+  rc = pomgpu_set_z_inputs(pom_ctx, merge(1_c_int, 0_c_int, pom_init_on_z), merge(1_c_int, 0_c_int, pom_clim_on_z))   ! initialize.f:410-422
+  if (rc == 0) rc = pomgpu_cold_start(pom_ctx, c_loc(cgrid), c_loc(cinit), c_loc(cclim), m, c_loc(info))
   if (rc /= 0) then                                ! handle_error_pnetcdf, io_pnetcdf.F:43-54: a message and error_status = 1
     error_status = 1
     pm = pomgpu_last_error(pom_ctx)                ! names the file and the cause

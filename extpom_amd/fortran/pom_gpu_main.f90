@@ -15,6 +15,7 @@
 !
 ! usage: pom_gpu_main <state.in> <state.out>     (pom.nml in the working directory)
 !        pom_gpu_main --cold <state.out> <nsteps>
+!        pom_gpu_main --cold-z <state.out> <nsteps>     (T, S and Tclim, Sclim on z levels: mapped with ztosig)
 program pom_gpu_main
   use pomgpu_iface
   implicit none
@@ -33,7 +34,10 @@ program pom_gpu_main
   n3 = n2*kb
   nbd = 8*jm_local + 8*im_local + (12+12+6+6)*0   ! filled below
   nbd = 20*jm_local + 20*im_local + 18*jm_local*kb + 18*im_local*kb   ! bdry: 20 J, 20 I... see pom_layout.h
-  cold = trim(fin) == '--cold'
+  cold = trim(fin) == '--cold' .or. trim(fin) == '--cold-z'
+  if (trim(fin) == '--cold-z') then          ! the init and the clim file are on z levels (initialize.f:410-422)
+    pom_init_on_z = .true.; pom_clim_on_z = .true.
+  end if
   if (cold) then                             ! one tile, the whole grid; read_input's constants (initialize.f:80-168)
     call get_command_argument(3, arg3)
     read(arg3, *) nsteps

@@ -10,6 +10,8 @@ module pomgpu_iface
   type(c_ptr), save :: pom_ctx = c_null_ptr
   ! which forcing files the library reads itself (set by pomgpu_open_forcing_files' caller; pom_gpu_main's advance_hot looks at them)
   logical, save :: pom_frc_sfrc = .false., pom_frc_lbry = .false., pom_frc_clim = .false.
+  ! the init / clim file holds z levels (pomgpu_set_z_inputs): cold_start_files and pomgpu_open_forcing_files pass the two on
+  logical, save :: pom_init_on_z = .false., pom_clim_on_z = .false.
   type, bind(C) :: pomgpu_file_meta               ! include/pomgpu.h
     type(c_ptr) :: title, time_start
     integer(c_int) :: im_global, jm_global, i0, j0, create
@@ -104,6 +106,9 @@ module pomgpu_iface
     integer(c_int) function pomgpu_cold_start(ctx, grid, init, clim, meta, info) bind(C, name='pomgpu_cold_start')
       import; type(c_ptr), value :: ctx, grid, init, clim, info; type(pomgpu_file_meta) :: meta   ! info may be c_null_ptr
     end function
+    integer(c_int) function pomgpu_set_z_inputs(ctx, init_on_z, clim_on_z) bind(C, name='pomgpu_set_z_inputs')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: init_on_z, clim_on_z
+    end function
     integer(c_int) function pomgpu_domain_stats(ctx, out, sums_only) bind(C, name='pomgpu_domain_stats')
       import; type(c_ptr), value :: ctx; real(c_double) :: out(8); integer(c_int), value :: sums_only
     end function
@@ -121,6 +126,9 @@ module pomgpu_iface
     end function
     integer(c_int) function pomgpu_proft(ctx, f, wfsurf, fsurf, nbc) bind(C, name='pomgpu_proft')
       import; type(c_ptr), value :: ctx, f, wfsurf, fsurf; integer(c_int), value :: nbc
+    end function
+    integer(c_int) function pomgpu_ztosig(ctx, zs, ks, src, t) bind(C, name='pomgpu_ztosig')
+      import; type(c_ptr), value :: ctx, zs, src, t; integer(c_int), value :: ks   ! zs(ks), src(im_local,jm_local,ks): the caller's own arrays; t: a COMMON array
     end function
     integer(c_int) function pomgpu_bcond(ctx, idx) bind(C, name='pomgpu_bcond')
       import; type(c_ptr), value :: ctx; integer(c_int), value :: idx

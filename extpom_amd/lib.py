@@ -107,6 +107,8 @@ _SIGS = {
     "pomgpu_advt2": (_I, [_P, _P, _P, _P, _P]),
     "pomgpu_dens": (_I, [_P, _P, _P, _P]),
     "pomgpu_proft": (_I, [_P, _P, _P, _P, _I]),
+    "pomgpu_ztosig": (_I, [_P, _P, _I, _P, _P]),
+    "pomgpu_set_z_inputs": (_I, [_P, _I, _I]),
     "pomgpu_bcond": (_I, [_P, _I]),
     "pomgpu_bcondorl": (_I, [_P, _I]),
     "pomgpu_prof_begin": (_I, [_P]),

@@ -246,6 +246,11 @@ class PomGpu:
         self.get_con()
         return {"cflmin": info.cflmin, "period": info.period}
 
+    def set_z_inputs(self, init: bool = False, clim: bool = False):
+        """pomgpu_set_z_inputs: cold_start takes T, S of the init file (levels in `Level`) and / or Tclim, Sclim of the clim file (levels in
+        `z`) as z-level data and maps them onto the sigma levels with ztosig (initialize.f:410-422)"""
+        self._chk(self.L.pomgpu_set_z_inputs(self.h, 1 if init else 0, 1 if clim else 0), "set_z_inputs")
+
     def set_forcing_files(self, sfrc=None, lbry=None, clim=None, im_global=None, jm_global=None):
         """pomgpu_set_forcing_files: from now on wind / heat / surface (sfrc), lateral_bc (lbry) and restore_interior (clim) take the
         records their schedule asks for from these classic NetCDF files, on the device; None leaves a source as it is.  This tile's
@@ -275,6 +280,15 @@ class PomGpu:
         fn = getattr(self.L, "pomgpu_" + name)
         args = [self._a(a) if isinstance(a, str) else a for a in fields_or_ints]
         self._chk(fn(self.h, *args), name)
+
+    def ztosig(self, zs, src, t: str):
+        """pomgpu_ztosig (initialize.f:547-595): the z-level array src (ks, jm_local, im_local) on the levels zs (metres, positive down)
+        splined onto the sigma levels of the COMMON array named t, with the h and zz of the mirrors; nothing is downloaded"""
+        zs = np.ascontiguousarray(zs, dtype=np.float64)
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        if zs.ndim != 1 or src.shape != (zs.size, self.st.jm_local, self.st.im_local):
+            raise ValueError(f"ztosig: src {src.shape} is not (ks, jm_local, im_local) = {(zs.size, self.st.jm_local, self.st.im_local)}")
+        self._chk(self.L.pomgpu_ztosig(self.h, self._p(zs), int(zs.size), self._p(src), self._a(t)), "ztosig")
 
     def advance(self):
         self.call("advance")

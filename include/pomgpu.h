@@ -323,6 +323,24 @@ typedef struct pomgpu_cold_info {
 } pomgpu_cold_info;
 int pomgpu_cold_start(pomgpu_ctx *ctx, const char *grid, const char *init, const char *clim, const pomgpu_file_meta *meta,
                       pomgpu_cold_info *info);
+/* Z-level input (a context setting; default 0 / 0: the files hold sigma levels, everything above as it stands).  init_on_z: pomgpu_cold_start
+ * takes the init file as z-level data -- what the reference's commented call sites (initialize.f:410-422, io_pnetcdf.F:2805-2817) are for:
+ * `Level` must be a 1-D NC_FLOAT / NC_DOUBLE variable of ks values, 2 <= ks <= 300, finite and strictly increasing (metres, positive down),
+ * T and S (record, ks, jm_global, im_global); record 1, ALL ks levels, is read over the tile's window and tb, sb are the ztosig of it
+ * (pomgpu_ztosig below), all kb levels -- level kb is the spline's extrapolation, not +0.0 -- and t, s, tsurf, ssurf and the eight boundary
+ * lines follow from tb, sb as initialize.f:437-460 and update_initial have them.  clim_on_z: the same for Tclim, Sclim as (record, ks,
+ * jm_global, im_global) with the levels in the clim file's variable `z` (io_pnetcdf.F:2858); record 10 is read; the two files may have
+ * different levels.  Still no message round: ztosig's fill-in looks at all four neighbours of a column, so a tile reads one more column /
+ * row towards EVERY neighbour, forms its ghost lines with the owner's arithmetic where the reference exchanges t (initialize.f:586), and
+ * makes the copies onto physical edges only where it has no neighbour.  Every cell of a tile is the single tile's result on that window.
+ * More refusals of pomgpu_cold_start, before anything changes: the level variable absent, not 1-D, of another type, outside 2..300 values,
+ * not finite and strictly increasing; T / S / Tclim / Sclim with another level count than it; a tile whose window does not fit the grid.
+ * pomgpu_set_forcing_files under clim_on_z: the clim check wants `z` and (ks, jm_global, im_global) with at least 12 records; restore_interior's
+ * monthly fetch reads the window's ks levels and maps them into the (im,jm,kb) record in place of the plain unpack, on the stream the step is
+ * enqueued on, with buffers allocated at registration (a step still allocates nothing); t_w s_w t_n s_n come from the tclim, sclim mirrors as
+ * ever.  This call refuses (POMGPU_EINVAL) to change clim_on_z once a clim file is registered.  Z-level .lbry.nc files
+ * (bounds_forcing.f:636-716) are NOT read: lateral files hold sigma levels. */
+int pomgpu_set_z_inputs(pomgpu_ctx *ctx, int init_on_z, int clim_on_z);
 
 /* The forcing files without PnetCDF: read_wind_pnetcdf, read_heat_pnetcdf, read_surface_pnetcdf (io_pnetcdf.F:2912-3224),
  * read_boundary_conditions_pnetcdf (:3393-3621), read_restore_ts_interior_pnetcdf (:3275-3333).  The host names the files once --
@@ -401,6 +419,19 @@ int pomgpu_advv(pomgpu_ctx *ctx);                /* solver.f:791-845 */
 int pomgpu_baropg(pomgpu_ctx *ctx);              /* solver.f:848-940 */
 int pomgpu_baropg_mcc(pomgpu_ctx *ctx);          /* solver.f:943-1159 (npg = 2) */
 int pomgpu_dens(pomgpu_ctx *ctx, const double *si, const double *ti, const double *rhoo); /* :1162-1209 */
+/* ztosig(zs,tb,zz,h,t,...) (initialize.f:547-595) with splinc / splint (:598-667): the vertical natural-cubic-spline mapping of z-level
+ * temperature or salinity onto the sigma levels -- the routine behind the reference's commented call sites initialize.f:410-422.
+ * zs: ks HOST doubles, the z levels in metres, positive down; src: the HOST array (im_local, jm_local, ks) in the reference's layout, the
+ * tile's own ghost cells included (the reference's `tb` argument, a caller's temporary: it is uploaded for the call); t: the HOST address
+ * of a 3-D COMMON array, mapped to its mirror like every array argument.  h and zz are the mirrors', the four neighbours the context's.
+ * On X(1:im, 1:jm): t = 0, then every column 2 <= i <= im-1, 2 <= j <= jm-1 with h > 1.0 fills its missing values (< 0.01) from the four
+ * RAW neighbours where zs(k) <= h -- amax1 is the REAL(4) intrinsic: the maximum arrives rounded to single precision -- and from the
+ * level above, and is splined onto -zz(k)*h for ALL kb levels (level kb is an extrapolation); the ghost lines of t go through the
+ * exchange hook / transport (nothing on one tile), then the copies onto physical edges, west east south north.  Bit for bit what the
+ * reference's compiled routine leaves; the fp32-storage variants compute in fp64 and round once at the store.
+ * Refused with POMGPU_EINVAL, error_status = 1 and the cause in pomgpu_last_error before t changes: ks outside 2..300 (splinc's nmax), zs
+ * not finite or not strictly increasing, t not a blk3d array of the bound host block.  Synchronous. */
+int pomgpu_ztosig(pomgpu_ctx *ctx, const double *zs, int ks, const double *src, const double *t);
 int pomgpu_profq(pomgpu_ctx *ctx);               /* solver.f:1212-1538 */
 int pomgpu_proft(pomgpu_ctx *ctx, const double *f, const double *wfsurf, const double *fsurf, int nbc); /* :1541-1683 */
 int pomgpu_profu(pomgpu_ctx *ctx);               /* solver.f:1686-1780 */

@@ -1,0 +1,25 @@
+"""Launched by tests/test_gpu_ztosig.py: the tile checks of tests/ztosig_checks.py and tests/ztosig_files_checks.py on the device, in a process of its own like
+tests/gpu_cold_start_tiles.py -- 2x2 tiles as four contexts on GPU 0, one host thread and one stream each, the asynchronous event-ordered
+mover between them, which needs torch (imported FIRST, so that the library and torch share one HIP runtime).
+
+    python tests/gpu_ztosig_tiles.py
+"""
+import os
+import pathlib
+import sys
+import tempfile
+
+import torch  # noqa: F401  (before the library is loaded)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ztosig_checks as chk
+import ztosig_files_checks as fchk
+
+if __name__ == "__main__":
+    chk.tiles(None)
+    print("ZTOSIG-TILES-OK")
+    with tempfile.TemporaryDirectory(prefix="ztosig_tiles_") as d:
+        fchk.tiles(None, pathlib.Path(d))
+    print("ZTOSIG-FILE-TILES-OK")
