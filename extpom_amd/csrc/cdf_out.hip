@@ -660,6 +660,10 @@ struct FFiles {
   int zks = 0, wi = 0, we = 0, wj = 0, wn = 0;
   double *zdev = NULL;
   size_t zwin = 0, zwork = 0;
+  // an lbry file on z levels (pomgpu_set_z_lateral): its level count, the window points of the east lines (lwj, lwn: towards the south, north
+  // neighbour) and of the south lines (lwi, lwe), and one allocation: ztosig's table, then the two work arrays of the record's four lines
+  int lks = 0, lwi = 0, lwe = 0, lwj = 0, lwn = 0;
+  double *ldev = NULL;
 };
 const char *const FF_WHAT[3] = {"sfrc", "lbry", "clim"};
 const char *const FF_SFRC[6] = {"sustr", "svstr", "shflux", "swrad", "SST", "SSS"};
@@ -734,7 +738,8 @@ __global__ void k_frc_unpack(KP P, int kind, double *da, double *db, const void 
 // (the tile's jm or im values per level): src[0] zeta.east, [1] zeta.south, [2..5] u v temp salt .east, [6..9] u v temp salt .south;
 // f32 bit q: that variable is NC_FLOAT.  t_w s_w / t_n s_n: line i = 1 / j = jm of tclim, sclim; u_w v_w u_n v_n: zero; everything
 // beyond jm / im: zero, but in the elevations, which the reader leaves as they are there -- as it leaves elw, eln everywhere.
-struct LatSrc { const void *p[10]; unsigned f32; };
+// zts (an lbry file on z levels): temp / salt .east / .south hold other levels and are left to k_ztosig_line, which fills those four arrays.
+struct LatSrc { const void *p[10]; unsigned f32; int zts; };
 __device__ __forceinline__ double lat_raw(const LatSrc &s, int q, size_t at) { return (s.f32 >> q) & 1u ? CdfRaw<float>::get(s.p[q], at) : CdfRaw<double>::get(s.p[q], at); }
 __global__ void k_lat_unpack(KP P, double *rec, LatSrc s) {
   const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -751,8 +756,10 @@ __global__ void k_lat_unpack(KP P, double *rec, LatSrc s) {
       rec[njk + o] = in ? (double)F3(sclim, 1, a, k) : 0.;
       rec[2 * njk + o] = 0.;
       rec[3 * njk + o] = 0.;
-      rec[4 * njk + o] = in ? lat_raw(s, 4, f) : 0.;
-      rec[5 * njk + o] = in ? lat_raw(s, 5, f) : 0.;
+      if (!s.zts) {
+        rec[4 * njk + o] = in ? lat_raw(s, 4, f) : 0.;
+        rec[5 * njk + o] = in ? lat_raw(s, 5, f) : 0.;
+      }
       rec[6 * njk + o] = in ? lat_raw(s, 2, f) : 0.;
       rec[7 * njk + o] = in ? lat_raw(s, 3, f) : 0.;
     }
@@ -768,8 +775,10 @@ __global__ void k_lat_unpack(KP P, double *rec, LatSrc s) {
       r[nik + o] = in ? (double)F3(sclim, a, P.jm, k) : 0.;
       r[2 * nik + o] = 0.;
       r[3 * nik + o] = 0.;
-      r[4 * nik + o] = in ? lat_raw(s, 8, f) : 0.;
-      r[5 * nik + o] = in ? lat_raw(s, 9, f) : 0.;
+      if (!s.zts) {
+        r[4 * nik + o] = in ? lat_raw(s, 8, f) : 0.;
+        r[5 * nik + o] = in ? lat_raw(s, 9, f) : 0.;
+      }
       r[6 * nik + o] = in ? lat_raw(s, 7, f) : 0.;
       r[7 * nik + o] = in ? lat_raw(s, 6, f) : 0.;
     }
@@ -791,6 +800,11 @@ static FFiles *FF(pomgpu_ctx *c) { return (FFiles *)c->frc_files; }
 static std::string z_levels(const RHeader &H, const FSource &S, const char *name, std::vector<double> &zs);
 static void ztosig_table(const double *zs, int ks, double *tab);
 static void launch_ztosig_window(pomgpu_ctx *c, double *out, int record, const double *zsrc, const double *tab, double *wa, double *wb, int ks, int wi, int we, int wj, int wn);
+// ztosig for the lines of an lbry file on z levels (defined with the kernel, further down)
+struct ZtlLine { double *out; const void *src; int fmt, edge, n, npad, lo, hi, sp, so, op; };
+struct ZtlJob { ZtlLine l[4]; };
+static ZtlLine ztosig_line_of(const KP &P, int edge, double *out, const void *src, int fmt, int sp, int so);
+static void launch_ztosig_lines(pomgpu_ctx *c, const ZtlJob &job, int nlines, const double *tab, double *wa, double *wb, int ks, int pitch);
 int pomgpu_ff_has(pomgpu_ctx *c, int src) { return c->frc_files && FF(c)->s[src].fd >= 0; }
 void pomgpu_ff_free(pomgpu_ctx *c) {
   FFiles *F = FF(c);
@@ -803,6 +817,7 @@ void pomgpu_ff_free(pomgpu_ctx *c) {
   if (F->pin[0]) (void)hipFree(F->pin[0]);
 #endif
   if (F->zdev) (void)hipFree(F->zdev);
+  if (F->ldev) (void)hipFree(F->ldev);
   delete F;
   c->frc_files = NULL;
 }
@@ -884,7 +899,14 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
   if (m->i0 - wi < 1 || m->j0 - wj < 1 || m->i0 + P.im - 1 + we > m->im_global || m->j0 + P.jm - 1 + wn > m->jm_global)
     return fail(c, POMGPU_EINVAL, "set_forcing_files: %s: the tile (%d..%d, %d..%d) with its window lines towards every neighbour does not fit the global grid %d x %d", clim,
                 m->i0, m->i0 + P.im - 1, m->j0, m->j0 + P.jm - 1, m->im_global, m->jm_global);
-  std::vector<double> zlev;
+  // an lbry file on z levels (pomgpu_set_z_lateral): the fill-in of a line point looks at the points before and after it, so the fetch reads one
+  // more point of temp / salt towards every neighbour of the tile: .east towards the south and north one, .south towards the west and east one
+  const int zl = lbry && c->z_lbry, lwi = zl && !P.W, lwe = zl && !P.E, lwj = zl && !P.S, lwn = zl && !P.N;
+  if (zl && (P.im < 4 || P.jm < 4)) return fail(c, POMGPU_EINVAL, "set_forcing_files: %s: a z-level lbry file needs a tile of at least 4 x 4 cells, this one has %d x %d", lbry, P.im, P.jm);
+  if (m->i0 - lwi < 1 || m->j0 - lwj < 1 || m->i0 + P.im - 1 + lwe > m->im_global || m->j0 + P.jm - 1 + lwn > m->jm_global)
+    return fail(c, POMGPU_EINVAL, "set_forcing_files: %s: the tile (%d..%d, %d..%d) with its window points towards every neighbour does not fit the global grid %d x %d", lbry,
+                m->i0, m->i0 + P.im - 1, m->j0, m->j0 + P.jm - 1, m->im_global, m->jm_global);
+  std::vector<double> zlev, llev;
   FFiles *old = FF(c);
   if (old && (old->im_global != m->im_global || old->jm_global != m->jm_global || old->i0 != m->i0 || old->j0 != m->j0))
     return fail(c, POMGPU_EINVAL, "set_forcing_files: files are registered under another global grid or tile origin");
@@ -906,7 +928,11 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
     if (ff_header(S.fd, S.fsize, H, what) < 0) { drop(); return fail(c, POMGPU_EINVAL, "set_forcing_files: %s is not a %s file this library reads: %s", paths[q], FF_WHAT[q], what.c_str()); }
     std::string why;
     if (q == 0) why = ff_check(H, S, FF_SFRC, std::vector<std::vector<uint64_t>>(6, {jmg, img}), 1);
-    else if (q == 1) why = ff_check(H, S, FF_LBRY, {{jmg}, {img}, {kb, jmg}, {kb, jmg}, {kb, jmg}, {kb, jmg}, {kb, img}, {kb, img}, {kb, img}, {kb, img}}, 1);
+    else if (q == 1) {
+      if (zl) why = z_levels(H, S, "z", llev);
+      const uint64_t kl = zl && why.empty() ? (uint64_t)llev.size() : kb;   // temp, salt on the levels of z; u, v stay on the sigma levels
+      if (why.empty()) why = ff_check(H, S, FF_LBRY, {{jmg}, {img}, {kb, jmg}, {kb, jmg}, {kl, jmg}, {kl, jmg}, {kb, img}, {kb, img}, {kl, img}, {kl, img}}, 1);
+    }
     else {
       if (zc) why = z_levels(H, S, "z", zlev);
       const uint64_t kc = zc && why.empty() ? (uint64_t)zlev.size() : kb;
@@ -924,6 +950,9 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
   size_t need = 2 * band2;                                        // sfrc: two variables' bands
   const size_t lat = 8 * ((size_t)P.jm + P.im) + 4 * 8 * (size_t)P.kb * ((size_t)P.jm + P.im);
   if (need < lat) need = lat;
+  const size_t lks = llev.size();                                 // a z-level lbry record: two of the four arrays of either edge on lks levels over the window
+  const size_t latz = 8 * ((size_t)P.jm + P.im) + 2 * 8 * (size_t)P.kb * ((size_t)P.jm + P.im) + 2 * 8 * lks * ((size_t)P.jm + P.im + 4);
+  if (lks && need < latz) need = latz;
   if (need < run) need = run;
   int bad = 0;
   if (F->cap < need) {
@@ -962,6 +991,28 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
       bad = 1;
       if (znew) (void)hipFree(znew);
       znew = NULL;
+    }
+  }
+  const size_t lpitch = (size_t)(P.jml > P.iml ? P.jml : P.iml);
+  double *lnew = NULL;
+  if (!bad && lks) {
+    std::vector<double> tab(4 * lks);
+    ztosig_table(llev.data(), (int)lks, tab.data());
+    if (hipMalloc((void **)&lnew, (4 * lks + 8 * lks * lpitch) * sizeof(double)) != hipSuccess ||
+        hipMemcpyAsync(lnew, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {           // (and an earlier fetch has stopped mapping out of the old buffers)
+      bad = 1;
+      if (lnew) (void)hipFree(lnew);
+      if (znew) (void)hipFree(znew);
+      lnew = znew = NULL;
+    }
+  }
+  if (!bad && paths[1]) {
+    if (F->ldev && !lks && hipStreamSynchronize(c->stream) != hipSuccess) { bad = 1; if (znew) (void)hipFree(znew); znew = NULL; }
+    else {
+      if (F->ldev) (void)hipFree(F->ldev);
+      F->ldev = lnew;
+      F->lks = (int)lks; F->lwi = lwi; F->lwe = lwe; F->lwj = lwj; F->lwn = lwn;
     }
   }
   if (!bad && paths[2]) {
@@ -1075,23 +1126,42 @@ int pomgpu_ff_fetch_lateral(pomgpu_ctx *c, int n) {
   LatSrc src;
   src.f32 = 0;
   size_t at = 0, off[10];
+  // a z-level lbry file: temp, salt of either edge on all lks levels over the line and its window points, mapped by k_ztosig_line behind k_lat_unpack
+  const int onz = F->lks > 0;
+  int cnt[10], wlo[10];
   for (int q = 0; q < 10; q++) {
     const FVar &f = S.v[q];
     const bool east = q == 0 || (q >= 2 && q <= 5);              // along j: the tile's jm values from j0; else im values from i0
-    const int nlev = q < 2 ? 1 : P.kb;
-    const uint64_t glen = east ? (uint64_t)F->jm_global : (uint64_t)F->im_global, first = (uint64_t)((east ? F->j0 : F->i0) - 1);
-    const size_t len = (size_t)(east ? P.jm : P.im) * f.esize();
+    const bool zq = onz && (q == 4 || q == 5 || q == 8 || q == 9);
+    const int nlev = q < 2 ? 1 : (zq ? F->lks : P.kb);
+    wlo[q] = zq ? (east ? F->lwj : F->lwi) : 0;
+    cnt[q] = (east ? P.jm : P.im) + wlo[q] + (zq ? (east ? F->lwn : F->lwe) : 0);
+    const uint64_t glen = east ? (uint64_t)F->jm_global : (uint64_t)F->im_global, first = (uint64_t)((east ? F->j0 : F->i0) - 1 - wlo[q]);
+    const size_t len = (size_t)cnt[q] * f.esize();
     const uint64_t base = f.begin + (uint64_t)(n - 1) * f.stride + first * f.esize();
     off[q] = at;
-    if ((uint64_t)(east ? P.jm : P.im) == glen) { if (pread_all(S.fd, pin + at, len * nlev, base)) return ff_io_error(c, "lateral_bc", n, S, 0); }
+    if ((uint64_t)cnt[q] == glen) { if (pread_all(S.fd, pin + at, len * nlev, base)) return ff_io_error(c, "lateral_bc", n, S, 0); }
     else for (int k = 0; k < nlev; k++) if (pread_all(S.fd, pin + at + (size_t)k * len, len, base + (uint64_t)k * glen * f.esize())) return ff_io_error(c, "lateral_bc", n, S, 0);
     at += (len * nlev + 7) & ~(size_t)7;
     if (f.type == 5) src.f32 |= 1u << q;
   }
   if (ff_send(c, F, at)) return ff_io_error(c, "lateral_bc", n, S, 1);
   for (int q = 0; q < 10; q++) src.p[q] = F->stage + off[q];
+  src.zts = onz;
   const int nt = P.jml + P.iml;
   LAUNCH(c, k_lat_unpack, dim3((unsigned)((nt + 63) / 64), 1, 1), dim3(64, 1, 1), P, c->lat_dev[sl], src);
+  if (onz) {                                                     // tbe sbe / tbs sbs: the record's arrays 4, 5 of either edge
+    const size_t njk = (size_t)P.jml * P.kb, nik = (size_t)P.iml * P.kb;
+    const int pitch = P.jml > P.iml ? P.jml : P.iml;
+    static const int zq[4] = {4, 5, 8, 9};
+    ZtlJob job;
+    for (int l = 0; l < 4; l++) {
+      const int q = zq[l];
+      double *out = c->lat_dev[sl] + (l < 2 ? (size_t)(4 + l) * njk : 8 * njk + (size_t)(2 + l) * nik);
+      job.l[l] = ztosig_line_of(P, l < 2 ? 0 : 1, out, src.p[q], S.v[q].type == 5 ? 1 : 2, cnt[q], wlo[q]);
+    }
+    launch_ztosig_lines(c, job, 4, F->ldev, F->ldev + 4 * (size_t)F->lks, F->ldev + 4 * (size_t)F->lks + 4 * (size_t)F->lks * pitch, F->lks, pitch);
+  }
   c->lat_n[sl] = n;
   return POMGPU_OK;
 }
@@ -1269,6 +1339,121 @@ static void launch_ztosig_window(pomgpu_ctx *c, double *out, int record, const d
     g.op = P.im; g.ol = (size_t)P.im * P.jm;
     LAUNCHN(c, "k_ztosig", k_ztosig<double>, grid2(P), blk2(), P, out, zsrc, tab, wa, wb, ks, g);
   } else LAUNCHN(c, "k_ztosig", k_ztosig<pomgpu_st>, grid2(P), blk2(), P, (pomgpu_st *)out, zsrc, tab, wa, wb, ks, g);
+}
+
+// ---- ztosig for the lines of a lateral record (bounds_forcing.f:636-716: the commented blocks behind read_boundary_conditions_pnetcdf) ----
+// The block spreads a line, temp.east say, across the tile -- ts1(i,j,k) = t_e(j,k), hs(i,j) = h(imm1,j) --, calls ztosig and keeps the
+// column im/2 (south: the row jm/2).  The source does not vary across the line, so every sampled column is the same ztosig column per line
+// point `a`: depth hl(a) (east h(imm1,a), south h(a,2), west h(2,a), north h(a,jmm1)); of the four neighbours of the fill-in two are the
+// point's own raw value and two the raw values of the points a-1 and a+1, in the order of amax1's arguments (:567-568).
+//   k_ztosig_line: one line point per lane, threadIdx.x along the line, blockIdx.y the line of the job, the level loops in the thread and
+//   k_ztosig's march (fill-in one level ahead of the decomposition, ztosig_table, splint's bisection as written).  tin and u / y2 live in
+//   two work arrays laid out (point, level), the point contiguous, one slice per line; a lane reads back only what it stored itself.
+//   The raw source (fmt 0: doubles; 1 / 2: the file's big-endian NC_FLOAT / NC_DOUBLE) holds `sp` values per level, point 1 at `so`.  A
+//   lane reads the raw values of as-1, as, as+1 alone, as = its point moved into lo..hi: lo = 2 / hi = n-1 at a physical end, whose point
+//   so redoes the column of the point next to it (the copies of :589-592, zeros included), and 1 / n towards a neighbour tile, whose ghost
+//   point is formed from the window point beyond it with the owner's arithmetic and the owner's depth, which h's ghost cell holds -- what
+//   the exchange of :586 would bring.  Every load is unconditional (the three addresses are inside the source for every lane that is
+//   not beyond the line); points beyond n, up to the record's npad, and those with hl <= 1.0 get +0.0 on all kb levels.
+static ZtlLine ztosig_line_of(const KP &P, int edge, double *out, const void *src, int fmt, int sp, int so) {
+  const bool alongj = edge == 0 || edge == 2;
+  const int n = alongj ? P.jm : P.im, npad = alongj ? P.jml : P.iml;
+  const int plo = alongj ? P.S : P.W, phi = alongj ? P.N : P.E;
+  return ZtlLine{out, src, fmt, edge, n, npad, plo ? 2 : 1, phi ? n - 1 : n, sp, so, npad};
+}
+__device__ __forceinline__ double ztl_raw(const void *p, int fmt, size_t q) {
+  if (fmt == 1) return CdfRaw<float>::get(p, q);                   // fmt is the line's: uniform across the workgroup
+  if (fmt == 2) return CdfRaw<double>::get(p, q);
+  return ((const double *)p)[q];
+}
+__global__ void k_ztosig_line(KP P, ZtlJob job, const double *tab, double *wa, double *wb, int ks, int pitch) {
+  const ZtlLine &L = job.l[blockIdx.y];
+  const int a = TID_I;
+  if (a > L.npad) return;
+  const int as = a < L.lo ? L.lo : (a > L.hi ? L.hi : a);
+  const bool alongj = L.edge == 0 || L.edge == 2;
+  const int hi = L.edge == 0 ? P.imm1 : (L.edge == 2 ? 2 : as), hj = L.edge == 1 ? 2 : (L.edge == 3 ? P.jmm1 : as);
+  const double hc = F2(h, hi, hj);
+  double *const oc = L.out + (size_t)(a - 1);
+  if (a > L.n || !(hc > (double)1.f)) {
+    for (int k = 0; k < P.kb; k++) oc[(size_t)k * L.op] = 0.;
+    return;
+  }
+  const double *xs = tab, *sg = tab + ks, *pp = tab + 2 * (size_t)ks, *d2 = tab + 3 * (size_t)ks;
+  const size_t lv = (size_t)pitch, o = (size_t)blockIdx.y * (size_t)ks * lv + (size_t)(a - 1);
+  const size_t sc = (size_t)L.so + (size_t)(as - 1);
+  const double miss = (double)0.01f;
+  auto raw = [&](int k) {                                       // tin(k) before the copy from above; k is 0-based
+    const size_t q = (size_t)k * (size_t)L.sp + sc;
+    const double v = ztl_raw(L.src, L.fmt, q), vl = ztl_raw(L.src, L.fmt, q - 1), vh = ztl_raw(L.src, L.fmt, q + 1);
+    // amax1(tb(i-1,j,k), tb(i+1,j,k), tb(i,j-1,k), tb(i,j+1,k)): along j the first two are the point's own value, along i the last two
+    const double n0 = alongj ? v : vl, n1 = alongj ? v : vh, n2 = alongj ? vl : v, n3 = alongj ? vh : v;
+    double m = n0;
+    m = n1 > m ? n1 : m;
+    m = n2 > m ? n2 : m;
+    m = n3 > m ? n3 : m;
+    return (xs[k] <= hc && v < miss) ? (double)(float)m : v;
+  };
+  double y0 = raw(0), y1 = raw(1), up = 0.;
+  if (y1 < miss) y1 = y0;
+  wa[o] = y0;
+  wb[o] = 0.;
+  for (int n = 1; n < ks - 1; n++) {
+    double yn = raw(n + 1);
+    if (yn < miss) yn = y1;
+    const double u = ((double)6.f * ((yn - y1) / (xs[n + 1] - xs[n]) - (y1 - y0) / (xs[n] - xs[n - 1])) / (xs[n + 1] - xs[n - 1]) - sg[n] * up) / pp[n];
+    wa[(size_t)n * lv + o] = y1;
+    wb[(size_t)n * lv + o] = u;
+    up = u; y0 = y1; y1 = yn;
+  }
+  wa[(size_t)(ks - 1) * lv + o] = y1;
+  const double qn = (double)0.f, un = 0.;
+  double y2 = (un - qn * up) / (qn * d2[ks - 2] + (double)1.f);
+  wb[(size_t)(ks - 1) * lv + o] = y2;
+  for (int k = ks - 2; k >= 0; k--) {
+    y2 = d2[k] * y2 + wb[(size_t)k * lv + o];
+    wb[(size_t)k * lv + o] = y2;
+  }
+  for (int k = 1; k <= P.kb; k++) {
+    const double x = -F1(zz, k) * hc;
+    int klo = 1, khi = ks;
+    while (khi - klo > 1) {
+      const int kk = (khi + klo) / 2;
+      if (xs[kk - 1] > x) khi = kk; else klo = kk;
+    }
+    const double xl = xs[klo - 1], xh = xs[khi - 1], hh = xh - xl;
+    const double a_ = (xh - x) / hh, b = (x - xl) / hh;
+    const size_t ql = (size_t)(klo - 1) * lv + o, qh = (size_t)(khi - 1) * lv + o;
+    oc[(size_t)(k - 1) * L.op] = a_ * wa[ql] + b * wa[qh] + ((a_ * a_ * a_ - a_) * wb[ql] + (b * b * b - b) * wb[qh]) * (hh * hh) / (double)6.f;
+  }
+}
+// the lines of `job` (nlines of them; wa, wb: nlines slices of ks * pitch values each), enqueued on c->cur
+static void launch_ztosig_lines(pomgpu_ctx *c, const ZtlJob &job, int nlines, const double *tab, double *wa, double *wb, int ks, int pitch) {
+  LAUNCH(c, k_ztosig_line, dim3((unsigned)((pitch + 63) / 64), (unsigned)nlines, 1), dim3(64, 1, 1), c->P, job, tab, wa, wb, ks, pitch);
+}
+// One line on its own (pomgpu_ztosig_line): zs: ks host doubles (vetted); src: host, ks levels of npad + 2 values, point a at a (0-based),
+// so that the window points sit at 0 and n + 1; out: host, kb levels of npad values.  Launched as the fetch launches it; synchronous
+int launch_ztosig_line(pomgpu_ctx *c, int edge, const double *zs, int ks, const double *src, double *out) {
+  const KP &P = c->P;
+  const int npad = (edge == 0 || edge == 2) ? P.jml : P.iml;
+  const size_t nsrc = (size_t)ks * (npad + 2), nwork = (size_t)ks * npad, nout = (size_t)P.kb * npad;
+  std::vector<double> tab(4 * (size_t)ks);
+  ztosig_table(zs, ks, tab.data());
+  double *dev = NULL;                                            // source, table, tin, u / y2, result
+  if (hipMalloc((void **)&dev, (nsrc + tab.size() + 2 * nwork + nout) * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return POMGPU_ENOMEM; }
+  double *dtab = dev + nsrc, *wa = dtab + tab.size(), *wb = wa + nwork, *dout = wb + nwork;
+  int rc = POMGPU_OK;
+  if (hipMemcpyAsync(dev, src, nsrc * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = POMGPU_EHIP;
+  if (!rc) {
+    ZtlJob job;
+    for (int l = 0; l < 4; l++) job.l[l] = ztosig_line_of(P, edge, dout, dev, 0, npad + 2, 1);
+    launch_ztosig_lines(c, job, 1, dtab, wa, wb, ks, npad);
+    if (hipMemcpyAsync(out, dout, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = POMGPU_EHIP;
+  }
+  if (hipStreamSynchronize(c->stream) != hipSuccess) rc = POMGPU_EHIP;
+  (void)hipFree(dev);
+  return rc;
 }
 
 // ---- a cold start from the reference's input files (pomgpu_cold_start) ---------------------------------------------------------------
@@ -1515,6 +1700,14 @@ extern "C" int pomgpu_set_z_inputs(pomgpu_ctx *c, int init_on_z, int clim_on_z) 
     return fail(c, POMGPU_EINVAL, "set_z_inputs: a clim file is registered (pomgpu_set_forcing_files) as a %s file", c->z_clim ? "z-level" : "sigma-level");
   c->z_init = init_on_z != 0;
   c->z_clim = clim_on_z != 0;
+  return POMGPU_OK;
+}
+
+extern "C" int pomgpu_set_z_lateral(pomgpu_ctx *c, int lbry_on_z) {
+  if (!c) return POMGPU_EINVAL;
+  if (pomgpu_ff_has(c, 1) && (lbry_on_z != 0) != (c->z_lbry != 0))
+    return fail(c, POMGPU_EINVAL, "set_z_lateral: an lbry file is registered (pomgpu_set_forcing_files) as a %s file", c->z_lbry ? "z-level" : "sigma-level");
+  c->z_lbry = lbry_on_z != 0;
   return POMGPU_OK;
 }
 

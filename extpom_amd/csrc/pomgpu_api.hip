@@ -2285,6 +2285,21 @@ extern "C" int pomgpu_ztosig(pomgpu_ctx *c, const double *zs, int ks, const doub
   launch_ztosig_edges(c, d);                                  // :589-592
   return POMGPU_OK;
 }
+// the line form of ztosig (bounds_forcing.f:636-716): one lateral line of T or S on the z levels zs onto the sigma levels, with the depth the
+// reference's block names for that edge; zs, src and out are the caller's own host arrays, no mirror changes
+extern "C" int pomgpu_ztosig_line(pomgpu_ctx *c, int edge, const double *zs, int ks, const double *src, double *out) {
+  NEED(c);
+  if (edge < 0 || edge > 3) return fail(c, POMGPU_EINVAL, "ztosig_line: edge = %d is none of 0 east, 1 south, 2 west, 3 north", edge);
+  if (!zs || !src || !out) return fail(c, POMGPU_EINVAL, "ztosig_line: zs, src and out must be given");
+  if (ks < 2 || ks > 300) return fail(c, POMGPU_EINVAL, "ztosig_line: ks = %d is outside 2..300 (splinc's nmax)", ks);
+  for (int k = 0; k < ks; k++)
+    if (!__builtin_isfinite(zs[k]) || (k && !(zs[k] > zs[k - 1])))
+      return fail(c, POMGPU_EINVAL, "ztosig_line: zs(%d) = %g is not finite or not above zs(%d): the levels must increase strictly", k + 1, zs[k], k);
+  if (c->P.im < 4 || c->P.jm < 4) return fail(c, POMGPU_EINVAL, "ztosig_line: the tile has fewer than 4 x 4 cells");
+  const int rc = launch_ztosig_line(c, edge, zs, ks, src, out);
+  if (rc) return fail(c, rc, "ztosig_line: %s", rc == POMGPU_ENOMEM ? "no device memory for the source and the work arrays" : "a HIP call failed");
+  return POMGPU_OK;
+}
 extern "C" int pomgpu_profq(pomgpu_ctx *c) { NEED(c); seq_profq(c); return POMGPU_OK; }
 extern "C" int pomgpu_proft(pomgpu_ctx *c, const double *f, const double *wfsurf, const double *fsurf, int nbc) {
   NEED(c);

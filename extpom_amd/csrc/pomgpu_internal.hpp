@@ -752,6 +752,7 @@ struct pomgpu_ctx {
   int ext_loop_off;          // a k_ext_loop launch of this context gave up at its barrier: the substeps run as launches of their own from then on
   void *io_job;              // the output / restart file being written behind the model's back (cdf_out.hip), NULL = none
   int z_init, z_clim;        // pomgpu_set_z_inputs: the init / clim file holds z levels and goes through ztosig (cdf_out.hip)
+  int z_lbry;                // pomgpu_set_z_lateral: temp, salt of the lbry file are on z levels and go through k_ztosig_line (cdf_out.hip)
   void *frc_files;           // pomgpu_set_forcing_files: the open forcing files and their read buffers (cdf_out.hip), NULL = none
   int launch_err;            // first hipError_t a kernel launch returned (0 = none); reported by the next sync / get_con
   char err[512];
@@ -948,6 +949,8 @@ void pomgpu_ff_free(pomgpu_ctx *c);
 // physical edges, after the exchange
 int launch_ztosig(pomgpu_ctx *c, double *t, const double *zs, int ks, const double *src);
 void launch_ztosig_edges(pomgpu_ctx *c, double *t);
+// one line of a lateral record (bounds_forcing.f:636-716), edge 0 east, 1 south, 2 west, 3 north: src host, ks levels of n_local + 2 values; out host, kb levels of n_local
+int launch_ztosig_line(pomgpu_ctx *c, int edge, const double *zs, int ks, const double *src, double *out);
 // k_reduce.hip
 void launch_check_velocity(pomgpu_ctx *c);
 void launch_domain_stats(pomgpu_ctx *c, double *out_dev);

@@ -12,6 +12,8 @@ module pomgpu_iface
   logical, save :: pom_frc_sfrc = .false., pom_frc_lbry = .false., pom_frc_clim = .false.
   ! the init / clim file holds z levels (pomgpu_set_z_inputs): cold_start_files and pomgpu_open_forcing_files pass the two on
   logical, save :: pom_init_on_z = .false., pom_clim_on_z = .false.
+  ! temp, salt of the lbry file are on z levels (pomgpu_set_z_lateral): pomgpu_open_forcing_files passes it on
+  logical, save :: pom_lbry_on_z = .false.
   type, bind(C) :: pomgpu_file_meta               ! include/pomgpu.h
     type(c_ptr) :: title, time_start
     integer(c_int) :: im_global, jm_global, i0, j0, create
@@ -109,6 +111,9 @@ module pomgpu_iface
     integer(c_int) function pomgpu_set_z_inputs(ctx, init_on_z, clim_on_z) bind(C, name='pomgpu_set_z_inputs')
       import; type(c_ptr), value :: ctx; integer(c_int), value :: init_on_z, clim_on_z
     end function
+    integer(c_int) function pomgpu_set_z_lateral(ctx, lbry_on_z) bind(C, name='pomgpu_set_z_lateral')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: lbry_on_z
+    end function
     integer(c_int) function pomgpu_domain_stats(ctx, out, sums_only) bind(C, name='pomgpu_domain_stats')
       import; type(c_ptr), value :: ctx; real(c_double) :: out(8); integer(c_int), value :: sums_only
     end function
@@ -129,6 +134,9 @@ module pomgpu_iface
     end function
     integer(c_int) function pomgpu_ztosig(ctx, zs, ks, src, t) bind(C, name='pomgpu_ztosig')
       import; type(c_ptr), value :: ctx, zs, src, t; integer(c_int), value :: ks   ! zs(ks), src(im_local,jm_local,ks): the caller's own arrays; t: a COMMON array
+    end function
+    integer(c_int) function pomgpu_ztosig_line(ctx, edge, zs, ks, src, out) bind(C, name='pomgpu_ztosig_line')
+      import; type(c_ptr), value :: ctx, zs, src, out; integer(c_int), value :: edge, ks   ! zs(ks), src(0:n_local+1,ks), out(n_local,kb): the caller's own arrays
     end function
     integer(c_int) function pomgpu_bcond(ctx, idx) bind(C, name='pomgpu_bcond')
       import; type(c_ptr), value :: ctx; integer(c_int), value :: idx

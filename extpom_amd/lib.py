@@ -109,6 +109,8 @@ _SIGS = {
     "pomgpu_proft": (_I, [_P, _P, _P, _P, _I]),
     "pomgpu_ztosig": (_I, [_P, _P, _I, _P, _P]),
     "pomgpu_set_z_inputs": (_I, [_P, _I, _I]),
+    "pomgpu_set_z_lateral": (_I, [_P, _I]),
+    "pomgpu_ztosig_line": (_I, [_P, _I, _P, _I, _P, _P]),
     "pomgpu_bcond": (_I, [_P, _I]),
     "pomgpu_bcondorl": (_I, [_P, _I]),
     "pomgpu_prof_begin": (_I, [_P]),

@@ -246,10 +246,13 @@ class PomGpu:
         self.get_con()
         return {"cflmin": info.cflmin, "period": info.period}
 
-    def set_z_inputs(self, init: bool = False, clim: bool = False):
+    def set_z_inputs(self, init: bool = False, clim: bool = False, lbry: bool | None = None):
         """pomgpu_set_z_inputs: cold_start takes T, S of the init file (levels in `Level`) and / or Tclim, Sclim of the clim file (levels in
-        `z`) as z-level data and maps them onto the sigma levels with ztosig (initialize.f:410-422)"""
+        `z`) as z-level data and maps them onto the sigma levels with ztosig (initialize.f:410-422).  lbry (given: pomgpu_set_z_lateral):
+        temp, salt of the lbry file are on the levels of its `z` and every fetched record's lines are mapped (bounds_forcing.f:636-716)"""
         self._chk(self.L.pomgpu_set_z_inputs(self.h, 1 if init else 0, 1 if clim else 0), "set_z_inputs")
+        if lbry is not None:
+            self._chk(self.L.pomgpu_set_z_lateral(self.h, 1 if lbry else 0), "set_z_lateral")
 
     def set_forcing_files(self, sfrc=None, lbry=None, clim=None, im_global=None, jm_global=None):
         """pomgpu_set_forcing_files: from now on wind / heat / surface (sfrc), lateral_bc (lbry) and restore_interior (clim) take the
@@ -289,6 +292,19 @@ class PomGpu:
         if zs.ndim != 1 or src.shape != (zs.size, self.st.jm_local, self.st.im_local):
             raise ValueError(f"ztosig: src {src.shape} is not (ks, jm_local, im_local) = {(zs.size, self.st.jm_local, self.st.im_local)}")
         self._chk(self.L.pomgpu_ztosig(self.h, self._p(zs), int(zs.size), self._p(src), self._a(t)), "ztosig")
+
+    def ztosig_line(self, edge: int, zs, src):
+        """pomgpu_ztosig_line (bounds_forcing.f:636-716): one lateral line, edge 0 east, 1 south, 2 west, 3 north, of z-level values
+        src (ks, n_local + 2) -- line point a at [:, a], the window points beyond the ends at [:, 0] and [:, n + 1] -- onto the sigma levels
+        with that edge's depth line; returns (kb, n_local), n_local = jm_local (east, west) or im_local (south, north)"""
+        zs = np.ascontiguousarray(zs, dtype=np.float64)
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        nl = self.st.jm_local if edge in (0, 2) else self.st.im_local
+        if zs.ndim != 1 or src.shape != (zs.size, nl + 2):
+            raise ValueError(f"ztosig_line: src {src.shape} is not (ks, n_local + 2) = {(zs.size, nl + 2)}")
+        out = np.empty((self.st.kb, nl))
+        self._chk(self.L.pomgpu_ztosig_line(self.h, int(edge), self._p(zs), int(zs.size), self._p(src), self._p(out)), "ztosig_line")
+        return out
 
     def advance(self):
         self.call("advance")

@@ -339,8 +339,21 @@ int pomgpu_cold_start(pomgpu_ctx *ctx, const char *grid, const char *init, const
  * monthly fetch reads the window's ks levels and maps them into the (im,jm,kb) record in place of the plain unpack, on the stream the step is
  * enqueued on, with buffers allocated at registration (a step still allocates nothing); t_w s_w t_n s_n come from the tclim, sclim mirrors as
  * ever.  This call refuses (POMGPU_EINVAL) to change clim_on_z once a clim file is registered.  Z-level .lbry.nc files
- * (bounds_forcing.f:636-716) are NOT read: lateral files hold sigma levels. */
+ * (bounds_forcing.f:636-716) are pomgpu_set_z_lateral's, below. */
 int pomgpu_set_z_inputs(pomgpu_ctx *ctx, int init_on_z, int clim_on_z);
+/* Z-level lateral files (a context setting; default 0: the lbry file holds sigma levels, today's behaviour bit for bit and refusal for
+ * refusal) -- what the reference's commented blocks behind read_boundary_conditions_pnetcdf (bounds_forcing.f:636-716, :757-836) are for.
+ * Under lbry_on_z pomgpu_set_forcing_files wants of the lbry file: `z`, a 1-D NC_FLOAT / NC_DOUBLE variable of ks values, 2 <= ks <= 300,
+ * finite and strictly increasing; temp.east salt.east as (record, ks, jm_global), temp.south salt.south as (record, ks, im_global); zeta, u
+ * and v as ever (the reference maps T and S only).  lateral_bc's fetch reads the four variables on all ks levels over the tile's line and
+ * one more point towards every neighbour, and maps each line onto the sigma levels into the record's tbe sbe / tbs sbs with the line form of
+ * ztosig (pomgpu_ztosig_line below: east with h(imm1,j), south with h(i,2)), behind the unpack of everything else, on the stream the step is
+ * enqueued on, with buffers allocated at registration.  Every rank maps every line with its own h, as the reference does; no message round.
+ * t_w s_w t_n s_n come from the tclim, sclim mirrors as ever.  More refusals of pomgpu_set_forcing_files, before anything changes: `z`
+ * absent, not 1-D, of another type, outside 2..300 values, not finite and strictly increasing; one of the four variables with another
+ * level count than it; a tile whose window does not fit the grid; im or jm below 4.  This call refuses (POMGPU_EINVAL) to change the
+ * setting once an lbry file is registered. */
+int pomgpu_set_z_lateral(pomgpu_ctx *ctx, int lbry_on_z);
 
 /* The forcing files without PnetCDF: read_wind_pnetcdf, read_heat_pnetcdf, read_surface_pnetcdf (io_pnetcdf.F:2912-3224),
  * read_boundary_conditions_pnetcdf (:3393-3621), read_restore_ts_interior_pnetcdf (:3275-3333).  The host names the files once --
@@ -432,6 +445,16 @@ int pomgpu_dens(pomgpu_ctx *ctx, const double *si, const double *ti, const doubl
  * Refused with POMGPU_EINVAL, error_status = 1 and the cause in pomgpu_last_error before t changes: ks outside 2..300 (splinc's nmax), zs
  * not finite or not strictly increasing, t not a blk3d array of the bound host block.  Synchronous. */
 int pomgpu_ztosig(pomgpu_ctx *ctx, const double *zs, int ks, const double *src, const double *t);
+/* ztosig for one lateral line (bounds_forcing.f:636-716): the block spreads the line across the tile, calls ztosig with the depth
+ * hs = h(imm1,j) (edge 0, east), h(i,2) (1, south), h(2,j) (2, west) or h(i,jmm1) (3, north) and keeps the column im/2 / the row jm/2.  The
+ * source does not vary across the line, so each line point is one ztosig column: of the fill-in's four neighbours two are the point's own
+ * raw value, two the raw values of the points before and after it.  n_local = jm_local (east, west) or im_local (south, north), n = jm or im.
+ * zs: ks HOST doubles; src: HOST, ks levels of n_local + 2 doubles each, line point a (1-based) at index a of its level: index 0 and
+ * index n + 1 are the window points beyond the line's ends, ignored at a physical end, where the point takes the finished value of the
+ * point next to it (zeros included); out: HOST, kb levels of n_local doubles, points beyond n zero, filled when the call returns.  h, zz
+ * and the neighbours are the context's; no mirror changes and no message round is posted (a ghost end is formed from the window point
+ * with the owner's arithmetic).  Refused with POMGPU_EINVAL as pomgpu_ztosig refuses ks and zs; also edge outside 0..3, im or jm below 4. */
+int pomgpu_ztosig_line(pomgpu_ctx *ctx, int edge, const double *zs, int ks, const double *src, double *out);
 int pomgpu_profq(pomgpu_ctx *ctx);               /* solver.f:1212-1538 */
 int pomgpu_proft(pomgpu_ctx *ctx, const double *f, const double *wfsurf, const double *fsurf, int nbc); /* :1541-1683 */
 int pomgpu_profu(pomgpu_ctx *ctx);               /* solver.f:1686-1780 */

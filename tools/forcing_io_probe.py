@@ -11,7 +11,12 @@ offsets the library reads, found through scipy's mapping) into one bytearray, ri
 fraction of their pages was resident (mincore) before the first and after the last turn -- the read times are then memory-to-memory.
 
     python tools/forcing_io_probe.py [--grid 1024x1024x40] [--dir /scratch] [--turns 3] [--out profiles/forcing_read_1024x1024x40.json]
+    python tools/forcing_io_probe.py --lbry-z [--ks 33] [--out profiles/forcing_read_lbry_z_1024x1024x40.json]
     python tools/forcing_io_probe.py --check      (no GPU: arguments, paths and free space only; reports no time)
+
+--lbry-z: a third context of the same job takes its lateral records from an lbry file whose temp / salt lines are on ks z levels
+(PomGpu.set_z_inputs(lbry=True)): its fetch steps stand beside the sigma file's, with the bare pread of the bytes it reads, and one more
+fetch step with every kernel bracketed gives k_lat_unpack and k_ztosig_line their own durations.
 """
 import argparse
 import json
@@ -35,11 +40,13 @@ def main():
     ap.add_argument("--dir", default=None, help="where the files go (default: the temporary directory)")
     ap.add_argument("--turns", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the JSON here")
+    ap.add_argument("--lbry-z", action="store_true", help="also fetch from an lbry file with temp / salt on z levels")
+    ap.add_argument("--ks", type=int, default=33, help="--lbry-z: the z levels of that file")
     ap.add_argument("--check", action="store_true", help="arguments, paths and free space only; no GPU, no time")
     args = ap.parse_args()
     im, jm, kb = (int(v) for v in args.grid.lower().split("x"))
     where = args.dir or tempfile.gettempdir()
-    nrec, nlat = args.turns + 2, 3 * args.turns + 2
+    nrec, nlat = args.turns + 2 + (1 if args.lbry_z else 0), 3 * args.turns + 2 + (3 if args.lbry_z else 0)   # --lbry-z: one more turn, the bracketed one
     nbytes = 8 * (6 * nrec * im * jm + nlat * (im + jm) * (1 + 4 * kb))
     free = shutil.disk_usage(where).free
     out = dict(tool="forcing_io_probe", grid=f"{im}x{jm}x{kb}", case=args.case, dir=where, file_bytes_about=nbytes, free_bytes=free)
@@ -68,6 +75,9 @@ def main():
     try:
         sfrc = fx.write_sfrc(os.path.join(tmp, "probe.sfrc.nc"), raw_s)
         lbry = fx.write_lbry(os.path.join(tmp, "probe.lbry.nc"), raw_l)
+        if args.lbry_z:
+            import ztosig_line_files_checks as zl               # the z-level lines for the state's own depths, the file's writer
+            lbry_z = zl.write_lbry_z(os.path.join(tmp, "probe_z.lbry.nc"), zl.raw_lbry_z(st, nlat, ks=args.ks))
         del raw_s, raw_l
         out["file_bytes"] = [os.path.getsize(sfrc), os.path.getsize(lbry)]
         out["resident_before"] = [resident_fraction(sfrc), resident_fraction(lbry)]
@@ -78,6 +88,14 @@ def main():
         fs, fl = netcdf_file(sfrc, "r", mmap=True), netcdf_file(lbry, "r", mmap=True)
         rec_bytes = 8 * (5 * im * jm + (im + jm) * (1 + 4 * kb))          # SSS is not read by the file path; the host path reads it as the reference does
         fd_s, fd_l = os.open(sfrc, os.O_RDONLY), os.open(lbry, os.O_RDONLY)
+        if args.lbry_z:
+            c = st.copy()
+            gz = PomGpu(c, device=0)
+            gz.set_z_inputs(lbry=True)
+            gz.set_forcing_files(sfrc=sfrc, lbry=lbry_z)
+            fz, fd_z = netcdf_file(lbry_z, "r", mmap=True), os.open(lbry_z, os.O_RDONLY)
+            z_bytes = 8 * (5 * im * jm + (im + jm) * (1 + 2 * kb + 2 * args.ks))
+            out["z_file_bytes"], out["ks"] = os.path.getsize(lbry_z), args.ks
 
         def timed(fn):
             t = time.perf_counter()
@@ -109,6 +127,18 @@ def main():
 
         dest = bytearray(rec_bytes)
 
+        def pread_plan_z(n):
+            # the same for the z-level context: the sfrc pieces and record rl of the ten variables of ITS lbry file
+            r, rl, at = n // PERIOD + 2, n // LPERIOD + 2, 0
+            pieces = [(fd_s, "sustr", r), (fd_s, "svstr", r), (fd_s, "shflux", r), (fd_s, "swrad", r), (fd_s, "SST", r - 1)] + [(fd_z, k, rl) for k in fx.LBRY]
+            plan = []
+            for fd, var, rec in pieces:
+                off, nb = where_in_file(fs if fd == fd_s else fz, var, rec)
+                plan.append((fd, off, at, nb))
+                at += nb
+            assert at == z_bytes
+            return plan
+
         def pread_plan(n):
             # the very reads the file path makes for step n: records r / r-1 of the five sfrc variables it reads and record rl of the ten
             # lbry variables (one tile: each a contiguous piece), every piece into its own place of one buffer
@@ -128,6 +158,10 @@ def main():
                     raise OSError("pread failed")
 
         res = dict(file_step_ms=[], file_step_nofetch_ms=[], host_step_ms=[], host_step_nofetch_ms=[], bare_pread_ms=[])
+        if args.lbry_z:
+            res.update(z_file_step_ms=[], z_file_step_nofetch_ms=[], z_bare_pread_ms=[])
+            gz.set_con(iint=2)
+            step(gz)
         # warm both contexts (first launches, allocations) on a step of their own, and give the host path the "b" generation of records
         for g in (gf, gh):
             g.set_con(iint=2)
@@ -144,6 +178,30 @@ def main():
             res["host_step_ms"].append(timed(lambda: host_fetch_and_step(n)))
             plan = pread_plan(n)
             res["bare_pread_ms"].append(timed(lambda: bare_pread(plan)))
+            if args.lbry_z:
+                gz.get_con()
+                gz.set_con(iint=n - 2)
+                res["z_file_step_nofetch_ms"].append(timed(lambda: step(gz)))
+                res["z_file_step_ms"].append(timed(lambda: step(gz)))
+                plan = pread_plan_z(n)
+                dest_z = bytearray(z_bytes)
+                keep, dest = dest, dest_z
+                res["z_bare_pread_ms"].append(timed(lambda: bare_pread(plan)))
+                dest = keep
+        if args.lbry_z:                                           # one more fetch step, every kernel bracketed: the two lateral kernels' own time
+            gz.get_con()
+            gz.set_con(iint=PERIOD * (args.turns + 1) - 1)
+            gz.prof_begin()
+            step(gz)
+            prof = gz.prof_end()
+            out["z_kernels_ms"] = {k: [prof[k][0], round(prof[k][1], 4)] for k in ("k_lat_unpack", "k_ztosig_line") if k in prof}
+            gz.download()
+            out["z_error_status"] = int(c.error_status)
+            out["z_tbef_level_kb_nonzero"] = bool(c.tbef[kb - 1].any())
+            out["z_fetch_bytes"] = z_bytes
+            os.close(fd_z)
+            fz.close()
+            gz.close()
         os.close(fd_s)
         os.close(fd_l)
         gf.download()
@@ -155,6 +213,8 @@ def main():
         out["fetch_bytes"] = rec_bytes
         out.update(res)
         out["file_fetch_ms"] = [round(x - y, 3) for x, y in zip(res["file_step_ms"], res["file_step_nofetch_ms"])]
+        if args.lbry_z:
+            out["z_file_fetch_ms"] = [round(x - y, 3) for x, y in zip(res["z_file_step_ms"], res["z_file_step_nofetch_ms"])]
         out["host_fetch_ms"] = [round(x - y, 3) for x, y in zip(res["host_step_ms"], res["host_step_nofetch_ms"])]
         out["page_cache"] = "the files were written by this process just before: resident_* is the fraction of their pages in the page cache"
         fs.close()
