@@ -102,6 +102,9 @@ DDX_HD ddx ddx_exp(double x, int *kout) {
   return p;
 }
 // real( swrad * ( r*exp(real(x1,16)) + omr*exp(real(x2,16)) ), 8 ),  omr = 1.d0 - r as the reference forms it in REAL(8)
+// Documented limit: |swrad| >= 1e-6 (or swrad = 0).  With |swrad| around 1e-300 one result in 2e5 was an ulp off the REAL(16) value on the
+// host; no surface flux is that small.  tests/device_math_checks.py holds the device to the quad values for |swrad| in [1e-6, 1]: results
+// in the subnormal band, both cut-offs (-11400, the exponent gap -240), x1 = x2, |x| < 1e-10, x up to 700, NaN, the plain formula above 700
 DDX_HD double proft_rad_q(double swrad, double r, double omr, double x1, double x2) {
   // below -11400 even REAL(16)'s exp is 0 (its smallest subnormal is 2^-16494); NaN operands take the plain formula
   if (!(x1 == x1) || !(x2 == x2) || x1 > 700. || x2 > 700.) return swrad * (r * exp(x1) + omr * exp(x2));

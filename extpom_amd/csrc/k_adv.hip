@@ -597,19 +597,42 @@ static __device__ const double GP_A[7] = GPOW_A;
 static __device__ const double GP_LT[128][3] = GPOW_LOGTAB;
 static __device__ const double GP_C[4] = GEXP_C;
 static __device__ const unsigned long long GP_ET[256] = GEXP_TAB;
-__device__ __forceinline__ double pow15_dd(double x) {   // correctly rounded x*sqrt(x); only for non-normal x
-  if (x == 0.) return 0.;
-  const double s = sqrt(x);
-  const double e = __builtin_fma(-s, s, x) / (2. * s);
-  const double p = x * s;
-  const double pe = __builtin_fma(x, s, -p);
-  return p + (pe + x * e);
+// exp_inline's specialcase(): 2^(k/N) is outside the normal range (the result over- or underflows, or is subnormal).  For k > 0 the
+// product is fused like the fast path's; for k < 0 it is NOT: the host's libm forms scale * tmp once and adds it twice
+// (tools/check_glibc_pow_clone.c: 2000 arguments in every binade)
+__device__ __forceinline__ double gexp_specialcase(double tmp, unsigned long long sbits, unsigned long long ki) {
+  if ((ki & 0x80000000ULL) == 0) {                       // k > 0: the exponent of scale may have overflowed
+    sbits -= 1009ULL << 52;
+    const double scale = __builtin_bit_cast(double, sbits);
+    return 0x1p1009 * __builtin_fma(scale, tmp, scale);
+  }
+  sbits += 1022ULL << 52;                                // k < 0: care in the subnormal range
+  const double scale = __builtin_bit_cast(double, sbits);
+  double y = scale + scale * tmp;
+  if (fabs(y) < 1.0) {                                   // round to the subnormal's precision once, before scaling
+    double one = 1.0;
+    if (y < 0.0) one = -1.0;
+    double lo = scale - y + scale * tmp;
+    const double hi = one + y;
+    lo = one - hi + y + lo;
+    y = (hi + lo) - one;
+    if (y == 0.0) y = __builtin_bit_cast(double, sbits & 0x8000000000000000ULL);
+  }
+  return 0x1p-1022 * y;
 }
-__device__ __forceinline__ double gpow15(double x) {
+// pow(x, 1.5) as glibc 2.35 computes it.  EDGES: with pow's entry for zero, subnormal, inf and NaN and with exp_inline's range test,
+// specialcase() and its overflow and underflow returns; without: the fast path alone, which is all a result in the normal range needs
+template <bool EDGES> __device__ __forceinline__ double gpow15_t(double x) {
   const double y = 1.5;
-  const unsigned long long ix = __builtin_bit_cast(unsigned long long, x);
+  unsigned long long ix = __builtin_bit_cast(unsigned long long, x);
   const unsigned top = (unsigned)(ix >> 52);
-  if (top - 1u >= 0x7feu) return pow15_dd(x);   // zero, subnormal, inf, nan: glibc's slow paths
+  if (EDGES && top - 1u >= 0x7feu) {                     // pow's entry: x < 0x1p-1022, inf or nan
+    if (2 * ix - 1 >= 2 * 0x7ff0000000000000ULL - 1) return x * x;   // zero, inf, nan
+    if (ix >> 63) return (x - x) / (x - x);
+    ix = __builtin_bit_cast(unsigned long long, x * 0x1p52);   // a subnormal, normalised: the exponent goes negative
+    ix &= 0x7fffffffffffffffULL;
+    ix -= 52ULL << 52;
+  }
   const unsigned long long tmp = ix - 0x3fe6955500000000ULL;
   const int i = (int)((tmp >> 45) & 127);
   const long long k = (long long)tmp >> 52;
@@ -643,6 +666,13 @@ __device__ __forceinline__ double gpow15(double x) {
   const double ehi = y * yl;
   const double e2 = __builtin_fma(yl, y, -ehi);
   const double elo = __builtin_fma(y, tl, e2);
+  const unsigned abstop = (unsigned)(__builtin_bit_cast(unsigned long long, ehi) >> 52) & 0x7ffu;
+  bool special = false;
+  if (EDGES && abstop - 0x3c9u >= 0x3fu) {               // exp_inline's range test: |ehi| < 0x1p-54 or >= 0x1p9
+    if (abstop - 0x3c9u >= 0x80000000u) return 1.0 + ehi;
+    if (abstop >= 0x409u) return (__builtin_bit_cast(unsigned long long, ehi) >> 63) ? 0x1p-767 * 0x1p-767 : 0x1p769 * 0x1p769;   // __math_uflow, __math_oflow
+    special = true;
+  }
   double kd2 = __builtin_fma(ehi, GEXP_INVLN2N, GEXP_SHIFT);
   const unsigned long long ki = __builtin_bit_cast(unsigned long long, kd2);
   kd2 = kd2 - GEXP_SHIFT;
@@ -658,8 +688,24 @@ __device__ __forceinline__ double gpow15(double x) {
   const double s2 = __builtin_fma(p1, r2, s1);
   const double r4 = r2 * r2;
   const double tm = __builtin_fma(p2, r4, s2);
+  if (EDGES && special) return gexp_specialcase(tm, sbits, ki);
   const double sc = __builtin_bit_cast(double, sbits);
   return __builtin_fma(tm, sc, sc);
+}
+// pow(x, 1.5) as glibc 2.35 returns it, on every double (tests/device_math_checks.py: every binade, every row of both tables, the
+// values where the path changes).  For x in [0x1p-491, 0x1p491) the exponent's argument 1.5 ln x stays below 511 in magnitude, short
+// of exp_inline's bound 512, and is below 0x1p-54 only for x = 1, where both paths return 1: the fast path alone, at the cost of the
+// one test on x's exponent it always had.  Everything else -- zero, subnormal, inf, NaN, a result that is subnormal or overflows --
+// goes through glibc's tests.  dens passes fabs(sr); a negative x gives NaN, as pow does
+__device__ __forceinline__ double gpow15(double x) {
+  const unsigned top = (unsigned)(__builtin_bit_cast(unsigned long long, x) >> 52);
+  if (top - 0x214u >= 0x3d6u) return gpow15_t<true>(x);
+  return gpow15_t<false>(x);
+}
+// pomgpu_math_probe's GPOW15: gpow15 on one value per lane
+__global__ void k_probe_gpow15(long n, const double *x, double *out) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) out[e] = gpow15(x[e]);
 }
 __device__ __forceinline__ void c_dens(const KP &P, const int i, const int j, const int k, const double *si, const double *ti, double *rhoo);
 __global__ void k_dens(KP P, const double *si, const double *ti, double *rhoo) {
@@ -906,6 +952,7 @@ void launch_mask_w(pomgpu_ctx *c) { LAUNCH(c, k_mask_w, gridm(c->P), blk2(), c->
 void launch_restore(pomgpu_ctx *c, double fold, double fnew) { LAUNCH(c, k_restore, gridm(c->P), blk2(), c->P, fold, fnew); }
 void launch_restore_shift(pomgpu_ctx *c) { LAUNCH(c, k_restore_shift, gridm(c->P), blk2(), c->P); }
 void launch_restore_load(pomgpu_ctx *c, const double *tr, const double *sr, double tau) { LAUNCH(c, k_restore_load, gridm(c->P), blk2(), c->P, tr, sr, tau); }
+void launch_probe_gpow15(pomgpu_ctx *c, long n, const double *x, double *out) { LAUNCH(c, k_probe_gpow15, dim3((unsigned)((n + 255) / 256), 1, 1), dim3(256, 1, 1), n, x, out); }
 void launch_dens(pomgpu_ctx *c, const double *si, const double *ti, double *rhoo) { LAUNCH(c, k_dens, gridm(c->P), blk2(), c->P, si, ti, rhoo); }
 void launch_realvertvl(pomgpu_ctx *c, int etf_is_et) {
   if (SW(c, REALVERTVL_CELLS)) LAUNCH(c, k_realvertvl, gridm(c->P), blk2(), c->P, etf_is_et);

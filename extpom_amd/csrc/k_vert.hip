@@ -2072,3 +2072,24 @@ void launch_uv_filter(pomgpu_ctx *c, int own) {
   if (launch_uv_filter_reg(c, own)) return;
   LAUNCH(c, k_uv_filter, colgrid(c->P), colblk(), c->P, own);
 }
+
+// ---- pomgpu_math_probe: the scalar device functions on one value per lane, as the kernels above call them ------------------------------
+// DIVI / DIVI_F32: divi(a, inv_of(b)); the float overload takes a and b narrowed here and its quotient is widened on store.  Under
+// POMGPU_EMU divi is the plain quotient a / b (pomgpu_internal.hpp), so the host build checks the path to the entry, not the algorithm.
+__global__ void k_probe_divi(long n, const double *a, const double *b, double *out, int f32) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  if (f32) out[e] = (double)divi((float)a[e], inv_of((float)b[e]));
+  else out[e] = divi(a[e], inv_of(b[e]));
+}
+__global__ void k_probe_rad_q(long n, const double *swrad, const double *r, const double *omr, const double *x1, const double *x2, double *out) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) out[e] = proft_rad_q(swrad[e], r[e], omr[e], x1[e], x2[e]);
+}
+static inline dim3 probe_grid(long n) { return dim3((unsigned)((n + 255) / 256), 1, 1); }
+void launch_probe_divi(pomgpu_ctx *c, long n, const double *a, const double *b, double *out, int f32) {
+  LAUNCH(c, k_probe_divi, probe_grid(n), dim3(256, 1, 1), n, a, b, out, f32);
+}
+void launch_probe_rad_q(pomgpu_ctx *c, long n, const double *const *in, double *out) {
+  LAUNCH(c, k_probe_rad_q, probe_grid(n), dim3(256, 1, 1), n, in[0], in[1], in[2], in[3], in[4], out);
+}

@@ -2300,6 +2300,36 @@ extern "C" int pomgpu_ztosig_line(pomgpu_ctx *c, int edge, const double *zs, int
   if (rc) return fail(c, rc, "ztosig_line: %s", rc == POMGPU_ENOMEM ? "no device memory for the source and the work arrays" : "a HIP call failed");
   return POMGPU_OK;
 }
+// the scalar device functions on the caller's own host arrays (tests): refused before anything is allocated or launched
+extern "C" int pomgpu_math_probe(pomgpu_ctx *c, int op, long n, const double *const *in, int nin, double *out) {
+  NEED(c);
+  static const int NIN[4] = {2, 2, 1, 5};
+  if (op < 0 || op > 3) return fail(c, POMGPU_EINVAL, "math_probe: op = %d is none of 0 DIVI, 1 DIVI_F32, 2 GPOW15, 3 RAD_Q", op);
+  if (nin != NIN[op]) return fail(c, POMGPU_EINVAL, "math_probe: op %d takes %d input arrays, not %d", op, NIN[op], nin);
+  if (n < 1 || n > (1L << 22)) return fail(c, POMGPU_EINVAL, "math_probe: n = %ld is outside 1..2^22", n);
+  if (!in || !out) return fail(c, POMGPU_EINVAL, "math_probe: in and out must be given");
+  for (int q = 0; q < nin; q++)
+    if (!in[q]) return fail(c, POMGPU_EINVAL, "math_probe: input array %d is NULL", q);
+  double *dev = NULL;                                            // the inputs one after the other, then the result
+  if (hipMalloc((void **)&dev, (size_t)(nin + 1) * n * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return fail(c, POMGPU_ENOMEM, "math_probe: no device memory for %d arrays of %ld", nin + 1, n); }
+  const double *din[5];
+  int rc = POMGPU_OK;
+  for (int q = 0; q < nin; q++) {
+    din[q] = dev + (size_t)q * n;
+    if (hipMemcpyAsync(dev + (size_t)q * n, in[q], n * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = POMGPU_EHIP;
+  }
+  double *dout = dev + (size_t)nin * n;
+  if (!rc) {
+    if (op == POMGPU_PROBE_GPOW15) launch_probe_gpow15(c, n, din[0], dout);
+    else if (op == POMGPU_PROBE_RAD_Q) launch_probe_rad_q(c, n, din, dout);
+    else launch_probe_divi(c, n, din[0], din[1], dout, op == POMGPU_PROBE_DIVI_F32);
+    if (hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = POMGPU_EHIP;
+  }
+  if (hipStreamSynchronize(c->stream) != hipSuccess) rc = POMGPU_EHIP;
+  (void)hipFree(dev);
+  if (rc) return fail(c, rc, "math_probe: a HIP call failed");
+  return POMGPU_OK;
+}
 extern "C" int pomgpu_profq(pomgpu_ctx *c) { NEED(c); seq_profq(c); return POMGPU_OK; }
 extern "C" int pomgpu_proft(pomgpu_ctx *c, const double *f, const double *wfsurf, const double *fsurf, int nbc) {
   NEED(c);

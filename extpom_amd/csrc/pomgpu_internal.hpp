@@ -461,7 +461,9 @@ template <int NS> __device__ __forceinline__ const double *rowshare_pick(const d
 //   r1 = a - b*q1 (exact);                        q  = RN(q1 + r1*y)   -- = RN(a/b): Markstein's theorem (y correctly
 // rounded, q1 faithful; Muller et al., Handbook of Floating-Point Arithmetic, Thm. 4.9) -- five full-rate
 // instructions, no special cases as long as nothing over- or underflows (metric sums and depths: never).
-// tools/micro/f64_rates.hip compares it with the hardware quotient on 3e9 operand pairs; tests compare whole steps.
+// tools/micro/f64_rates.hip compares it with the hardware quotient on 3e9 operand pairs; tests compare whole steps, and
+// tests/test_gpu_device_math.py this function through pomgpu_math_probe with a / b on 2^18 structured pairs per precision
+// (2^-100 <= |b| <= 2^100, a = +-0 or 2^-900 <= |a| <= 2^900; fp32: 2^+-20, 2^+-60) and at the floor named below, |a| in [2^-968, 2^-960].
 // InvDc / the float overloads: the same for the compute type of the fp32-arithmetic variant (with y = RN32(1/b); where y is a
 // narrowed fp64 reciprocal, R1(), the quotient is faithful rather than correctly rounded)
 template <class T> struct InvDT { T b, y; };
@@ -952,5 +954,9 @@ void launch_ztosig_edges(pomgpu_ctx *c, double *t);
 // one line of a lateral record (bounds_forcing.f:636-716), edge 0 east, 1 south, 2 west, 3 north: src host, ks levels of n_local + 2 values; out host, kb levels of n_local
 int launch_ztosig_line(pomgpu_ctx *c, int edge, const double *zs, int ks, const double *src, double *out);
 // k_reduce.hip
+// pomgpu_math_probe: n values per operand in device memory, one per lane (gpow15: k_adv.hip; divi, proft_rad_q: k_vert.hip)
+void launch_probe_gpow15(pomgpu_ctx *c, long n, const double *x, double *out);
+void launch_probe_divi(pomgpu_ctx *c, long n, const double *a, const double *b, double *out, int f32);
+void launch_probe_rad_q(pomgpu_ctx *c, long n, const double *const *in, double *out);
 void launch_check_velocity(pomgpu_ctx *c);
 void launch_domain_stats(pomgpu_ctx *c, double *out_dev);

@@ -306,6 +306,21 @@ class PomGpu:
         self._chk(self.L.pomgpu_ztosig_line(self.h, int(edge), self._p(zs), int(zs.size), self._p(src), self._p(out)), "ztosig_line")
         return out
 
+    PROBE_OPS = {"DIVI": (0, 2), "DIVI_F32": (1, 2), "GPOW15": (2, 1), "RAD_Q": (3, 5)}
+
+    def math_probe(self, op, *arrays):
+        """pomgpu_math_probe: the device's divi (op "DIVI": a, b; "DIVI_F32": the float overload on a, b narrowed), gpow15 ("GPOW15": x)
+        or proft_rad_q ("RAD_Q": swrad, r, omr, x1, x2) on 1-D float64 arrays of one length, one element per lane; returns the results"""
+        code = self.PROBE_OPS[op][0] if isinstance(op, str) else int(op)
+        arrs = [np.ascontiguousarray(a, dtype=np.float64).ravel() for a in arrays]
+        n = arrs[0].size if arrs else 0
+        if any(a.size != n for a in arrs):
+            raise ValueError(f"math_probe: arrays of different lengths {[a.size for a in arrs]}")
+        out = np.empty(max(n, 1))
+        ptrs = (ctypes.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
+        self._chk(self.L.pomgpu_math_probe(self.h, code, n, ptrs, len(arrs), self._p(out)), "math_probe")
+        return out[:n]
+
     def advance(self):
         self.call("advance")
 

@@ -455,6 +455,17 @@ int pomgpu_ztosig(pomgpu_ctx *ctx, const double *zs, int ks, const double *src, 
  * and the neighbours are the context's; no mirror changes and no message round is posted (a ghost end is formed from the window point
  * with the owner's arithmetic).  Refused with POMGPU_EINVAL as pomgpu_ztosig refuses ks and zs; also edge outside 0..3, im or jm below 4. */
 int pomgpu_ztosig_line(pomgpu_ctx *ctx, int edge, const double *zs, int ks, const double *src, double *out);
+/* The scalar device functions that restate host arithmetic, run as the kernels run them (tests; no counterpart in the reference).
+ * in: nin HOST arrays of n doubles, out: n HOST doubles; the arrays are uploaded, one kernel computes one element per lane, the result
+ * is copied back on the context's stream.  No mirror changes.  Synchronous.
+ *   POMGPU_PROBE_DIVI      a, b                      divi(a, inv_of(b)): the quotient from the stored reciprocal, fp64
+ *   POMGPU_PROBE_DIVI_F32  a, b                      the same in fp32: a and b are narrowed on the device, the quotient widened
+ *   POMGPU_PROBE_GPOW15    x                         gpow15(x): glibc 2.35's pow(x, 1.5) as dens calls it
+ *   POMGPU_PROBE_RAD_Q     swrad, r, omr, x1, x2     proft_rad_q(...): proft's short-wave term, the REAL(16) expression rounded once
+ * Refused with POMGPU_EINVAL and the cause in pomgpu_last_error, before anything is allocated or launched: an unknown op, nin other than
+ * the op's number of inputs, n outside 1..2^22, a NULL pointer. */
+enum { POMGPU_PROBE_DIVI = 0, POMGPU_PROBE_DIVI_F32 = 1, POMGPU_PROBE_GPOW15 = 2, POMGPU_PROBE_RAD_Q = 3 };
+int pomgpu_math_probe(pomgpu_ctx *ctx, int op, long n, const double *const *in, int nin, double *out);
 int pomgpu_profq(pomgpu_ctx *ctx);               /* solver.f:1212-1538 */
 int pomgpu_proft(pomgpu_ctx *ctx, const double *f, const double *wfsurf, const double *fsurf, int nbc); /* :1541-1683 */
 int pomgpu_profu(pomgpu_ctx *ctx);               /* solver.f:1686-1780 */
