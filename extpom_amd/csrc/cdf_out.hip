@@ -646,7 +646,7 @@ struct FSource {
   std::vector<FVar> v;
 };
 struct FFiles {
-  FSource s[3];                                                 // sfrc, lbry, clim
+  FSource s[4];                                                 // sfrc, lbry, clim; [3]: the restore rate (pomgpu_set_restore_rate_file)
   int im_global = 0, jm_global = 0, i0 = 1, j0 = 1;
   unsigned char *pin[2] = {NULL, NULL}, *stage = NULL;          // two pinned buffers and the device buffer their copies land in
   size_t cap = 0;                                               // bytes of each
@@ -664,11 +664,17 @@ struct FFiles {
   // neighbour) and of the south lines (lwi, lwe), and one allocation: ztosig's table, then the two work arrays of the record's four lines
   int lks = 0, lwi = 0, lwe = 0, lwj = 0, lwn = 0;
   double *ldev = NULL;
+  // the rate file: `tau` on the rks levels of its `z`, always through ztosig; window lines and one allocation as for the z-level clim file;
+  // rsteady: it holds one record (or has no record dimension), which serves every record number
+  int rks = 0, rwi = 0, rwe = 0, rwj = 0, rwn = 0, rsteady = 0;
+  double *rdev = NULL;
+  size_t rwin = 0, rwork = 0;
 };
 const char *const FF_WHAT[3] = {"sfrc", "lbry", "clim"};
 const char *const FF_SFRC[6] = {"sustr", "svstr", "shflux", "swrad", "SST", "SSS"};
 const char *const FF_LBRY[10] = {"zeta.east", "zeta.south", "u.east", "v.east", "temp.east", "salt.east", "u.south", "v.south", "temp.south", "salt.south"};
 const char *const FF_CLIM[2] = {"Tclim", "Sclim"};
+const char *const FF_RATE[1] = {"tau"};
 
 template <class T> struct CdfRaw;
 template <> struct CdfRaw<float> {
@@ -818,6 +824,7 @@ void pomgpu_ff_free(pomgpu_ctx *c) {
 #endif
   if (F->zdev) (void)hipFree(F->zdev);
   if (F->ldev) (void)hipFree(F->ldev);
+  if (F->rdev) (void)hipFree(F->rdev);
   delete F;
   c->frc_files = NULL;
 }
@@ -883,6 +890,28 @@ static std::string ff_check(const RHeader &H, FSource &S, const char *const *nam
   }
   if (min_rec > 1 && S.v[0].rec && H.numrecs < min_rec) return std::string("variable ") + names[0] + " has " + std::to_string(H.numrecs) + " records, wanted >= " + std::to_string(min_rec);
   return std::string();
+}
+
+// the two pinned buffers and the device buffer behind them, grown to `need` bytes each (never inside a step); 1 = a HIP call failed
+static int ff_reserve(pomgpu_ctx *c, FFiles *F, size_t need) {
+  int bad = 0;
+  if (F->cap < need) {
+    if (hipStreamSynchronize(c->stream) != hipSuccess) bad = 1;   // (a second registration: earlier fetches may still be copying)
+#ifndef POMGPU_EMU
+    for (int b = 0; b < 2; b++) { if (F->pin[b]) (void)hipHostFree(F->pin[b]); F->pin[b] = NULL; F->used[b] = 0; }
+    if (F->stage) (void)hipFree(F->stage);
+    F->stage = NULL;
+    if (hipHostMalloc((void **)&F->pin[0], need, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void **)&F->pin[1], need, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc((void **)&F->stage, need) != hipSuccess) bad = 1;
+    for (int b = 0; b < 2 && !bad; b++) if (!F->ev[b] && hipEventCreateWithFlags(&F->ev[b], hipEventDisableTiming) != hipSuccess) bad = 1;
+#else
+    if (F->pin[0]) (void)hipFree(F->pin[0]);
+    if (hipMalloc((void **)&F->pin[0], need) != hipSuccess) bad = 1;
+    F->stage = F->pin[0];                                         // host emulation: one buffer, no copy
+#endif
+    F->cap = bad ? 0 : need;
+  }
+  return bad;
 }
 
 extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const char *lbry, const char *clim, const pomgpu_file_meta *m) {
@@ -954,23 +983,7 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
   const size_t latz = 8 * ((size_t)P.jm + P.im) + 2 * 8 * (size_t)P.kb * ((size_t)P.jm + P.im) + 2 * 8 * lks * ((size_t)P.jm + P.im + 4);
   if (lks && need < latz) need = latz;
   if (need < run) need = run;
-  int bad = 0;
-  if (F->cap < need) {
-    if (hipStreamSynchronize(c->stream) != hipSuccess) bad = 1;   // (a second registration: earlier fetches may still be copying)
-#ifndef POMGPU_EMU
-    for (int b = 0; b < 2; b++) { if (F->pin[b]) (void)hipHostFree(F->pin[b]); F->pin[b] = NULL; F->used[b] = 0; }
-    if (F->stage) (void)hipFree(F->stage);
-    F->stage = NULL;
-    if (hipHostMalloc((void **)&F->pin[0], need, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void **)&F->pin[1], need, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void **)&F->stage, need) != hipSuccess) bad = 1;
-    for (int b = 0; b < 2 && !bad; b++) if (!F->ev[b] && hipEventCreateWithFlags(&F->ev[b], hipEventDisableTiming) != hipSuccess) bad = 1;
-#else
-    if (F->pin[0]) (void)hipFree(F->pin[0]);
-    if (hipMalloc((void **)&F->pin[0], need) != hipSuccess) bad = 1;
-    F->stage = F->pin[0];                                         // host emulation: one buffer, no copy
-#endif
-    F->cap = bad ? 0 : need;
-  }
+  int bad = ff_reserve(c, F, need);
   // the slots the setters would have allocated on their first call
   const size_t rec2 = sizeof(double) * (size_t)P.im * P.jm, rec3 = rec2 * (size_t)P.kb;
   const size_t latrec = sizeof(double) * (8 * (size_t)P.jml * P.kb + 8 * (size_t)P.iml * P.kb + 2 * (size_t)P.jml + 2 * (size_t)P.iml);
@@ -1198,6 +1211,136 @@ int pomgpu_ff_fetch_restore(pomgpu_ctx *c, int n) {
     }
     if (onz) launch_ztosig_window(c, dst, 1, F->zdev, F->zdev + F->zwin + 2 * F->zwork, F->zdev + F->zwin, F->zdev + F->zwin + F->zwork, F->zks, F->wi, F->we, F->wj, F->wn);
   }
+  return POMGPU_OK;
+}
+
+// ---- the restore rate from a z-level file (read_restore_tau_interior_pnetcdf, io_pnetcdf.F:3053-3107, and the ztosig behind it that
+// bounds_forcing.f:1049-1051, :1076-1079 keep commented) ---------------------------------------------------------------------------------
+// `z` (ks levels) and `tau` (ks, jm_global, im_global), with or without a leading record dimension.  The rate that goes with T/S record n
+// is record n of the file; a file with one record (or no record dimension) is steady and serves every n.  Registered beside the three
+// forcing files: the same header parser and checks, the same pinned buffers, the window and the work arrays of the z-level clim file.
+static std::string rate_check(const RHeader &H, FSource &S, uint64_t ks, uint64_t jmg, uint64_t img) {
+  const RVar *v = NULL;
+  for (const RVar &x : H.vars) if (x.name == FF_RATE[0]) { v = &x; break; }
+  if (!v) return std::string("variable tau is absent");
+  if (v->dimids.size() != 3) return ff_check(H, S, FF_RATE, {{ks, jmg, img}}, 1);   // a leading record dimension, unlimited or fixed
+  if (v->type != 5 && v->type != 6) return "variable tau has NetCDF type " + std::to_string(v->type) + ", neither NC_FLOAT (5) nor NC_DOUBLE (6)";
+  if (H.dimlen[v->dimids[0]] != ks || H.dimlen[v->dimids[1]] != jmg || H.dimlen[v->dimids[2]] != img)
+    return "variable tau has the dimension lengths " + lengths_of(H, *v) + ", wanted ([records, ]" + std::to_string(ks) + ", " + std::to_string(jmg) + ", " + std::to_string(img) + ")";
+  FVar f;
+  f.name = FF_RATE[0]; f.type = v->type; f.begin = v->begin;
+  f.slab = f.esize() * ks * jmg * img;
+  f.rec = false; f.stride = f.slab; f.nfixed = 1;
+  if (f.begin > S.fsize || f.slab > S.fsize - f.begin)
+    return "variable tau (1 records of " + std::to_string(f.slab) + " bytes from " + std::to_string(f.begin) + ") reaches beyond the file's " + std::to_string(S.fsize) + " bytes: a truncated file";
+  S.v.assign(1, f);
+  S.numrecs = H.numrecs;
+  return std::string();
+}
+extern "C" int pomgpu_set_restore_rate_file(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m) {
+  if (!c) return POMGPU_EINVAL;
+  if (!path || !m) return fail(c, POMGPU_EINVAL, "set_restore_rate_file: %s", path ? "no file meta was given" : "no path was given (NULL)");
+  (void)hipSetDevice(c->device);
+  const KP &P = c->P;
+  if (c->flags & POMGPU_CTX_2D) return fail(c, POMGPU_EINVAL, "set_restore_rate_file: %s: not on a 2-D context", path);
+  if (P.im < 4 || P.jm < 4) return fail(c, POMGPU_EINVAL, "set_restore_rate_file: %s: a rate file needs a tile of at least 4 x 4 cells, this one has %d x %d", path, P.im, P.jm);
+  // ztosig's fill-in looks at all four neighbours: one more column / row towards every neighbour of the tile, as for a z-level clim file
+  const int wi = !P.W, we = !P.E, wj = !P.S, wn = !P.N;
+  if (m->i0 - wi < 1 || m->j0 - wj < 1 || m->i0 + P.im - 1 + we > m->im_global || m->j0 + P.jm - 1 + wn > m->jm_global)
+    return fail(c, POMGPU_EINVAL, "set_restore_rate_file: %s: the tile (%d..%d, %d..%d) with its window lines towards every neighbour does not fit the global grid %d x %d", path,
+                m->i0, m->i0 + P.im - 1, m->j0, m->j0 + P.jm - 1, m->im_global, m->jm_global);
+  FFiles *old = FF(c);
+  if (old && (old->im_global != m->im_global || old->jm_global != m->jm_global || old->i0 != m->i0 || old->j0 != m->j0))
+    return fail(c, POMGPU_EINVAL, "set_restore_rate_file: %s: files are registered under another global grid or tile origin", path);
+  const uint64_t img = (uint64_t)m->im_global, jmg = (uint64_t)m->jm_global;
+  FSource S;
+  S.path = path;
+  S.fd = open(path, O_RDONLY);
+  if (S.fd < 0) return fail(c, POMGPU_EINVAL, "set_restore_rate_file: cannot open %s", path);
+  struct stat sb;
+  if (fstat(S.fd, &sb)) { (void)close(S.fd); return fail(c, POMGPU_EINVAL, "set_restore_rate_file: cannot stat %s", path); }
+  S.fsize = (uint64_t)sb.st_size;
+  RHeader H;
+  std::string what;
+  if (ff_header(S.fd, S.fsize, H, what) < 0) { (void)close(S.fd); return fail(c, POMGPU_EINVAL, "set_restore_rate_file: %s is not a rate file this library reads: %s", path, what.c_str()); }
+  std::vector<double> zlev;
+  std::string why = z_levels(H, S, "z", zlev);
+  if (why.empty()) why = rate_check(H, S, (uint64_t)zlev.size(), jmg, img);
+  if (!why.empty()) { (void)close(S.fd); return fail(c, POMGPU_EINVAL, "set_restore_rate_file: %s: %s", path, why.c_str()); }
+  // ---- accepted: the buffers and the table every fetch uses (no allocation inside a step) ----
+  FFiles *F = old ? old : new FFiles();
+  const size_t ks = zlev.size();
+  const size_t band2 = (size_t)(P.jm + wj + wn) * (size_t)img * 8;   // one level's band of the window's rows at the file's full width, doubles
+  size_t need = (SW(c, IO_CHUNK_KB) && SWV(c, IO_CHUNK_KB) > 0 ? (size_t)SWV(c, IO_CHUNK_KB) << 10 : (size_t)64 << 20);
+  if (need < band2) need = band2;
+  if (need > band2 * ks) need = band2 * ks;
+  int bad = ff_reserve(c, F, need);
+  const size_t rwin = ks * (size_t)(P.im + wi + we) * (size_t)(P.jm + wj + wn), rwork = ks * P.n2;
+  double *rnew = NULL;
+  if (!bad) {
+    std::vector<double> tab(4 * ks);
+    ztosig_table(zlev.data(), (int)ks, tab.data());
+    if (hipMalloc((void **)&rnew, (rwin + 2 * rwork + 4 * ks) * sizeof(double)) != hipSuccess ||
+        hipMemcpyAsync(rnew + rwin + 2 * rwork, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {          // (and an earlier fetch has stopped mapping out of the old buffers)
+      bad = 1;
+      if (rnew) (void)hipFree(rnew);
+      rnew = NULL;
+    }
+  }
+  c->frc_files = F;
+  if (bad) {
+    (void)close(S.fd);
+    (void)hipGetLastError();
+    if (!old) pomgpu_ff_free(c);
+    return fail(c, POMGPU_ENOMEM, "set_restore_rate_file: %s: no memory for the read buffers (%zu bytes, twice pinned) and the window", path, need);
+  }
+  if (F->rdev) (void)hipFree(F->rdev);
+  F->rdev = rnew;
+  F->rks = (int)ks; F->rwi = wi; F->rwe = we; F->rwj = wj; F->rwn = wn;
+  F->rwin = rwin; F->rwork = rwork;
+  F->im_global = m->im_global; F->jm_global = m->jm_global; F->i0 = m->i0; F->j0 = m->j0;
+  if (F->s[3].fd >= 0) (void)close(F->s[3].fd);
+  F->s[3] = S;
+  const FVar &f = F->s[3].v[0];
+  F->rsteady = f.rec ? S.numrecs == 1 : f.nfixed == 1;
+  c->tau_gen++;                                                   // what the arrays were made from before is not this file's
+  c->rate_in_f = 0;
+  return POMGPU_OK;
+}
+int pomgpu_ff_rate_steady(pomgpu_ctx *c) { return FF(c)->rsteady; }
+int pomgpu_ff_rate_have(pomgpu_ctx *c, int n) {
+  FFiles *F = FF(c);
+  if (n < 1) return fail(c, POMGPU_EINVAL, "restore_interior: rate record %d", n);
+  return ff_have(c, F->s[3], "restore_interior (rate)", F->rsteady ? 1 : n, {0});
+}
+// record n of `tau`: all rks levels over the tile's window into the window buffer, then k_ztosig straight into the mirror taurstrf -- every
+// cell of (1:im, 1:jm) on all kb levels, the padding beyond keeps what k_restore_load has put there; on the stream the step is enqueued on
+int pomgpu_ff_fetch_rate(pomgpu_ctx *c, int n) {
+  FFiles *F = FF(c);
+  FSource &S = F->s[3];
+  const KP &P = c->P;
+  const int rec = F->rsteady ? 1 : n;
+  const uint64_t img = (uint64_t)F->im_global, jmg = (uint64_t)F->jm_global;
+  const int rows = P.jm + F->rwj + F->rwn, cols = P.im + F->rwi + F->rwe, nlev = F->rks;
+  const size_t band = (size_t)rows * (size_t)img;               // values of one level's band
+  const bool whole_rows = (uint64_t)rows == jmg;
+  const FVar &f = S.v[0];
+  const int lev_per_run = (int)(F->cap / (band * f.esize())) < nlev ? (int)(F->cap / (band * f.esize())) : nlev;
+  for (int k0 = 0; k0 < nlev; k0 += lev_per_run) {
+    const int nl = nlev - k0 < lev_per_run ? nlev - k0 : lev_per_run;
+    unsigned char *pin = ff_buffer(F);
+    if (!pin) return ff_io_error(c, "restore_interior (rate)", n, S, 1);
+    const uint64_t first = f.begin + (uint64_t)(rec - 1) * f.stride + (((uint64_t)k0 * jmg + (uint64_t)(F->j0 - 1 - F->rwj)) * img) * f.esize();
+    if (whole_rows) { if (pread_all(S.fd, pin, (size_t)nl * band * f.esize(), first)) return ff_io_error(c, "restore_interior (rate)", n, S, 0); }
+    else for (int k = 0; k < nl; k++) if (pread_all(S.fd, pin + (size_t)k * band * f.esize(), band * f.esize(), first + (uint64_t)k * jmg * img * f.esize())) return ff_io_error(c, "restore_interior (rate)", n, S, 0);
+    if (ff_send(c, F, (size_t)nl * band * f.esize())) return ff_io_error(c, "restore_interior (rate)", n, S, 1);
+    const dim3 grid((unsigned)((cols + 63) / 64), (unsigned)((rows + 3) / 4), (unsigned)nl);
+    if (f.type == 5) LAUNCHN(c, "k_rst_unpack", k_rst_unpack<float>, grid, blk2(), F->rdev, (const void *)F->stage, cols, rows, rows, (int)img, F->i0 - 1 - F->rwi, k0);
+    else LAUNCHN(c, "k_rst_unpack", k_rst_unpack<double>, grid, blk2(), F->rdev, (const void *)F->stage, cols, rows, rows, (int)img, F->i0 - 1 - F->rwi, k0);
+  }
+  double *taurstrf = c->P.b3 + (size_t)P3_taurstrf * c->P.a3;
+  launch_ztosig_window(c, taurstrf, 0, F->rdev, F->rdev + F->rwin + 2 * F->rwork, F->rdev + F->rwin, F->rdev + F->rwin + F->rwork, F->rks, F->rwi, F->rwe, F->rwj, F->rwn);
   return POMGPU_OK;
 }
 

@@ -443,9 +443,15 @@ __device__ __forceinline__ void c_advt2_diff(const KP &P, const int i, const int
 // of the 38 array passes of the five separate kernels.
 __device__ __forceinline__ double dens_point(const KP &P, double si, double ti, int i, int j, int k);
 // TAU: 1 = taurstrb, taurstrf hold the values tau_b, tau_f everywhere (pomgpu_ctx::tau_known): not read
+//      2 (k_ts_update_same) = a rate field whose two arrays hold the same bits wherever this kernel looks (pomgpu_ctx::tau_same, the steady sponge): taurstrf
+//          alone is read and stands for both.  The arithmetic stays fold*x + fnew*x: that is not x.
 template <int TAU> __device__ __forceinline__ void c_ts_update(const KP &P, const int i, const int j, const int k, double fold, double fnew, int rt, int store_rst, double tau_b, double tau_f);
 template <int TAU> __global__ void k_ts_update(KP P, double fold, double fnew, int rt, int store_rst, double tau_b, double tau_f) {
   MARCH3(c_ts_update<TAU>(P, i, j, k, fold, fnew, rt, store_rst, tau_b, tau_f))
+}
+// TAU = 2 under a kernel name of its own: profiles and ISA listings tell it from the two forms above by name
+__global__ void k_ts_update_same(KP P, double fold, double fnew, int rt, int store_rst) {
+  MARCH3(c_ts_update<2>(P, i, j, k, fold, fnew, rt, store_rst, 0., 0.))
 }
 template <int TAU> __device__ __forceinline__ void c_ts_update(const KP &P, const int i, const int j, const int k, double fold, double fnew, int rt, int store_rst, double tau_b, double tau_f) {
   // pomgpu_ct: fp32 in the fp32-arithmetic variant (pomgpu_internal.hpp) -- all but dens, which takes the widened t, s
@@ -470,7 +476,10 @@ template <int TAU> __device__ __forceinline__ void c_ts_update(const KP &P, cons
     if (act) {                                                         // restore_interior
       const pomgpu_ct tr = CT(fold) * CT(F3(trstrb, i, j, k)) + CT(fnew) * CT(F3(trstrf, i, j, k));
       const pomgpu_ct sr = CT(fold) * CT(F3(srstrb, i, j, k)) + CT(fnew) * CT(F3(srstrf, i, j, k));
-      const pomgpu_ct ta = TAU ? CT(fold) * CT(tau_b) + CT(fnew) * CT(tau_f) : CT(fold) * CT(F3(taurstrb, i, j, k)) + CT(fnew) * CT(F3(taurstrf, i, j, k));
+      pomgpu_ct ta;
+      if (TAU == 1) ta = CT(fold) * CT(tau_b) + CT(fnew) * CT(tau_f);
+      else if (TAU == 2) { const pomgpu_ct x = CT(F3(taurstrf, i, j, k)); ta = CT(fold) * x + CT(fnew) * x; }
+      else ta = CT(fold) * CT(F3(taurstrb, i, j, k)) + CT(fnew) * CT(F3(taurstrf, i, j, k));
       if (store_rst) {                                                 // else left to k_restore_fields (on demand)
         F3(trstr, i, j, k) = tr;
         F3(srstr, i, j, k) = sr;
@@ -572,14 +581,17 @@ __device__ __forceinline__ void c_restore_shift(const KP &P, const int i, const 
   F3(taurstrb, i, j, k) = F3(taurstrf, i, j, k);
 }
 // trstrf(1:im,1:jm,:) = tr ; srstrf = sr ; taurstrf = 1./trst (whole array)
-__device__ __forceinline__ void c_restore_load(const KP &P, const int i, const int j, const int k, const double *tr, const double *sr, double tau);
-__global__ void k_restore_load(KP P, const double *tr, const double *sr, double tau) {
-  MARCH3(c_restore_load(P, i, j, k, tr, sr, tau))
+// taur: the rate record that goes with tr, sr, (im,jm,kb) like them, over the fill: taurstrf(1:im,1:jm,1:kb) = taur; fill_tau = 0: taurstrf
+// holds a steady rate file's record already and stays as it is
+__device__ __forceinline__ void c_restore_load(const KP &P, const int i, const int j, const int k, const double *tr, const double *sr, double tau, const double *taur, int fill_tau);
+__global__ void k_restore_load(KP P, const double *tr, const double *sr, double tau, const double *taur, int fill_tau) {
+  MARCH3(c_restore_load(P, i, j, k, tr, sr, tau, taur, fill_tau))
 }
-__device__ __forceinline__ void c_restore_load(const KP &P, const int i, const int j, const int k, const double *tr, const double *sr, double tau) {
-  F3(taurstrf, i, j, k) = tau;
-  if (i > P.im || j > P.jm) return;
+__device__ __forceinline__ void c_restore_load(const KP &P, const int i, const int j, const int k, const double *tr, const double *sr, double tau, const double *taur, int fill_tau) {
+  const bool in = i <= P.im && j <= P.jm;
   const size_t n = ((size_t)(k - 1) * P.jm + (size_t)(j - 1)) * P.im + (size_t)(i - 1);   // (im,jm,kb) record
+  if (fill_tau) F3(taurstrf, i, j, k) = in && taur ? taur[n] : tau;
+  if (!in) return;
   F3(trstrf, i, j, k) = tr[n];
   F3(srstrf, i, j, k) = sr[n];
 }
@@ -940,8 +952,10 @@ void launch_smol(pomgpu_ctx *c, const double *ff) { LAUNCH(c, k_smol, gridm(c->P
 void launch_copy3(pomgpu_ctx *c, double *dst, const double *src) { LAUNCH(c, k_copy3, gridm(c->P), blk2(), c->P, dst, src); }
 void launch_advt2_diff(pomgpu_ctx *c, const double *fb, const double *fc, double *ff) { LAUNCH(c, k_advt2_diff, gridm(c->P), blk2(), c->P, fb, fc, ff); }
 void launch_ts_update(pomgpu_ctx *c, double fold, double fnew, int rt, int store_rst) {
-  if (c->tau_known[0] && c->tau_known[1] && !SW(c, TAU_ARRAYS))
+  if (c->tau_known[0] && c->tau_known[1] && !c->tau_handed && !SW(c, TAU_ARRAYS))
     LAUNCHN(c, "k_ts_update", (k_ts_update<1>), gridm(c->P), blk2(), c->P, fold, fnew, rt, store_rst, c->tau_val[0], c->tau_val[1]);
+  else if (c->tau_same && !c->tau_handed && !SW(c, TAU_ARRAYS))
+    LAUNCH(c, k_ts_update_same, gridm(c->P), blk2(), c->P, fold, fnew, rt, store_rst);
   else
     LAUNCHN(c, "k_ts_update", (k_ts_update<0>), gridm(c->P), blk2(), c->P, fold, fnew, rt, store_rst, 0., 0.);
 }
@@ -951,7 +965,7 @@ void launch_mask_uv(pomgpu_ctx *c) { LAUNCH(c, k_mask_uv, gridm(c->P), blk2(), c
 void launch_mask_w(pomgpu_ctx *c) { LAUNCH(c, k_mask_w, gridm(c->P), blk2(), c->P); }
 void launch_restore(pomgpu_ctx *c, double fold, double fnew) { LAUNCH(c, k_restore, gridm(c->P), blk2(), c->P, fold, fnew); }
 void launch_restore_shift(pomgpu_ctx *c) { LAUNCH(c, k_restore_shift, gridm(c->P), blk2(), c->P); }
-void launch_restore_load(pomgpu_ctx *c, const double *tr, const double *sr, double tau) { LAUNCH(c, k_restore_load, gridm(c->P), blk2(), c->P, tr, sr, tau); }
+void launch_restore_load(pomgpu_ctx *c, const double *tr, const double *sr, double tau, const double *taur, int fill_tau) { LAUNCH(c, k_restore_load, gridm(c->P), blk2(), c->P, tr, sr, tau, taur, fill_tau); }
 void launch_probe_gpow15(pomgpu_ctx *c, long n, const double *x, double *out) { LAUNCH(c, k_probe_gpow15, dim3((unsigned)((n + 255) / 256), 1, 1), dim3(256, 1, 1), n, x, out); }
 void launch_dens(pomgpu_ctx *c, const double *si, const double *ti, double *rhoo) { LAUNCH(c, k_dens, gridm(c->P), blk2(), c->P, si, ti, rhoo); }
 void launch_realvertvl(pomgpu_ctx *c, int etf_is_et) {

@@ -439,7 +439,7 @@ extern "C" void pomgpu_destroy(pomgpu_ctx *c) {
   (void)hipFree(c->alt2[0]); (void)hipFree(c->alt3[0]);         // one block each
   (void)hipFree(P.m8);
   for (int n = 0; n < 2; n++) { (void)hipFree(c->ord_send[n]); (void)hipFree(c->ord_recv[n]); }
-  for (int n = 0; n <= POMGPU_MAXREC; n++) { (void)hipFree(c->rec_t[n]); (void)hipFree(c->rec_s[n]); }
+  for (int n = 0; n <= POMGPU_MAXREC; n++) { (void)hipFree(c->rec_t[n]); (void)hipFree(c->rec_s[n]); (void)hipFree(c->rec_tau[n]); }
   (void)hipFree(c->d_vel); (void)hipFree(c->d_err); (void)hipFree(c->d_areas); (void)hipFree(c->d_stats); (void)hipFree(c->ext_bar);
   for (int k = 0; k < 3; k++) for (int sl = 0; sl < 4; sl++) { (void)hipFree(c->frc_dev[k][sl][0]); (void)hipFree(c->frc_dev[k][sl][1]); }
   for (int sl = 0; sl < 4; sl++) (void)hipFree(c->lat_dev[sl]);
@@ -545,7 +545,7 @@ extern "C" int pomgpu_upload(pomgpu_ctx *c, const double *b1, const double *b2, 
   if (b1) HIPCHK(c, hipMemcpyAsync(P.b1, b1, sizeof(double) * POM_NBLK1D * P.kb, hipMemcpyHostToDevice, c->stream));
   if (b2) HIPCHK(c, hipMemcpyAsync(P.b2, b2, sizeof(double) * POM_NBLK2D * P.n2, hipMemcpyHostToDevice, c->stream));
   if (b3) {
-    c->tau_known[0] = c->tau_known[1] = 0;                      // taurstrb, taurstrf are the caller's now
+    pomgpu_tau_touched(c, 0); pomgpu_tau_touched(c, 1);         // taurstrb, taurstrf are the caller's now
 #ifndef POMGPU_STORE_F32
     if (P.a3 == P.n3) HIPCHK(c, hipMemcpyAsync(P.b3, b3, sizeof(double) * POM_NBLK3D * P.n3, hipMemcpyHostToDevice, c->stream));
     else
@@ -619,8 +619,8 @@ extern "C" int pomgpu_upload_2d(pomgpu_ctx *c, int s, const double *h) {
 }
 extern "C" int pomgpu_upload_3d(pomgpu_ctx *c, int s, const double *h) {
   SLOTCHK(c, s, POM_NBLK3D);
-  if (s == P3_taurstrb) c->tau_known[0] = 0;
-  if (s == P3_taurstrf) c->tau_known[1] = 0;
+  if (s == P3_taurstrb) pomgpu_tau_touched(c, 0);
+  if (s == P3_taurstrf) pomgpu_tau_touched(c, 1);
   { const int rc3 = copy3_h2d(c, SLOT3(c, s), h); if (rc3) return rc3; }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return POMGPU_OK;
@@ -650,6 +650,10 @@ extern "C" double *pomgpu_device_3d(pomgpu_ctx *c, int s) {
   restore_materialize(c);
   c->wr_eager = 1;                                            // reads of wr (and writes of w, u, v) the library no longer sees: realvertvl ends every step from now on
   c->dev3_handed = 1;                                         // pomgpu_tune_placement would leave this address dangling: it refuses from now on (pomgpu.h)
+  if (s == P3_taurstrb || s == P3_taurstrf) {                 // the caller may write the rate through the address at any time: k_ts_update reads both arrays from now on
+    c->tau_handed = 1;
+    pomgpu_tau_touched(c, s == P3_taurstrf);
+  }
   return SLOT3(c, s);
 }
 extern "C" int pomgpu_bind_host(pomgpu_ctx *c, const double *h2, const double *h3) {
@@ -669,6 +673,16 @@ extern "C" int pomgpu_set_restore_record(pomgpu_ctx *c, int n, const double *tr,
   HIPCHK(c, hipMemcpyAsync(c->rec_t[n], tr, cnt * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->rec_s[n], sr, cnt * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_set_restore_rate_record(pomgpu_ctx *c, int n, const double *tau) {
+  if (!c || n < 1 || n > POMGPU_MAXREC || !tau) return POMGPU_EINVAL;
+  if (pomgpu_ff_has(c, 3)) return fail(c, POMGPU_EINVAL, "set_restore_rate_record: the restore rate comes from a file (pomgpu_set_restore_rate_file)");
+  const size_t cnt = (size_t)c->P.im * c->P.jm * c->P.kb;
+  if (!c->rec_tau[n]) HIPCHK(c, hipMalloc((void **)&c->rec_tau[n], cnt * sizeof(double)));
+  HIPCHK(c, hipMemcpyAsync(c->rec_tau[n], tau, cnt * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->tau_gen++;                                               // what an array was made from under this number before is not this record
   return POMGPU_OK;
 }
 extern "C" int pomgpu_set_exchange(pomgpu_ctx *c, pomgpu_exchange_fn fn, void *user) {
@@ -709,6 +723,9 @@ static double *dev3(pomgpu_ctx *c, const double *host) {
   if (!c->host3 || !host) return NULL;
   const ptrdiff_t off = host - c->host3;
   if (off < 0 || (size_t)off >= (size_t)POM_NBLK3D * c->P.n3 || (size_t)off % c->P.n3) return NULL;
+  // an array argument of a stand-alone entry point may be written (ztosig's t, dens's rhoo, advt's ff ...): a rate array among them is no longer the library's
+  if ((size_t)off / c->P.n3 == P3_taurstrb) pomgpu_tau_touched(c, 0);
+  if ((size_t)off / c->P.n3 == P3_taurstrf) pomgpu_tau_touched(c, 1);
   return SLOT3(c, (size_t)off / c->P.n3);
 }
 static double *dev2(pomgpu_ctx *c, const double *host) {
@@ -872,25 +889,51 @@ static int restore_prepare(pomgpu_ctx *c, double *fold_out, double *fnew_out) { 
   const double trst = 30.;
   const int irst = (int)(trst * 86400. / k.dti);
   const int ntime = (int)(k.time / trst);
+  // One load of record n: "taurstrf = 1./trst" over the whole padded array as ever, then the rate that goes with T/S record n -- (a) a rate
+  // file: record n's window mapped by k_ztosig straight into taurstrf, (b) a rate record n: taurstrf(1:im,1:jm,1:kb) = tau, (c) neither.
+  // Whether every record is there is settled before a slot or a mirror is written.
   auto load = [&](int n) -> int {
+    const int rfile = pomgpu_ff_has(c, 3), steady = rfile && pomgpu_ff_rate_steady(c);
+    if (rfile) { const int rc = pomgpu_ff_rate_have(c, n); if (rc) return rc; }
+    const double *tr, *sr;
     if (pomgpu_ff_has(c, 2)) {                                  // read_restore_ts_interior_pnetcdf(n, ...) from the file
       const int rc = pomgpu_ff_fetch_restore(c, n);
       if (rc) return rc;
-      launch_restore_load(c, c->rec_t[0], c->rec_s[0], 1. / trst);
-      c->tau_known[1] = 1; c->tau_val[1] = 1. / trst;
-      return POMGPU_OK;
+      tr = c->rec_t[0]; sr = c->rec_s[0];
+    } else {
+      if (n < 1 || n > POMGPU_MAXREC || !c->rec_t[n])
+        return fail(c, POMGPU_EINVAL, "restore_interior: record %d was not supplied (pomgpu_set_restore_record)", n);
+      tr = c->rec_t[n]; sr = c->rec_s[n];
     }
-    if (n < 1 || n > POMGPU_MAXREC || !c->rec_t[n])
-      return fail(c, POMGPU_EINVAL, "restore_interior: record %d was not supplied (pomgpu_set_restore_record)", n);
-    launch_restore_load(c, c->rec_t[n], c->rec_s[n], 1. / trst);
-    c->tau_known[1] = 1; c->tau_val[1] = 1. / trst;             // "taurstrf = 1./trst", the whole array
+    const double *taur = !rfile && n >= 1 && n <= POMGPU_MAXREC ? c->rec_tau[n] : NULL;
+    const int keep = steady && c->rate_in_f && !c->tau_handed;  // the file's one record is in taurstrf already: the same bits
+    launch_restore_load(c, tr, sr, 1. / trst, taur, !keep);
+    if (rfile) {
+      c->tau_known[1] = 0;
+      if (!keep) {
+        c->rate_in_f = 0; c->tau_id[1] = 0;
+        const int rc = pomgpu_ff_fetch_rate(c, n);
+        if (rc) return rc;
+        c->rate_in_f = steady;
+        c->tau_id[1] = (c->tau_gen << 32) | (long)(steady ? 1 : n + 1);
+      }
+    } else if (taur) {
+      c->tau_known[1] = 0; c->rate_in_f = 0;
+      c->tau_id[1] = (c->tau_gen << 32) | (long)(n + 1);
+    } else {
+      c->tau_known[1] = 1; c->tau_val[1] = 1. / trst;             // "taurstrf = 1./trst", the whole array
+      c->tau_id[1] = 0; c->rate_in_f = 0;
+    }
     return POMGPU_OK;
   };
-  if (k.iint == 2) { int rc = load((k.iint / irst) + 1); if (rc) return rc; }
+  auto same = [&]() { c->tau_same = !c->tau_handed && !c->tau_known[0] && !c->tau_known[1] && c->tau_id[0] && c->tau_id[0] == c->tau_id[1]; };
+  if (k.iint == 2) { c->tau_same = 0; int rc = load((k.iint / irst) + 1); if (rc) return rc; }
   if (k.iint == 2 || (irst > 0 && k.iint % irst == 0)) {
+    c->tau_same = 0;
     launch_restore_shift(c);
-    c->tau_known[0] = c->tau_known[1]; c->tau_val[0] = c->tau_val[1];
+    c->tau_known[0] = c->tau_known[1]; c->tau_val[0] = c->tau_val[1]; c->tau_id[0] = c->tau_id[1];
     if (k.iint != k.iend) { int rc = load((k.iint + irst) / irst + 1); if (rc) return rc; }
+    same();
   }
   *fnew_out = k.time / trst - ntime;
   *fold_out = 1. - *fnew_out;
@@ -1034,7 +1077,7 @@ void pomgpu_cold_tail(pomgpu_ctx *c, void (*update_initial)(pomgpu_ctx *), void 
   update_initial(c);
   if (c->con.npg == 2) seq_baropg_mcc(c); else seq_baropg(c);
   sums(c);
-  c->tau_known[0] = c->tau_known[1] = 0;                       // taurstrb, taurstrf are zero arrays now, not the library's value
+  pomgpu_tau_touched(c, 0); pomgpu_tau_touched(c, 1);         // taurstrb, taurstrf are zero arrays now, not the library's value
   pomgpu_mirrors_written(c);
 }
 extern "C" int pomgpu_get_time(pomgpu_ctx *c) {               // advance.f:62-75

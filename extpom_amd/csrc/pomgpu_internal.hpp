@@ -710,6 +710,16 @@ struct pomgpu_ctx {
   // forms taurstr from the two scalars instead of reading two 3-D arrays.  Any upload of those arrays ends the knowledge.
   int tau_known[2];
   double tau_val[2];
+  // A rate FIELD (pomgpu_set_restore_rate_record / _file): restore_prepare puts record n's rate into taurstrf behind "taurstrf = 1./trst"
+  // and the knowledge above ends for that array.  tau_id: which record the library itself made the array from (0 = unknown: not the
+  // library's, or the scalar), handed from f to b by the shift; tau_gen makes the ids of a re-registered file or a record set again differ.
+  // tau_same: "b and f are the same array content" on (1:im, 1:jm, 1:kbm1) -- both made by the library from the same record, the steady
+  // sponge's case -- and k_ts_update reads taurstrf alone (k_ts_update<2>).  rate_in_f: taurstrf holds the one record of a steady rate
+  // file (padding 1./trst included), so the next load skips the read and the map.  Whatever writes either array from outside the step
+  // ends all of it (pomgpu_tau_touched); an address handed out (pomgpu_device_3d) ends it for good (tau_handed).
+  double *rec_tau[POMGPU_MAXREC + 1];
+  long tau_id[2], tau_gen;
+  int tau_same, rate_in_f, tau_handed;
   // rho's round trip through rho - rmean (baropg, solver.f:854,937) has not been stored for levels 1..kbm1: inside
   // pomgpu_advance its only reader before dens rewrites rho is k_profq, which applies it to what it loads
   int rho_rt_pending;
@@ -893,7 +903,7 @@ void launch_mask_uv(pomgpu_ctx *c);
 void launch_mask_w(pomgpu_ctx *c);
 void launch_restore(pomgpu_ctx *c, double fold, double fnew);
 void launch_restore_shift(pomgpu_ctx *c);
-void launch_restore_load(pomgpu_ctx *c, const double *tr, const double *sr, double tau);
+void launch_restore_load(pomgpu_ctx *c, const double *tr, const double *sr, double tau, const double *taur = NULL, int fill_tau = 1);   // taur: an (im,jm,kb) rate record over the fill; fill_tau = 0: taurstrf stays as it is
 void launch_dens(pomgpu_ctx *c, const double *si, const double *ti, double *rhoo);
 void launch_realvertvl(pomgpu_ctx *c, int etf_is_et = 0);   // etf_is_et: read et where solver.f:2052 reads etf (a pending wr, pomgpu_ctx::wr_pending)
 // k_vert.hip
@@ -945,6 +955,15 @@ int pomgpu_ff_has(pomgpu_ctx *c, int src);
 int pomgpu_ff_fetch_surface(pomgpu_ctx *c, int kind, int n);                    // record n of kind 0..2 into frc_dev[kind][n % 4], frc_n set
 int pomgpu_ff_fetch_lateral(pomgpu_ctx *c, int n);                              // record n into lat_dev[n % 4], lat_n set
 int pomgpu_ff_fetch_restore(pomgpu_ctx *c, int n);                              // month mod(n+9,12)+1 into rec_t[0], rec_s[0]
+// the rate file (pomgpu_set_restore_rate_file; src 3).  steady: it has one record, which serves every n.  have: is record n inside the file
+// (nothing is written)?  fetch: record n's window, mapped by k_ztosig straight into the mirror taurstrf
+int pomgpu_ff_rate_steady(pomgpu_ctx *c);
+int pomgpu_ff_rate_have(pomgpu_ctx *c, int n);
+int pomgpu_ff_fetch_rate(pomgpu_ctx *c, int n);
+static inline void pomgpu_tau_touched(pomgpu_ctx *c, int which) {               // taurstrb (0) / taurstrf (1) is somebody else's now
+  c->tau_known[which] = 0; c->tau_id[which] = 0; c->tau_same = 0;
+  if (which) c->rate_in_f = 0;
+}
 void pomgpu_ff_free(pomgpu_ctx *c);
 // cdf_out.hip: ztosig (initialize.f:547-595).  launch_ztosig: the interior columns of `t` from the host's zs (ks values) and z-level source
 // (im_local, jm_local, ks), every other cell of (1:im, 1:jm) zero; synchronous, 0 or a pomgpu_status.  launch_ztosig_edges: the copies onto

@@ -38,6 +38,8 @@ end subroutine
 ! The three paths as the reference's readers build them (io_pnetcdf.F:2929, :3445, :3289: trim(wrk_pth)//'in/'//trim(netcdf_file)//
 ! '.sfrc.nc', '.lbry.nc', '.clim.nc'); those that exist are registered, this tile's patch at (i_global(1), j_global(1)).
 ! have_sfrc / have_lbry / have_clim: which did.  A file that exists and is refused: error_status = 1 and the library's message.
+! Next to them '.restore_tau_interior.nc' (io_pnetcdf.F:3067), the restore rate on z levels: registered when it exists
+! (pomgpu_set_restore_rate_file); restore_interior then maps the rate that goes with every T/S record it loads.
 subroutine pomgpu_open_forcing_files(have_sfrc, have_lbry, have_clim)
   use pomgpu_iface
   implicit none
@@ -46,11 +48,11 @@ subroutine pomgpu_open_forcing_files(have_sfrc, have_lbry, have_clim)
   type(pomgpu_file_meta) :: m
   character(len=400) :: fname
   character(len=256) :: wp
-  character(kind=c_char, len=401), target :: cname(3)
+  character(kind=c_char, len=401), target :: cname(3), rname
   character(len=8), parameter :: suffix(3) = (/ '.sfrc.nc', '.lbry.nc', '.clim.nc' /)
   character(kind=c_char), pointer :: msg(:)
   type(c_ptr) :: p(3), pm
-  logical :: have(3)
+  logical :: have(3), have_rate
   integer(c_int) :: rc
   integer :: q, n
   wp = wrk_pth                                     ! a namelist without wrk_pth leaves the COMMON member as the loader did: NULs, not blanks
@@ -65,14 +67,18 @@ subroutine pomgpu_open_forcing_files(have_sfrc, have_lbry, have_clim)
     if (have(q)) p(q) = c_loc(cname(q))
   end do
   have_sfrc = have(1); have_lbry = have(2); have_clim = have(3)
-  if (.not. any(have)) return
+  write(fname, '(a,''in/'',a,a)') trim(wp), trim(netcdf_file), '.restore_tau_interior.nc'
+  inquire(file=trim(fname), exist=have_rate)
+  rname = trim(fname)//c_null_char
+  if (.not. any(have) .and. .not. have_rate) return
   m%title = c_null_ptr; m%time_start = c_null_ptr; m%stats = c_null_ptr; m%create = 0
   m%im_global = im_global; m%jm_global = jm_global
   m%i0 = i_global(1); m%j0 = j_global(1)
   rc = 0
   if (have(3)) rc = pomgpu_set_z_inputs(pom_ctx, merge(1_c_int, 0_c_int, pom_init_on_z), merge(1_c_int, 0_c_int, pom_clim_on_z))   ! a z-level clim file: the months go through ztosig
   if (rc == 0 .and. have(2)) rc = pomgpu_set_z_lateral(pom_ctx, merge(1_c_int, 0_c_int, pom_lbry_on_z))   ! a z-level lbry file: every record's temp, salt lines go through ztosig
-  if (rc == 0) rc = pomgpu_set_forcing_files(pom_ctx, p(1), p(2), p(3), m)
+  if (rc == 0 .and. any(have)) rc = pomgpu_set_forcing_files(pom_ctx, p(1), p(2), p(3), m)
+  if (rc == 0 .and. have_rate) rc = pomgpu_set_restore_rate_file(pom_ctx, c_loc(rname), m)
   if (rc /= 0) then                                ! handle_error_pnetcdf, io_pnetcdf.F:43-54: a message and error_status = 1
     error_status = 1
     have_sfrc = .false.; have_lbry = .false.; have_clim = .false.

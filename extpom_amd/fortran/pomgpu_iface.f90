@@ -90,6 +90,12 @@ module pomgpu_iface
     integer(c_int) function pomgpu_set_forcing_files(ctx, sfrc, lbry, clim, meta) bind(C, name='pomgpu_set_forcing_files')
       import; type(c_ptr), value :: ctx, sfrc, lbry, clim; type(pomgpu_file_meta) :: meta   ! any path may be c_null_ptr
     end function
+    integer(c_int) function pomgpu_set_restore_rate_record(ctx, n, tau) bind(C, name='pomgpu_set_restore_rate_record')
+      import; type(c_ptr), value :: ctx, tau; integer(c_int), value :: n
+    end function
+    integer(c_int) function pomgpu_set_restore_rate_file(ctx, path, meta) bind(C, name='pomgpu_set_restore_rate_file')
+      import; type(c_ptr), value :: ctx, path; type(pomgpu_file_meta) :: meta
+    end function
     integer(c_int) function pomgpu_io_wait(ctx) bind(C, name='pomgpu_io_wait')
       import; type(c_ptr), value :: ctx
     end function

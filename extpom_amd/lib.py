@@ -70,6 +70,8 @@ _SIGS = {
     "pomgpu_get_con": (_I, [_P, _P]),
     "pomgpu_bind_host": (_I, [_P, _P, _P]),
     "pomgpu_set_restore_record": (_I, [_P, _I, _P, _P]),
+    "pomgpu_set_restore_rate_record": (_I, [_P, _I, _P]),
+    "pomgpu_set_restore_rate_file": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
     "pomgpu_set_forcing_record": (_I, [_P, _I, _I, _P, _P]),
     "pomgpu_set_lateral_record": (_I, [_P, _I, ctypes.POINTER(ctypes.c_void_p)]),
     "pomgpu_device_2d": (_P, [_P, _I]),

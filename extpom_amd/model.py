@@ -71,6 +71,27 @@ class PomGpu:
             tr = np.ascontiguousarray(tr, dtype=np.float64)
             sr = np.ascontiguousarray(sr, dtype=np.float64)
             self._chk(self.L.pomgpu_set_restore_record(self.h, n, self._p(tr), self._p(sr)), "set_restore_record")
+        if getattr(st, "restore_rate_records", None):
+            self.set_restore_rate_records(st.restore_rate_records)
+
+    def set_restore_rate_records(self, records):
+        """pomgpu_set_restore_rate_record: records[n-1], (kb, jm, im) in 1/day on the sigma levels, is the restore rate that goes with
+        T/S record n (a sponge); None leaves that record's rate at the reference's 1/trst"""
+        for n, tau in enumerate(records, start=1):
+            if tau is None:
+                continue
+            tau = np.ascontiguousarray(tau, dtype=np.float64)
+            if tau.shape != (self.st.kb, self.st.jm, self.st.im):
+                raise ValueError(f"set_restore_rate_records: record {n} is {tau.shape}, not (kb, jm, im) = {(self.st.kb, self.st.jm, self.st.im)}")
+            self._chk(self.L.pomgpu_set_restore_rate_record(self.h, n, self._p(tau)), "set_restore_rate_record")
+
+    def set_restore_rate_file(self, path, im_global=None, jm_global=None):
+        """pomgpu_set_restore_rate_file: restore_interior takes the rate that goes with T/S record n from record n of this classic NetCDF
+        file (`z`, and `tau` on its levels; one record serves every n) and maps it onto the sigma levels with ztosig, on the device.  This
+        tile's patch starts at (i_off+1, j_off+1) of the global grid, as in set_forcing_files."""
+        st = self.st
+        m = _lib.FileMeta(b"", b"", im_global or st.im, jm_global or st.jm, st.i_off + 1, st.j_off + 1, 0, None)
+        self._chk(self.L.pomgpu_set_restore_rate_file(self.h, None if path is None else str(path).encode(), ctypes.byref(m)), "set_restore_rate_file")
 
     def set_forcing_records(self, first: int = 1, count: int = 4):
         """hand records first..first+count-1 of st.forcing_records (wind / heat / surface) to the library: what the

@@ -83,10 +83,33 @@ int pomgpu_bind_host(pomgpu_ctx *ctx, const double *host_blk2d, const double *ho
  * arrays dimensioned (im,jm,kb).  Copied to the device.  Refused (POMGPU_EINVAL) once the records come from a file
  * (pomgpu_set_forcing_files). */
 int pomgpu_set_restore_record(pomgpu_ctx *ctx, int n, const double *tr, const double *sr);
+/* The restore RATE as a field -- a sponge: taurstr(i,j,k) in 1/day, which the reference keeps in COMMON and never fills (it assigns
+ * taurstrf = 1./trst and leaves read_restore_tau_interior_pnetcdf + ztosig commented, bounds_forcing.f:1049-1051, :1076-1079).
+ * pomgpu_set_restore_rate_record: `tau`, (im,jm,kb) on the sigma levels, is the rate that goes with T/S record n (1..POMGPU_MAXREC; same
+ * lifetime and copy as pomgpu_set_restore_record).  Refused (POMGPU_EINVAL) once the rate comes from a file.
+ * pomgpu_set_restore_rate_file: the reference's reader without PnetCDF, registered like the files of pomgpu_set_forcing_files (its parser,
+ * checks, pinned buffers; of `meta` only im_global, jm_global, i0, j0; not collective, no message round).  Classic NetCDF (CDF-1 / CDF-2),
+ * variables BY NAME: `z`, 1-D NC_FLOAT / NC_DOUBLE, ks values, 2 <= ks <= 300, finite and strictly increasing; `tau`, NC_FLOAT / NC_DOUBLE,
+ * (ks, jm_global, im_global) with or without a leading record dimension (unlimited or fixed).  Anything else -- a file shorter than its
+ * header says, a tile whose window (one more column / row towards every neighbour) does not fit the grid, im or jm below 4, a NULL path --
+ * is refused before anything changes, with POMGPU_EINVAL, error_status = 1 and the file and the cause in pomgpu_last_error.  Buffers and
+ * ztosig's table are allocated here; a step allocates nothing.
+ * The rate that accompanies T/S record n is record n (1-based) of the file; a file with exactly one record, or without a record dimension,
+ * serves every n, is read and mapped once, and later loads skip both.  A record beyond the file's count or end fails that step before any
+ * slot is written.
+ * A load of record n in restore_interior (T/S by setter or from the clim file alike) assigns taurstrf = 1./trst over the whole padded array
+ * as ever, then (a) with a rate file: the ks levels of the tile's window are mapped by ztosig (initialize.f:547-595) straight into the
+ * mirror taurstrf -- all kb levels of (1:im, 1:jm), the +0.0 of dry and rim columns and the copies onto physical edges included, the padding
+ * keeps 1./trst; on the stream of the step; the fp32 builds round once at the store -- or (b) with a rate record n: taurstrf(1:im,1:jm,1:kb)
+ * = tau, or (c) neither: nothing more.  Two properties of the map are the reference's own: a rate below the REAL(4) 0.01 on a level the
+ * depth covers counts as MISSING and is filled from the neighbour maximum or the level above (a sponge's edge creeps by a cell), and the
+ * natural spline may undershoot below zero.  A host that wants exact rates uses the sigma-level setter. */
+int pomgpu_set_restore_rate_record(pomgpu_ctx *ctx, int n, const double *tau);   /* pomgpu_set_restore_rate_file: declared beside pomgpu_set_forcing_files */
 /* Device address of a mirror (for halo exchange by the caller, e.g. RCCL send/recv).  An address of a 3-D array stays valid until
  * pomgpu_destroy -- pomgpu_tune_placement, which moves those arrays, refuses once one has been handed out.  Through an address the
  * caller reads and writes behind the library's back: a pending wr (see pomgpu_run) is formed before the address is returned, and from
- * then on the context forms wr at the end of every step. */
+ * then on the context forms wr at the end of every step.  An address of taurstrb or taurstrf ends what the library knows about the restore
+ * rate for good: every step reads both arrays from then on. */
 double *pomgpu_device_2d(pomgpu_ctx *ctx, int slot2d);
 double *pomgpu_device_3d(pomgpu_ctx *ctx, int slot3d);
 
@@ -374,6 +397,8 @@ int pomgpu_set_z_lateral(pomgpu_ctx *ctx, int lbry_on_z);
  * record beyond the file's count or end (looked at once more: the file may have grown) fails that step the same way, before the record
  * slot is written. */
 int pomgpu_set_forcing_files(pomgpu_ctx *ctx, const char *sfrc, const char *lbry, const char *clim, const pomgpu_file_meta *meta);
+/* the restore rate's file: see pomgpu_set_restore_rate_record above */
+int pomgpu_set_restore_rate_file(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta);
 
 /* One internal step for the current blkcon.iint: get_time, [surface_forcing, lateral_bc -- once the host has named
  * forcing files or supplied forcing / lateral records, see above; skipped otherwise: constant forcing], lateral_viscosity,
