@@ -1060,7 +1060,7 @@ int pomgpu_materialize(pomgpu_ctx *c) {
   NEED(c);
   return POMGPU_OK;
 }
-// pomgpu_read_restart (cdf_out.hip) has written 2-D and 3-D mirrors with its own kernel: what pomgpu_upload_2d invalidates for
+// pomgpu_read_restart (cdf_in.hip) has written 2-D and 3-D mirrors with its own kernel: what pomgpu_upload_2d invalidates for
 // those slots (none of them is a mask or a taurstr array; upload_3d invalidates nothing else)
 void pomgpu_mirrors_written(pomgpu_ctx *c) {
   c->uvm_valid = 0;                                           // u, v are the file's now
@@ -1068,9 +1068,9 @@ void pomgpu_mirrors_written(pomgpu_ctx *c) {
   early_invalidate(c);
   refresh_coefs(c);
 }
-// pomgpu_cold_start (cdf_out.hip) has filled the grid, tb sb t s and tclim sclim: the rest of initial_conditions and update_initial
+// pomgpu_cold_start (cdf_in.hip) has filled the grid, tb sb t s and tclim sclim: the rest of initial_conditions and update_initial
 // (initialize.f:416-425, :472-518) in the reference's order, with the launchers the stand-alone entry points use; the two kernels of
-// cdf_out.hip come in as functions.  Then what pomgpu_upload of all blocks invalidates.  The caller has vetted npg
+// cdf_in.hip come in as functions.  Then what pomgpu_upload of all blocks invalidates.  The caller has vetted npg
 void pomgpu_cold_tail(pomgpu_ctx *c, void (*update_initial)(pomgpu_ctx *), void (*sums)(pomgpu_ctx *)) {
   launch_dens(c, D3(c, sclim), D3(c, tclim), D3(c, rmean));
   launch_dens(c, D3(c, sb), D3(c, tb), D3(c, rho));

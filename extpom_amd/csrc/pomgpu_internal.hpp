@@ -762,10 +762,10 @@ struct pomgpu_ctx {
   unsigned *ext_bar;         // device: arrival counter + abort word of k_ext_loop's grid barrier (k_ext.hip)
   unsigned ext_bar_base;     // the counter's value when the next k_ext_loop starts (every workgroup arrives once per barrier)
   int ext_loop_off;          // a k_ext_loop launch of this context gave up at its barrier: the substeps run as launches of their own from then on
-  void *io_job;              // the output / restart file being written behind the model's back (cdf_out.hip), NULL = none
-  int z_init, z_clim;        // pomgpu_set_z_inputs: the init / clim file holds z levels and goes through ztosig (cdf_out.hip)
-  int z_lbry;                // pomgpu_set_z_lateral: temp, salt of the lbry file are on z levels and go through k_ztosig_line (cdf_out.hip)
-  void *frc_files;           // pomgpu_set_forcing_files: the open forcing files and their read buffers (cdf_out.hip), NULL = none
+  void *io_job;              // the output / restart file being written behind the model's back (cdf_out.hip, the writer), NULL = none
+  int z_init, z_clim;        // pomgpu_set_z_inputs: the init / clim file holds z levels and goes through ztosig (cdf_in.hip)
+  int z_lbry;                // pomgpu_set_z_lateral: temp, salt of the lbry file are on z levels and go through k_ztosig_line (cdf_in.hip sets it, frc_files.hip reads it)
+  void *frc_files;           // pomgpu_set_forcing_files: the open forcing files and their read buffers (frc_files.hip), NULL = none
   int launch_err;            // first hipError_t a kernel launch returned (0 = none); reported by the next sync / get_con
   char err[512];
 };
@@ -950,7 +950,7 @@ void pomgpu_cold_tail(pomgpu_ctx *c, void (*update_initial)(pomgpu_ctx *), void 
 int pomgpu_side_stream(pomgpu_ctx *c);                                          // create the side stream and its events (pomgpu_api.hip); 1 = there
 int pomgpu_tp_side_ok(pomgpu_ctx *c);                                           // can rounds run on the side stream (second communicator / callback mover)?
 int pomgpu_tp_move_side(pomgpu_ctx *c, const size_t *scount, const size_t *rcount);   // send2 / recv2, on c->side
-// cdf_out.hip: forcing records from the files pomgpu_set_forcing_files named (src 0 = sfrc, 1 = lbry, 2 = clim)
+// frc_files.hip: forcing records from the files pomgpu_set_forcing_files named (src 0 = sfrc, 1 = lbry, 2 = clim)
 int pomgpu_ff_has(pomgpu_ctx *c, int src);
 int pomgpu_ff_fetch_surface(pomgpu_ctx *c, int kind, int n);                    // record n of kind 0..2 into frc_dev[kind][n % 4], frc_n set
 int pomgpu_ff_fetch_lateral(pomgpu_ctx *c, int n);                              // record n into lat_dev[n % 4], lat_n set
@@ -965,7 +965,7 @@ static inline void pomgpu_tau_touched(pomgpu_ctx *c, int which) {               
   if (which) c->rate_in_f = 0;
 }
 void pomgpu_ff_free(pomgpu_ctx *c);
-// cdf_out.hip: ztosig (initialize.f:547-595).  launch_ztosig: the interior columns of `t` from the host's zs (ks values) and z-level source
+// ztosig.hip: ztosig (initialize.f:547-595).  launch_ztosig: the interior columns of `t` from the host's zs (ks values) and z-level source
 // (im_local, jm_local, ks), every other cell of (1:im, 1:jm) zero; synchronous, 0 or a pomgpu_status.  launch_ztosig_edges: the copies onto
 // physical edges, after the exchange
 int launch_ztosig(pomgpu_ctx *c, double *t, const double *zs, int ks, const double *src);

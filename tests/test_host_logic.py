@@ -384,6 +384,27 @@ def test_short_wave_term_in_double_double_equals_the_quad_evaluation(tmp_path):
     assert r.returncode == 0 and " 0 results differ" in r.stdout, r.stdout[-500:]
 
 
+def test_header_parser_survives_damaged_headers_under_sanitizers(tmp_path):
+    """csrc/cdf_io.hpp's host part (read_header, check_var: what every file reader of the library runs before it touches the state) as a
+    stand-alone program under AddressSanitizer and UBSan (tools/check_cdf_header.cpp): the three classic files of tests/golden/
+    (tests/golden/make_cdf_header_fixtures.py) intact, with every header word overwritten by 0xffffffff in turn and cut to every prefix of
+    their headers.  Refusals are expected; a crash or a sanitizer report fails the run."""
+    import shutil
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    san = ["g++", "-std=c++17", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    probe = tmp_path / "probe.cpp"
+    probe.write_text("int main() { return 0; }\n")
+    if subprocess.run(san + ["-o", str(tmp_path / "probe"), str(probe)], capture_output=True).returncode != 0 or subprocess.run([str(tmp_path / "probe")]).returncode != 0:
+        pytest.skip("the sanitizer runtime is not installed")
+    exe = str(tmp_path / "check_cdf_header")
+    build = subprocess.run(san + ["-I" + os.path.join(ROOT, "extpom_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tools", "check_cdf_header.cpp")], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-2000:]
+    files = [os.path.join(ROOT, "tests", "golden", f"cdf_header_{n}.nc") for n in ("grid", "clim", "restart")]
+    r = subprocess.run([exe, *files], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "CDF-HEADER-OK" in r.stdout and r.stdout.count("damaged words") == 3, r.stdout[-1000:] + r.stderr[-3000:]
+
+
 @pytest.mark.bg_oracle("seamount", 33, 29, 9, 2)
 def test_background_oracle_leaves_the_digests_of_an_in_process_run(bg_oracle):
     """tests/oracle_bg.py + tests/conftest.py: the child process that computes the full-size oracle steps beside the GPU tests
