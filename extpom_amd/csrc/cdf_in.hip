@@ -294,6 +294,15 @@ extern "C" int pomgpu_set_z_lateral(pomgpu_ctx *c, int lbry_on_z) {
   return POMGPU_OK;
 }
 
+extern "C" int pomgpu_set_lateral_sides(pomgpu_ctx *c, int sides) {
+  if (!c) return POMGPU_EINVAL;
+  if (sides < 1 || sides > 15) return fail(c, POMGPU_EINVAL, "set_lateral_sides: the mask %d is outside 1..15 (east 1, south 2, west 4, north 8)", sides);
+  if (pomgpu_ff_has(c, 1) && sides != c->lbry_sides)
+    return fail(c, POMGPU_EINVAL, "set_lateral_sides: an lbry file is registered (pomgpu_set_forcing_files) under the mask %d, not %d", c->lbry_sides, sides);
+  c->lbry_sides = sides;
+  return POMGPU_OK;
+}
+
 extern "C" int pomgpu_cold_start(pomgpu_ctx *c, const char *grid, const char *init, const char *clim, const pomgpu_file_meta *m, pomgpu_cold_info *info) {
   if (!c || !grid || !init || !clim || !m) return POMGPU_EINVAL;
   (void)hipSetDevice(c->device);

@@ -385,7 +385,7 @@ void ztosig_table(const double *zs, int ks, double *tab);
 void launch_ztosig_window(pomgpu_ctx *c, double *out, int record, const ZWindow &Z, int q);
 // the lines of an lbry file on z levels
 struct ZtlLine { double *out; const void *src; int fmt, edge, n, npad, lo, hi, sp, so, op; };
-struct ZtlJob { ZtlLine l[4]; };
+struct ZtlJob { ZtlLine l[8]; };                                // temp, salt of up to four sides
 ZtlLine ztosig_line_of(const KP &P, int edge, double *out, const void *src, int fmt, int sp, int so);
 void launch_ztosig_lines(pomgpu_ctx *c, const ZtlJob &job, int nlines, const double *tab, double *wa, double *wb, int ks, int pitch);
 #endif

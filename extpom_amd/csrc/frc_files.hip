@@ -16,8 +16,11 @@ struct FFiles {
   int im_global = 0, jm_global = 0, i0 = 1, j0 = 1;
   BandReader rd;                                                // sized at registration, never inside a step; copies on c->cur
   ZWindow z;                                                    // a clim file on z levels (pomgpu_set_z_inputs); z.ks[0] = 0: it is on the sigma levels
-  // an lbry file on z levels (pomgpu_set_z_lateral): its level count, the window points of the east lines (lwj, lwn: towards the south, north
-  // neighbour) and of the south lines (lwi, lwe), and one allocation: ztosig's table, then the two work arrays of the record's four lines
+  // the lbry file's sides that are ON (pomgpu_set_lateral_sides, as registered) and what s[1].v[j] is: lq[j], LatSrc's number, lnv of them
+  int lsides = 0, lnv = 0, lq[20];
+  // an lbry file on z levels (pomgpu_set_z_lateral): its level count, the window points of the east and west lines (lwj, lwn: towards the
+  // south, north neighbour) and of the south and north lines (lwi, lwe), and one allocation: ztosig's table, then the two work arrays of
+  // eight lines (temp, salt of four sides)
   int lks = 0, lwi = 0, lwe = 0, lwj = 0, lwn = 0;
   double *ldev = NULL;
   // the rate file: `tau` on the levels of its `z`, always through ztosig; rsteady: it holds one record (or has no record dimension), which
@@ -27,7 +30,8 @@ struct FFiles {
 };
 static const char *const FF_WHAT[3] = {"sfrc", "lbry", "clim"};
 static const char *const FF_SFRC[6] = {"sustr", "svstr", "shflux", "swrad", "SST", "SSS"};
-static const char *const FF_LBRY[10] = {"zeta.east", "zeta.south", "u.east", "v.east", "temp.east", "salt.east", "u.south", "v.south", "temp.south", "salt.south"};
+static const char *const FF_LBRY[20] = {"zeta.east",  "u.east",  "v.east",  "temp.east",  "salt.east",  "zeta.south", "u.south", "v.south", "temp.south", "salt.south",   // LatSrc's numbers
+                                        "zeta.west",  "u.west",  "v.west",  "temp.west",  "salt.west",  "zeta.north", "u.north", "v.north", "temp.north", "salt.north"};
 const char *const FF_CLIM[2] = {"Tclim", "Sclim"};
 static const char *const FF_RATE[1] = {"tau"};
 
@@ -77,13 +81,42 @@ __global__ void k_frc_unpack(KP P, int kind, double *da, double *db, const void 
 }
 // One record of read_boundary_conditions_pnetcdf (:3426-3614) into the 20 concatenated arrays pomgpu_set_lateral_record fills (the order
 // of the reader's arguments; k_lateral's phase 0 consumes them).  One thread per edge point, as in k_lateral.  From the file, compact
-// (the tile's jm or im values per level): src[0] zeta.east, [1] zeta.south, [2..5] u v temp salt .east, [6..9] u v temp salt .south;
-// f32 bit q: that variable is NC_FLOAT.  t_w s_w / t_n s_n: line i = 1 / j = jm of tclim, sclim; u_w v_w u_n v_n: zero; everything
-// beyond jm / im: zero, but in the elevations, which the reader leaves as they are there -- as it leaves elw, eln everywhere.
-// zts (an lbry file on z levels): temp / salt .east / .south hold other levels and are left to k_ztosig_line, which fills those four arrays.
-struct LatSrc { const void *p[10]; unsigned f32; int zts; };
-__device__ __forceinline__ double lat_raw(const LatSrc &s, int q, size_t at) { return (s.f32 >> q) & 1u ? CdfRaw<float>::get(s.p[q], at) : CdfRaw<double>::get(s.p[q], at); }
-__global__ void k_lat_unpack(KP P, double *rec, LatSrc s) {
+// (the tile's jm or im values per level): src 5 * side + (0 zeta, 1 u, 2 v, 3 temp, 4 salt), side 0 east, 1 south, 2 west, 3 north -- the
+// edge numbers of k_ztosig_line; f32 bit q: that variable is NC_FLOAT.  `sides` (pomgpu_set_lateral_sides, bit = side; a kernel argument:
+// every side's branch is uniform across the grid): a side that is ON takes its four (., kb) arrays and its elevation line from the file;
+// one that is OFF has t s from the line of tclim, sclim next to it (i = 1, i = im, j = 1, j = jm: :3606-3614 and the commented :3607-3608,
+// :3612-3613), u v zero and its elevation line as the state holds it (:3393-3621 never writes elw, eln).  Everything beyond jm / im: zero,
+// but in the elevations, which the reader leaves as they are there.  The arrays of a side in the reader's order: t s u v west and east,
+// t s v u north and south.
+// zts (an lbry file on z levels): temp / salt of the ON sides hold other levels and are left to k_ztosig_line, which fills those arrays.
+// Source q lies at base + off[q] (8-byte aligned); a variable of a side that is OFF has none.  The table reaches the kernel through memory
+// -- it travels behind the data in the fetch's one copy -- and not as an argument: twenty sources held in scalar registers beside KP for
+// the whole kernel spilled 79 of them; read where a side's loop needs them they spill none.
+struct LatSrc { const unsigned char *base; unsigned off[20]; unsigned f32; int zts; };
+__device__ __forceinline__ double lat_raw(const LatSrc &s, int q, size_t at) {
+  const void *p = s.base + s.off[q];
+  return (s.f32 >> q) & 1u ? CdfRaw<float>::get(p, at) : CdfRaw<double>::get(p, at);
+}
+// level k of the four arrays of `side` (n values each from r) at the point whose place in them is o and in the file's compact level f;
+// (ci, cj): the cell of tclim, sclim next to the point
+__device__ __forceinline__ void lat_four(const KP &P, const LatSrc &s, int sides, int side, double *r, size_t n, size_t o, size_t f, bool in, int ci, int cj, int k) {
+  const int q = 5 * side, qa = q + ((side & 1) ? 2 : 1), qb = q + ((side & 1) ? 1 : 2);   // south, north: v before u
+  if ((sides >> side) & 1) {
+    if (!s.zts) {
+      r[o] = in ? lat_raw(s, q + 3, f) : 0.;
+      r[n + o] = in ? lat_raw(s, q + 4, f) : 0.;
+    }
+    r[2 * n + o] = in ? lat_raw(s, qa, f) : 0.;
+    r[3 * n + o] = in ? lat_raw(s, qb, f) : 0.;
+  } else {
+    r[o] = in ? (double)F3(tclim, ci, cj, k) : 0.;
+    r[n + o] = in ? (double)F3(sclim, ci, cj, k) : 0.;
+    r[2 * n + o] = 0.;
+    r[3 * n + o] = 0.;
+  }
+}
+__global__ void k_lat_unpack(KP P, double *__restrict__ rec, const LatSrc *__restrict__ sp, int sides) {
+  const LatSrc &s = *sp;
   const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   const int kb = P.kb, jml = P.jml, iml = P.iml;
   if (t >= jml + iml) return;
@@ -94,39 +127,37 @@ __global__ void k_lat_unpack(KP P, double *rec, LatSrc s) {
     const bool in = a <= P.jm;
     for (int k = 1; k <= kb; k++) {
       const size_t o = (size_t)(k - 1) * jml + (a - 1), f = (size_t)(k - 1) * P.jm + (a - 1);
-      rec[o] = in ? (double)F3(tclim, 1, a, k) : 0.;
-      rec[njk + o] = in ? (double)F3(sclim, 1, a, k) : 0.;
-      rec[2 * njk + o] = 0.;
-      rec[3 * njk + o] = 0.;
-      if (!s.zts) {
-        rec[4 * njk + o] = in ? lat_raw(s, 4, f) : 0.;
-        rec[5 * njk + o] = in ? lat_raw(s, 5, f) : 0.;
-      }
-      rec[6 * njk + o] = in ? lat_raw(s, 2, f) : 0.;
-      rec[7 * njk + o] = in ? lat_raw(s, 3, f) : 0.;
+      lat_four(P, s, sides, 2, rec, njk, o, f, in, 1, a, k);
     }
-    e[a - 1] = BD1(elw, a);
-    e[jml + a - 1] = in ? lat_raw(s, 0, (size_t)(a - 1)) : BD1(ele, a);
+    for (int k = 1; k <= kb; k++) {                               // (a loop per side: either needs the sources of one side alone)
+      const size_t o = (size_t)(k - 1) * jml + (a - 1), f = (size_t)(k - 1) * P.jm + (a - 1);
+      lat_four(P, s, sides, 0, rec + 4 * njk, njk, o, f, in, P.im, a, k);
+    }
+    e[a - 1] = (sides & 4) && in ? lat_raw(s, 10, (size_t)(a - 1)) : BD1(elw, a);
+    e[jml + a - 1] = (sides & 1) && in ? lat_raw(s, 0, (size_t)(a - 1)) : BD1(ele, a);
   } else {
     const int a = t - jml + 1;
     const bool in = a <= P.im;
     double *r = rec + 8 * njk;
     for (int k = 1; k <= kb; k++) {
       const size_t o = (size_t)(k - 1) * iml + (a - 1), f = (size_t)(k - 1) * P.im + (a - 1);
-      r[o] = in ? (double)F3(tclim, a, P.jm, k) : 0.;
-      r[nik + o] = in ? (double)F3(sclim, a, P.jm, k) : 0.;
-      r[2 * nik + o] = 0.;
-      r[3 * nik + o] = 0.;
-      if (!s.zts) {
-        r[4 * nik + o] = in ? lat_raw(s, 8, f) : 0.;
-        r[5 * nik + o] = in ? lat_raw(s, 9, f) : 0.;
-      }
-      r[6 * nik + o] = in ? lat_raw(s, 7, f) : 0.;
-      r[7 * nik + o] = in ? lat_raw(s, 6, f) : 0.;
+      lat_four(P, s, sides, 3, r, nik, o, f, in, a, P.jm, k);
     }
-    e[2 * (size_t)jml + a - 1] = BD1(eln, a);
-    e[2 * (size_t)jml + iml + a - 1] = in ? lat_raw(s, 1, (size_t)(a - 1)) : BD1(els, a);
+    for (int k = 1; k <= kb; k++) {
+      const size_t o = (size_t)(k - 1) * iml + (a - 1), f = (size_t)(k - 1) * P.im + (a - 1);
+      lat_four(P, s, sides, 1, r + 4 * nik, nik, o, f, in, a, 1, k);
+    }
+    e[2 * (size_t)jml + a - 1] = (sides & 8) && in ? lat_raw(s, 15, (size_t)(a - 1)) : BD1(eln, a);
+    e[2 * (size_t)jml + iml + a - 1] = (sides & 2) && in ? lat_raw(s, 5, (size_t)(a - 1)) : BD1(els, a);
   }
+}
+// the variables of the ON sides in the order they are looked up -- the elevations, then u v temp salt of every side; the sides east,
+// south, west, north -- as LatSrc's numbers into lq; their count
+static int lat_vars(int sides, int *lq) {
+  int n = 0;
+  for (int sd = 0; sd < 4; sd++) if ((sides >> sd) & 1) lq[n++] = 5 * sd;
+  for (int sd = 0; sd < 4; sd++) if ((sides >> sd) & 1) for (int v = 1; v <= 4; v++) lq[n++] = 5 * sd + v;
+  return n;
 }
 
 static FFiles *FF(pomgpu_ctx *c) { return (FFiles *)c->frc_files; }
@@ -208,8 +239,13 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
     return fail(c, POMGPU_EINVAL, "set_forcing_files: %s: the tile (%d..%d, %d..%d) with its window lines towards every neighbour does not fit the global grid %d x %d", clim,
                 m->i0, m->i0 + P.im - 1, m->j0, m->j0 + P.jm - 1, m->im_global, m->jm_global);
   // an lbry file on z levels (pomgpu_set_z_lateral): the fill-in of a line point looks at the points before and after it, so the fetch reads one
-  // more point of temp / salt towards every neighbour of the tile: .east towards the south and north one, .south towards the west and east one
+  // more point of temp / salt towards every neighbour of the tile: .east / .west towards the south and north one, .south / .north towards the
+  // west and east one
   const int zl = lbry && c->z_lbry, lwi = zl && !P.W, lwe = zl && !P.E, lwj = zl && !P.S, lwn = zl && !P.N;
+  // the lbry file's variables: those of the sides that are ON (pomgpu_set_lateral_sides), a side's along j (east, west) or i
+  int lq[20];
+  const int sides = c->lbry_sides, lnv = lat_vars(sides, lq);
+  const size_t nej = (size_t)((sides & 1) + ((sides >> 2) & 1)), nei = (size_t)(((sides >> 1) & 1) + ((sides >> 3) & 1));
   if (zl && (P.im < 4 || P.jm < 4)) return fail(c, POMGPU_EINVAL, "set_forcing_files: %s: a z-level lbry file needs a tile of at least 4 x 4 cells, this one has %d x %d", lbry, P.im, P.jm);
   if (!tile_fits(m, P, lwi, lwe, lwj, lwn))
     return fail(c, POMGPU_EINVAL, "set_forcing_files: %s: the tile (%d..%d, %d..%d) with its window points towards every neighbour does not fit the global grid %d x %d", lbry,
@@ -239,7 +275,16 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
     else if (q == 1) {
       if (zl) why = z_levels(H, S, "z", llev);
       const uint64_t kl = zl && why.empty() ? (uint64_t)llev.size() : kb;   // temp, salt on the levels of z; u, v stay on the sigma levels
-      if (why.empty()) why = ff_check(H, S, FF_LBRY, {{jmg}, {img}, {kb, jmg}, {kb, jmg}, {kl, jmg}, {kl, jmg}, {kb, img}, {kb, img}, {kl, img}, {kl, img}}, 1);
+      const char *names[20];
+      std::vector<std::vector<uint64_t>> want;
+      for (int j = 0; j < lnv; j++) {
+        const int var = lq[j] % 5;
+        const uint64_t len = (lq[j] / 5) & 1 ? img : jmg;
+        names[j] = FF_LBRY[lq[j]];
+        if (var == 0) want.push_back({len});
+        else want.push_back({var >= 3 ? kl : kb, len});
+      }
+      if (why.empty()) why = ff_check(H, S, names, want, 1);
     }
     else {
       if (zc) why = z_levels(H, S, "z", zlev);
@@ -254,10 +299,11 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
   const size_t zks = zlev.size(), nlevmax = zks > (size_t)P.kb ? zks : (size_t)P.kb;
   const size_t run = io_run_bytes(c, band2, band2 * nlevmax);
   size_t need = 2 * band2;                                        // sfrc: two variables' bands
-  const size_t lat = 8 * ((size_t)P.jm + P.im) + 4 * 8 * (size_t)P.kb * ((size_t)P.jm + P.im);
+  const size_t lpts = nej * (size_t)P.jm + nei * (size_t)P.im;    // an lbry record: the elevation line and four arrays of every side that is ON
+  const size_t lat = 8 * lpts + 4 * 8 * (size_t)P.kb * lpts + sizeof(LatSrc);   // (k_lat_unpack's table goes behind the data)
   if (need < lat) need = lat;
-  const size_t lks = llev.size();                                 // a z-level lbry record: two of the four arrays of either edge on lks levels over the window
-  const size_t latz = 8 * ((size_t)P.jm + P.im) + 2 * 8 * (size_t)P.kb * ((size_t)P.jm + P.im) + 2 * 8 * lks * ((size_t)P.jm + P.im + 4);
+  const size_t lks = llev.size();                                 // a z-level lbry record: two of the four arrays of such a side on lks levels over the window
+  const size_t latz = 8 * lpts + 2 * 8 * (size_t)P.kb * lpts + 2 * 8 * lks * (lpts + 2 * (nej + nei)) + sizeof(LatSrc);
   if (lks && need < latz) need = latz;
   if (need < run) need = run;
   int bad = ff_reserve(c, F, need);
@@ -277,7 +323,7 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
   if (!bad && lks) {
     std::vector<double> tab(4 * lks);
     ztosig_table(llev.data(), (int)lks, tab.data());
-    if (hipMalloc((void **)&lnew, (4 * lks + 8 * lks * lpitch) * sizeof(double)) != hipSuccess ||
+    if (hipMalloc((void **)&lnew, (4 * lks + 2 * 8 * lks * lpitch) * sizeof(double)) != hipSuccess ||   // the table, tin and u / y2 of eight lines
         hipMemcpyAsync(lnew, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) {           // (and an earlier fetch has stopped mapping out of the old buffers)
       bad = 1;
@@ -292,6 +338,8 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
       if (F->ldev) (void)hipFree(F->ldev);
       F->ldev = lnew;
       F->lks = (int)lks; F->lwi = lwi; F->lwe = lwe; F->lwj = lwj; F->lwn = lwn;
+      F->lsides = sides; F->lnv = lnv;
+      for (int j = 0; j < lnv; j++) F->lq[j] = lq[j];
     }
   }
   if (!bad && paths[2]) {
@@ -319,11 +367,11 @@ extern "C" int pomgpu_set_forcing_files(pomgpu_ctx *c, const char *sfrc, const c
 
 // Is record n (1-based) of every variable in `which` inside the file?  A record beyond numrecs or the file's end gets ONE second look
 // (the file may have grown); then the step fails, before anything is written.
-static int ff_have(pomgpu_ctx *c, FSource &S, const char *who, int n, std::initializer_list<int> which) {
+static int ff_have(pomgpu_ctx *c, FSource &S, const char *who, int n, const int *which, int nwhich) {
   for (int pass = 0; pass < 2; pass++) {
     bool ok = n >= 1;
-    for (int q : which) {
-      const FVar &f = S.v[q];
+    for (int w = 0; w < nwhich; w++) {
+      const FVar &f = S.v[which[w]];
       const uint64_t nrec = f.rec ? (uint64_t)S.numrecs : f.nfixed;
       if (!ok || (uint64_t)n > nrec) { ok = false; break; }
       if (f.begin > S.fsize || (uint64_t)(n - 1) > (S.fsize - f.begin) / (f.stride ? f.stride : 1) || (uint64_t)(n - 1) * f.stride + f.slab > S.fsize - f.begin) { ok = false; break; }
@@ -338,6 +386,7 @@ static int ff_have(pomgpu_ctx *c, FSource &S, const char *who, int n, std::initi
   }
   return fail(c, POMGPU_EINVAL, "%s: record %d is not in %s (%u records, %llu bytes)", who, n, S.path.c_str(), (unsigned)S.numrecs, (unsigned long long)S.fsize);
 }
+static int ff_have(pomgpu_ctx *c, FSource &S, const char *who, int n, std::initializer_list<int> which) { return ff_have(c, S, who, n, which.begin(), (int)which.size()); }
 static int ff_io_error(pomgpu_ctx *c, const char *who, int n, const FSource &S, int hip) {
   if (hip) (void)hipGetLastError();
   return fail(c, hip ? POMGPU_EHIP : POMGPU_EINVAL, hip ? "%s: a HIP call failed while reading record %d of %s" : "%s: I/O error reading record %d of %s", who, n, S.path.c_str());
@@ -378,48 +427,59 @@ int pomgpu_ff_fetch_lateral(pomgpu_ctx *c, int n) {
   FFiles *F = FF(c);
   FSource &S = F->s[1];
   const KP &P = c->P;
-  int rc = ff_have(c, S, "lateral_bc", n, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9});
+  const int nv = F->lnv;                                          // the variables of the sides that are ON: S.v[j] is LatSrc's F->lq[j]
+  int all[20];
+  for (int j = 0; j < nv; j++) all[j] = j;
+  int rc = ff_have(c, S, "lateral_bc", n, all, nv);
   if (rc) return rc;
   const int sl = n % 4;
   unsigned char *pin = F->rd.acquire();
   if (!pin) return ff_io_error(c, "lateral_bc", n, S, 1);
   LatSrc src;
   src.f32 = 0;
-  size_t at = 0, off[10];
-  // a z-level lbry file: temp, salt of either edge on all lks levels over the line and its window points, mapped by k_ztosig_line behind k_lat_unpack
+  for (int q = 0; q < 20; q++) src.off[q] = 0;
+  size_t at = 0, off[20];
+  // a z-level lbry file: temp, salt of every such side on all lks levels over the line and its window points, mapped by k_ztosig_line behind k_lat_unpack
   const int onz = F->lks > 0;
-  int cnt[10], wlo[10];
-  for (int q = 0; q < 10; q++) {
-    const FVar &f = S.v[q];
-    const bool east = q == 0 || (q >= 2 && q <= 5);              // along j: the tile's jm values from j0; else im values from i0
-    const bool zq = onz && (q == 4 || q == 5 || q == 8 || q == 9);
-    const int nlev = q < 2 ? 1 : (zq ? F->lks : P.kb);
-    wlo[q] = zq ? (east ? F->lwj : F->lwi) : 0;
-    cnt[q] = (east ? P.jm : P.im) + wlo[q] + (zq ? (east ? F->lwn : F->lwe) : 0);
-    const uint64_t glen = east ? (uint64_t)F->jm_global : (uint64_t)F->im_global, first = (uint64_t)((east ? F->j0 : F->i0) - 1 - wlo[q]);
-    const size_t len = (size_t)cnt[q] * f.esize();
+  int cnt[20], wlo[20];
+  for (int j = 0; j < nv; j++) {
+    const FVar &f = S.v[j];
+    const int q = F->lq[j], var = q % 5;
+    const bool alongj = !((q / 5) & 1);                          // east, west: the tile's jm values from j0; else im values from i0
+    const bool zq = onz && var >= 3;
+    const int nlev = var == 0 ? 1 : (zq ? F->lks : P.kb);
+    wlo[j] = zq ? (alongj ? F->lwj : F->lwi) : 0;
+    cnt[j] = (alongj ? P.jm : P.im) + wlo[j] + (zq ? (alongj ? F->lwn : F->lwe) : 0);
+    const uint64_t glen = alongj ? (uint64_t)F->jm_global : (uint64_t)F->im_global, first = (uint64_t)((alongj ? F->j0 : F->i0) - 1 - wlo[j]);
+    const size_t len = (size_t)cnt[j] * f.esize();
     const uint64_t base = f.begin + (uint64_t)(n - 1) * f.stride + first * f.esize();
-    off[q] = at;
+    off[j] = at;
     if (read_bands(S.fd, pin + at, base, len, glen * f.esize(), nlev)) return ff_io_error(c, "lateral_bc", n, S, 0);
     at += (len * nlev + 7) & ~(size_t)7;
     if (f.type == 5) src.f32 |= 1u << q;
   }
-  if (F->rd.send(c, at)) return ff_io_error(c, "lateral_bc", n, S, 1);
-  for (int q = 0; q < 10; q++) src.p[q] = F->rd.stage + off[q];
+  for (int j = 0; j < nv; j++) src.off[F->lq[j]] = (unsigned)off[j];
+  src.base = F->rd.stage;
   src.zts = onz;
+  memcpy(pin + at, &src, sizeof src);                             // the table travels behind the data, in the one copy
+  if (F->rd.send(c, at + sizeof src)) return ff_io_error(c, "lateral_bc", n, S, 1);
   const int nt = P.jml + P.iml;
-  LAUNCH(c, k_lat_unpack, dim3((unsigned)((nt + 63) / 64), 1, 1), dim3(64, 1, 1), P, c->lat_dev[sl], src);
-  if (onz) {                                                     // tbe sbe / tbs sbs: the record's arrays 4, 5 of either edge
+  LAUNCH(c, k_lat_unpack, dim3((unsigned)((nt + 63) / 64), 1, 1), dim3(64, 1, 1), P, c->lat_dev[sl], (const LatSrc *)(F->rd.stage + at), F->lsides);
+  if (onz) {                                                     // t s of every such side: the record's first two arrays of it, one launch
     const size_t njk = (size_t)P.jml * P.kb, nik = (size_t)P.iml * P.kb;
     const int pitch = P.jml > P.iml ? P.jml : P.iml;
-    static const int zq[4] = {4, 5, 8, 9};
+    const size_t first4[4] = {4 * njk, 8 * njk + 4 * nik, 0, 8 * njk};   // where the four arrays of east, south, west, north start
     ZtlJob job;
-    for (int l = 0; l < 4; l++) {
-      const int q = zq[l];
-      double *out = c->lat_dev[sl] + (l < 2 ? (size_t)(4 + l) * njk : 8 * njk + (size_t)(2 + l) * nik);
-      job.l[l] = ztosig_line_of(P, l < 2 ? 0 : 1, out, src.p[q], S.v[q].type == 5 ? 1 : 2, cnt[q], wlo[q]);
+    int nl = 0;
+    for (int j = 0; j < nv; j++) {
+      const int q = F->lq[j], sd = q / 5, var = q % 5;
+      if (var < 3) continue;
+      double *out = c->lat_dev[sl] + first4[sd] + (size_t)(var - 3) * ((sd & 1) ? nik : njk);
+      job.l[nl++] = ztosig_line_of(P, sd, out, src.base + src.off[q], S.v[j].type == 5 ? 1 : 2, cnt[j], wlo[j]);
     }
-    launch_ztosig_lines(c, job, 4, F->ldev, F->ldev + 4 * (size_t)F->lks, F->ldev + 4 * (size_t)F->lks + 4 * (size_t)F->lks * pitch, F->lks, pitch);
+    for (int l = nl; l < 8; l++) job.l[l] = job.l[0];
+    const size_t work = 8 * (size_t)F->lks * pitch;              // one work array: eight lines' slices (sized at registration)
+    launch_ztosig_lines(c, job, nl, F->ldev, F->ldev + 4 * (size_t)F->lks, F->ldev + 4 * (size_t)F->lks + work, F->lks, pitch);
   }
   c->lat_n[sl] = n;
   return POMGPU_OK;

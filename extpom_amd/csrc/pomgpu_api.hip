@@ -331,6 +331,7 @@ static int ctx_create(pomgpu_ctx **out, const pomgpu_dims *d, int device, void *
   if (!c) return POMGPU_ENOMEM;
   c->device = device;
   c->flags = flags;
+  c->lbry_sides = POMGPU_SIDE_EAST | POMGPU_SIDE_SOUTH;
   if (hipSetDevice(device) != hipSuccess) { free(c); return POMGPU_EHIP; }
   KP &P = c->P;
   P.im = d->im; P.jm = d->jm; P.kb = d->kb; P.imm1 = d->im - 1; P.jmm1 = d->jm - 1; P.kbm1 = d->kb - 1; P.kbm2 = d->kb - 2;

@@ -765,6 +765,7 @@ struct pomgpu_ctx {
   void *io_job;              // the output / restart file being written behind the model's back (cdf_out.hip, the writer), NULL = none
   int z_init, z_clim;        // pomgpu_set_z_inputs: the init / clim file holds z levels and goes through ztosig (cdf_in.hip)
   int z_lbry;                // pomgpu_set_z_lateral: temp, salt of the lbry file are on z levels and go through k_ztosig_line (cdf_in.hip sets it, frc_files.hip reads it)
+  int lbry_sides;            // pomgpu_set_lateral_sides: the sides of the lbry file that are ON (POMGPU_SIDE_*; pomgpu_create: EAST|SOUTH; cdf_in.hip sets it, frc_files.hip reads it)
   void *frc_files;           // pomgpu_set_forcing_files: the open forcing files and their read buffers (frc_files.hip), NULL = none
   int launch_err;            // first hipError_t a kernel launch returned (0 = none); reported by the next sync / get_con
   char err[512];

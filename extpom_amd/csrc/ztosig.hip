@@ -265,7 +265,7 @@ int launch_ztosig_line(pomgpu_ctx *c, int edge, const double *zs, int ks, const 
       hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = POMGPU_EHIP;
   if (!rc) {
     ZtlJob job;
-    for (int l = 0; l < 4; l++) job.l[l] = ztosig_line_of(P, edge, dout, dev, 0, npad + 2, 1);
+    for (int l = 0; l < 8; l++) job.l[l] = ztosig_line_of(P, edge, dout, dev, 0, npad + 2, 1);
     launch_ztosig_lines(c, job, 1, dtab, wa, wb, ks, npad);
     if (hipMemcpyAsync(out, dout, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = POMGPU_EHIP;
   }

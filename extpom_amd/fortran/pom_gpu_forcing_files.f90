@@ -77,6 +77,7 @@ subroutine pomgpu_open_forcing_files(have_sfrc, have_lbry, have_clim)
   rc = 0
   if (have(3)) rc = pomgpu_set_z_inputs(pom_ctx, merge(1_c_int, 0_c_int, pom_init_on_z), merge(1_c_int, 0_c_int, pom_clim_on_z))   ! a z-level clim file: the months go through ztosig
   if (rc == 0 .and. have(2)) rc = pomgpu_set_z_lateral(pom_ctx, merge(1_c_int, 0_c_int, pom_lbry_on_z))   ! a z-level lbry file: every record's temp, salt lines go through ztosig
+  if (rc == 0 .and. have(2)) rc = pomgpu_set_lateral_sides(pom_ctx, int(pom_lbry_sides, c_int))   ! the sides the lbry file feeds; the others: tclim, sclim lines
   if (rc == 0 .and. any(have)) rc = pomgpu_set_forcing_files(pom_ctx, p(1), p(2), p(3), m)
   if (rc == 0 .and. have_rate) rc = pomgpu_set_restore_rate_file(pom_ctx, c_loc(rname), m)
   if (rc /= 0) then                                ! handle_error_pnetcdf, io_pnetcdf.F:43-54: a message and error_status = 1

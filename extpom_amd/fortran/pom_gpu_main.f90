@@ -17,6 +17,8 @@
 !        pom_gpu_main --cold <state.out> <nsteps>
 !        pom_gpu_main --cold-z <state.out> <nsteps>     (T, S and Tclim, Sclim on z levels: mapped with ztosig)
 !        ... --cold | --cold-z <state.out> <nsteps> --lbry-z     (temp, salt of the lbry file on z levels: bounds_forcing.f:636-716)
+!        ... --cold | --cold-z <state.out> <nsteps> --lbry-sides <n>     (the sides the lbry file feeds: east 1 + south 2 + west 4 + north 8;
+!                                                                         default 3, the reference's reader; beside --lbry-z, either first)
 program pom_gpu_main
   use pomgpu_iface
   implicit none
@@ -42,8 +44,17 @@ program pom_gpu_main
   if (cold) then                             ! one tile, the whole grid; read_input's constants (initialize.f:80-168)
     call get_command_argument(3, arg3)
     read(arg3, *) nsteps
-    call get_command_argument(4, arg3)
-    if (trim(arg3) == '--lbry-z') pom_lbry_on_z = .true.
+    n = 4                                    ! --lbry-z and --lbry-sides <n>, in either order
+    do while (n <= command_argument_count())
+      call get_command_argument(n, arg3)
+      if (trim(arg3) == '--lbry-z') pom_lbry_on_z = .true.
+      if (trim(arg3) == '--lbry-sides') then
+        n = n + 1
+        call get_command_argument(n, arg3)
+        read(arg3, *) pom_lbry_sides
+      end if
+      n = n + 1
+    end do
     im = im_local; jm = jm_local; nrec = 0
     n_west = -1; n_east = -1; n_south = -1; n_north = -1
     rhoref=1025.d0; tbias=0.d0; sbias=0.d0; grav=9.806d0; kappa=0.4d0; z0b=.01d0; cbcmin=.0025d0; cbcmax=1.d0

@@ -14,6 +14,9 @@ module pomgpu_iface
   logical, save :: pom_init_on_z = .false., pom_clim_on_z = .false.
   ! temp, salt of the lbry file are on z levels (pomgpu_set_z_lateral): pomgpu_open_forcing_files passes it on
   logical, save :: pom_lbry_on_z = .false.
+  ! the open boundaries the lbry file feeds (pomgpu_set_lateral_sides: east 1, south 2, west 4, north 8; the default is the reference's
+  ! reader, io_pnetcdf.F:3393-3621): pomgpu_open_forcing_files passes it on
+  integer, save :: pom_lbry_sides = 3
   type, bind(C) :: pomgpu_file_meta               ! include/pomgpu.h
     type(c_ptr) :: title, time_start
     integer(c_int) :: im_global, jm_global, i0, j0, create
@@ -119,6 +122,9 @@ module pomgpu_iface
     end function
     integer(c_int) function pomgpu_set_z_lateral(ctx, lbry_on_z) bind(C, name='pomgpu_set_z_lateral')
       import; type(c_ptr), value :: ctx; integer(c_int), value :: lbry_on_z
+    end function
+    integer(c_int) function pomgpu_set_lateral_sides(ctx, sides) bind(C, name='pomgpu_set_lateral_sides')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: sides
     end function
     integer(c_int) function pomgpu_domain_stats(ctx, out, sums_only) bind(C, name='pomgpu_domain_stats')
       import; type(c_ptr), value :: ctx; real(c_double) :: out(8); integer(c_int), value :: sums_only

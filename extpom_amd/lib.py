@@ -112,6 +112,7 @@ _SIGS = {
     "pomgpu_ztosig": (_I, [_P, _P, _I, _P, _P]),
     "pomgpu_set_z_inputs": (_I, [_P, _I, _I]),
     "pomgpu_set_z_lateral": (_I, [_P, _I]),
+    "pomgpu_set_lateral_sides": (_I, [_P, _I]),
     "pomgpu_ztosig_line": (_I, [_P, _I, _P, _I, _P, _P]),
     "pomgpu_math_probe": (_I, [_P, _I, ctypes.c_long, ctypes.POINTER(ctypes.c_void_p), _I, _P]),
     "pomgpu_bcond": (_I, [_P, _I]),

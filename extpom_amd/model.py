@@ -275,6 +275,13 @@ class PomGpu:
         if lbry is not None:
             self._chk(self.L.pomgpu_set_z_lateral(self.h, 1 if lbry else 0), "set_z_lateral")
 
+    def set_lateral_sides(self, east: bool = True, south: bool = True, west: bool = False, north: bool = False):
+        """pomgpu_set_lateral_sides: the open boundaries the lbry file feeds (the default is the reference's reader, io_pnetcdf.F:3393-3621).
+        A side that is on takes zeta u v temp salt .<side> from the file; one that is off has t s from the line of tclim sclim next to it,
+        u v zero and its elevation line as the state holds it, and its variables are not looked up.  Before set_forcing_files(lbry=...)."""
+        sides = (1 if east else 0) | (2 if south else 0) | (4 if west else 0) | (8 if north else 0)
+        self._chk(self.L.pomgpu_set_lateral_sides(self.h, sides), "set_lateral_sides")
+
     def set_forcing_files(self, sfrc=None, lbry=None, clim=None, im_global=None, jm_global=None):
         """pomgpu_set_forcing_files: from now on wind / heat / surface (sfrc), lateral_bc (lbry) and restore_interior (clim) take the
         records their schedule asks for from these classic NetCDF files, on the device; None leaves a source as it is.  This tile's

@@ -377,6 +377,34 @@ int pomgpu_set_z_inputs(pomgpu_ctx *ctx, int init_on_z, int clim_on_z);
  * level count than it; a tile whose window does not fit the grid; im or jm below 4.  This call refuses (POMGPU_EINVAL) to change the
  * setting once an lbry file is registered. */
 int pomgpu_set_z_lateral(pomgpu_ctx *ctx, int lbry_on_z);
+/* Which of the four open boundaries the lbry file feeds (a context setting; default EAST|SOUTH: today's behaviour bit for bit and refusal
+ * for refusal).  read_boundary_conditions_pnetcdf (io_pnetcdf.F:3393-3621) reads the .east and .south variables only, takes t_w s_w t_n s_n
+ * from line i = 1 / j = jm of tclim sclim (:3606-3614), leaves u_w v_w u_n v_n zero and never writes elw eln; its commented look-ups for
+ * west and north (:3458-3463, :3474-3479, :3491-3498), its commented tclim fall-backs for east and south (:3607-3608, :3612-3613) and the
+ * commented z-level blocks for all four sides (bounds_forcing.f:657-716, :777-836) show the four-sided reader this setting completes;
+ * lateral_bc (bounds_forcing.f:841-865), bcond(2) (:47-78) and bcond(4) (:175-229) are four-sided already.
+ * Variable names follow the reference's active pattern <var>.<side>: zeta.west u.west v.west temp.west salt.west, and the same with .north
+ * (the commented 'west.u' / 'tw' are an older spelling and are not accepted); zeta.west is (record, jm_global), the other .west variables
+ * (record, kb, jm_global), zeta.north (record, im_global), the other .north variables (record, kb, im_global) -- the shapes of .east and
+ * .south --, each NC_FLOAT or NC_DOUBLE, found by name, CDF-1 or CDF-2, the record dimension unlimited or fixed.
+ * A side that is ON: its elevation line is the tile's piece of zeta.<side> over 1:jm / 1:im and untouched beyond, as ele els are today;
+ * its four (., kb) arrays are the tile's pieces of temp salt u v, zero beyond jm / im, in the reader's argument order (t_w s_w u_w v_w ...
+ * t_n s_n v_n u_n ...: v before u on north and south).
+ * A side that is OFF: t s are the line of tclim sclim next to that side -- i = 1, i = im, j = 1, j = jm of the TILE, as the reference's
+ * statements are per rank --, u v are zero, the elevation line is left as the state holds it, and the file's variables of that side are
+ * not looked up at all: the file need not hold them, and if it does they are ignored, as extra variables are.  For west and north OFF is
+ * the reference's live code, for east and south its commented code.
+ * Every rank reads every ON side with its own i0, j0, as the reference does: not collective, no message round.
+ * Under pomgpu_set_z_lateral(1) temp / salt of every ON side are on the levels of the file's `z` and are mapped into the record by the
+ * line form of ztosig with that side's edge number (0 east h(imm1,j), 1 south h(i,2), 2 west h(2,j), 3 north h(i,jmm1)), all lines in one
+ * launch; one window point is read towards every neighbour (.east / .west towards the south and north one, .south / .north towards the
+ * west and east one); u v zeta stay on sigma levels; OFF sides take the tclim line as above.
+ * pomgpu_set_forcing_files checks the header for the variables of the ON sides only (up to twenty), names the variable in every refusal
+ * and refuses before anything is kept; a fetch looks for its record in the ON sides' variables.
+ * Refused with POMGPU_EINVAL and the cause in pomgpu_last_error: `sides` outside 1..15; a change of the mask once an lbry file is
+ * registered. */
+enum { POMGPU_SIDE_EAST = 1, POMGPU_SIDE_SOUTH = 2, POMGPU_SIDE_WEST = 4, POMGPU_SIDE_NORTH = 8 };
+int pomgpu_set_lateral_sides(pomgpu_ctx *ctx, int sides);
 
 /* The forcing files without PnetCDF: read_wind_pnetcdf, read_heat_pnetcdf, read_surface_pnetcdf (io_pnetcdf.F:2912-3224),
  * read_boundary_conditions_pnetcdf (:3393-3621), read_restore_ts_interior_pnetcdf (:3275-3333).  The host names the files once --

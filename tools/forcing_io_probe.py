@@ -12,11 +12,15 @@ fraction of their pages was resident (mincore) before the first and after the la
 
     python tools/forcing_io_probe.py [--grid 1024x1024x40] [--dir /scratch] [--turns 3] [--out profiles/forcing_read_1024x1024x40.json]
     python tools/forcing_io_probe.py --lbry-z [--ks 33] [--out profiles/forcing_read_lbry_z_1024x1024x40.json]
+    python tools/forcing_io_probe.py --sides 15 [--lbry-z] [--out profiles/forcing_read_lbry_sides_1024x1024x40.json]
     python tools/forcing_io_probe.py --check      (no GPU: arguments, paths and free space only; reports no time)
 
 --lbry-z: a third context of the same job takes its lateral records from an lbry file whose temp / salt lines are on ks z levels
 (PomGpu.set_z_inputs(lbry=True)): its fetch steps stand beside the sigma file's, with the bare pread of the bytes it reads, and one more
 fetch step with every kernel bracketed gives k_lat_unpack and k_ztosig_line their own durations.
+--sides <n>: one more context of the same job feeds the sides of the mask n (PomGpu.set_lateral_sides: east 1, south 2, west 4, north 8)
+from an lbry file that holds those sides' variables (with --lbry-z: temp / salt of each on the ks z levels): its fetch steps stand beside
+the two-sided file's, and one more fetch step with every kernel bracketed gives the two lateral kernels' own durations.
 """
 import argparse
 import json
@@ -42,11 +46,13 @@ def main():
     ap.add_argument("--out", default=None, help="also write the JSON here")
     ap.add_argument("--lbry-z", action="store_true", help="also fetch from an lbry file with temp / salt on z levels")
     ap.add_argument("--ks", type=int, default=33, help="--lbry-z: the z levels of that file")
+    ap.add_argument("--sides", type=int, default=0, help="also fetch from an lbry file that feeds the sides of this mask (1..15)")
     ap.add_argument("--check", action="store_true", help="arguments, paths and free space only; no GPU, no time")
     args = ap.parse_args()
     im, jm, kb = (int(v) for v in args.grid.lower().split("x"))
     where = args.dir or tempfile.gettempdir()
-    nrec, nlat = args.turns + 2 + (1 if args.lbry_z else 0), 3 * args.turns + 2 + (3 if args.lbry_z else 0)   # --lbry-z: one more turn, the bracketed one
+    more = args.lbry_z or args.sides
+    nrec, nlat = args.turns + 2 + (1 if more else 0), 3 * args.turns + 2 + (3 if more else 0)   # --lbry-z, --sides: one more turn, the bracketed one
     nbytes = 8 * (6 * nrec * im * jm + nlat * (im + jm) * (1 + 4 * kb))
     free = shutil.disk_usage(where).free
     out = dict(tool="forcing_io_probe", grid=f"{im}x{jm}x{kb}", case=args.case, dir=where, file_bytes_about=nbytes, free_bytes=free)
@@ -78,6 +84,12 @@ def main():
         if args.lbry_z:
             import ztosig_line_files_checks as zl               # the z-level lines for the state's own depths, the file's writer
             lbry_z = zl.write_lbry_z(os.path.join(tmp, "probe_z.lbry.nc"), zl.raw_lbry_z(st, nlat, ks=args.ks))
+        if args.sides:
+            import lateral_sides_expect as ls                   # the four-sided fields and the writers of a file of the ON sides
+            if args.lbry_z:
+                lbry_s = ls.write_lbry_z(os.path.join(tmp, "probe_s.lbry.nc"), ls.raw_lbry_z(st, nlat, ks=args.ks), args.sides)
+            else:
+                lbry_s = ls.write_lbry(os.path.join(tmp, "probe_s.lbry.nc"), ls.raw_lbry(st, nlat), args.sides)
         del raw_s, raw_l
         out["file_bytes"] = [os.path.getsize(sfrc), os.path.getsize(lbry)]
         out["resident_before"] = [resident_fraction(sfrc), resident_fraction(lbry)]
@@ -96,6 +108,17 @@ def main():
             fz, fd_z = netcdf_file(lbry_z, "r", mmap=True), os.open(lbry_z, os.O_RDONLY)
             z_bytes = 8 * (5 * im * jm + (im + jm) * (1 + 2 * kb + 2 * args.ks))
             out["z_file_bytes"], out["ks"] = os.path.getsize(lbry_z), args.ks
+
+        if args.sides:
+            d = st.copy()
+            gs = PomGpu(d, device=0)
+            if args.lbry_z:
+                gs.set_z_inputs(lbry=True)
+            gs.set_lateral_sides(east=bool(args.sides & 1), south=bool(args.sides & 2), west=bool(args.sides & 4), north=bool(args.sides & 8))
+            gs.set_forcing_files(sfrc=sfrc, lbry=lbry_s)
+            nside = bin(args.sides).count("1")                   # every side: one elevation line and four arrays, two of them on ks levels under --lbry-z
+            out["sides"], out["sides_file_bytes"] = args.sides, os.path.getsize(lbry_s)
+            out["sides_fetch_bytes"] = 8 * (5 * im * jm + nside * ((im + jm) // 2) * (1 + (2 * kb + 2 * args.ks if args.lbry_z else 4 * kb)))
 
         def timed(fn):
             t = time.perf_counter()
@@ -162,6 +185,10 @@ def main():
             res.update(z_file_step_ms=[], z_file_step_nofetch_ms=[], z_bare_pread_ms=[])
             gz.set_con(iint=2)
             step(gz)
+        if args.sides:
+            res.update(sides_file_step_ms=[], sides_file_step_nofetch_ms=[])
+            gs.set_con(iint=2)
+            step(gs)
         # warm both contexts (first launches, allocations) on a step of their own, and give the host path the "b" generation of records
         for g in (gf, gh):
             g.set_con(iint=2)
@@ -188,6 +215,22 @@ def main():
                 keep, dest = dest, dest_z
                 res["z_bare_pread_ms"].append(timed(lambda: bare_pread(plan)))
                 dest = keep
+            if args.sides:
+                gs.get_con()
+                gs.set_con(iint=n - 2)
+                res["sides_file_step_nofetch_ms"].append(timed(lambda: step(gs)))
+                res["sides_file_step_ms"].append(timed(lambda: step(gs)))
+        if args.sides:                                            # one more fetch step, every kernel bracketed
+            gs.get_con()
+            gs.set_con(iint=PERIOD * (args.turns + 1) - 1)
+            gs.prof_begin()
+            step(gs)
+            prof = gs.prof_end()
+            out["sides_kernels_ms"] = {k: [prof[k][0], round(prof[k][1], 4)] for k in ("k_lat_unpack", "k_ztosig_line") if k in prof}
+            gs.download()
+            out["sides_error_status"] = int(d.error_status)
+            out["sides_tbwf_nonzero"] = bool(d.tbwf.any())
+            gs.close()
         if args.lbry_z:                                           # one more fetch step, every kernel bracketed: the two lateral kernels' own time
             gz.get_con()
             gz.set_con(iint=PERIOD * (args.turns + 1) - 1)
@@ -213,6 +256,8 @@ def main():
         out["fetch_bytes"] = rec_bytes
         out.update(res)
         out["file_fetch_ms"] = [round(x - y, 3) for x, y in zip(res["file_step_ms"], res["file_step_nofetch_ms"])]
+        if args.sides:
+            out["sides_file_fetch_ms"] = [round(x - y, 3) for x, y in zip(res["sides_file_step_ms"], res["sides_file_step_nofetch_ms"])]
         if args.lbry_z:
             out["z_file_fetch_ms"] = [round(x - y, 3) for x, y in zip(res["z_file_step_ms"], res["z_file_step_nofetch_ms"])]
         out["host_fetch_ms"] = [round(x - y, 3) for x, y in zip(res["host_step_ms"], res["host_step_nofetch_ms"])]
