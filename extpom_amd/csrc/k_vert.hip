@@ -1657,8 +1657,6 @@ static __device__ __forceinline__ void d_profuv_reg(const KP &P, const bool stor
 #undef KCB
 #undef PLANE
 }
-template <int KBT, int V>
-__global__ void __launch_bounds__(64 * ROWS_PROFUV) k_profuv_reg(KP P) { d_profuv_reg<KBT, V>(P, true); }
 // profu and profv (advance.f:461-462) as ONE grid, the component on blockIdx.z (see k_proft_reg2); the grid is profu's (62 columns per
 // wavefront), profv's workgroups beyond its 64-column count find nothing to do.  tps is the reference's shared scratch:
 // only profv, whose value the reference leaves there, stores it.
@@ -1750,8 +1748,6 @@ static __device__ __forceinline__ void d_int_uvmean_reg(const KP &P) {
   if (V) F2(tps, i, j) = s_;
 #undef KC
 }
-template <int KBT, int V>
-__global__ void __launch_bounds__(64 * ROWS_UVM) k_int_uvmean_reg(KP P) { d_int_uvmean_reg<KBT, V>(P); }
 template <int KBT>
 __global__ void __launch_bounds__(64 * ROWS_UVM) k_int_uvmean_reg2(KP P) {   // u and v as ONE grid, the component on blockIdx.z (see k_proft_reg2)
   if (blockIdx.z == 0) d_int_uvmean_reg<KBT, 0>(P);
@@ -1814,8 +1810,6 @@ static __device__ __forceinline__ void d_uv_filter_reg(const KP &P, const int ow
   if (V) F2(tps, i, j) = su;
 #undef KC
 }
-template <int KBT, int V>
-__global__ void __launch_bounds__(64 * ROWS_UVF) k_uv_filter_reg(KP P, int own) { d_uv_filter_reg<KBT, V>(P, own); }
 template <int KBT>
 __global__ void __launch_bounds__(64 * ROWS_UVF) k_uv_filter_reg2(KP P, int own) {   // u and v as ONE grid, the component on blockIdx.z (see k_proft_reg2)
   if (blockIdx.z == 0) d_uv_filter_reg<KBT, 0>(P, own);
@@ -1899,21 +1893,21 @@ void launch_order_pack(pomgpu_ctx *c, double *send_e, double *send_n) {
   LAUNCH(c, k_order_pack, dim3((len + 63) / 64, P.kb + 1, 1), dim3(64, 1, 1), c->P, send_e, send_n);
 }
 static inline dim3 twin(dim3 g) { g.z = 2; return g; }       // the two variants of a twin kernel on blockIdx.z
-template <int KBT> static void launch_int_uvmean_reg_t(pomgpu_ctx *c) {
-  if (!SW(c, NO_TWIN)) { LAUNCHN(c, "k_int_uvmean_reg2", (k_int_uvmean_reg2<KBT>), twin(rowgrid(c->P, ROWS_UVM)), rowblk(ROWS_UVM), c->P); return; }
-  LAUNCHN(c, "k_int_uvmean_reg", (k_int_uvmean_reg<KBT, 0>), rowgrid(c->P, ROWS_UVM), rowblk(ROWS_UVM), c->P);
-  LAUNCHN(c, "k_int_uvmean_reg", (k_int_uvmean_reg<KBT, 1>), rowgrid(c->P, ROWS_UVM), rowblk(ROWS_UVM), c->P);
+// The register kernels are instantiated for seven bounds KBT of the unrolled level loop.  with_kbt calls f(std::integral_constant<int, KBT>)
+// with the smallest of them that holds kb, for a context pomgpu_reg_kb accepts (6 <= kb <= 64); KBT_OF names the bound inside f
+template <class F> static void with_kbt(int kb, F f) {
+  if (kb <= 24) f(std::integral_constant<int, 24>{});
+  else if (kb <= 32) f(std::integral_constant<int, 32>{});
+  else if (kb <= 40) f(std::integral_constant<int, 40>{});
+  else if (kb <= 44) f(std::integral_constant<int, 44>{});
+  else if (kb <= 50) f(std::integral_constant<int, 50>{});
+  else if (kb <= 56) f(std::integral_constant<int, 56>{});
+  else f(std::integral_constant<int, 64>{});
 }
+#define KBT_OF(t) decltype(t)::value
 void launch_int_uvmean(pomgpu_ctx *c) {
-  const int kb = c->P.kb;
-  if (SW(c, THOMAS_SCRATCH) || kb > 64 || kb < 6) LAUNCH(c, k_int_uvmean, colgrid(c->P), colblk(), c->P);
-  else if (kb <= 24) launch_int_uvmean_reg_t<24>(c);
-  else if (kb <= 32) launch_int_uvmean_reg_t<32>(c);
-  else if (kb <= 40) launch_int_uvmean_reg_t<40>(c);
-  else if (kb <= 44) launch_int_uvmean_reg_t<44>(c);
-  else if (kb <= 50) launch_int_uvmean_reg_t<50>(c);
-  else if (kb <= 56) launch_int_uvmean_reg_t<56>(c);
-  else launch_int_uvmean_reg_t<64>(c);
+  if (!pomgpu_reg_kb(c)) { LAUNCH(c, k_int_uvmean, colgrid(c->P), colblk(), c->P); return; }
+  with_kbt(c->P.kb, [&](auto t) { LAUNCHN(c, "k_int_uvmean_reg2", (k_int_uvmean_reg2<KBT_OF(t)>), twin(rowgrid(c->P, ROWS_UVM)), rowblk(ROWS_UVM), c->P); });
 }
 void launch_vertvl(pomgpu_ctx *c, int mask) {
   if (SW(c, VERTVL_CELLS)) { LAUNCH(c, k_vertvl, COLV_G(c->P), COLV_B, c->P, mask); return; }   // developer switch: one thread per column, four loads per level
@@ -1954,15 +1948,8 @@ static void launch_proft_reg(pomgpu_ctx *c, double *f, const double *wfsurf, con
   else LAUNCHN(c, "k_proft_reg", (k_proft_reg<KBT, 0>), rowgrid(c->P, ROWS_PROFT), rowblk(ROWS_PROFT), c->P, f, wfsurf, fsurf, nbc);
 }
 void launch_proft(pomgpu_ctx *c, double *f, const double *wfsurf, const double *fsurf, int nbc) {
-  const int kb = c->P.kb;
-  if (SW(c, THOMAS_SCRATCH) || kb > 64 || kb < 6) LAUNCH(c, k_proft, colgrid(c->P), colblk(), c->P, f, wfsurf, fsurf, nbc);
-  else if (kb <= 24) launch_proft_reg<24>(c, f, wfsurf, fsurf, nbc);
-  else if (kb <= 32) launch_proft_reg<32>(c, f, wfsurf, fsurf, nbc);
-  else if (kb <= 40) launch_proft_reg<40>(c, f, wfsurf, fsurf, nbc);
-  else if (kb <= 44) launch_proft_reg<44>(c, f, wfsurf, fsurf, nbc);
-  else if (kb <= 50) launch_proft_reg<50>(c, f, wfsurf, fsurf, nbc);
-  else if (kb <= 56) launch_proft_reg<56>(c, f, wfsurf, fsurf, nbc);
-  else launch_proft_reg<64>(c, f, wfsurf, fsurf, nbc);
+  if (!pomgpu_reg_kb(c)) { LAUNCH(c, k_proft, colgrid(c->P), colblk(), c->P, f, wfsurf, fsurf, nbc); return; }
+  with_kbt(c->P.kb, [&](auto t) { launch_proft_reg<KBT_OF(t)>(c, f, wfsurf, fsurf, nbc); });
 }
 // proft for T and S in one launch (advance.f:439-440); 0 = not applicable (no register kernel for this kb, or the two tracers' surface
 // conditions differ in whether the short-wave term is compiled in): the caller launches them one by one.
@@ -1987,58 +1974,31 @@ static void launch_proft2_reg(pomgpu_ctx *c, const ProftArgs &a0, const ProftArg
   else LAUNCHN(c, "k_proft_reg2", (k_proft_reg2<KBT, 0>), twin(rowgrid(c->P, ROWS_PROFT)), rowblk(ROWS_PROFT), c->P, a0, a1);
 }
 int launch_proft2(pomgpu_ctx *c, double *f0, const double *wfsurf0, const double *fsurf0, int nbc0, double *f1, const double *wfsurf1, const double *fsurf1, int nbc1) {
-  const int kb = c->P.kb, sw0 = (nbc0 == 2 || nbc0 == 4), sw1 = (nbc1 == 2 || nbc1 == 4);
-  if (SW(c, NO_TWIN) || SW(c, THOMAS_SCRATCH) || kb > 64 || kb < 6 || sw0 != sw1) return 0;
+  const int sw0 = (nbc0 == 2 || nbc0 == 4), sw1 = (nbc1 == 2 || nbc1 == 4);
+  if (!pomgpu_reg_kb(c) || sw0 != sw1) return 0;
   const ProftArgs a0 = {f0, wfsurf0, fsurf0, nbc0}, a1 = {f1, wfsurf1, fsurf1, nbc1};
   const int lane = !SW(c, PROFT_TWIN) && !sw0 && (nbc0 <= 2) == (nbc1 <= 2);
-  if (kb <= 24) launch_proft2_reg<24>(c, a0, a1, sw0, lane);
-  else if (kb <= 32) launch_proft2_reg<32>(c, a0, a1, sw0, lane);
-  else if (kb <= 40) launch_proft2_reg<40>(c, a0, a1, sw0, lane);
-  else if (kb <= 44) launch_proft2_reg<44>(c, a0, a1, sw0, lane);
-  else if (kb <= 50) launch_proft2_reg<50>(c, a0, a1, sw0, lane);
-  else if (kb <= 56) launch_proft2_reg<56>(c, a0, a1, sw0, lane);
-  else launch_proft2_reg<64>(c, a0, a1, sw0, lane);
+  with_kbt(c->P.kb, [&](auto t) { launch_proft2_reg<KBT_OF(t)>(c, a0, a1, sw0, lane); });
   return 1;
 }
 void launch_advu_profu(pomgpu_ctx *c, int do_adv, int do_prof) { LAUNCH(c, k_advu_profu, colgrid(c->P), colblk(), c->P, do_adv, do_prof); }
 void launch_advv_profv(pomgpu_ctx *c, int do_adv, int do_prof) { LAUNCH(c, k_advv_profv, colgrid(c->P), colblk(), c->P, do_adv, do_prof); }
-template <int KBT> static void launch_profuv_reg_t(pomgpu_ctx *c) {
-  const KP &P = c->P;
-  if (!SW(c, NO_TWIN)) {
-    LAUNCHN(c, "k_profuv_reg2", (k_profuv_reg2<KBT>), dim3((P.iml + 61) / 62, (P.jml + ROWS_PROFUV - 1) / ROWS_PROFUV, 2), rowblk(ROWS_PROFUV), c->P);
-    return;
-  }
-  LAUNCHN(c, "k_profu_reg", (k_profuv_reg<KBT, 0>), dim3((P.iml + 61) / 62, (P.jml + ROWS_PROFUV - 1) / ROWS_PROFUV, 1), rowblk(ROWS_PROFUV), c->P);
-  LAUNCHN(c, "k_profv_reg", (k_profuv_reg<KBT, 1>), rowgrid(P, ROWS_PROFUV), rowblk(ROWS_PROFUV), c->P);
-}
 int launch_profuv_reg(pomgpu_ctx *c) {
-  const int kb = c->P.kb;
-  if (SW(c, THOMAS_SCRATCH) || kb > 64 || kb < 6) return 0;
-  if (kb <= 24) launch_profuv_reg_t<24>(c);
-  else if (kb <= 32) launch_profuv_reg_t<32>(c);
-  else if (kb <= 40) launch_profuv_reg_t<40>(c);
-  else if (kb <= 44) launch_profuv_reg_t<44>(c);
-  else if (kb <= 50) launch_profuv_reg_t<50>(c);
-  else if (kb <= 56) launch_profuv_reg_t<56>(c);
-  else launch_profuv_reg_t<64>(c);
+  const KP &P = c->P;
+  if (!pomgpu_reg_kb(c)) return 0;
+  with_kbt(P.kb, [&](auto t) {
+    LAUNCHN(c, "k_profuv_reg2", (k_profuv_reg2<KBT_OF(t)>), dim3((P.iml + 61) / 62, (P.jml + ROWS_PROFUV - 1) / ROWS_PROFUV, 2), rowblk(ROWS_PROFUV), c->P);
+  });
   return 1;
 }
 // the fused tail of one tile (pomgpu_api.hip: uv_fused): the snapshot of ub, vb at kbm1, then profu, profv with the interior's filter
-template <int KBT> static void launch_profuv_filter_reg_t(pomgpu_ctx *c, double *ubk, double *vbk) {
+void launch_profuv_filter_reg(pomgpu_ctx *c, double *ubk, double *vbk) {   // the caller has asked pomgpu_reg_kb
   const KP &P = c->P;
   LAUNCH(c, k_uvb_bottom, grid2(P), blk2(), c->P, ubk, vbk);
-  LAUNCHN(c, "k_profuv_filter_reg2", (k_profuv_filter_reg2<KBT>), dim3((P.iml + 61) / 62, (P.jml + ROWS_PROFUV - 1) / ROWS_PROFUV, 2), rowblk(ROWS_PROFUV), c->P,
-          (const double *)ubk, (const double *)vbk);
-}
-void launch_profuv_filter_reg(pomgpu_ctx *c, double *ubk, double *vbk) {   // the caller has checked kb (6..64)
-  const int kb = c->P.kb;
-  if (kb <= 24) launch_profuv_filter_reg_t<24>(c, ubk, vbk);
-  else if (kb <= 32) launch_profuv_filter_reg_t<32>(c, ubk, vbk);
-  else if (kb <= 40) launch_profuv_filter_reg_t<40>(c, ubk, vbk);
-  else if (kb <= 44) launch_profuv_filter_reg_t<44>(c, ubk, vbk);
-  else if (kb <= 50) launch_profuv_filter_reg_t<50>(c, ubk, vbk);
-  else if (kb <= 56) launch_profuv_filter_reg_t<56>(c, ubk, vbk);
-  else launch_profuv_filter_reg_t<64>(c, ubk, vbk);
+  with_kbt(P.kb, [&](auto t) {
+    LAUNCHN(c, "k_profuv_filter_reg2", (k_profuv_filter_reg2<KBT_OF(t)>), dim3((P.iml + 61) / 62, (P.jml + ROWS_PROFUV - 1) / ROWS_PROFUV, 2), rowblk(ROWS_PROFUV),
+            c->P, (const double *)ubk, (const double *)vbk);
+  });
 }
 void launch_uv_filter_rim(pomgpu_ctx *c) {
   const KP &P = c->P;
@@ -2051,26 +2011,9 @@ void launch_uvf_copy(pomgpu_ctx *c) {                          // a pending uf, 
   LAUNCH(c, k_uvf_copy, g, blk2(), c->P, P.b3 + (size_t)P3_uf * P.a3, (const double *)(P.b3 + (size_t)P3_u * P.a3));
   LAUNCH(c, k_uvf_copy, g, blk2(), c->P, P.b3 + (size_t)P3_vf * P.a3, (const double *)(P.b3 + (size_t)P3_v * P.a3));
 }
-template <int KBT> static void launch_uv_filter_reg_t(pomgpu_ctx *c, int own) {
-  if (!SW(c, NO_TWIN)) { LAUNCHN(c, "k_uv_filter_reg2", (k_uv_filter_reg2<KBT>), twin(rowgrid(c->P, ROWS_UVF)), rowblk(ROWS_UVF), c->P, own); return; }
-  LAUNCHN(c, "k_uv_filter_reg", (k_uv_filter_reg<KBT, 0>), rowgrid(c->P, ROWS_UVF), rowblk(ROWS_UVF), c->P, own);
-  LAUNCHN(c, "k_uv_filter_reg", (k_uv_filter_reg<KBT, 1>), rowgrid(c->P, ROWS_UVF), rowblk(ROWS_UVF), c->P, own);
-}
-static int launch_uv_filter_reg(pomgpu_ctx *c, int own) {
-  const int kb = c->P.kb;
-  if (SW(c, THOMAS_SCRATCH) || kb > 64 || kb < 6) return 0;
-  if (kb <= 24) launch_uv_filter_reg_t<24>(c, own);
-  else if (kb <= 32) launch_uv_filter_reg_t<32>(c, own);
-  else if (kb <= 40) launch_uv_filter_reg_t<40>(c, own);
-  else if (kb <= 44) launch_uv_filter_reg_t<44>(c, own);
-  else if (kb <= 50) launch_uv_filter_reg_t<50>(c, own);
-  else if (kb <= 56) launch_uv_filter_reg_t<56>(c, own);
-  else launch_uv_filter_reg_t<64>(c, own);
-  return 1;
-}
 void launch_uv_filter(pomgpu_ctx *c, int own) {
-  if (launch_uv_filter_reg(c, own)) return;
-  LAUNCH(c, k_uv_filter, colgrid(c->P), colblk(), c->P, own);
+  if (!pomgpu_reg_kb(c)) { LAUNCH(c, k_uv_filter, colgrid(c->P), colblk(), c->P, own); return; }
+  with_kbt(c->P.kb, [&](auto t) { LAUNCHN(c, "k_uv_filter_reg2", (k_uv_filter_reg2<KBT_OF(t)>), twin(rowgrid(c->P, ROWS_UVF)), rowblk(ROWS_UVF), c->P, own); });
 }
 
 // ---- pomgpu_math_probe: the scalar device functions on one value per lane, as the kernels above call them ------------------------------

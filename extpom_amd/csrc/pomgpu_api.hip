@@ -258,8 +258,8 @@ static bool wr_on_demand(const pomgpu_ctx *c) {
 // (as for wr), a grid with an interior, and the register kernels' range of kb
 static bool uv_fused(const pomgpu_ctx *c) {
   const KP &P = c->P;
-  return !c->exch && !c->tp.on && !c->wide.on && !c->parent && !(c->flags & POMGPU_CTX_2D) && !c->wr_eager && P.kb >= 6 && P.kb <= 64 &&
-         P.im >= 8 && P.jm >= 8 && !SW(c, THOMAS_SCRATCH) && !SW(c, NO_TWIN) && !SW(c, UV_NOFUSE);
+  return !c->exch && !c->tp.on && !c->wide.on && !c->parent && !(c->flags & POMGPU_CTX_2D) && !c->wr_eager && pomgpu_reg_kb(c) &&
+         P.im >= 8 && P.jm >= 8 && !SW(c, UV_NOFUSE);
 }
 // may mode_internal form w inside the q2 / q2l advection march (k_advq_col<2, true>) instead of launching vertvl in front of it?  One
 // tile with no exchange of any kind (on tiles w has a message round of its own, Rw, between the two kernels) and the one-pass q2 / q2l
@@ -451,9 +451,8 @@ extern "C" void pomgpu_destroy(pomgpu_ctx *c) {
     delete ps;
   }
   if (c->side) {
-    (void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_early); (void)hipEventDestroy(c->ev_side);
-    (void)hipEventDestroy(c->ev_r1); (void)hipEventDestroy(c->ev_r2); (void)hipEventDestroy(c->ev_r8);
-    (void)hipEventDestroy(c->ev_rw); (void)hipEventDestroy(c->ev_rq); (void)hipEventDestroy(c->ev_rts);
+    (void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_early);
+    for (auto &e : c->side_ev) (void)hipEventDestroy(e.ev);
     (void)hipStreamDestroy(c->side);
   }
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -783,10 +782,10 @@ static void seq_advct(pomgpu_ctx *c, int sum2d = 0, int defer_xch = 0) {   // so
     if (side) side_begin(c);
     launch_advct_edge(c, T.nbr[1] >= 0 ? snd[1] : NULL, T.nbr[3] >= 0 ? snd[3] : NULL);
     const int rcm = side ? pomgpu_tp_move_side(c, sc, rc) : pomgpu_tp_move(c, sc, rc);
-    if (side) side_end(c, c->ev_r1);
+    if (side) side_end(c, c->side_ev[SIDE_R1].ev);
     if (rcm) return;
     launch_advct_col(c, sum2d);
-    if (side) (void)hipStreamWaitEvent(c->stream, c->ev_r1, 0);
+    if (side) (void)hipStreamWaitEvent(c->stream, c->side_ev[SIDE_R1].ev, 0);
     launch_advct_fix(c, T.nbr[0] >= 0 ? rcv[0] : NULL, T.nbr[2] >= 0 ? rcv[2] : NULL);
     if (sum2d) launch_advct_fix2d(c, T.nbr[0] >= 0, T.nbr[2] >= 0);
     if (!defer_xch) xch(c, 2, D3(c, advx), P.kb, D3(c, advy), P.kb);   // :315, :405
@@ -950,7 +949,8 @@ static int seq_restore_interior(pomgpu_ctx *c) {              // bounds_forcing.
 
 // ---- the side stream --------------------------------------------------------------------------------------------------
 // side_begin: what is enqueued from here on goes to the side stream, after everything the main stream holds so far;
-// side_end(ev): back to the main stream; `ev` marks the end of the side work.  side_join: the main stream waits for it.
+// side_end(ev): back to the main stream; `ev` marks the end of the side work.  side_post(r): side_end on round r's event, and the main
+// stream owes it a wait; side_wait(r): the main stream waits for round r if it still owes that.  side_join: ... for all of them.
 static void side_begin(pomgpu_ctx *c) {
   (void)hipEventRecord(c->ev_fork, c->stream);
   (void)hipStreamWaitEvent(c->side, c->ev_fork, 0);
@@ -962,18 +962,22 @@ static void side_end(pomgpu_ctx *c, hipEvent_t ev) {
   c->cur = c->stream;
   if (c->wide.x) c->wide.x->cur = c->stream;
 }
+static void side_post(pomgpu_ctx *c, side_round r) {
+  side_end(c, c->side_ev[r].ev);
+  c->side_ev[r].pending = 1;
+}
+static void side_wait(pomgpu_ctx *c, side_round r) {
+  if (!c->side_ev[r].pending) return;
+  (void)hipStreamWaitEvent(c->stream, c->side_ev[r].ev, 0);
+  c->side_ev[r].pending = 0;
+}
 // "The early part of this step's wide exchange has been posted" (early_started) is a fact about the MESSAGE PATTERN of the step:
 // wide_begin posts the late part only while it holds, and every rank must post alike.  Joining the side stream therefore only
 // waits; the flag falls when wide_begin has used it, or when something rewrites the arrays the early part carried (an upload:
 // early_invalidate -- to be called on all ranks alike, like the upload itself).
 static void side_join(pomgpu_ctx *c) {                        // everything the side stream holds, before the main stream goes on
   if (c->early_started) (void)hipStreamWaitEvent(c->stream, c->ev_early, 0);
-  if (c->side_pending) { (void)hipStreamWaitEvent(c->stream, c->ev_side, 0); c->side_pending = 0; }
-  if (c->r2_pending) { (void)hipStreamWaitEvent(c->stream, c->ev_r2, 0); c->r2_pending = 0; }
-  if (c->r8_pending) { (void)hipStreamWaitEvent(c->stream, c->ev_r8, 0); c->r8_pending = 0; }
-  if (c->rw_pending) { (void)hipStreamWaitEvent(c->stream, c->ev_rw, 0); c->rw_pending = 0; }
-  if (c->rq_pending) { (void)hipStreamWaitEvent(c->stream, c->ev_rq, 0); c->rq_pending = 0; }
-  if (c->rts_pending) { (void)hipStreamWaitEvent(c->stream, c->ev_rts, 0); c->rts_pending = 0; }
+  for (int r = 0; r < SIDE__count; r++) side_wait(c, (side_round)r);
 }
 // ---- rim rounds: exchange points on the side stream, beside the kernels of the main stream ------------------------------------------
 // north_star: "halo exchange ... overlapped with interior stencil compute on a second HIP stream".  Four of the step's exchange points
@@ -1002,44 +1006,49 @@ static void side_join(pomgpu_ctx *c) {                        // everything the 
 // POMGPU_RIM_RESULTS_MAIN keeps the reference's three input exchanges (on the kernels' stream).
 // All ranks post the same rounds in the same order on either communicator: whether this path is taken depends on nothing but the
 // agreed side stream (pomgpu_tp_side_ok) and the collective switch set (POMGPU_RIM_MAIN keeps the four rounds on the main stream).
+// Each round's event and "the main stream has not waited yet" are entry SIDE_<round> of pomgpu_ctx::side_ev (R7 uses R8's event).
 static int rim_side(pomgpu_ctx *c) { return c->tp.on && c->exch && c->wide.on && c->wide.split && !SW(c, RIM_MAIN); }
-static void rim_wait_r2(pomgpu_ctx *c) { if (c->r2_pending) { (void)hipStreamWaitEvent(c->stream, c->ev_r2, 0); c->r2_pending = 0; } }
-static void rim_wait_r8(pomgpu_ctx *c) { if (c->r8_pending) { (void)hipStreamWaitEvent(c->stream, c->ev_r8, 0); c->r8_pending = 0; } }
-static void rim_wait_rw(pomgpu_ctx *c) { if (c->rw_pending) { (void)hipStreamWaitEvent(c->stream, c->ev_rw, 0); c->rw_pending = 0; } }
-static void rim_wait_rq(pomgpu_ctx *c) { if (c->rq_pending) { (void)hipStreamWaitEvent(c->stream, c->ev_rq, 0); c->rq_pending = 0; } }
-static void rim_wait_rts(pomgpu_ctx *c) { if (c->rts_pending) { (void)hipStreamWaitEvent(c->stream, c->ev_rts, 0); c->rts_pending = 0; } }
-// one exchange point on the side stream (the caller has called side_begin): `dev2`, if given, is a second list of arrays of the same
-// shapes that receive the same ghost values (u, v behind uf, vf)
-static int rim_exchange(pomgpu_ctx *c, double *const *dev, const int *nz, int count, double *const *dev2 = NULL) {
+// One exchange point: pack8 towards the eight neighbours -> one message round -> unpack8 (parallel_mpi.f:154-351), all on one stream.
+// side = 0: the main stream, the transport's first set of staging buffers.  side = 1: the side stream and its own set (the caller has
+// called side_begin).  `dev2`, if given, is a second list of arrays of the same shapes that receive the same ghost values (u, v behind uf, vf)
+static int round8(pomgpu_ctx *c, int side, double *const *dev, const int *nz, int count, double *const *dev2 = NULL) {
   const KP &P = c->P;
   pomgpu_transport &T = c->tp;
+  const char *what = side ? "exchange (side stream)" : "exchange";
+  double *const *snd = side ? T.send2 : T.send, *const *rcv = side ? T.recv2 : T.recv;
+  const size_t *cap = side ? T.cap2 : T.cap;
   size_t total = 0;
   for (int a = 0; a < count; a++) total += (size_t)nz[a];
   const size_t len[8] = {(size_t)P.jm, (size_t)P.jm, (size_t)P.im, (size_t)P.im, 1, 1, 1, 1};
   size_t cnt[8];
   for (int d = 0; d < 8; d++) {
     cnt[d] = T.nbr[d] >= 0 ? total * len[d] : 0;
-    if (cnt[d] > T.cap2[d]) return fail(c, POMGPU_EINVAL, "exchange (side stream): %zu doubles exceed the staging buffer", cnt[d]);
+    if (cnt[d] > cap[d]) return fail(c, POMGPU_EINVAL, "%s: %zu doubles exceed the staging buffer", what, cnt[d]);
   }
-  if (launch_halo_pack8(c, dev, nz, count, T.send2)) return fail(c, POMGPU_EINVAL, "exchange (side stream): bad array list");
-  const int rc = pomgpu_tp_move_side(c, cnt, cnt);
+  if (launch_halo_pack8(c, dev, nz, count, snd)) return fail(c, POMGPU_EINVAL, "%s: bad array list", what);
+  const int rc = side ? pomgpu_tp_move_side(c, cnt, cnt) : pomgpu_tp_move(c, cnt, cnt);
   if (rc) return rc;
-  (void)launch_halo_unpack8(c, dev, nz, count, (const double *const *)T.recv2);
-  if (dev2) (void)launch_halo_unpack8(c, dev2, nz, count, (const double *const *)T.recv2);
+  (void)launch_halo_unpack8(c, dev, nz, count, rcv);
+  if (dev2) (void)launch_halo_unpack8(c, dev2, nz, count, rcv);
   return POMGPU_OK;
+}
+// one rim round: the exchange point on the side stream, behind everything the main stream holds so far; the main stream owes side_wait(c, r)
+static int rim_round(pomgpu_ctx *c, side_round r, double *const *dev, const int *nz, int count, double *const *dev2 = NULL) {
+  side_begin(c);
+  const int rc = round8(c, 1, dev, nz, count, dev2);
+  side_post(c, r);
+  return rc;
 }
 static void early_invalidate(pomgpu_ctx *c) {
   if (c->early_started) { (void)hipStreamWaitEvent(c->stream, c->ev_early, 0); c->early_started = 0; }
 }
-// the side stream and its three events, created on first use; 1 = they exist
+// the side stream and its events, created on first use; 1 = they exist
 int pomgpu_side_stream(pomgpu_ctx *c) {
   if (c->side) return 1;
   if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess) { c->side = NULL; return 0; }
-  if (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_early, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_side, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_r1, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_r2, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_r8, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_rw, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_rq, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_rts, hipEventDisableTiming) != hipSuccess) {
+  bool ok = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_early, hipEventDisableTiming) == hipSuccess;
+  for (auto &e : c->side_ev) ok = ok && hipEventCreateWithFlags(&e.ev, hipEventDisableTiming) == hipSuccess;
+  if (!ok) {
     (void)hipStreamDestroy(c->side);
     c->side = NULL;
     return 0;
@@ -1095,7 +1104,7 @@ extern "C" int pomgpu_get_time(pomgpu_ctx *c) {               // advance.f:62-75
 // would otherwise gather by reading advx, advy, drhox, drhoy again (advance.f:152-168)
 static int lateral_viscosity(pomgpu_ctx *c, int sum2d, int defer_rt = 0) {      // advance.f:96-141
   NEED_HOT(c);
-  rim_wait_rts(c);                                            // rho's ghost lines (rim round Rts of the step before; posted ahead of R8 on the same stream)
+  side_wait(c, SIDE_RTS);                                     // rho's ghost lines (rim round Rts of the step before; posted ahead of R8 on the same stream)
   rho_materialize(c);                                         // a deferred round trip no step has consumed (baropg reads rho)
   KP &P = c->P;
   if (P.mode != 2) {
@@ -1110,20 +1119,19 @@ static int lateral_viscosity(pomgpu_ctx *c, int sum2d, int defer_rt = 0) {      
     };
     // rim round R8 of the step before (the ghost cells of u, v, ub, vb) may still be in flight: baropg reads none of them and
     // shares nothing with advct, so it goes first and advct waits
-    const bool pg_first = c->r8_pending != 0;
+    const bool pg_first = c->side_ev[SIDE_R8].pending != 0;
     if (pg_first) pressure_gradient();
-    rim_wait_r8(c);
+    side_wait(c, SIDE_R8);
     seq_advct(c, sum2d, lib_x);                               // lib_x: advx, advy travel with aam below
     if (!pg_first) pressure_gradient();
     launch_aam(c);
     if (lib_x && sum2d && rim_side(c)) {                      // rim round R2: solver.f:315,405 + :137 on the side stream
       double *arr[3] = {D3(c, advx), D3(c, advy), D3(c, aam)};
       const int nz[3] = {P.kb, P.kb, P.kbm1};
-      side_begin(c);
-      const int rc2 = rim_exchange(c, arr, nz, 3);
+      side_begin(c);                                          // (rim_round by hand: one more launch behind the round)
+      const int rc2 = round8(c, 1, arr, nz, 3);
       if (!rc2) launch_vint(c, 1, -1);                        // aam2d on the ghost lines (advance.f:158-168), from the aam that has just arrived
-      side_end(c, c->ev_r2);
-      c->r2_pending = 1;
+      side_post(c, SIDE_R2);
       if (rc2) return rc2;
     }
     else if (lib_x) xch(c, 3, D3(c, advx), P.kb, D3(c, advy), P.kb, D3(c, aam), P.kbm1);   // solver.f:315,405 + :137 in one round
@@ -1152,7 +1160,7 @@ static int mode_interaction(pomgpu_ctx *c, int sums_done) {   // advance.f:144-2
   if (c->wide.on) {                                           // one wide exchange instead of ~180 narrow ones
     // :152-168; while rim round R2 is in flight aam's ghost lines are not there yet: this launch leaves aam2d's alone, the side stream
     // fills them behind the round (lateral_viscosity)
-    if (c->P.mode != 2) launch_vint(c, sums_done, sums_done && c->r2_pending ? 1 : 0);
+    if (c->P.mode != 2) launch_vint(c, sums_done, sums_done && c->side_ev[SIDE_R2].pending ? 1 : 0);
     return wide_begin(c);                                     // :170-199 on the extended tile
   }
   if (c->P.mode != 2) {
@@ -1308,23 +1316,8 @@ static int ext_loop_all(pomgpu_ctx *c) {
   return 1;
 }
 // ---- the library's own exchange (include/pomgpu.h "transport") -----------------------------------------------
-// every exchange point: pack8 -> one message round -> unpack8, all on the stream (parallel_mpi.f:154-351)
-static void tp_exchange(void *user, double *const *dev, const int *nz, int count) {
-  pomgpu_ctx *c = (pomgpu_ctx *)user;
-  const KP &P = c->P;
-  pomgpu_transport &T = c->tp;
-  size_t total = 0;
-  for (int a = 0; a < count; a++) total += (size_t)nz[a];
-  const size_t len[8] = {(size_t)P.jm, (size_t)P.jm, (size_t)P.im, (size_t)P.im, 1, 1, 1, 1};
-  size_t cnt[8];
-  for (int d = 0; d < 8; d++) {
-    cnt[d] = T.nbr[d] >= 0 ? total * len[d] : 0;
-    if (cnt[d] > T.cap[d]) { (void)fail(c, POMGPU_EINVAL, "exchange: %zu doubles exceed the staging buffer", cnt[d]); return; }
-  }
-  if (launch_halo_pack8(c, dev, nz, count, T.send)) { (void)fail(c, POMGPU_EINVAL, "exchange: bad array list"); return; }
-  if (pomgpu_tp_move(c, cnt, cnt)) return;
-  (void)launch_halo_unpack8(c, dev, nz, count, T.recv);
-}
+// every exchange point: round8 on the stream (the hook has no return value: a failed round has set error_status)
+static void tp_exchange(void *user, double *const *dev, const int *nz, int count) { (void)round8((pomgpu_ctx *)user, 0, dev, nz, count); }
 // order2d_mpi / order3d_mpi (parallel_mpi.f:353-480): eastward and northward only
 static void tp_order(void *user, const double *send_e, int n_e, const double *send_n, int n_n, double *recv_w, double *recv_s) {
   pomgpu_ctx *c = (pomgpu_ctx *)user;
@@ -1695,19 +1688,13 @@ extern "C" int pomgpu_mode_external(pomgpu_ctx *c) {
 // output file), so realvertvl itself may run there as well (with_kernel: beside the NEXT step's external substeps, below)
 static int wr_on_side(pomgpu_ctx *c, int with_kernel) {
   const KP &P = c->P;
-  if (c->side_pending) { (void)hipStreamWaitEvent(c->stream, c->ev_side, 0); c->side_pending = 0; }   // at most one piece of side work outstanding per event
+  side_wait(c, SIDE_WR);                                      // at most one piece of side work outstanding per event
   side_begin(c);
   if (with_kernel) launch_realvertvl(c);
   double *arr[1] = {D3(c, wr)};
   const int nz[1] = {P.kbm1};
-  const size_t len[8] = {(size_t)P.jm, (size_t)P.jm, (size_t)P.im, (size_t)P.im, 1, 1, 1, 1};
-  size_t cnt[8];
-  for (int d = 0; d < 8; d++) cnt[d] = c->tp.nbr[d] >= 0 ? (size_t)P.kbm1 * len[d] : 0;
-  int rcw = launch_halo_pack8(c, arr, nz, 1, c->tp.send2) ? fail(c, POMGPU_EINVAL, "wr exchange: bad array list") : POMGPU_OK;
-  if (!rcw) rcw = pomgpu_tp_move_side(c, cnt, cnt);
-  if (!rcw) (void)launch_halo_unpack8(c, arr, nz, 1, (const double *const *)c->tp.recv2);
-  side_end(c, c->ev_side);
-  c->side_pending = 1;
+  const int rcw = round8(c, 1, arr, nz, 1);                   // (kbm1 lines fit the side stream's buffers: pomgpu_set_wide_external sized them for kb)
+  side_post(c, SIDE_WR);
   return rcw;                                                 // a failed round is the step's failure (error_status is set)
 }
 // defer_wr (pomgpu_run, every step but the last of the call): realvertvl and wr's exchange are left to the next step, which runs
@@ -1719,8 +1706,8 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
   NEED_HOT(c);
   KP &P = c->P;
   const pom_blkcon &k = c->con;
-  rim_wait_r2(c);                                             // advx, advy, aam: ghost cells from the side stream (advq, advt2 read aam's)
-  rim_wait_r8(c);                                             // (a step whose lateral_viscosity did not run: nothing else has waited)
+  side_wait(c, SIDE_R2);                                      // advx, advy, aam: ghost cells from the side stream (advq, advt2 read aam's)
+  side_wait(c, SIDE_R8);                                      // (a step whose lateral_viscosity did not run: nothing else has waited)
   if ((k.iint != 1 || k.time0 != 0.) && k.mode != 2) {
     c->uvf_pending = 0;                                       // u, v change now and advq rewrites uf, vf whole: nobody has asked for the copy
     // :365-393 as a pass over u, v -- or applied by every kernel below to what it loads of them, u, v staying raw in memory until the
@@ -1734,14 +1721,11 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
     // column only), so on tiles it travels with profq's bottom-boundary exchange below -- one round less
     const bool lib_x = c->tp.on && c->exch;                   // the library's own exchange: rounds may be merged
     // rim rounds Rw, Rq, Rts (see "rim rounds" above): results behind the kernels instead of inputs in front of them
-    const bool rimr = lib_x && rim_side(c) && !SW(c, RIM_RESULTS_MAIN) && !SW(c, UV_FULL_EXCHANGE) && !SW(c, ADVQ_EXCHANGE) && !SW(c, PROD_FULL);
+    const bool rimr = lib_x && rim_side(c) && !SW(c, RIM_RESULTS_MAIN) && !SW(c, ADVQ_EXCHANGE) && !SW(c, PROD_FULL);
     if (rimr) {
       double *aw[1] = {D3(c, w)};
       const int nw[1] = {P.kb};
-      side_begin(c);
-      const int rcw = rim_exchange(c, aw, nw, 1);             // :400
-      side_end(c, c->ev_rw);
-      c->rw_pending = 1;
+      const int rcw = rim_round(c, SIDE_RW, aw, nw, 1);       // :400
       if (rcw) return rcw;
     }
     else if (!lib_x) xch(c, 1, D3(c, w), P.kb);
@@ -1786,13 +1770,10 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
     if (rimr) {
       double *aq[9] = {D3(c, q2), D3(c, q2b), D3(c, q2l), D3(c, q2lb), D3(c, km), D3(c, kh), D3(c, kq), D3(c, l), D3(c, dtef)};
       const int nq[9] = {P.kb, P.kb, P.kb, P.kb, P.kb, P.kb, P.kb, P.kb, P.kb};
-      side_begin(c);
-      const int rcq = rim_exchange(c, aq, nq, 9);
-      side_end(c, c->ev_rq);
-      c->rq_pending = 1;
+      const int rcq = rim_round(c, SIDE_RQ, aq, nq, 9);
       if (rcq) return rcq;
     }
-    rim_wait_rw(c);                                           // the tracer advection and advu / advv read w's ghost lines
+    side_wait(c, SIDE_RW);                                    // the tracer advection and advu / advv read w's ghost lines
     if (k.mode != 4) {
       if (k.nadv == 1) {
         seq_advt1(c, D3(c, tb), D3(c, t), D3(c, tclim), D3(c, uf));
@@ -1818,7 +1799,7 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
       // (without Rts but with Rq: uf(:,:,kb) still holds profq's bottom boundary value, which the reference exchanges at solver.f:1290 and
       // later copies into t(:,:,kb) with `t = uf` -- Rq does not carry it, so it rides here)
       if (!rts) xch(c, 2, D3(c, uf), rimr ? P.kb : P.kbm1, D3(c, vf), P.kbm1);   // :436-437
-      if (!rts) rim_wait_rq(c);                               // ... and proft's ghost columns, which nothing will replace, need kh of the ghost lines
+      if (!rts) side_wait(c, SIDE_RQ);                        // ... and proft's ghost columns, which nothing will replace, need kh of the ghost lines
       if (!launch_proft2(c, D3(c, uf), D2(c, wtsurf), D2(c, tsurf), k.nbct, D3(c, vf), D2(c, wssurf), D2(c, ssurf), k.nbcs)) {   // :439-440, T and S in one launch
         launch_proft(c, D3(c, uf), D2(c, wtsurf), D2(c, tsurf), k.nbct);
         launch_proft(c, D3(c, vf), D2(c, wssurf), D2(c, ssurf), k.nbcs);
@@ -1833,16 +1814,13 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
       if (rts) {
         double *at[5] = {D3(c, t), D3(c, tb), D3(c, s), D3(c, sb), D3(c, rho)};
         const int nt[5] = {P.kb, P.kb, P.kb, P.kb, P.kb};
-        side_begin(c);
-        const int rct = rim_exchange(c, at, nt, 5);
-        side_end(c, c->ev_rts);
-        c->rts_pending = 1;
+        const int rct = rim_round(c, SIDE_RTS, at, nt, 5);
         if (rct) return rct;
       }
     }
-    rim_wait_rq(c);                                           // profu / profv average km with the neighbour line's
+    side_wait(c, SIDE_RQ);                                    // profu / profv average km with the neighbour line's
     const bool fuse = uv_fused(c);                            // :461-462 and the interior of :469-514 in one kernel (one tile)
-    if (c->P.kb >= 6 && c->P.kb <= 64 && !SW(c, THOMAS_SCRATCH)) {
+    if (pomgpu_reg_kb(c)) {
       launch_advuv_col(c);                                    // :459-460 advu, advv in one pass
       if (fuse) launch_profuv_filter_reg(c, c->uvb_bot[0], c->uvb_bot[1]);
       else launch_profuv_reg(c);                              // :461-462 profu, profv with register-resident elimination vectors
@@ -1852,7 +1830,7 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
     }
     if (!lib_x) xch(c, 2, D2(c, wubot), 1, D2(c, wvbot), 1);  // solver.f:1777, :1874
     launch_bcondorl3(c);                                      // :464 (does not read wubot, wvbot)
-    const bool rim78 = lib_x && !SW(c, UV_FULL_EXCHANGE) && rim_side(c);
+    const bool rim78 = lib_x && rim_side(c);
     if (rim78) {
       // rim rounds R7 and R8: both of the step's last velocity exchanges on the side stream.  R7 brings uf, vf (and wubot, wvbot); the
       // filter below runs on the cells this tile OWNS and leaves the ghost lines alone -- there :469-514 ends in u = uf, v = vf
@@ -1860,23 +1838,21 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
       const int top = P.kb - 1;
       double *a7[4] = {D2(c, wubot), D2(c, wvbot), D3(c, uf), D3(c, vf)}, *b7[4] = {D2(c, wubot), D2(c, wvbot), D3(c, u), D3(c, v)};
       const int n7[4] = {1, 1, P.kbm1, P.kbm1};
-      side_begin(c);
-      int rcs = rim_exchange(c, a7, n7, 4, b7);               // solver.f:1777,1874 + :466-467
-      side_end(c, c->ev_r8);
+      side_begin(c);                                          // (R7 records R8's event without owing a wait: R8 below records it again)
+      const int rc7 = round8(c, 1, a7, n7, 4, b7);            // solver.f:1777,1874 + :466-467
+      side_end(c, c->side_ev[SIDE_R8].ev);
       launch_uv_filter(c, 1);                                 // :469-514 on owned cells, beside R7
       double *a8[6] = {D3(c, ub), D3(c, vb), LEV3(c, D3(c, u), top), LEV3(c, D3(c, uf), top), LEV3(c, D3(c, v), top), LEV3(c, D3(c, vf), top)};
       const int n8[6] = {P.kb, P.kb, 1, 1, 1, 1};
-      side_begin(c);                                          // behind the filter: R8 sends what it wrote
-      if (!rcs) rcs = rim_exchange(c, a8, n8, 6);             // :516-521
-      side_end(c, c->ev_r8);
-      c->r8_pending = 1;
-      if (rcs) return rcs;
+      if (rc7) { side_begin(c); side_post(c, SIDE_R8); return rc7; }   // a failed R7: what it left on the side stream is still waited for
+      const int rc8 = rim_round(c, SIDE_R8, a8, n8, 6);       // :516-521, behind the filter: R8 sends what it wrote
+      if (rc8) return rc8;
     } else {
       if (lib_x) xch(c, 4, D2(c, wubot), 1, D2(c, wvbot), 1, D3(c, uf), P.kbm1, D3(c, vf), P.kbm1);   // solver.f:1777,1874 + :466-467
       else xch(c, 2, D3(c, uf), P.kbm1, D3(c, vf), P.kbm1);   // :466-467
       if (fuse) { launch_uv_filter_rim(c); c->uvf_pending = 1; }   // :469-514 on the frame; the interior's uf, vf stay a flag
       else launch_uv_filter(c);                               // :469-514
-      if (lib_x && !SW(c, UV_FULL_EXCHANGE)) {
+      if (lib_x) {
         // :516-521 exchange all kb levels of ub, u, uf, vb, v, vf.  For u, uf, v, vf the levels 1..kbm1 are redundant: uf, vf
         // were exchanged at :466-467 and not written since, and u = uf, v = vf are copies.  What is not valid in a ghost
         // column is their level kb (profu / profv write it on owned columns only).  ub, vb are needed in full: the filter
@@ -1899,7 +1875,7 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
   // mirrors (pomgpu_wr_materialize) -- in a run of steps nobody does, and the next step's end simply sets the flag again
   if (wr_on_demand(c)) { c->wr_pending = 1; return POMGPU_OK; }
   c->wr_pending = 0;
-  rim_wait_r8(c);                                             // realvertvl reads u, v of the eastern / northern ghost line
+  side_wait(c, SIDE_R8);                                      // realvertvl reads u, v of the eastern / northern ghost line
   launch_realvertvl(c);                                       // :534
   // solver.f:2055 on the side stream: the round runs beside check_velocity and the next step's lateral_viscosity; the next
   // step's early gather follows it on the same stream, and whoever looks at the state waits for it (side_join)

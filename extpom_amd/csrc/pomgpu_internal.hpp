@@ -578,8 +578,8 @@ static inline dim3 grid2_halo(const KP &P) { return dim3((P.iml + 61) / 62, (P.j
   X(EXT_ROWS) X(EXT_NOPAIR) X(EXT_PAIR) X(EXT_ROWS2) X(EXT_TWO_SETS) X(EXT_AREAS_LOAD) X(BAROPG_CELLS) X(VERTVL_CELLS)        \
   X(NO_LIN) X(ADVQ_SINGLE) X(ADVT2_SINGLE) X(REALVERTVL_CELLS) X(RHO_ROUNDTRIP) X(TAU_ARRAYS) X(PROFQ_ROWS8) X(PROFQ_ROWS2)    \
   X(PROFQ_NOPACE) X(COL_STRIP) X(BAND_BYTES) X(PAD3) X(IO_SYNC) X(ADVCT_SPLIT) X(ADVQ_EXCHANGE) X(PROD_FULL) X(QFILTER_SPLIT) \
-  X(UV_FULL_EXCHANGE) X(NO_OVERLAP) X(NO_SIDE_COMM) X(WR_MAIN) X(WIDE_W) X(WIDE_FULL) X(DEBUG_ALLOC) X(TEST_SPLIT_FAIL_RANK)  \
-  X(EDGE_SPLIT) X(WR_NODEFER) X(EXT_RING_FIRST) X(TUNE_FORCE) X(NO_TWIN) X(RIM_MAIN) X(RIM_RESULTS_MAIN) X(SUM2D_OFF) X(ADVCT_ROWS4) X(ADVCT_ROWS8) \
+  X(NO_OVERLAP) X(NO_SIDE_COMM) X(WR_MAIN) X(WIDE_W) X(WIDE_FULL) X(DEBUG_ALLOC) X(TEST_SPLIT_FAIL_RANK)  \
+  X(WR_NODEFER) X(EXT_RING_FIRST) X(TUNE_FORCE) X(RIM_MAIN) X(RIM_RESULTS_MAIN) X(SUM2D_OFF) X(ADVCT_ROWS4) X(ADVCT_ROWS8) \
   X(IO_CHUNK_KB) X(UV_NOFUSE) X(W_NOFUSE) X(UVMEAN_PASS) X(PROFT_TWIN)
 enum pomgpu_sw {
 #define POMGPU_SW_(name) SW_##name,
@@ -610,8 +610,8 @@ static inline void pomgpu_switches_read(pomgpu_switches &s) {
 // order-independent digest of the switches that every rank of a decomposition must share (they choose which message
 // rounds exist and on which stream / communicator they run): the ranks compare it before any collective depends on it
 static inline unsigned pomgpu_switches_collective_digest(const pomgpu_switches &s) {
-  static const int coll[] = {SW_ADVCT_SPLIT, SW_ADVQ_EXCHANGE, SW_PROD_FULL, SW_QFILTER_SPLIT, SW_UV_FULL_EXCHANGE, SW_NO_OVERLAP,
-                             SW_NO_SIDE_COMM, SW_WR_MAIN, SW_WIDE_W, SW_WIDE_FULL, SW_EXT_SPLIT, SW_ADVAVE_SEPARATE, SW_EDGE_SPLIT, SW_WR_NODEFER, SW_RIM_MAIN, SW_ADVT2_SINGLE, SW_RIM_RESULTS_MAIN, SW_SUM2D_OFF};
+  static const int coll[] = {SW_ADVCT_SPLIT, SW_ADVQ_EXCHANGE, SW_PROD_FULL, SW_QFILTER_SPLIT, SW_NO_OVERLAP,
+                             SW_NO_SIDE_COMM, SW_WR_MAIN, SW_WIDE_W, SW_WIDE_FULL, SW_EXT_SPLIT, SW_ADVAVE_SEPARATE, SW_WR_NODEFER, SW_RIM_MAIN, SW_ADVT2_SINGLE, SW_RIM_RESULTS_MAIN, SW_SUM2D_OFF};
   unsigned h = 2166136261u;
   for (size_t n = 0; n < sizeof coll / sizeof coll[0]; n++) {
     h = (h ^ (unsigned)(s.on[coll[n]] ? 1 + coll[n] : 0)) * 16777619u;
@@ -664,6 +664,12 @@ struct pomgpu_wide {
   int pending;               // the 2-D state of the running external loop lives in x (between wide_begin and the last substep)
   int static_done;           // every blk2d array (grid metrics, masks ...) has been widened since the last upload
 };
+// Work on the side stream that the main stream waits for by event: the message rounds of exchange points that run there beside the main
+// stream's kernels (pomgpu_api.hip "rim rounds") and the wr exchange.  SIDE_WR = wr's round, with realvertvl where it runs there too;
+// SIDE_R1 = advct's edge lines have arrived (recorded and awaited inside seq_advct: never pending), SIDE_R2 = advx, advy, aam have their
+// ghost cells, SIDE_R8 = the velocity rounds that end mode_internal (uf, vf, wubot, wvbot; then ub, vb and level kb of u, uf, v, vf),
+// SIDE_RW = w has its ghost cells, SIDE_RQ = the turbulence arrays (q2, q2b, q2l, q2lb, km, kh, kq, l, dtef), SIDE_RTS = t, tb, s, sb, rho
+enum side_round { SIDE_WR, SIDE_R1, SIDE_R2, SIDE_R8, SIDE_RW, SIDE_RQ, SIDE_RTS, SIDE__count };
 
 struct pomgpu_ctx {
   KP P;
@@ -676,13 +682,9 @@ struct pomgpu_ctx {
   // second communicator, joined by events (no host synchronisation).  `cur` is the stream LAUNCH and the profiler use:
   // the main stream except while work for the side stream is being enqueued.
   hipStream_t cur, side;
-  hipEvent_t ev_fork, ev_early, ev_side;
-  // Message rounds of exchange points that run on the side stream beside the main stream's kernels (pomgpu_api.hip "rim rounds"):
-  // ev_r1 = advct's edge lines have arrived, ev_r2 = advx, advy, aam have their ghost cells (r2_pending: the main stream has not
-  // waited yet), ev_r8 = the velocity rounds that end mode_internal (uf, vf, wubot, wvbot; then ub, vb and level kb of u, uf, v, vf)
-  // ev_rw = w has its ghost cells, ev_rq = the turbulence arrays (q2, q2b, q2l, q2lb, km, kh, kq, l, dtef), ev_rts = t, tb, s, sb, rho
-  hipEvent_t ev_r1, ev_r2, ev_r8, ev_rw, ev_rq, ev_rts;
-  int r2_pending, r8_pending, rw_pending, rq_pending, rts_pending;
+  hipEvent_t ev_fork, ev_early;
+  // one event per side_round (above); pending: the main stream has not waited for it yet (side_post sets it, side_wait / side_join wait)
+  struct { hipEvent_t ev; int pending; } side_ev[SIDE__count];
   int early_started;         // this step's early part of the wide exchange is in flight on the side stream (ev_early ends it)
   double *tune_block;        // pomgpu_tune_placement: blk3d and the 3-D scratch arrays live in ONE allocation with room in front ...
   size_t tune_front;         // ... and start this many doubles into it
@@ -691,7 +693,6 @@ struct pomgpu_ctx {
   int dev3_handed;           // pomgpu_device_3d has given out an address of a 3-D array: pomgpu_tune_placement, which moves them, refuses from then on
   int broken;                // a relayout of the 3-D arrays failed half way (pomgpu_tune_placement): the mirrors no longer hold the state, every hot-path entry point refuses
   int wr_deferred;           // pomgpu_run: the last step's realvertvl + wr exchange are still to come (beside the next step's external substeps)
-  int side_pending;          // work on the side stream that the main stream has not waited for yet (ev_side ends it)
   pom_blkcon con;            // host copy of blkcon (iint, iext, error_status live here)
   int lramp;
   double *rec_t[POMGPU_MAXREC + 1], *rec_s[POMGPU_MAXREC + 1];
@@ -770,6 +771,10 @@ struct pomgpu_ctx {
   int launch_err;            // first hipError_t a kernel launch returned (0 = none); reported by the next sync / get_con
   char err[512];
 };
+// The register-resident column kernels (k_vert.hip: their level loops are unrolled for a template bound, with_kbt) serve this context's
+// kb: the bounds that are instantiated, and the scratch kernels not asked for.  Every launcher of such a kernel and every caller that
+// chooses between the two families asks here
+static inline bool pomgpu_reg_kb(const pomgpu_ctx *c) { return c->P.kb >= 6 && c->P.kb <= 64 && !SW(c, THOMAS_SCRATCH); }
 
 // launch helpers -----------------------------------------------------------------------------
 int pomgpu_prof_slot(pomgpu_ctx *c, const char *name);
@@ -854,8 +859,8 @@ void launch_advq2_col(pomgpu_ctx *c, const double *q, const double *qb, double *
 void launch_advq2w_col(pomgpu_ctx *c, const double *q, const double *qb, double *qf, const double *ql, const double *qlb, double *qlf, int zero_else);
 #endif
 void launch_advuv_col(pomgpu_ctx *c);
-int launch_profuv_reg(pomgpu_ctx *c);   // 0 when kb is outside the instantiated range
-void launch_profuv_filter_reg(pomgpu_ctx *c, double *ubk, double *vbk);   // k_uvb_bottom + k_profuv_filter_reg2 (kb in 6..64); ubk, vbk: two planes of n2 doubles
+int launch_profuv_reg(pomgpu_ctx *c);   // 0 when kb is outside the instantiated range (pomgpu_reg_kb)
+void launch_profuv_filter_reg(pomgpu_ctx *c, double *ubk, double *vbk);   // k_uvb_bottom + k_profuv_filter_reg2 (the caller has asked pomgpu_reg_kb); ubk, vbk: two planes of n2 doubles
 void launch_uv_filter_rim(pomgpu_ctx *c);   // the filter on the frame the fused kernel leaves out (im, jm >= 8)
 void launch_uvf_copy(pomgpu_ctx *c);        // u -> uf, v -> vf on that kernel's interior, levels 1..kbm1
 void launch_advave_m2a(pomgpu_ctx *c);

@@ -520,7 +520,7 @@ def test_restart_and_determinism_properties_1024x1024x40(bg_oracle):
 # ---- the instantiations bench.py runs: kb = 50 and 2048-wide rows ---------------------------------------------------
 @pytest.mark.parametrize("name", ["basin50_default", "basin50_nadv1", "basin50_npg2", "seamount50_default"])
 def test_gpu_reproduces_reference_digests_kb50(golden_kb50, name):
-    """256x192x50: the <50> instantiations of k_proft_reg / k_profuv_reg / k_uv_filter_reg / k_int_uvmean_reg (what the
+    """256x192x50: the <50> instantiations of k_proft_reg2 / k_profuv_reg2 / k_uv_filter_reg2 / k_int_uvmean_reg2 (what the
     2048x1536x50 bench dispatches) against digests of the REFERENCE's own state (oracle/_ref/libpomref_256x192x50.so,
     tests/golden/make_golden.py kb50)"""
     _reproduces(golden_kb50, name)

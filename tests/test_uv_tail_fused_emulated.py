@@ -38,7 +38,8 @@ def test_unobserved_steps_one_interior_column(case):
 
 @pytest.mark.parametrize("size", chk.SIZES_FALLBACK, ids=str)
 def test_unobserved_steps_fallback_shapes(size):
-    """no interior (7x9x6), kb beyond the register kernels (65): the fused kernel does not run, the state is the oracle's"""
+    """no interior (7x9x6), kb above and below the register kernels' range (65, 5: k_advu_profu / k_advv_profv run, and only there): the
+    fused kernel does not run, the state is the oracle's"""
     chk.unobserved_steps(EMU, "archipelago", None, size, fused=False)
 
 

@@ -18,11 +18,13 @@ NAMELISTS = {"default": dict(), "mode4": dict(mode=4), "nadv1": dict(nadv=1), "n
 # (im, jm, kb): a wavefront's 62-column edge inside the interior (65, 66), a flat tile, one interior column at the smallest register kb,
 # both sides of a template bound, the benchmark's kb, the largest register kb
 SIZES_FUSED = [(65, 49, 21), (66, 50, 21), (128, 12, 21), (8, 8, 6), (20, 14, 24), (20, 14, 25), (20, 14, 50), (20, 14, 64)]
-# no interior; kb beyond the register kernels: the unfused pair / the scratch kernels
-SIZES_FALLBACK = [(7, 9, 6), (20, 14, 65)]
+# no interior; kb on either side of the register kernels' range (6..64, whose two ends are fused above): the unfused pair / the scratch
+# kernels.  9x8: the smallest grid the fused tail accepts, so nothing but kb = 5 keeps it off
+SIZES_FALLBACK = [(7, 9, 6), (20, 14, 65), (9, 8, 5)]
 POINTS = ["mode_internal", "check_velocity", "lateral_viscosity", "mode_external_last"]
 ISPLIT = 30
 FUSED, RIM, UNFUSED, COPY = "k_profuv_filter_reg2", "k_uv_filter_rim", "k_uv_filter_reg2", "k_uvf_copy"
+SCRATCH_U, SCRATCH_V = "k_advu_profu", "k_advv_profv"        # advu + profu, advv + profv where kb is outside the register kernels' range
 
 
 def same_bits(x, y):
@@ -93,6 +95,8 @@ def unobserved_steps(lib, case, nml, size, fused=True, calls=(2, 1, 3)):
     else:
         assert launches(prof, FUSED) == 0 and launches(prof, RIM) == 0, prof
     assert launches(prof, COPY) == 0, prof
+    scratch = 0 if 6 <= size[2] <= 64 else body               # the scratch pair runs at exactly the kb the register kernels do not serve
+    assert launches(prof, SCRATCH_U) == scratch and launches(prof, SCRATCH_V) == scratch, prof
     OracleTile(a).run(sum(calls))
     g.download()
     assert a.iint == b.iint and not diff(a, b), diff(a, b)
