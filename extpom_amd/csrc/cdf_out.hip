@@ -1,5 +1,6 @@
-// cdf_out.hip -- the writer: the output and restart files of the reference WITHOUT PnetCDF.  Host code plus device-to-host copies, no
-// kernel; the readers are cdf_in.hip (restart, cold start) and frc_files.hip (forcing records).
+// cdf_out.hip -- the writer: the output and restart files of the reference WITHOUT PnetCDF.  Host code plus device-to-host copies; the
+// only kernels are the two of the time-mean output at the end of the file (k_mean_accum, k_mean_snapshot).  The readers are cdf_in.hip
+// (restart, cold start) and frc_files.hip (forcing records).
 // io_pnetcdf.F writes NetCDF "64-bit offset" files
 // (nf_64bit_offset = CDF-2) through the parallel library: write_output_pnetcdf (:57-410) and
 // write_restart_pnetcdf (:1661-2083).  The classic format is simple enough to emit directly: a header (dimensions,
@@ -165,7 +166,19 @@ extern "C" int pomgpu_io_wait(pomgpu_ctx *c) {
   return rc;
 }
 
-static int write_file(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m, Spec &S) {
+// the nine time-dependent fields of the output file, in the order of pomgpu_ctx::mean_off
+#define MEAN_NF 9
+static const int MEAN_3D[MEAN_NF] = {0, 0, 0, 1, 1, 1, 1, 1, 1};
+static const int MEAN_SLOT[MEAN_NF] = {P2_uab, P2_vab, P2_elb, P3_u, P3_v, P3_t, P3_s, P3_rho, P3_w};
+static int mean_field(const Var &v) {                                 // which of them a variable of the file is, -1 = none
+  for (int q = 0; q < MEAN_NF; q++)
+    if ((v.src == VOLUME3D) == (MEAN_3D[q] != 0) && (v.src == VOLUME3D || v.src == PLANE2D) && v.slot == MEAN_SLOT[q]) return q;
+  return -1;
+}
+static void launch_mean_snapshot(pomgpu_ctx *c, double *const *dst, const size_t *nout);
+// mean != 0 (pomgpu_write_output_mean): the nine fields come from the accumulators -- k_mean_snapshot stores acc / count into the snapshot
+// and +0.0 into acc in one pass, on the kernels' stream -- and the count returns to 0
+static int write_file(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m, Spec &S, int mean = 0) {
   const KP &P = c->P;
   if (!tile_fits(m, P, 0, 0, 0, 0))
     return fail(c, POMGPU_EINVAL, "write: the tile (%d..%d, %d..%d) does not fit the global grid %d x %d", m->i0, m->i0 + P.im - 1, m->j0,
@@ -207,15 +220,38 @@ static int write_file(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m
   if (async && hipMalloc((void **)&J->snap, total * sizeof(double)) != hipSuccess) { J->snap = NULL; (void)hipGetLastError(); async = false; }
 #endif
   auto dev_of = [&](const Var &v) { return v.src == PLANE2D ? P.b2 + (size_t)v.slot * P.n2 : P.b3 + (size_t)v.slot * P.a3; };
+  // the means: where each of the nine lands in `base` (the snapshot, or on the synchronous path a buffer for the nine alone), one launch
+  double *mdst[MEAN_NF] = {NULL};
+  size_t mout[MEAN_NF] = {0};
+  auto take_means = [&](double *base, bool nine_only) {
+    size_t o = 0;
+    for (const Var &v : S.vars) {
+      const size_t n = var_doubles(*J, v);
+      const int q = mean_field(v);
+      if (q >= 0 && n) { mdst[q] = base + o; mout[q] = n; }
+      if (q >= 0 || !nine_only) o += n;
+    }
+    launch_mean_snapshot(c, mdst, mout);
+    c->mean_count = 0;
+  };
   if (!async) {                                                        // the synchronous path: variable by variable through pageable memory
+    double *nine = NULL;
+    if (mean && !bad) {
+      size_t tot9 = 0;
+      for (const Var &v : S.vars) if (mean_field(v) >= 0) tot9 += var_doubles(*J, v);
+      if (hipMalloc((void **)&nine, (tot9 ? tot9 : 1) * sizeof(double)) != hipSuccess) { nine = NULL; (void)hipGetLastError(); bad = 1; }
+      else take_means(nine, true);
+    }
     for (const Var &v : S.vars) {
       const size_t n = var_doubles(*J, v);
       if (bad || !n) continue;
       host.resize(n);
-      if (hipMemcpyAsync(host.data(), dev_of(v), sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      const int q = mean ? mean_field(v) : -1;
+      if (hipMemcpyAsync(host.data(), q >= 0 ? mdst[q] : dev_of(v), sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
           hipStreamSynchronize(c->stream) != hipSuccess) { bad = 1; break; }
       bad |= put_var(*J, v, host.data(), tmp);
     }
+    if (nine) { (void)hipStreamSynchronize(c->stream); (void)hipFree(nine); }
     if (close(fd)) bad = 1;
     J->fd = -1;
     c->io_job = J;
@@ -227,9 +263,11 @@ static int write_file(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m
   for (const Var &v : S.vars) {                                        // the snapshot, on the kernels' stream
     const size_t n = var_doubles(*J, v);
     if (!n) continue;
-    if (hipMemcpyAsync(J->snap + off, dev_of(v), n * sizeof(double), hipMemcpyDeviceToDevice, c->stream) != hipSuccess) bad = 1;
+    if (!(mean && mean_field(v) >= 0) &&
+        hipMemcpyAsync(J->snap + off, dev_of(v), n * sizeof(double), hipMemcpyDeviceToDevice, c->stream) != hipSuccess) bad = 1;
     off += n;
   }
+  if (mean) take_means(J->snap, false);
   if (hipEventCreateWithFlags(&J->ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(J->ev, c->stream) != hipSuccess ||
       hipStreamCreateWithFlags(&J->st, hipStreamNonBlocking) != hipSuccess) bad = 1;
   J->S = S;
@@ -246,16 +284,11 @@ static void stats_for_file(pomgpu_ctx *c, const pomgpu_file_meta *m, double *s8)
   (void)pomgpu_domain_stats(c, s8, 0);
 }
 
-extern "C" int pomgpu_write_output(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m) {   // io_pnetcdf.F:57-410
-#ifdef POMGPU_STORE_F32
-  if (c) return pomgpu_fail(c, POMGPU_EINVAL, "write_output: not in the fp32-storage variant (download and write from the host)");
-#endif
-  if (!c || !path || !m) return POMGPU_EINVAL;
-  (void)hipSetDevice(c->device);
+// the output file's layout (io_pnetcdf.F:57-410) with `time` and the statistics as of now: the snapshot file's and the mean file's alike
+static void output_spec(pomgpu_ctx *c, const pomgpu_file_meta *m, Spec &S) {
   const KP &P = c->P;
   double s8[8];
   stats_for_file(c, m, s8);                                   // also brings every lazily kept array up to date (NEED)
-  Spec S;
   S.dims = {{"time", 1}, {"z", P.kb}, {"zz", P.kbm1}, {"y", m->jm_global}, {"x", m->im_global}};
   S.gatts = {{"title", m->title ? m->title : ""}, {"description", "output file"}};
   const std::string since = std::string("days since ") + (m->time_start ? m->time_start : "");
@@ -294,6 +327,15 @@ extern "C" int pomgpu_write_output(pomgpu_ctx *c, const char *path, const pomgpu
   S.vars.push_back(mk("s", {T, ZZ, Y, X}, "salinity x rho / rhoref", "PSS", "east_e north_e zz", VOLUME3D, P3_s, P.kbm1));
   S.vars.push_back(mk("rho", {T, ZZ, Y, X}, "(density-1000)/rhoref", "dimensionless", "east_e north_e zz", VOLUME3D, P3_rho, P.kbm1));
   S.vars.push_back(mk("w", {T, Z, Y, X}, "z-velocity", "metre/sec", "east_e north_e z", VOLUME3D, P3_w, P.kb));
+}
+extern "C" int pomgpu_write_output(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m) {   // io_pnetcdf.F:57-410
+#ifdef POMGPU_STORE_F32
+  if (c) return pomgpu_fail(c, POMGPU_EINVAL, "write_output: not in the fp32-storage variant (download and write from the host)");
+#endif
+  if (!c || !path || !m) return POMGPU_EINVAL;
+  (void)hipSetDevice(c->device);
+  Spec S;
+  output_spec(c, m, S);
   return write_file(c, path, m, S);
 }
 
@@ -344,6 +386,148 @@ extern "C" int pomgpu_write_restart(pomgpu_ctx *c, const char *path, const pomgp
       {"q2lb", "q2 x l at time -dt", "metre^3/sec^2", "east_e north_e zz", P3_q2lb}};
   for (auto &q : p3) S.vars.push_back(mk(q.n, {Z, Y, X}, q.ln, q.u, q.co, VOLUME3D, q.slot, P.kb));
   return write_file(c, path, m, S);
+}
+
+// ---- the time-mean output (include/pomgpu.h: pomgpu_set_mean_output; no counterpart in the reference) -------------------------------
+// One fp64 accumulator per time-dependent field of the output file.  k_mean_accum, once per internal step behind mode_internal: acc =
+// acc + x, one add per cell in step order, for all nine fields in ONE launch -- blockIdx.y picks the field from a table passed by value.
+// A pure stream: x read, acc read, acc written.  A workgroup moves 1024 consecutive doubles of its field, 16 bytes per lane and access
+// where x and acc are 16-byte aligned alike (pomgpu_set_mean_output places every accumulator that way for the mirror as it lies then).
+// Array n of blk3d starts n * a3 doubles into the block: with an odd a3 (65x49x21: 66885) every other one is 8-byte aligned only and the
+// length is odd, so a field is [one head element] + pairs + [one tail element].  Head and tail are lanes 0 and 1 of the field's first
+// workgroup with an 8-byte access of their own; everywhere a lane without work carries the offset BOFF_NONE, which the descriptor's range
+// check drops (pomgpu_internal.hpp), so no load or store stands in a divergent branch: the only branches are uniform per workgroup.
+// A field whose x and acc differ in alignment (uab, vab, elb while the external mode's result lives in the other generation of its
+// arrays and n2 is odd) takes the 8-byte form throughout.
+struct MeanJob { const double *x; double *acc; double *dst; unsigned n, nout; };
+struct MeanTab { MeanJob j[MEAN_NF]; double cnt; };
+struct Pair2 { double a, b; };
+#ifndef POMGPU_EMU
+typedef unsigned int pomgpu_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ Pair2 bld2x2(const BufA &b, unsigned voff) {
+  const pomgpu_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(b.r, (int)voff, 0, 0);
+  Pair2 r;
+  r.a = __hiloint2double((int)v.y, (int)v.x); r.b = __hiloint2double((int)v.w, (int)v.z);
+  return r;
+}
+__device__ __forceinline__ void bst2x2(const BufA &b, unsigned voff, Pair2 x) {
+  pomgpu_u32x4 v;
+  v.x = (unsigned)__double2loint(x.a); v.y = (unsigned)__double2hiint(x.a); v.z = (unsigned)__double2loint(x.b); v.w = (unsigned)__double2hiint(x.b);
+  __builtin_amdgcn_raw_buffer_store_b128(v, b.r, (int)voff, 0, 0);
+}
+#else
+static inline Pair2 bld2x2(const BufA &b, unsigned voff) { Pair2 r = {0., 0.}; if (voff < BOFF_NONE) { r.a = b.p[voff >> 3]; r.b = b.p[(voff >> 3) + 1]; } return r; }
+static inline void bst2x2(const BufA &b, unsigned voff, Pair2 x) { if (voff < BOFF_NONE) { b.p[voff >> 3] = x.a; b.p[(voff >> 3) + 1] = x.b; } }
+#endif
+#define MEAN_WG 1024u                                                  /* doubles of a field per workgroup of 256 lanes */
+// workgroup and lane: the launch's own (the workgroup number is a scalar, so every branch on it is one the compiler knows to be uniform);
+// the host emulation runs workgroups of width 1 and takes both from the global lane number
+#ifndef POMGPU_EMU
+#define MEAN_WG_ID blockIdx.x
+#define MEAN_LANE_ID threadIdx.x
+#else
+#define MEAN_WG_ID ((blockIdx.x * blockDim.x + threadIdx.x) >> 8)
+#define MEAN_LANE_ID ((blockIdx.x * blockDim.x + threadIdx.x) & 255u)
+#endif
+__global__ void __launch_bounds__(256) k_mean_accum(MeanTab T) {
+  const MeanJob J = T.j[blockIdx.y];
+  const unsigned wg = MEAN_WG_ID, lane = MEAN_LANE_ID, n = J.n;
+  if ((size_t)wg * MEAN_WG >= n) return;
+  if (((((size_t)J.x ^ (size_t)J.acc) >> 3) & 1) == 0) {
+    const unsigned head = (unsigned)(((size_t)J.x >> 3) & 1), np = (n - head) >> 1, tail = (n - head) & 1u;
+    const BufA bx = buf2_of(J.x + head, 2 * (size_t)np), ba = buf2_of(J.acc + head, 2 * (size_t)np);
+    unsigned off[2];
+    Pair2 x[2], a[2];
+#pragma unroll
+    for (int u = 0; u < 2; u++) { const unsigned p = wg * (MEAN_WG / 2) + (unsigned)u * 256u + lane; off[u] = p < np ? p * 16u : BOFF_NONE; }
+#pragma unroll
+    for (int u = 0; u < 2; u++) { x[u] = bld2x2(bx, off[u]); a[u] = bld2x2(ba, off[u]); }
+#pragma unroll
+    for (int u = 0; u < 2; u++) { a[u].a = a[u].a + x[u].a; a[u].b = a[u].b + x[u].b; bst2x2(ba, off[u], a[u]); }
+    if (wg == 0) {                                                     // the element in front of the pairs and the one behind them
+      const BufA b1 = buf2_of(J.x, n), b2 = buf2_of(J.acc, n);
+      const unsigned o = (lane == 0 && head) ? 0u : ((lane == 1 && tail) ? (n - 1) * 8u : BOFF_NONE);
+      bst2(b2, o, 0, bld2(b2, o, 0) + bld2(b1, o, 0));
+    }
+  } else {
+    const BufA bx = buf2_of(J.x, n), ba = buf2_of(J.acc, n);
+    unsigned off[4];
+    double x[4], a[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) { const unsigned e = wg * MEAN_WG + (unsigned)u * 256u + lane; off[u] = e < n ? e * 8u : BOFF_NONE; }
+#pragma unroll
+    for (int u = 0; u < 4; u++) { x[u] = bld2(bx, off[u], 0); a[u] = bld2(ba, off[u], 0); }
+#pragma unroll
+    for (int u = 0; u < 4; u++) bst2(ba, off[u], 0, a[u] + x[u]);
+  }
+}
+// The mean file's snapshot: dst = acc / count -- one IEEE division per cell, no reciprocal -- over the `nout` doubles the file holds of a
+// field (kbm1 levels of u v t s rho) and acc = +0.0 over all n of them, in one pass: a pomgpu_run issued right after the call accumulates
+// into clean sums behind this kernel while the writer's thread is still copying the snapshot.  Once per output interval: 8 bytes per lane
+__global__ void __launch_bounds__(256) k_mean_snapshot(MeanTab T) {
+  const MeanJob J = T.j[blockIdx.y];
+  const unsigned wg = MEAN_WG_ID, lane = MEAN_LANE_ID, n = J.n;
+  if ((size_t)wg * MEAN_WG >= n) return;
+  const BufA ba = buf2_of(J.acc, n), bd = buf2_of(J.dst, J.nout);
+  unsigned off[4];
+  double a[4];
+#pragma unroll
+  for (int u = 0; u < 4; u++) { const unsigned e = wg * MEAN_WG + (unsigned)u * 256u + lane; off[u] = e < n ? e * 8u : BOFF_NONE; }
+#pragma unroll
+  for (int u = 0; u < 4; u++) a[u] = bld2(ba, off[u], 0);
+#pragma unroll
+  for (int u = 0; u < 4; u++) {
+    bst2(bd, off[u] < J.nout * 8u ? off[u] : BOFF_NONE, 0, a[u] / T.cnt);
+    bst2(ba, off[u], 0, 0.);
+  }
+}
+static size_t mean_len(const pomgpu_ctx *c, int q) { return MEAN_3D[q] ? c->P.n3 : c->P.n2; }
+static dim3 mean_grid(const pomgpu_ctx *c) { return dim3((unsigned)((c->P.n3 + MEAN_WG - 1) / MEAN_WG), MEAN_NF, 1); }
+void launch_mean_accum(pomgpu_ctx *c, const double *const *x) {
+  MeanTab T;
+  for (int q = 0; q < MEAN_NF; q++) { T.j[q].x = x[q]; T.j[q].acc = c->mean_acc + c->mean_off[q]; T.j[q].dst = NULL; T.j[q].n = (unsigned)mean_len(c, q); T.j[q].nout = 0; }
+  T.cnt = 0.;
+  LAUNCH(c, k_mean_accum, mean_grid(c), dim3(256), T);
+}
+static void launch_mean_snapshot(pomgpu_ctx *c, double *const *dst, const size_t *nout) {
+  MeanTab T;
+  for (int q = 0; q < MEAN_NF; q++) {
+    T.j[q].x = NULL; T.j[q].acc = c->mean_acc + c->mean_off[q]; T.j[q].dst = dst[q] ? dst[q] : T.j[q].acc; T.j[q].n = (unsigned)mean_len(c, q);
+    T.j[q].nout = dst[q] ? (unsigned)nout[q] : 0;
+  }
+  T.cnt = (double)c->mean_count;
+  LAUNCH(c, k_mean_snapshot, mean_grid(c), dim3(256), T);
+}
+static int mean_which(int is3d, int slot) {
+  for (int q = 0; q < MEAN_NF; q++)
+    if ((is3d != 0) == (MEAN_3D[q] != 0) && slot == MEAN_SLOT[q]) return q;
+  return -1;
+}
+extern "C" int pomgpu_mean_download(pomgpu_ctx *c, int is3d, int slot, double *host) {
+  if (!c || !host) return POMGPU_EINVAL;
+  if (!c->mean_acc) return pomgpu_fail(c, POMGPU_EINVAL, "mean_download: the time-mean output is off (pomgpu_set_mean_output)");
+  const int q = mean_which(is3d, slot);
+  if (q < 0) return pomgpu_fail(c, POMGPU_EINVAL, "mean_download: %s slot %d is not accumulated (uab vab elb; u v t s rho w)", is3d ? "blk3d" : "blk2d", slot);
+  if (c->mean_count < 1) return pomgpu_fail(c, POMGPU_EINVAL, "mean_download: no step has been accumulated since the switch or the last mean file");
+  (void)hipSetDevice(c->device);
+  const size_t n = mean_len(c, q);
+  if (hipMemcpyAsync(host, c->mean_acc + c->mean_off[q], n * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) return pomgpu_fail(c, POMGPU_EHIP, "mean_download: the copy failed");
+  const double cnt = (double)c->mean_count;
+  for (size_t e = 0; e < n; e++) host[e] = host[e] / cnt;            // the division k_mean_snapshot makes
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_write_output_mean(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m) {
+#ifdef POMGPU_STORE_F32
+  if (c) return pomgpu_fail(c, POMGPU_EINVAL, "write_output_mean: not in the fp32-storage variant (download and write from the host)");
+#endif
+  if (!c || !path || !m) return POMGPU_EINVAL;
+  if (!c->mean_acc) return pomgpu_fail(c, POMGPU_EINVAL, "write_output_mean: the time-mean output is off (pomgpu_set_mean_output)");
+  if (c->mean_count < 1) return pomgpu_fail(c, POMGPU_EINVAL, "write_output_mean: no step has been accumulated since the switch or the last mean file -- %s is not written", path);
+  (void)hipSetDevice(c->device);
+  Spec S;
+  output_spec(c, m, S);
+  return write_file(c, path, m, S, 1);
 }
 
 // A source list from before the readers moved out names this file for writer and readers alike.  Every list of the project names the

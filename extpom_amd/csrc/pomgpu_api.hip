@@ -444,6 +444,7 @@ extern "C" void pomgpu_destroy(pomgpu_ctx *c) {
   (void)hipFree(c->d_vel); (void)hipFree(c->d_err); (void)hipFree(c->d_areas); (void)hipFree(c->d_stats); (void)hipFree(c->ext_bar);
   for (int k = 0; k < 3; k++) for (int sl = 0; sl < 4; sl++) { (void)hipFree(c->frc_dev[k][sl][0]); (void)hipFree(c->frc_dev[k][sl][1]); }
   for (int sl = 0; sl < 4; sl++) (void)hipFree(c->lat_dev[sl]);
+  (void)hipFree(c->mean_acc);
   ProfState *ps = PS(c);
   if (ps) {
     for (auto &p : ps->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -2029,6 +2030,65 @@ extern "C" int pomgpu_domain_stats(pomgpu_ctx *c, double *out, int sums_only) { 
   out[0] = s[0]; out[1] = s[1]; out[2] = s[2]; out[3] = s[3]; out[4] = tavg; out[5] = savg; out[6] = eavg; out[7] = s[6];
   return POMGPU_OK;
 }
+// ---- the time-mean output (include/pomgpu.h; the kernels and the mean file: cdf_out.hip) ------------------------------------------------
+// The step's accumulation: acc = acc + x with x what pomgpu_download would show now, read from wherever it lives.  uab, vab, elb come from
+// the CURRENT generation of the external mode's arrays (KP::x2) -- no ext_canonical, whose seven copies a step that ends in the other
+// buffer set would otherwise pay every step; u v t s rho w are final in their mirrors when mode_internal returns (the depth-mean
+// correction is stored by the filter, dens has rewritten rho, w has no lazy form); wr, uf / vf and the restore fields, which the step
+// keeps lazily, are not among the nine and stay lazy.  On tiles the ghost lines of u, v (R8) and t, s, rho (Rts) are still travelling on
+// the side stream: the main stream waits for those two events here -- which the next step's first kernels would do a few launches later
+// -- and posts no round of its own.  The wide-halo mode has scattered the 2-D result back when the last substep ended (wide_flush).
+// What only a host that calls this out of the step's order can leave behind -- a held substep, the extended tile's 2-D state, rho's round
+// trip -- is completed first: correct values come first.
+static int mean_accumulate(pomgpu_ctx *c) {
+  ext_flush_deferred(c);
+  wide_flush(c);
+  side_wait(c, SIDE_RW); side_wait(c, SIDE_R8); side_wait(c, SIDE_RTS);
+  rho_materialize(c);
+  const KP &P = c->P;
+  const double *x[9] = {P.x2[X2_uab], P.x2[X2_vab], P.x2[X2_elb], D3(c, u), D3(c, v), D3(c, t), D3(c, s), D3(c, rho), D3(c, w)};
+  launch_mean_accum(c, x);
+  c->mean_count += 1;
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_mean_accumulate(pomgpu_ctx *c) {
+  NEED_RAW(c);
+  if (!c->mean_acc) return fail(c, POMGPU_EINVAL, "mean_accumulate: the time-mean output is off (pomgpu_set_mean_output)");
+  return mean_accumulate(c);
+}
+extern "C" int pomgpu_mean_count(pomgpu_ctx *c) { return c && c->mean_acc ? c->mean_count : -1; }
+extern "C" int pomgpu_set_mean_output(pomgpu_ctx *c, int on) {
+#ifdef POMGPU_STORE_F32
+  if (c) return fail(c, POMGPU_EINVAL, "set_mean_output: not in the fp32-storage variant (download and write from the host)");
+#endif
+  NEED_RAW(c);
+  if (c->flags & POMGPU_CTX_2D) return fail(c, POMGPU_EINVAL, "set_mean_output: a context with 3-D arrays");
+  const KP &P = c->P;
+  if (!on) {
+    if (c->mean_acc) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->mean_acc); }
+    c->mean_acc = NULL; c->mean_count = 0;
+    return POMGPU_OK;
+  }
+  // nine accumulators in one allocation, each n2 / n3 doubles: a 3-D one starts on a 16-byte boundary exactly where its mirror does
+  // (k_mean_accum's 16-byte form), a 2-D one where its blk2d array does
+  static const int is3d[9] = {0, 0, 0, 1, 1, 1, 1, 1, 1};
+  const double *mirror[9] = {D2(c, uab), D2(c, vab), D2(c, elb), D3(c, u), D3(c, v), D3(c, t), D3(c, s), D3(c, rho), D3(c, w)};
+  size_t off[9], cur = 0;
+  for (int q = 0; q < 9; q++) {
+    if ((cur & 1) != (((size_t)mirror[q] >> 3) & 1)) cur++;
+    off[q] = cur;
+    cur += is3d[q] ? P.n3 : P.n2;
+  }
+  if (!c->mean_acc) {
+    double *acc = NULL;
+    if (hipMalloc((void **)&acc, cur * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return fail(c, POMGPU_ENOMEM, "set_mean_output: no memory for the accumulators (%zu MB)", cur * sizeof(double) >> 20); }
+    c->mean_acc = acc;
+  }
+  for (int q = 0; q < 9; q++) c->mean_off[q] = off[q];
+  c->mean_count = 0;
+  HIPCHK(c, hipMemsetAsync(c->mean_acc, 0, cur * sizeof(double), c->stream));   // +0.0 everywhere, behind whatever still accumulates
+  return POMGPU_OK;
+}
 static int advance(pomgpu_ctx *c, int more_steps_follow);
 extern "C" int pomgpu_advance(pomgpu_ctx *c) { return advance(c, 0); }
 static int advance(pomgpu_ctx *c, int more_steps_follow) {    // advance.f:6-59
@@ -2066,6 +2126,7 @@ static int advance(pomgpu_ctx *c, int more_steps_follow) {    // advance.f:6-59
   prof_phase_close(c, ph_ext, "phase_external");
   c->con.iext = c->con.isplit + 1;
   if ((rc = mode_internal(c, more_steps_follow))) return rc;
+  if (c->mean_acc && (rc = mean_accumulate(c))) return rc;    // the time-mean output, where advance.f:38 writes
   launch_check_velocity(c);   // result stays on the device; error flag is merged at the next get_con
   prof_phase_close(c, ph_step, "phase_step");
   return POMGPU_OK;
@@ -2141,6 +2202,8 @@ extern "C" int pomgpu_tune_placement(pomgpu_ctx *c, int steps, int max_try, doub
   NEED(c);
   if (ntried) *ntried = 0;
   if (kept) *kept = 0;
+  if (c->mean_acc)                                            // the trial steps are real steps: they would be accumulated
+    return fail(c, POMGPU_EINVAL, "tune_placement: the time-mean output is on and the trial steps would count -- tune first, switch the mean on afterwards");
 #ifdef POMGPU_EMU
   (void)steps; (void)max_try; (void)ms_out; (void)front_mib_out; (void)pad_mib_out;
   return POMGPU_OK;

@@ -769,6 +769,13 @@ struct pomgpu_ctx {
   int lbry_sides;            // pomgpu_set_lateral_sides: the sides of the lbry file that are ON (POMGPU_SIDE_*; pomgpu_create: EAST|SOUTH; cdf_in.hip sets it, frc_files.hip reads it)
   void *frc_files;           // pomgpu_set_forcing_files: the open forcing files and their read buffers (frc_files.hip), NULL = none
   int launch_err;            // first hipError_t a kernel launch returned (0 = none); reported by the next sync / get_con
+  // pomgpu_set_mean_output: one fp64 accumulator per time-dependent field of the output file (MEAN_FIELDS below: uab vab elb, u v t s rho
+  // w), each laid out like its mirror, in ONE allocation; mean_off[q]: where field q's starts, in doubles -- n2 or n3 apart plus at most
+  // one double, so that an accumulator is 16-byte aligned exactly where its 3-D mirror is (k_mean_accum moves 16 bytes per lane then).
+  // mean_count: internal steps accumulated since the switch or the last mean file.  NULL = the mean is off
+  double *mean_acc;
+  size_t mean_off[9];
+  int mean_count;
   char err[512];
 };
 // The register-resident column kernels (k_vert.hip: their level loops are unrolled for a template bound, with_kbt) serve this context's
@@ -978,6 +985,8 @@ int launch_ztosig(pomgpu_ctx *c, double *t, const double *zs, int ks, const doub
 void launch_ztosig_edges(pomgpu_ctx *c, double *t);
 // one line of a lateral record (bounds_forcing.f:636-716), edge 0 east, 1 south, 2 west, 3 north: src host, ks levels of n_local + 2 values; out host, kb levels of n_local
 int launch_ztosig_line(pomgpu_ctx *c, int edge, const double *zs, int ks, const double *src, double *out);
+// cdf_out.hip: the time-mean output.  launch_mean_accum: acc = acc + x for the nine fields in one launch, x[q] where field q lives now
+void launch_mean_accum(pomgpu_ctx *c, const double *const *x);
 // k_reduce.hip
 // pomgpu_math_probe: n values per operand in device memory, one per lane (gpow15: k_adv.hip; divi, proft_rad_q: k_vert.hip)
 void launch_probe_gpow15(pomgpu_ctx *c, long n, const double *x, double *out);

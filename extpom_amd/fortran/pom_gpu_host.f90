@@ -149,6 +149,32 @@ subroutine mode_internal
   if (pomgpu_mode_internal(pom_ctx) /= 0) error_status = 1
 end subroutine
 
+! The time-mean output (no counterpart in the reference): pom_output_mean(.true.) after pomgpu_upload_state -- and after
+! pomgpu_tune_placement, which refuses while the mean is on -- makes the library accumulate uab vab elb u v t s rho w every internal step,
+! and write_output_pnetcdf (pom_gpu_io.f90) write their means since the last output file in place of the snapshot.  Calling it again
+! zeroes the sums; .false. frees them.  mean_accumulate is the step's accumulation: `advance` calls it behind mode_internal, where
+! advance.f:38 writes (nothing while the mean is off).
+subroutine pom_output_mean(on)
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  logical, intent(in) :: on
+  if (pomgpu_set_mean_output(pom_ctx, merge(1_c_int, 0_c_int, on)) /= 0) then
+    error_status = 1
+    pom_mean_on = .false.
+  else
+    pom_mean_on = on
+  end if
+end subroutine
+
+subroutine mean_accumulate
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  if (.not. pom_mean_on) return
+  if (pomgpu_mean_accumulate(pom_ctx) /= 0) error_status = 1
+end subroutine
+
 subroutine check_velocity
   use pomgpu_iface
   implicit none

@@ -1,7 +1,8 @@
 ! pom_gpu_io.f90 -- write_output_pnetcdf, write_restart_pnetcdf and read_restart_pnetcdf (reference pom/io_pnetcdf.F:57-410,
 ! :1661-2083, :2420-2768) without PnetCDF: the file names are built as the reference builds them, the files themselves (CDF-2, same
 ! dimensions / variables / attributes) are written by the library straight from the device state
-! (pomgpu_write_output / pomgpu_write_restart); every rank writes its patch, rank 0 creates the file first.
+! (pomgpu_write_output / pomgpu_write_restart); every rank writes its patch, rank 0 creates the file first.  With the time-mean output on
+! (pom_output_mean, pom_gpu_host.f90) write_output_pnetcdf writes the same file with the means of its nine time-dependent fields.
 ! read_restart_pnetcdf reads such a file (or one PnetCDF wrote) back into the device state and the COMMON blocks.
 ! cold_start_files is initialize.f:24-36 (initialize_arrays, read_grid, initial_conditions, update_initial, bottom_friction) from the
 ! reference's grid, init and clim files (pomgpu_cold_start).
@@ -56,7 +57,9 @@ subroutine pomgpu_write_file(fname, restart)
     m%create = 0
     if (pass == 1 .and. my_task == 0) m%create = 1
     if ((pass == 1) .eqv. (my_task == 0)) then
-      if (restart == 0) then
+      if (restart == 0 .and. pom_mean_on) then
+        rc = pomgpu_write_output_mean(pom_ctx, c_loc(cname), m)   ! the means since the last output file, in the snapshot's place
+      else if (restart == 0) then
         rc = pomgpu_write_output(pom_ctx, c_loc(cname), m)
       else
         rc = pomgpu_write_restart(pom_ctx, c_loc(cname), m)

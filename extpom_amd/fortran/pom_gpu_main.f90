@@ -19,6 +19,9 @@
 !        ... --cold | --cold-z <state.out> <nsteps> --lbry-z     (temp, salt of the lbry file on z levels: bounds_forcing.f:636-716)
 !        ... --cold | --cold-z <state.out> <nsteps> --lbry-sides <n>     (the sides the lbry file feeds: east 1 + south 2 + west 4 + north 8;
 !                                                                         default 3, the reference's reader; beside --lbry-z, either first)
+!        ... --cold | --cold-z <state.out> <nsteps> --mean     (the time-mean output: every iprint steps write_output_pnetcdf writes
+!                                                                <wrk_pth>out/<netcdf_file>.<nnnn>.nc with the means since the last one;
+!                                                                beside the other two, in any order)
 program pom_gpu_main
   use pomgpu_iface
   implicit none
@@ -29,7 +32,7 @@ program pom_gpu_main
   double precision :: vtot, atot, mtot, stot, tavg, savg, eavg, ekin
   double precision, allocatable, target :: tr(:,:,:,:), sr(:,:,:,:)
   character(len=256) :: fin, fout, arg3
-  logical :: cold
+  logical :: cold, mean
 
   call get_command_argument(1, fin)
   call get_command_argument(2, fout)
@@ -38,16 +41,18 @@ program pom_gpu_main
   nbd = 8*jm_local + 8*im_local + (12+12+6+6)*0   ! filled below
   nbd = 20*jm_local + 20*im_local + 18*jm_local*kb + 18*im_local*kb   ! bdry: 20 J, 20 I... see pom_layout.h
   cold = trim(fin) == '--cold' .or. trim(fin) == '--cold-z'
+  mean = .false.
   if (trim(fin) == '--cold-z') then          ! the init and the clim file are on z levels (initialize.f:410-422)
     pom_init_on_z = .true.; pom_clim_on_z = .true.
   end if
   if (cold) then                             ! one tile, the whole grid; read_input's constants (initialize.f:80-168)
     call get_command_argument(3, arg3)
     read(arg3, *) nsteps
-    n = 4                                    ! --lbry-z and --lbry-sides <n>, in either order
+    n = 4                                    ! --lbry-z, --lbry-sides <n> and --mean, in any order
     do while (n <= command_argument_count())
       call get_command_argument(n, arg3)
       if (trim(arg3) == '--lbry-z') pom_lbry_on_z = .true.
+      if (trim(arg3) == '--mean') mean = .true.
       if (trim(arg3) == '--lbry-sides') then
         n = n + 1
         call get_command_argument(n, arg3)
@@ -105,10 +110,15 @@ program pom_gpu_main
       rc = pomgpu_set_restore_record(pom_ctx, int(n, c_int), c_loc(tr(1,1,1,n)), c_loc(sr(1,1,1,n)))
     end do
   end if
+  if (mean) call pom_output_mean(.true.)
   do n = 1, nsteps                           ! pom.f:17-19
     iint = iint + 1
     call advance_hot
+    if (pom_mean_on .and. iprint > 0) then   ! advance.f:35-38: the mean file in the snapshot's place (Fortran does not short-circuit: iprint is tested first)
+      if (mod(iint, iprint) == 0) call write_output_pnetcdf
+    end if
   end do
+  if (pom_mean_on) call pom_output_mean(.false.)
   my_task = 0; master_task = 0
   call domain_stats(vtot, atot, mtot, stot, tavg, savg, eavg, ekin)   ! print_section's sums, no state download needed
   write(6,'(a,8es25.16e3)') 'domain_stats:', vtot, atot, mtot, stot, tavg, savg, eavg, ekin
@@ -147,6 +157,7 @@ subroutine advance_hot
     call mode_external
   end do
   call mode_internal
+  call mean_accumulate                       ! the time-mean output, where advance.f:38 writes (nothing while it is off)
   call check_velocity
 end subroutine
 

@@ -158,6 +158,7 @@ subroutine advance_hot(forced)
     call mode_external
   end do
   call mode_internal
+  call mean_accumulate                       ! the time-mean output (pom_output_mean), where advance.f:38 writes; nothing while it is off
   call check_velocity
 end subroutine
 

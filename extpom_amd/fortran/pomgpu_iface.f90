@@ -17,6 +17,8 @@ module pomgpu_iface
   ! the open boundaries the lbry file feeds (pomgpu_set_lateral_sides: east 1, south 2, west 4, north 8; the default is the reference's
   ! reader, io_pnetcdf.F:3393-3621): pomgpu_open_forcing_files passes it on
   integer, save :: pom_lbry_sides = 3
+  ! the time-mean output is on (pom_output_mean): `advance` accumulates behind mode_internal, write_output_pnetcdf writes the mean file
+  logical, save :: pom_mean_on = .false.
   type, bind(C) :: pomgpu_file_meta               ! include/pomgpu.h
     type(c_ptr) :: title, time_start
     integer(c_int) :: im_global, jm_global, i0, j0, create
@@ -105,6 +107,18 @@ module pomgpu_iface
     integer(c_int) function pomgpu_write_output(ctx, path, meta) bind(C, name='pomgpu_write_output')
       import; type(c_ptr), value :: ctx, path; type(pomgpu_file_meta) :: meta
     end function
+    integer(c_int) function pomgpu_write_output_mean(ctx, path, meta) bind(C, name='pomgpu_write_output_mean')
+      import; type(c_ptr), value :: ctx, path; type(pomgpu_file_meta) :: meta
+    end function
+    integer(c_int) function pomgpu_set_mean_output(ctx, on) bind(C, name='pomgpu_set_mean_output')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: on
+    end function
+    integer(c_int) function pomgpu_mean_count(ctx) bind(C, name='pomgpu_mean_count')
+      import; type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function pomgpu_mean_download(ctx, is3d, slot, host) bind(C, name='pomgpu_mean_download')
+      import; type(c_ptr), value :: ctx, host; integer(c_int), value :: is3d, slot
+    end function
     integer(c_int) function pomgpu_write_restart(ctx, path, meta) bind(C, name='pomgpu_write_restart')
       import; type(c_ptr), value :: ctx, path; type(pomgpu_file_meta) :: meta
     end function
@@ -167,6 +181,7 @@ module pomgpu_iface
   procedure(pomgpu_noarg), bind(C, name='pomgpu_mode_interaction') :: pomgpu_mode_interaction
   procedure(pomgpu_noarg), bind(C, name='pomgpu_mode_external') :: pomgpu_mode_external
   procedure(pomgpu_noarg), bind(C, name='pomgpu_mode_internal') :: pomgpu_mode_internal
+  procedure(pomgpu_noarg), bind(C, name='pomgpu_mean_accumulate') :: pomgpu_mean_accumulate
   procedure(pomgpu_noarg), bind(C, name='pomgpu_advave') :: pomgpu_advave
   procedure(pomgpu_noarg), bind(C, name='pomgpu_advct') :: pomgpu_advct
   procedure(pomgpu_noarg), bind(C, name='pomgpu_advu') :: pomgpu_advu

@@ -99,6 +99,11 @@ _SIGS = {
     "pomgpu_run": (_I, [_P, _I]),
     "pomgpu_io_wait": (_I, [_P]),
     "pomgpu_write_output": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
+    "pomgpu_write_output_mean": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
+    "pomgpu_set_mean_output": (_I, [_P, _I]),
+    "pomgpu_mean_accumulate": (_I, [_P]),
+    "pomgpu_mean_count": (_I, [_P]),
+    "pomgpu_mean_download": (_I, [_P, _I, _I, _P]),
     "pomgpu_write_restart": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
     "pomgpu_read_restart": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "pomgpu_set_forcing_files": (_I, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),

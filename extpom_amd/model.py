@@ -235,12 +235,37 @@ class PomGpu:
 
     def write_file(self, kind, path, title="", time_start="", im_global=None, jm_global=None, create=True, stats=None):
         """kind = "output" | "restart": the reference's NetCDF (CDF-2) files without PnetCDF (io_pnetcdf.F:57-410,
-        :1661-2083); this tile's patch at (i_off+1, j_off+1) of the global grid"""
+        :1661-2083); this tile's patch at (i_off+1, j_off+1) of the global grid.  kind = "output_mean": the output file with the
+        time means of uab vab elb u v t s rho w since set_mean_output or the last such file in place of their values now"""
         st = self.st
         m = _lib.FileMeta(title.encode(), time_start.encode(), im_global or st.im, jm_global or st.jm, st.i_off + 1, st.j_off + 1,
                           1 if create else 0, (ctypes.c_double * 8)(*stats) if stats is not None else None)
-        fn = self.L.pomgpu_write_output if kind == "output" else self.L.pomgpu_write_restart
+        fn = {"output": self.L.pomgpu_write_output, "output_mean": self.L.pomgpu_write_output_mean, "restart": self.L.pomgpu_write_restart}[kind]
         self._chk(fn(self.h, str(path).encode(), ctypes.byref(m)), "write_" + kind)
+
+    MEAN_FIELDS = ("uab", "vab", "elb", "u", "v", "t", "s", "rho", "w")
+
+    def set_mean_output(self, on: bool = True):
+        """pomgpu_set_mean_output: from now on every internal step adds uab vab elb u v t s rho w, as they stand after mode_internal,
+        to fp64 accumulators on the device; calling it again zeroes them, on=False frees them.  Tune the placement first."""
+        self._chk(self.L.pomgpu_set_mean_output(self.h, 1 if on else 0), "set_mean_output")
+
+    def mean_count(self) -> int:
+        """internal steps accumulated since set_mean_output or the last mean file; -1 while the mean is off"""
+        return int(self.L.pomgpu_mean_count(self.h))
+
+    def mean_accumulate(self):
+        """pomgpu_mean_accumulate, for a host that strings the routines together: after mode_internal (advance and run do it themselves)"""
+        self._chk(self.L.pomgpu_mean_accumulate(self.h), "mean_accumulate")
+
+    def mean(self, name: str):
+        """pomgpu_mean_download: accumulator / count of one of MEAN_FIELDS, shaped like self.st.field(name); resets nothing"""
+        if name not in self.MEAN_FIELDS:
+            raise PomGpuError(f"mean: {name!r} is not accumulated (one of {' '.join(self.MEAN_FIELDS)})")
+        out = np.empty_like(self.st.field(name))
+        is3d = name in P3
+        self._chk(self.L.pomgpu_mean_download(self.h, 1 if is3d else 0, P3[name] if is3d else P2[name], self._p(out)), "mean_download")
+        return out
 
     def read_restart(self, path, im_global=None, jm_global=None):
         """read_restart_pnetcdf (io_pnetcdf.F:2420-2768) without PnetCDF: this tile's patch of the 37 restart fields from a classic

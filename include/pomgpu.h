@@ -467,9 +467,41 @@ int pomgpu_run(pomgpu_ctx *ctx, int nsteps);
  * and uploads it again (state and blkcon) before its first step.
  * The call MOVES the 3-D arrays (and frees the allocations they lived in): every address obtained from pomgpu_device_3d before it
  * would dangle, so the call refuses (POMGPU_EINVAL) once pomgpu_device_3d has been used on the context -- tune first, take addresses
- * afterwards.  If a move fails half way (a HIP error inside it) the mirrors no longer hold the state: error_status = 1 and every later
+ * afterwards.  It also refuses while the time-mean output is on (pomgpu_set_mean_output: the trial steps would be accumulated) -- tune
+ * first, switch the mean on afterwards; that is checked before "nothing tried".  If a move fails half way (a HIP error inside it) the mirrors no longer hold the state: error_status = 1 and every later
  * hot-path call on this context returns POMGPU_EHIP; destroy it and upload the state into a new one. */
 int pomgpu_tune_placement(pomgpu_ctx *ctx, int steps, int max_try, double *ms_out, long *front_mib_out, long *pad_mib_out, int *ntried, int *kept);
+
+/* ---- time-mean output (no counterpart in the reference; optional, off by default: with it off every byte is as without it) --------------
+ * pomgpu_write_output copies uab vab elb u v t s rho w as they stand at the step of the call; a snapshot every iprint steps aliases whatever
+ * is faster than iprint * dti.  With the mean on, the library keeps one fp64 accumulator per field -- the nine above, which are the variables
+ * of the output file that depend on time -- laid out like the field's mirror, and one integer count.
+ * pomgpu_set_mean_output: on != 0 allocates the accumulators (3 x n2 + 6 x n3 doubles) and sets every one of them to +0.0 and the count to 0;
+ * if they exist already it zeroes them and the count.  on == 0 frees them.  Nothing else but pomgpu_write_output_mean resets them: not an
+ * upload, not pomgpu_read_restart, not pomgpu_cold_start -- a host that replaces the state inside an interval switches the mean on again.
+ * The accumulators are not in the restart file, whose schema is the reference's: a job that restarts inside an output interval loses that
+ * interval's partial sums.  Refused with POMGPU_EINVAL: the fp32-storage variants (which refuse pomgpu_write_output too), a 2-D-only context.
+ * pomgpu_tune_placement refuses while the mean is on -- its trial steps are real steps and would count: tune first, switch the mean on afterwards.
+ * pomgpu_mean_accumulate: the step's accumulation -- every accumulator becomes acc + x, ONE fp64 add per cell, in step order, x being what
+ * pomgpu_download would show at that moment (read from wherever it lives: no lazily kept array is formed for it, no message round is posted;
+ * one kernel launch for the nine fields).  pomgpu_advance and pomgpu_run make the call themselves behind mode_internal, where advance.f:38
+ * writes, while the mean is on; the entry point is for hosts that string the routines together (the Fortran `advance`): call it after
+ * pomgpu_mode_internal.  POMGPU_EINVAL while the mean is off.
+ * pomgpu_mean_count: the steps accumulated since the switch or the last mean file; -1 while the mean is off.
+ * pomgpu_mean_download: acc / (double)count -- one IEEE division per cell, not a multiplication by a reciprocal -- of one accumulated array
+ * (is3d, slot: enum pom_slot2d / pom_slot3d) into `host`, n2 or n3 doubles in the mirror's shape.  Padding cells, and cells beyond (im, jm) of
+ * a trimmed tile, may hold anything.  Resets nothing.  POMGPU_EINVAL: a slot that is not accumulated, count 0, the mean off.
+ * pomgpu_write_output_mean: pomgpu_write_output's file, byte for byte in the header -- dimensions, variables, attributes, offsets, `time` and
+ * the statistics as of the call; every reader of an output file reads it -- with the MEANS as the values of the nine fields.  Same asynchronous
+ * writer; the snapshot of the nine is taken by a kernel that stores acc / count into it and +0.0 into the accumulator in the same pass, on
+ * the kernels' stream: steps enqueued right after the call accumulate into clean sums while the file is still being written.  The count
+ * returns to 0.  On tiles every rank writes its patch, as pomgpu_write_output does.  Count 0 at the call: POMGPU_EINVAL, error_status = 1, the
+ * cause in pomgpu_last_error; no file is touched, nothing changes. */
+int pomgpu_set_mean_output(pomgpu_ctx *ctx, int on);
+int pomgpu_mean_accumulate(pomgpu_ctx *ctx);
+int pomgpu_mean_count(pomgpu_ctx *ctx);
+int pomgpu_mean_download(pomgpu_ctx *ctx, int is3d, int slot, double *host);
+int pomgpu_write_output_mean(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta);
 
 /* ---- the hot path: kernels (solver.f, bounds_forcing.f), device-resident ---------------- */
 int pomgpu_advave(pomgpu_ctx *ctx);              /* solver.f:6-198   */

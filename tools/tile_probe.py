@@ -26,7 +26,8 @@ def main():
     ap.add_argument("--no-wide", action="store_true")
     ap.add_argument("--tune", action="store_true", help="pomgpu_tune_placement before the measurement")
     ap.add_argument("--ab", default="", help="NAME=V[,NAME=V...]: developer switches set on the LIVE context for every other block of steps -- "
-                                             "the step with and without them, interleaved in one context (placement moves a kernel more than most changes do)")
+                                             "the step with and without them, interleaved in one context (placement moves a kernel more than most changes do); "
+                                             "MEAN=1 is no developer switch but the time-mean output (pomgpu_set_mean_output), on for every other block")
     ap.add_argument("--ab-rounds", type=int, default=6)
     ap.add_argument("--rccl-self", action="store_true", help="the REAL transport instead of the stand-in mover: an RCCL communicator of one rank whose tile is its own "
                                                              "neighbour (periodic), so every round is a grouped ncclSend / ncclRecv on the kernels' or the second stream "
@@ -109,14 +110,20 @@ def main():
         for _ in range(a.ab_rounds):
             for tag in acc:
                 for k, v in sw.items():
-                    g.switch(k, v if tag != "default" else None)
+                    if k == "MEAN":
+                        g.set_mean_output(tag != "default")
+                    else:
+                        g.switch(k, v if tag != "default" else None)
                 g.run(1); g.sync()
                 t1 = time.perf_counter()
                 g.run(a.steps)
                 g.sync()
                 acc[tag].append((time.perf_counter() - t1) / a.steps * 1e3)
         for k in sw:
-            g.switch(k, None)
+            if k == "MEAN":
+                g.set_mean_output(False)
+            else:
+                g.switch(k, None)
         ab = {tag: {"min": round(min(v), 3), "median": round(sorted(v)[len(v) // 2], 3)} for tag, v in acc.items()}
     prof.pop("phase_step", None); prof.pop("phase_external", None)     # brackets around other brackets (pomgpu.h): not kernels
     msg = prof.pop("msg_round", (0, 0.0))
