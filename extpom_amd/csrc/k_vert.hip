@@ -540,7 +540,12 @@ struct LevB { double e1, g1, e2, g2, qb, qlb, q, ql; };
 #ifndef PROFQ_BIG
 #define PROFQ_BIG 8                                         /* rows per workgroup on large grids */
 #endif
-template <int FP, int FF, int ROWS>
+// LD: 1 = the walk down stores l and dtef (every level, every column), 0 = it forms them for the eliminations and stores neither.
+// Nothing on the device reads the two arrays back (the walk up does not, no other kernel of the step does; profq rewrites both
+// whole in every call), so they need to be in memory only when somebody can look: pomgpu_api.hip decides (ld_on_demand), two
+// of the kernel's 23 array passes less in a step nobody observes.  A compile-time flag, not one more per-lane offset aimed at
+// BOFF_NONE: <1, 1, 8> holds 256 of 256 VGPRs.  Instantiated for <1, 1, *> alone (launch_profq)
+template <int FP, int FF, int ROWS, int LD = 1>
 // jfirst, jlast: the rows this launch covers (1..jm: everything).  On tiles whose ghost lines are filled by a message round behind this
 // kernel (pomgpu_api.hip, rim round Rq) the ghost rows are left out: a 2048x194 tile is 25 row blocks x 32 = 800 workgroups for the 768 that
 // are resident at once -- a fourth, nearly empty round -- and 24 x 32 = 768 without its two ghost rows
@@ -678,11 +683,11 @@ __global__ void __launch_bounds__(64 * ROWS) k_profq(KP P, int rho_rt_pace, int 
     }
     bst(bq2b, mid ? o_abs : BOFF_NONE, lv, q2b);
     bst(bq2lb, mid ? o_abs : BOFF_NONE, lv, q2lb);
-    bst(bl, oc, lv, l);
+    if (LD) bst(bl, oc, lv, l);
     const double dtef1 = sqrt(fabs(q2b)) * 1. / (b1 * l + P.small_);                        // :1388-1389
     double dtef2 = dtef1;
     if (mid) dtef2 = dtef1 * (1. + e2 * sq(divi((1. / fabs(F1(z, k) - z1) + 1. / fabs(F1(z, k) - zkb)) * l, dhk)));   // :1429-1432
-    bst(bdt, oc, lv, dtef2);
+    if (LD) bst(bdt, oc, lv, dtef2);
     // ---- both forward eliminations -- :1394-1404, :1436-1446
     if (mid) {
       const double a = -P.dti2 * (kqp + kqc + umol2) * .5 / (F1(dzz, k - 1) * F1(dz, k) * dh * dh);      // :1261-1264
@@ -817,11 +822,11 @@ __global__ void __launch_bounds__(64 * ROWS) k_profq(KP P, int rho_rt_pace, int 
     } else {
       l = (PH == PH_1) ? P.kappa * l0 : 0.;                                                 // :1351-1354
     }
-    bst(bl, oc, lv, l);
+    if (LD) bst(bl, oc, lv, l);
     const double dtef1 = sqrt(fabs(q2b)) * 1. / (b1 * l + P.small_);                        // :1388-1389
     double dtef2 = dtef1;
     if (mid) dtef2 = dtef1 * (1. + e2 * sq(divi((1. / fabs(F1(z, k) - z1) + 1. / fabs(F1(z, k) - zkb)) * l, dhk)));   // :1429-1432
-    bst(bdt, oc, lv, dtef2);
+    if (LD) bst(bdt, oc, lv, dtef2);
     // ---- both forward eliminations -- :1394-1404, :1436-1446
     if (mid) {
       const double a = -P.dti2 * (kqp + kqc + umol2) * .5 / (F1(dzz, k - 1) * F1(dz, k) * dh * dh);      // :1261-1264
@@ -1920,21 +1925,29 @@ void launch_profq_prod(pomgpu_ctx *c, int lines_only, int rho_rt) {
   const int len = P.im > P.jm ? P.im : P.jm;
   LAUNCH(c, k_profq_prod_lines, dim3((len + 63) / 64, 8, P.kb), dim3(64, 1, 1), c->P, rho_rt);
 }
-void launch_profq(pomgpu_ctx *c, int fuse_prod, int fuse_filter, int rho_rt, int jfirst, int jlast) {
+// store_ld = 0: l and dtef stay out of memory in this launch (k_profq's LD; the caller has made sure nobody can look before the next
+// launch rewrites them).  Honoured on the one-tile path with both fusions, <1, 1, *>, alone -- every other path stores.
+// profq_ld_store of the event profile counts the launches that store: a count without events, as proft_ts_lane
+void launch_profq(pomgpu_ctx *c, int fuse_prod, int fuse_filter, int rho_rt, int jfirst, int jlast, int store_ld) {
   if (jlast < jfirst) { jfirst = 1; jlast = c->P.jml; }      // (default arguments 0, -1: every row)
+  const int ld = store_ld || fuse_prod != 1 || !fuse_filter;
+  if (ld && c->prof_on) {
+    const int s = pomgpu_prof_slot(c, "profq_ld_store");
+    if (s >= 0) (c->parent ? c->parent : c)->prof[s].launches++;
+  }
   const int nrows = jlast - jfirst + 1;
   // 8 paced rows per workgroup (one workgroup per CU at 2 waves per SIMD) where that still leaves every CU three workgroups
   // (a 514x769 tile of an 8-tile split: 3.4 per CU, k_profq 1.27 -> 1.22 ms, the tile's step 7.15 -> 6.9)
   // (developer switches: POMGPU_PROFQ_ROWS8 / _ROWS2 force a shape, POMGPU_PROFQ_NOPACE drops the barrier)
   const int rows8 = !SW(c, PROFQ_ROWS2) && (SW(c, PROFQ_ROWS8) || (long)((c->P.iml + 63) / 64) * ((c->P.jml + 7) / 8) >= 3 * 256);
   rho_rt = (rho_rt ? 1 : 0) | (SW(c, PROFQ_NOPACE) ? 0 : 2);
-#define PQ(FP, FF)                                                                                                                       \
+#define PQ(FP, FF, LD)                                                                                                                   \
   do {                                                                                                                                   \
-    if (rows8) LAUNCHN(c, "k_profq", (k_profq<FP, FF, PROFQ_BIG>), dim3((c->P.iml + 63) / 64, (nrows + PROFQ_BIG - 1) / PROFQ_BIG, 1), dim3(64, PROFQ_BIG, 1), c->P, rho_rt, jfirst, jlast); \
-    else LAUNCHN(c, "k_profq", (k_profq<FP, FF, 2>), dim3((c->P.iml + 63) / 64, (nrows + 1) / 2, 1), dim3(64, 2, 1), c->P, rho_rt, jfirst, jlast);       \
+    if (rows8) LAUNCHN(c, "k_profq", (k_profq<FP, FF, PROFQ_BIG, LD>), dim3((c->P.iml + 63) / 64, (nrows + PROFQ_BIG - 1) / PROFQ_BIG, 1), dim3(64, PROFQ_BIG, 1), c->P, rho_rt, jfirst, jlast); \
+    else LAUNCHN(c, "k_profq", (k_profq<FP, FF, 2, LD>), dim3((c->P.iml + 63) / 64, (nrows + 1) / 2, 1), dim3(64, 2, 1), c->P, rho_rt, jfirst, jlast);       \
   } while (0)
-  if (fuse_filter) { if (fuse_prod == 0) PQ(0, 1); else if (fuse_prod == 1) PQ(1, 1); else PQ(2, 1); }
-  else { if (fuse_prod == 0) PQ(0, 0); else if (fuse_prod == 1) PQ(1, 0); else PQ(2, 0); }
+  if (fuse_filter) { if (fuse_prod == 0) PQ(0, 1, 1); else if (fuse_prod == 1) { if (ld) PQ(1, 1, 1); else PQ(1, 1, 0); } else PQ(2, 1, 1); }
+  else { if (fuse_prod == 0) PQ(0, 0, 1); else if (fuse_prod == 1) PQ(1, 0, 1); else PQ(2, 0, 1); }
 #undef PQ
   const KP &P = c->P;
   if (P.W || P.E || P.S || P.N) {

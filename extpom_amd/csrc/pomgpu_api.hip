@@ -280,6 +280,26 @@ static bool uvm_onload(const pomgpu_ctx *c) {
   return POMGPU_UVM_ONLOAD && w_fused(c) && uv_fused(c) && c->uvm_valid && !SW(c, UVMEAN_PASS) &&
          (k.mode == 4 || (k.nadv == 2 && c->P.nitera == 1 && !SW(c, ADVT2_SINGLE)));
 }
+// may k_profq of a step that another step of the same pomgpu_run follows keep l and dtef out of memory (launch_profq, store_ld = 0)?
+// Nothing on the device reads them back and the next step's profq rewrites both whole, so the question is only who can look between
+// the two: nobody on one tile whose mirrors only the library reads (as for wr).  No lazy state comes with it -- they cannot be formed
+// afterwards, l = |q2lb / q2b| takes the OLD q2b, q2lb, which the fused filter overwrites on the way up -- the last step of every
+// call stores them, and after every call that returns the arrays are those of the last completed step.  POMGPU_LD_EAGER (read here,
+// at launch time) stores in every step
+static bool ld_on_demand(const pomgpu_ctx *c) {
+  return !c->exch && !c->tp.on && !c->wide.on && !c->parent && !(c->flags & POMGPU_CTX_2D) && !c->wr_eager && !SW(c, LD_EAGER);
+}
+// will the step after this one ask for a forcing or lateral record (pomgpu_wind / _heat / _surface / _lateral_bc: steps whose iint +
+// cont_bry is a multiple of the record interval)?  That is where a pomgpu_run ends early for a reason outside the device -- a record the
+// file or the host does not have -- and surface_forcing / lateral_bc come first in a step: the step in front of it stores l, dtef, so
+// that such a run leaves the whole state of its last completed step.  (One step per record interval, 1/24 day: every 20th at dti = 180 s.)
+static bool next_step_fetches_record(const pomgpu_ctx *c) {
+  if (!c->frc_on && !c->lat_on) return false;
+  const pom_blkcon &k = c->con;
+  const int isrf = (int)(.125 * 86400. / k.dti), ibc = (int)((double)(1.f / 24.f) * 86400. / k.dti);
+  const int next = k.iint + 1 + k.cont_bry;
+  return (c->frc_on && (isrf < 1 || next % isrf == 0)) || (c->lat_on && (ibc < 1 || next % ibc == 0));
+}
 static void uvf_materialize(pomgpu_ctx *c) {
   if (!c->uvf_pending) return;
   c->uvf_pending = 0;
@@ -832,7 +852,7 @@ static void seq_advq(pomgpu_ctx *c, double *qb, double *q, double *qf, int pair,
   xch(c, 2, xf, P.kbm1, yf, P.kbm1);                          // :458-459
   launch_advq_step(c, q, qb, qf, xf, yf, zero_else);
 }
-static void seq_profq(pomgpu_ctx *c, int fuse_filter = 0, int with_w = 0) {   // solver.f:1212-1538
+static void seq_profq(pomgpu_ctx *c, int fuse_filter = 0, int with_w = 0, int store_ld = 1) {   // solver.f:1212-1538
   KP &P = c->P;
   launch_profq_bc(c);
   double *ufkb = LEV3(c, D3(c, uf), P.kb - 1);
@@ -848,7 +868,7 @@ static void seq_profq(pomgpu_ctx *c, int fuse_filter = 0, int with_w = 0) {   //
   }
   if (with_w) xch(c, 3, P.s2[4], 1, ufkb, 1, D3(c, w), P.kb);   // :1289-1290 + advance.f:400
   else xch(c, 2, P.s2[4], 1, ufkb, 1);                        // :1289-1290
-  if (!c->exch) { launch_profq(c, 1, fuse_filter, c->rho_rt_pending); return; }  // one tile: prod is formed inside the solve kernel
+  if (!c->exch) { launch_profq(c, 1, fuse_filter, c->rho_rt_pending, 0, -1, store_ld); return; }  // one tile: prod is formed inside the solve kernel
   launch_profq_prod(c, 0, c->rho_rt_pending);
   xch(c, 1, LEV3(c, P.s3[0], 1), P.kbm2);                          // :1374
   launch_profq(c, 0, fuse_filter, c->rho_rt_pending);
@@ -1762,7 +1782,8 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
       // full rounds of workgroups instead of three and a nearly empty fourth); ghost COLUMNS are computed from stale operands and overwritten.
       launch_profq(c, 1, qfuse, c->rho_rt_pending, P.S ? 1 : 2, P.N ? P.jm : P.jmm1);
     } else {
-      seq_profq(c, qfuse, lib_x);                             // with the interior's Asselin filter (:416-421) on its way up
+      // with the interior's Asselin filter (:416-421) on its way up; l, dtef reach memory in a step somebody can look after (ld_on_demand)
+      seq_profq(c, qfuse, lib_x, !(defer_wr && ld_on_demand(c) && !next_step_fetches_record(c)));
       xch(c, 2, LEV3(c, D3(c, uf), 1), P.kbm2, LEV3(c, D3(c, vf), 1), P.kbm2);   // :411-412
     }
     launch_bcond6_edges(c);                                   // :414

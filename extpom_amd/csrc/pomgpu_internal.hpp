@@ -580,7 +580,7 @@ static inline dim3 grid2_halo(const KP &P) { return dim3((P.iml + 61) / 62, (P.j
   X(PROFQ_NOPACE) X(COL_STRIP) X(BAND_BYTES) X(PAD3) X(IO_SYNC) X(ADVCT_SPLIT) X(ADVQ_EXCHANGE) X(PROD_FULL) X(QFILTER_SPLIT) \
   X(NO_OVERLAP) X(NO_SIDE_COMM) X(WR_MAIN) X(WIDE_W) X(WIDE_FULL) X(DEBUG_ALLOC) X(TEST_SPLIT_FAIL_RANK)  \
   X(WR_NODEFER) X(EXT_RING_FIRST) X(TUNE_FORCE) X(RIM_MAIN) X(RIM_RESULTS_MAIN) X(SUM2D_OFF) X(ADVCT_ROWS4) X(ADVCT_ROWS8) \
-  X(IO_CHUNK_KB) X(UV_NOFUSE) X(W_NOFUSE) X(UVMEAN_PASS) X(PROFT_TWIN)
+  X(IO_CHUNK_KB) X(UV_NOFUSE) X(W_NOFUSE) X(UVMEAN_PASS) X(PROFT_TWIN) X(LD_EAGER)
 enum pomgpu_sw {
 #define POMGPU_SW_(name) SW_##name,
   POMGPU_SWITCHES(POMGPU_SW_)
@@ -927,7 +927,7 @@ void launch_int_uvmean(pomgpu_ctx *c);
 void launch_vertvl(pomgpu_ctx *c, int mask);
 void launch_profq_bc(pomgpu_ctx *c);
 void launch_profq_prod(pomgpu_ctx *c, int lines_only, int rho_rt = 0);
-void launch_profq(pomgpu_ctx *c, int fuse_prod, int fuse_filter, int rho_rt = 0, int jfirst = 0, int jlast = -1);   // rows jfirst..jlast (default: all)
+void launch_profq(pomgpu_ctx *c, int fuse_prod, int fuse_filter, int rho_rt = 0, int jfirst = 0, int jlast = -1, int store_ld = 1);   // rows jfirst..jlast (default: all); store_ld = 0: l, dtef stay out of memory (<1, 1, *> only)
 void launch_proft(pomgpu_ctx *c, double *f, const double *wfsurf, const double *fsurf, int nbc);
 int launch_proft2(pomgpu_ctx *c, double *f0, const double *wfsurf0, const double *fsurf0, int nbc0, double *f1, const double *wfsurf1, const double *fsurf1, int nbc1);
 void launch_advu_profu(pomgpu_ctx *c, int do_adv, int do_prof);

@@ -451,7 +451,17 @@ int pomgpu_advance(pomgpu_ctx *ctx);
  * profv and the filter of advance.f:469-514 are one kernel on the interior (5 <= i <= im-3, 5 <= j <= jm-3), which leaves the step with
  * u = uf, v = vf there without storing uf, vf (levels 1..kbm1).  Nothing in the step reads them before the next advq rewrites both
  * arrays whole, so the copy u -> uf, v -> vf is kept lazily like wr: the same callers as above (all but pomgpu_set_con) make it first,
- * and the next pomgpu_mode_internal that runs its 3-D part drops it.  POMGPU_UV_NOFUSE keeps the two kernels apart. */
+ * and the next pomgpu_mode_internal that runs its 3-D part drops it.  POMGPU_UV_NOFUSE keeps the two kernels apart.
+ * l, dtef ON ONE TILE (the same kind of context, no address handed out by pomgpu_device_2d / _3d): profq forms both for its two solves
+ * and nothing else in the step reads them; the next profq rewrites both whole (solver.f:1338-1352, :1388).  They cannot be formed
+ * afterwards (l = |q2lb / q2b| takes the old q2b, q2lb, which the filter overwrites), so there is nothing lazy about them: a step of
+ * pomgpu_run that another step of the SAME call follows does not store them, the last step of every call does, and so do
+ * pomgpu_advance, pomgpu_mode_internal, pomgpu_profq and every context on tiles, always.  After every call that returns POMGPU_OK
+ * the two arrays are those of the last completed step, with nothing for an observer to wait for.  A step in front of one that asks
+ * for a forcing or lateral record stores them as well (one step per record interval): a pomgpu_run that ends at a record the file or
+ * the host does not have leaves the whole state of its last completed step.  A pomgpu_run that FAILS in step k < nsteps for another
+ * reason (a refused launch, a failed copy) leaves l, dtef of an earlier step (the last one that stored) beside the other arrays;
+ * blkcon.error_status is set in that case anyway.  POMGPU_LD_EAGER stores them in every step. */
 int pomgpu_run(pomgpu_ctx *ctx, int nsteps);
 
 /* Where the 3-D arrays live (no counterpart in the reference; optional).  The same kernels on the same bytes run up to 6 %
