@@ -1,4 +1,4 @@
-// frc_files.hip -- forcing records from the files (pomgpu_set_forcing_files, pomgpu_set_restore_rate_file).
+// frc_files.hip -- forcing records from the files (pomgpu_set_forcing_files, pomgpu_set_restore_rate_file, pomgpu_set_water_files).
 // read_wind_pnetcdf, read_heat_pnetcdf, read_surface_pnetcdf (io_pnetcdf.F:2912-2998, :3110-3224), read_boundary_conditions_pnetcdf
 // (:3393-3621) and read_restore_ts_interior_pnetcdf (:3275-3333) without PnetCDF.  The host names the files once; the schedule code of
 // pomgpu_api.hip (frc_read, lat_read, restore_prepare) asks for record n when the step needs it, and the fetch below puts it where
@@ -27,6 +27,9 @@ struct FFiles {
   // serves every record number
   ZWindow r;
   int rsteady = 0;
+  // the water files (pomgpu_set_water_files): record n is the ONE record of <wprefix>.water.NNNN.nc, opened when the schedule asks for it
+  std::string wprefix;
+  int won = 0;
 };
 static const char *const FF_WHAT[3] = {"sfrc", "lbry", "clim"};
 static const char *const FF_SFRC[6] = {"sustr", "svstr", "shflux", "swrad", "SST", "SSS"};
@@ -63,7 +66,8 @@ __device__ __forceinline__ double frc_taper(const KP &P, const double *m, int i,
 }
 // One record of wind (kind 0), heat (1) or surface (2): the tile's band of rows of one or two variables (raw bytes at sa, sb -- sb NULL:
 // the second field is not wanted -- `pitch` values per row, the tile's first column at i0) into the (im,jm) records da, db that
-// pomgpu_set_forcing_record fills.  Thread mapping of k_cdf_unpack: threadIdx.x runs along i.
+// pomgpu_set_forcing_record fills.  Kind 3 is water (read_water_pnetcdf, :3227-3272): one source, neither converted nor tapered, into the
+// record pomgpu_set_water_record fills.  Thread mapping of k_cdf_unpack: threadIdx.x runs along i.
 template <class TA, class TB>
 __global__ void k_frc_unpack(KP P, int kind, double *da, double *db, const void *sa, const void *sb, int pitch, int i0) {
   const int i = TID_I, j = TID_J;
@@ -398,8 +402,9 @@ int pomgpu_ff_fetch_surface(pomgpu_ctx *c, int kind, int n) {
   FSource &S = F->s[0];
   const KP &P = c->P;
   static const char *const who[3] = {"wind", "heat", "surface"};
-  const int va = 2 * kind, vb = 2 * kind + 1, nvar = kind == 2 ? 1 : 2;   // SSS is read by the reference and dropped (bounds_forcing.f:978-979): not read here
-  int rc = kind == 2 ? ff_have(c, S, who[kind], n, {va}) : ff_have(c, S, who[kind], n, {va, vb});
+  // SSS is read by the reference and dropped (bounds_forcing.f:978-979): read here only where pomgpu_set_surface_sss wants it
+  const int va = 2 * kind, vb = 2 * kind + 1, nvar = kind == 2 && !c->sss_on ? 1 : 2;
+  int rc = nvar == 1 ? ff_have(c, S, who[kind], n, {va}) : ff_have(c, S, who[kind], n, {va, vb});
   if (rc) return rc;
   const int sl = n % 4;
   unsigned char *pin = F->rd.acquire();
@@ -420,6 +425,74 @@ int pomgpu_ff_fetch_surface(pomgpu_ctx *c, int kind, int n) {
   else if (fb) LAUNCHN(c, "k_frc_unpack", (k_frc_unpack<double, float>), grid2(P), blk2(), P, kind, da, db, sa, sb, pitch, i0);
   else LAUNCHN(c, "k_frc_unpack", (k_frc_unpack<double, double>), grid2(P), blk2(), P, kind, da, db, sa, sb, pitch, i0);
   c->frc_n[kind][sl] = n;
+  return POMGPU_OK;
+}
+// ---- water (read_water_pnetcdf, io_pnetcdf.F:3227-3272): '(a,''in/'',a,''.water.'',i4.4,''.nc'')', one file per record and in it `w` as
+// (jm_global, im_global), found by name.  Nothing is opened at registration: the schedule (pomgpu_water) names the record, the file is opened,
+// checked by the shared header parser and check_var, its band read and unpacked into the slot pomgpu_set_water_record(n, ...) fills, and closed.
+extern "C" int pomgpu_set_water_files(pomgpu_ctx *c, const char *prefix, const pomgpu_file_meta *m) {
+  if (!c) return POMGPU_EINVAL;
+  if (!prefix || !m) return fail(c, POMGPU_EINVAL, "set_water_files: %s", prefix ? "no file meta was given" : "no prefix was given (NULL)");
+  (void)hipSetDevice(c->device);
+  const KP &P = c->P;
+  if (!tile_fits(m, P, 0, 0, 0, 0))
+    return fail(c, POMGPU_EINVAL, "set_water_files: the tile (%d..%d, %d..%d) does not fit the global grid %d x %d", m->i0, m->i0 + P.im - 1, m->j0,
+                m->j0 + P.jm - 1, m->im_global, m->jm_global);
+  FFiles *old = FF(c);
+  if (old && (old->im_global != m->im_global || old->jm_global != m->jm_global || old->i0 != m->i0 || old->j0 != m->j0))
+    return fail(c, POMGPU_EINVAL, "set_water_files: %s: files are registered under another global grid or tile origin", prefix);
+  FFiles *F = old ? old : new FFiles();
+  const size_t need = (size_t)P.jm * (size_t)m->im_global * 8;    // the tile's band of rows at the file's full width, doubles
+  int bad = ff_reserve(c, F, need);
+  for (int sl = 0; sl < 4 && !bad; sl++)                          // the slots the setter would have allocated: a step allocates nothing
+    if (!c->wat_dev[sl] && hipMalloc((void **)&c->wat_dev[sl], sizeof(double) * (size_t)P.im * P.jm) != hipSuccess) bad = 1;
+  c->frc_files = F;
+  if (bad) {
+    (void)hipGetLastError();
+    if (!old) pomgpu_ff_free(c);
+    return fail(c, POMGPU_ENOMEM, "set_water_files: %s: no memory for the read buffers (%zu bytes, twice pinned)", prefix, need);
+  }
+  F->im_global = m->im_global; F->jm_global = m->jm_global; F->i0 = m->i0; F->j0 = m->j0;
+  F->wprefix = prefix;
+  F->won = 1;
+  for (int sl = 0; sl < 4; sl++) c->wat_n[sl] = 0;                // records the setter left are not the files'
+  c->wat_on = 1;
+  return POMGPU_OK;
+}
+int pomgpu_ff_has_water(pomgpu_ctx *c) { return c->frc_files && FF(c)->won; }
+int pomgpu_ff_fetch_water(pomgpu_ctx *c, int n) {
+  FFiles *F = FF(c);
+  const KP &P = c->P;
+  if (n < 0 || n > 9999) return fail(c, POMGPU_EINVAL, "water: record %d has no file name (%s.water.NNNN.nc: 0..9999)", n, F->wprefix.c_str());
+  char num[16];
+  snprintf(num, sizeof num, "%04d", n);
+  FSource S;
+  S.path = F->wprefix + ".water." + num + ".nc";
+  S.fd = open(S.path.c_str(), O_RDONLY);
+  if (S.fd < 0) return fail(c, POMGPU_EINVAL, "water: cannot open %s", S.path.c_str());
+  struct Closer { int fd; ~Closer() { (void)close(fd); } } closer{S.fd};
+  struct stat sb;
+  if (fstat(S.fd, &sb)) return fail(c, POMGPU_EINVAL, "water: cannot stat %s", S.path.c_str());
+  S.fsize = (uint64_t)sb.st_size;
+  RHeader H;
+  std::string what;
+  if (read_header(S.fd, S.fsize, H, what) < 0) return fail(c, POMGPU_EINVAL, "water: %s is not a water file this library reads: %s", S.path.c_str(), what.c_str());
+  const RVar *v = NULL;
+  const std::string why = check_var(H, S.fsize, "w", VarWant::fixed(NC_REAL, {(uint64_t)F->jm_global, (uint64_t)F->im_global}), &v);
+  if (!why.empty()) return fail(c, POMGPU_EINVAL, "water: %s: %s", S.path.c_str(), why.c_str());
+  const unsigned esize = v->type == 5 ? 4u : 8u;
+  const int sl = n % 4;
+  unsigned char *pin = F->rd.acquire();
+  if (!pin) return ff_io_error(c, "water", n, S, 1);
+  const size_t bytes = (size_t)P.jm * (size_t)F->im_global * esize;
+  if (pread_all(S.fd, pin, bytes, v->begin + (uint64_t)(F->j0 - 1) * (uint64_t)F->im_global * esize)) return ff_io_error(c, "water", n, S, 0);
+  if (F->rd.send(c, bytes)) return ff_io_error(c, "water", n, S, 1);
+  const void *sa = F->rd.stage, *sb0 = NULL;
+  double *da = c->wat_dev[sl], *db = NULL;
+  const int pitch = F->im_global, i0 = F->i0 - 1;
+  if (v->type == 5) LAUNCHN(c, "k_frc_unpack", (k_frc_unpack<float, float>), grid2(P), blk2(), P, 3, da, db, sa, sb0, pitch, i0);
+  else LAUNCHN(c, "k_frc_unpack", (k_frc_unpack<double, double>), grid2(P), blk2(), P, 3, da, db, sa, sb0, pitch, i0);
+  c->wat_n[sl] = n + 1;
   return POMGPU_OK;
 }
 // record n of the lateral file into the slot pomgpu_set_lateral_record(n, ...) fills

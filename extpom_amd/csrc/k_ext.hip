@@ -1456,6 +1456,19 @@ __global__ void k_frc_interp(KP P, double fold, double fnew, double *x, const do
   G2(x, i, j) = fold * G2(xb, i, j) + fnew * G2(xf, i, j);                                  // :909-910 / :952-955
   G2(y, i, j) = fold * G2(yb, i, j) + fnew * G2(yf, i, j);
 }
+// water (bounds_forcing.f:986-1020): one field.  xb given: "wssurfb = wssurff" (:1001-1005) in front of the load that follows it, each
+// lane its own cell
+__global__ void k_frc_load1(KP P, const double *ra, double *xf, double *xb) {
+  const int i = TID_I, j = TID_J;
+  if (i > P.im || j > P.jm) return;
+  if (xb) G2(xb, i, j) = G2(xf, i, j);
+  G2(xf, i, j) = ra[(size_t)(j - 1) * P.im + (size_t)(i - 1)];
+}
+__global__ void k_frc_interp1(KP P, double fold, double fnew, double *x, const double *xb, const double *xf) {
+  const int i = TID_I, j = TID_J;
+  if (i > P.im || j > P.jm) return;
+  G2(x, i, j) = fold * G2(xb, i, j) + fnew * G2(xf, i, j);                                  // :1015
+}
 
 // ---- launchers --------------------------------------------------------------------------------
 void launch_frc_load(pomgpu_ctx *c, const double *ra, const double *rb, double *xf, double *yf) {
@@ -1464,6 +1477,10 @@ void launch_frc_load(pomgpu_ctx *c, const double *ra, const double *rb, double *
 void launch_frc_interp(pomgpu_ctx *c, double fold, double fnew, double *x, const double *xb, const double *xf, double *y, const double *yb,
                        const double *yf) {
   LAUNCH(c, k_frc_interp, grid2(c->P), blk2(), c->P, fold, fnew, x, xb, xf, y, yb, yf);
+}
+void launch_frc_load1(pomgpu_ctx *c, const double *ra, double *xf, double *xb) { LAUNCH(c, k_frc_load1, grid2(c->P), blk2(), c->P, ra, xf, xb); }
+void launch_frc_interp1(pomgpu_ctx *c, double fold, double fnew, double *x, const double *xb, const double *xf) {
+  LAUNCH(c, k_frc_interp1, grid2(c->P), blk2(), c->P, fold, fnew, x, xb, xf);
 }
 void launch_advave_a(pomgpu_ctx *c) { LAUNCH(c, k_advave_a, grid2(c->P), blk2(), c->P); }
 void launch_advave_b(pomgpu_ctx *c) { LAUNCH(c, k_advave_b, grid2(c->P), blk2(), c->P); }

@@ -290,15 +290,17 @@ static bool ld_on_demand(const pomgpu_ctx *c) {
   return !c->exch && !c->tp.on && !c->wide.on && !c->parent && !(c->flags & POMGPU_CTX_2D) && !c->wr_eager && !SW(c, LD_EAGER);
 }
 // will the step after this one ask for a forcing or lateral record (pomgpu_wind / _heat / _surface / _lateral_bc: steps whose iint +
-// cont_bry is a multiple of the record interval)?  That is where a pomgpu_run ends early for a reason outside the device -- a record the
+// cont_bry is a multiple of the record interval; pomgpu_water: steps whose iint alone is a multiple of a day's)?  That is where a pomgpu_run ends early for a reason outside the device -- a record the
 // file or the host does not have -- and surface_forcing / lateral_bc come first in a step: the step in front of it stores l, dtef, so
 // that such a run leaves the whole state of its last completed step.  (One step per record interval, 1/24 day: every 20th at dti = 180 s.)
 static bool next_step_fetches_record(const pomgpu_ctx *c) {
-  if (!c->frc_on && !c->lat_on) return false;
+  if (!c->frc_on && !c->lat_on && !c->wat_on) return false;
   const pom_blkcon &k = c->con;
-  const int isrf = (int)(.125 * 86400. / k.dti), ibc = (int)((double)(1.f / 24.f) * 86400. / k.dti);
+  const int isrf = (int)(.125 * 86400. / k.dti), ibc = (int)((double)(1.f / 24.f) * 86400. / k.dti), iwater = (int)(86400. / k.dti);
   const int next = k.iint + 1 + k.cont_bry;
-  return (c->frc_on && (isrf < 1 || next % isrf == 0)) || (c->lat_on && (ibc < 1 || next % ibc == 0));
+  // water's own condition (pomgpu_water): once a day, without cont_bry
+  return (c->frc_on && (isrf < 1 || next % isrf == 0)) || (c->lat_on && (ibc < 1 || next % ibc == 0)) ||
+         (c->wat_on && (iwater < 1 || (k.iint + 1) % iwater == 0));
 }
 static void uvf_materialize(pomgpu_ctx *c) {
   if (!c->uvf_pending) return;
@@ -463,7 +465,7 @@ extern "C" void pomgpu_destroy(pomgpu_ctx *c) {
   for (int n = 0; n <= POMGPU_MAXREC; n++) { (void)hipFree(c->rec_t[n]); (void)hipFree(c->rec_s[n]); (void)hipFree(c->rec_tau[n]); }
   (void)hipFree(c->d_vel); (void)hipFree(c->d_err); (void)hipFree(c->d_areas); (void)hipFree(c->d_stats); (void)hipFree(c->ext_bar);
   for (int k = 0; k < 3; k++) for (int sl = 0; sl < 4; sl++) { (void)hipFree(c->frc_dev[k][sl][0]); (void)hipFree(c->frc_dev[k][sl][1]); }
-  for (int sl = 0; sl < 4; sl++) (void)hipFree(c->lat_dev[sl]);
+  for (int sl = 0; sl < 4; sl++) { (void)hipFree(c->lat_dev[sl]); (void)hipFree(c->wat_dev[sl]); }
   (void)hipFree(c->mean_acc);
   ProfState *ps = PS(c);
   if (ps) {
@@ -1981,13 +1983,70 @@ extern "C" int pomgpu_surface(pomgpu_ctx *c) {                // bounds_forcing.
   const pom_blkcon &k = c->con;
   const int isrf = (int)(.125 * 86400. / k.dti);
   if (isrf < 1) return fail(c, POMGPU_EINVAL, "surface forcing: dti is longer than the record interval");
-  if (k.iint == 1 || (k.iint + k.cont_bry) % isrf == 0) return frc_read(c, 2, (k.iint + k.cont_bry) / isrf + 1, SLOT2(c, P2_tsurf), NULL);
+  // pomgpu_set_surface_sss: ":979 ssurf(1:im,1:jm) = sss", which the reference keeps commented, as the load's second target
+  if (k.iint == 1 || (k.iint + k.cont_bry) % isrf == 0)
+    return frc_read(c, 2, (k.iint + k.cont_bry) / isrf + 1, SLOT2(c, P2_tsurf), c->sss_on ? SLOT2(c, P2_ssurf) : NULL);
+  return POMGPU_OK;
+}
+// ---- water -- bounds_forcing.f:986-1020, the call advance.f:89 keeps commented ----------------------
+extern "C" int pomgpu_set_water_record(pomgpu_ctx *c, int n, const double *w) {
+  NEED(c);
+  if (n < 0 || !w) return fail(c, POMGPU_EINVAL, "set_water_record: n >= 0, one (im,jm) field");
+  if (pomgpu_ff_has_water(c)) return fail(c, POMGPU_EINVAL, "set_water_record: the water records come from a file (pomgpu_set_water_files)");
+  const int sl = n % 4;
+  const size_t bytes = sizeof(double) * (size_t)c->P.im * c->P.jm;
+  if (!c->wat_dev[sl]) HIPCHK(c, hipMalloc((void **)&c->wat_dev[sl], bytes));
+  HIPCHK(c, hipMemcpyAsync(c->wat_dev[sl], w, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));                 // the caller may reuse its buffer
+  c->wat_n[sl] = n + 1;
+  c->wat_on = 1;
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_set_water(pomgpu_ctx *c, int on) {
+  NEED_RAW(c);
+  c->wat_on = on ? 1 : 0;
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_set_surface_sss(pomgpu_ctx *c, int on) {
+  NEED_RAW(c);
+  c->sss_on = on ? 1 : 0;
+  return POMGPU_OK;
+}
+// what read_water_pnetcdf(n, wssurff) delivers; shift: "wssurfb = wssurff" (:1001-1005) goes in front of it, in the same launch.  A
+// record that cannot be had fails the step before any mirror is written: the shift is not made either
+static int wat_have(pomgpu_ctx *c, int n) {                   // record n in its slot: the file's, fetched now, or the setter's
+  if (pomgpu_ff_has_water(c)) return pomgpu_ff_fetch_water(c, n);
+  if (n < 0 || c->wat_n[n % 4] != n + 1) return fail(c, POMGPU_EINVAL, "water: record %d was not supplied (pomgpu_set_water_record)", n);
+  return POMGPU_OK;
+}
+static void wat_load(pomgpu_ctx *c, int n, int shift) {
+  launch_frc_load1(c, c->wat_dev[n % 4], SLOT2(c, P2_wssurff), shift ? SLOT2(c, P2_wssurfb) : NULL);
+}
+// Not wind's schedule: no cont_bry, no "+ 1" on the record number (the files count from 0) and no "iint /= iend" around the second
+// read -- a run whose last step is a multiple of iwater needs one more record
+extern "C" int pomgpu_water(pomgpu_ctx *c) {
+  NEED_HOT(c);
+  const pom_blkcon &k = c->con;
+  const double twater = 1.;                                   // "twater=1.": days
+  const int iwater = (int)(twater * 86400. / k.dti);          // :994
+  if (iwater < 1) return fail(c, POMGPU_EINVAL, "surface forcing: dti is longer than the record interval");
+  const bool first = k.iint == 1, next = first || k.iint % iwater == 0;
+  const int n0 = k.iint / iwater, n1 = (k.iint + iwater) / iwater;   // (n1 = n0 + 1 at iint == 1: two slots)
+  int rc;
+  if (first && (rc = wat_have(c, n0))) return rc;             // both records are had before either is loaded
+  if (next && (rc = wat_have(c, n1))) return rc;
+  if (first) wat_load(c, n0, 0);                                                                 // :998
+  if (next) wat_load(c, n1, 1);                                                                  // :1000-1007
+  const int ntime = (int)(k.time / twater);                                                      // :1010-1012
+  const double fnew = k.time / twater - ntime, fold = 1. - fnew;
+  launch_frc_interp1(c, fold, fnew, SLOT2(c, P2_wssurf), SLOT2(c, P2_wssurfb), SLOT2(c, P2_wssurff));
   return POMGPU_OK;
 }
 extern "C" int pomgpu_surface_forcing(pomgpu_ctx *c) {        // advance.f:77-93
   int rc;
   if ((rc = pomgpu_wind(c))) return rc;
   if ((rc = pomgpu_heat(c))) return rc;
+  if (c->wat_on && (rc = pomgpu_water(c))) return rc;         // advance.f:89, where the reference keeps the call commented
   return pomgpu_surface(c);
 }
 // ---- lateral_bc -- bounds_forcing.f:593-868 --------------------------------------------------------
@@ -2119,6 +2178,7 @@ static int advance(pomgpu_ctx *c, int more_steps_follow) {    // advance.f:6-59
   { KP g = c->P; set_band_geometry(g, c->sw); c->P.g_strip = g.g_strip; c->P.g_lin = g.g_lin; c->P.g_rb = g.g_rb; c->P.g_nbx = g.g_nbx; c->P.g_bpl = g.g_bpl; }   // developer switches POMGPU_COL_STRIP, POMGPU_BAND_BYTES, follow pomgpu_debug_switch from step to step (tools/kbench.py)
   // advance.f:14-18: file-driven in the reference; here they run once the host has supplied records
   if (c->frc_on && (rc = pomgpu_surface_forcing(c))) return rc;
+  if (!c->frc_on && c->wat_on && (rc = pomgpu_water(c))) return rc;   // water alone
   if (c->lat_on && (rc = pomgpu_lateral_bc(c))) return rc;
   // the vertical integrals of advx, advy, drhox, drhoy come out of advct / baropg themselves: on one tile, and on
   // tiles with the wide-halo external mode (there only the owned cells of adx2d ... are used)

@@ -751,6 +751,10 @@ struct pomgpu_ctx {
   double *lat_dev[4];        // lateral_bc records: the 20 arrays of one record, concatenated (slot = n % 4)
   int lat_n[4];
   int frc_on, lat_on;        // forcing / lateral records were supplied: pomgpu_advance runs surface_forcing / lateral_bc
+  double *wat_dev[4];        // water records (pomgpu_set_water_record / _files): one (im,jm) field, slot = n % 4
+  int wat_n[4];              // the record number a slot holds PLUS ONE (water's records start at 0; 0 = empty)
+  int wat_on;                // water records or files were registered (pomgpu_set_water switches): surface_forcing / advance run pomgpu_water
+  int sss_on;                // pomgpu_set_surface_sss: pomgpu_surface also loads ssurf from the record's SSS
   // profiling
   bool prof_on;
   ProfEntry prof[96];
@@ -887,6 +891,9 @@ void launch_lat(pomgpu_ctx *c, int phase, const double *rec, double fold, double
 void launch_frc_load(pomgpu_ctx *c, const double *ra, const double *rb, double *xf, double *yf);
 void launch_frc_interp(pomgpu_ctx *c, double fold, double fnew, double *x, const double *xb, const double *xf, double *y, const double *yb,
                        const double *yf);
+// water: one field.  load1: xb = xf over (1:im,1:jm) first where xb is given, then xf = the record
+void launch_frc_load1(pomgpu_ctx *c, const double *ra, double *xf, double *xb);
+void launch_frc_interp1(pomgpu_ctx *c, double fold, double fnew, double *x, const double *xb, const double *xf);
 void launch_int_tail(pomgpu_ctx *c);
 void launch_bcond1(pomgpu_ctx *c);
 // k_adv.hip
@@ -968,6 +975,9 @@ int pomgpu_ff_has(pomgpu_ctx *c, int src);
 int pomgpu_ff_fetch_surface(pomgpu_ctx *c, int kind, int n);                    // record n of kind 0..2 into frc_dev[kind][n % 4], frc_n set
 int pomgpu_ff_fetch_lateral(pomgpu_ctx *c, int n);                              // record n into lat_dev[n % 4], lat_n set
 int pomgpu_ff_fetch_restore(pomgpu_ctx *c, int n);                              // month mod(n+9,12)+1 into rec_t[0], rec_s[0]
+// the water files (pomgpu_set_water_files): one file per record, opened when the schedule asks for it
+int pomgpu_ff_has_water(pomgpu_ctx *c);
+int pomgpu_ff_fetch_water(pomgpu_ctx *c, int n);                                // <prefix>.water.NNNN.nc into wat_dev[n % 4], wat_n set
 // the rate file (pomgpu_set_restore_rate_file; src 3).  steady: it has one record, which serves every n.  have: is record n inside the file
 // (nothing is written)?  fetch: record n's window, mapped by k_ztosig straight into the mirror taurstrf
 int pomgpu_ff_rate_steady(pomgpu_ctx *c);

@@ -1,4 +1,4 @@
-! pom_gpu_forcing.f90 -- surface_forcing's three routines (reference pom/bounds_forcing.f:871-983) with the
+! pom_gpu_forcing.f90 -- surface_forcing's routines (reference pom/bounds_forcing.f:871-1020, `water` among them) with the
 ! fields on the device: the wrappers keep the reference's decisions about WHEN a record is read and call the
 ! reference's own readers (read_wind_pnetcdf, read_heat_pnetcdf, read_surface_pnetcdf: io_pnetcdf.F:2912,
 ! 3110,3170 -- host I/O stays the host's); the record goes to the library, which shifts, loads and
@@ -61,6 +61,34 @@ subroutine heat
   end if
   call pomgpu_push_con
   if (pomgpu_heat(pom_ctx) /= 0) error_status = 1
+end subroutine
+
+! water (bounds_forcing.f:986-1020; the reference keeps its call at advance.f:89 commented): not wind's schedule -- no cont_bry, no "+1"
+! on the record number, no "iint.ne.iend" around the second read
+subroutine water
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  integer :: iwater, n
+  integer(c_int) :: rc
+  double precision :: twater
+  double precision, dimension(im,jm), target :: wat
+  twater = 1.
+  iwater = int(twater*86400.d0/dti)
+  if (iint.eq.1) then                                            ! :998
+    n = iint/iwater
+    call read_water_pnetcdf(n, wat)
+    rc = pomgpu_set_water_record(pom_ctx, int(n, c_int), c_loc(wat))
+    if (rc /= 0) error_status = 1
+  end if
+  if (iint.eq.1 .or. mod(iint,iwater).eq.0) then                 ! :1000-1007
+    n = (iint+iwater)/iwater
+    call read_water_pnetcdf(n, wat)
+    rc = pomgpu_set_water_record(pom_ctx, int(n, c_int), c_loc(wat))
+    if (rc /= 0) error_status = 1
+  end if
+  call pomgpu_push_con
+  if (pomgpu_water(pom_ctx) /= 0) error_status = 1
 end subroutine
 
 subroutine surface

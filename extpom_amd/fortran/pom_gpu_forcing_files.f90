@@ -1,4 +1,4 @@
-! pom_gpu_forcing_files.f90 -- wind, heat, surface and lateral_bc (reference pom/bounds_forcing.f:871-983, :593-868) for a host WITHOUT
+! pom_gpu_forcing_files.f90 -- wind, heat, water, surface and lateral_bc (reference pom/bounds_forcing.f:871-1020, :593-868) for a host WITHOUT
 ! PnetCDF: link instead of pom_gpu_forcing.f90.  No reader call is left: the library has been told the three input files once
 ! (pomgpu_open_forcing_files below, called after the upload) and its own schedule code -- the reference's, bounds_forcing.f:884-902,
 ! :607-613, :740-758 -- reads the record a step asks for on the device (pomgpu_set_forcing_files, include/pomgpu.h).  Each routine is
@@ -17,6 +17,15 @@ subroutine heat
   include 'pom.h'
   call pomgpu_push_con
   if (pomgpu_heat(pom_ctx) /= 0) error_status = 1
+end subroutine
+
+subroutine water                                     ! bounds_forcing.f:986-1020; nothing unless the water files are registered
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  if (.not. pom_frc_water) return
+  call pomgpu_push_con
+  if (pomgpu_water(pom_ctx) /= 0) error_status = 1
 end subroutine
 
 subroutine surface
@@ -48,11 +57,11 @@ subroutine pomgpu_open_forcing_files(have_sfrc, have_lbry, have_clim)
   type(pomgpu_file_meta) :: m
   character(len=400) :: fname
   character(len=256) :: wp
-  character(kind=c_char, len=401), target :: cname(3), rname
+  character(kind=c_char, len=401), target :: cname(3), rname, wname
   character(len=8), parameter :: suffix(3) = (/ '.sfrc.nc', '.lbry.nc', '.clim.nc' /)
   character(kind=c_char), pointer :: msg(:)
   type(c_ptr) :: p(3), pm
-  logical :: have(3), have_rate
+  logical :: have(3), have_rate, have_water
   integer(c_int) :: rc
   integer :: q, n
   wp = wrk_pth                                     ! a namelist without wrk_pth leaves the COMMON member as the loader did: NULs, not blanks
@@ -70,7 +79,13 @@ subroutine pomgpu_open_forcing_files(have_sfrc, have_lbry, have_clim)
   write(fname, '(a,''in/'',a,a)') trim(wp), trim(netcdf_file), '.restore_tau_interior.nc'
   inquire(file=trim(fname), exist=have_rate)
   rname = trim(fname)//c_null_char
-  if (.not. any(have) .and. .not. have_rate) return
+  ! the water files (io_pnetcdf.F:3244: ...'.water.',i4.4,'.nc'): registered when record 0's exists; pom_frc_water makes `water` run
+  write(fname, '(a,''in/'',a,''.water.'',i4.4,''.nc'')') trim(wp), trim(netcdf_file), 0
+  inquire(file=trim(fname), exist=have_water)
+  write(fname, '(a,''in/'',a)') trim(wp), trim(netcdf_file)
+  wname = trim(fname)//c_null_char
+  pom_frc_water = .false.
+  if (.not. any(have) .and. .not. have_rate .and. .not. have_water) return
   m%title = c_null_ptr; m%time_start = c_null_ptr; m%stats = c_null_ptr; m%create = 0
   m%im_global = im_global; m%jm_global = jm_global
   m%i0 = i_global(1); m%j0 = j_global(1)
@@ -80,6 +95,10 @@ subroutine pomgpu_open_forcing_files(have_sfrc, have_lbry, have_clim)
   if (rc == 0 .and. have(2)) rc = pomgpu_set_lateral_sides(pom_ctx, int(pom_lbry_sides, c_int))   ! the sides the lbry file feeds; the others: tclim, sclim lines
   if (rc == 0 .and. any(have)) rc = pomgpu_set_forcing_files(pom_ctx, p(1), p(2), p(3), m)
   if (rc == 0 .and. have_rate) rc = pomgpu_set_restore_rate_file(pom_ctx, c_loc(rname), m)
+  if (rc == 0 .and. have_water) then
+    rc = pomgpu_set_water_files(pom_ctx, c_loc(wname), m)
+    pom_frc_water = rc == 0
+  end if
   if (rc /= 0) then                                ! handle_error_pnetcdf, io_pnetcdf.F:43-54: a message and error_status = 1
     error_status = 1
     have_sfrc = .false.; have_lbry = .false.; have_clim = .false.

@@ -167,6 +167,16 @@ subroutine pom_output_mean(on)
   end if
 end subroutine
 
+! bounds_forcing.f:979 "ssurf(1:im,1:jm) = sss" uncommented: pom_surface_sss(.true.) makes `surface` set ssurf from the record's SSS
+! (pomgpu_set_surface_sss), what proft's salt solve reads at nbcs = 3
+subroutine pom_surface_sss(on)
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  logical, intent(in) :: on
+  if (pomgpu_set_surface_sss(pom_ctx, merge(1_c_int, 0_c_int, on)) /= 0) error_status = 1
+end subroutine
+
 subroutine mean_accumulate
   use pomgpu_iface
   implicit none

@@ -22,6 +22,8 @@
 !        ... --cold | --cold-z <state.out> <nsteps> --mean     (the time-mean output: every iprint steps write_output_pnetcdf writes
 !                                                                <wrk_pth>out/<netcdf_file>.<nnnn>.nc with the means since the last one;
 !                                                                beside the other two, in any order)
+!        ... --cold | --cold-z <state.out> <nsteps> --sss      (surface sets ssurf from the record's SSS: bounds_forcing.f:979 uncommented)
+! The water files <wrk_pth>in/<netcdf_file>.water.NNNN.nc need no flag: they are registered when record 0000's exists.
 program pom_gpu_main
   use pomgpu_iface
   implicit none
@@ -32,7 +34,7 @@ program pom_gpu_main
   double precision :: vtot, atot, mtot, stot, tavg, savg, eavg, ekin
   double precision, allocatable, target :: tr(:,:,:,:), sr(:,:,:,:)
   character(len=256) :: fin, fout, arg3
-  logical :: cold, mean
+  logical :: cold, mean, sss
 
   call get_command_argument(1, fin)
   call get_command_argument(2, fout)
@@ -41,8 +43,8 @@ program pom_gpu_main
   nbd = 8*jm_local + 8*im_local + (12+12+6+6)*0   ! filled below
   nbd = 20*jm_local + 20*im_local + 18*jm_local*kb + 18*im_local*kb   ! bdry: 20 J, 20 I... see pom_layout.h
   cold = trim(fin) == '--cold' .or. trim(fin) == '--cold-z'
-  mean = .false.
-  if (trim(fin) == '--cold-z') then          ! the init and the clim file are on z levels (initialize.f:410-422)
+  mean = .false.; sss = .false.
+  if (trim(fin) == '--cold-z') then         ! the init and the clim file are on z levels (initialize.f:410-422)
     pom_init_on_z = .true.; pom_clim_on_z = .true.
   end if
   if (cold) then                             ! one tile, the whole grid; read_input's constants (initialize.f:80-168)
@@ -53,6 +55,7 @@ program pom_gpu_main
       call get_command_argument(n, arg3)
       if (trim(arg3) == '--lbry-z') pom_lbry_on_z = .true.
       if (trim(arg3) == '--mean') mean = .true.
+      if (trim(arg3) == '--sss') sss = .true.
       if (trim(arg3) == '--lbry-sides') then
         n = n + 1
         call get_command_argument(n, arg3)
@@ -111,7 +114,8 @@ program pom_gpu_main
     end do
   end if
   if (mean) call pom_output_mean(.true.)
-  do n = 1, nsteps                           ! pom.f:17-19
+  if (sss) call pom_surface_sss(.true.)
+  do n = 1, nsteps                          ! pom.f:17-19
     iint = iint + 1
     call advance_hot
     if (pom_mean_on .and. iprint > 0) then   ! advance.f:35-38: the mean file in the snapshot's place (Fortran does not short-circuit: iprint is tested first)
@@ -148,7 +152,10 @@ subroutine advance_hot
   if (pom_frc_sfrc) then
     call wind
     call heat
+    call water                               ! advance.f:89 (commented there); nothing unless <netcdf_file>.water.0000.nc was found
     call surface
+  else
+    call water
   end if
   if (pom_frc_lbry) call lateral_bc
   call lateral_viscosity

@@ -187,6 +187,15 @@ subroutine read_surface_pnetcdf(n, sst, sss)
   double precision sst(im,jm), sss(im,jm)
   call serve_record(3, n, sst, sss)
 end subroutine
+subroutine read_water_pnetcdf(n, wat)          ! (:3227) no water record comes with the state: this driver's advance_hot does not call `water`
+  implicit none
+  include 'pom.h'
+  integer n
+  double precision wat(im,jm)
+  write(6,'(a,i4,a)') 'pom_gpu_mpi_main: water record ', n, ' did not come with the state'
+  error_status = 1
+  stop 2
+end subroutine
 subroutine serve_record(kind, n, a, b)
   use pom_gpu_records
   implicit none

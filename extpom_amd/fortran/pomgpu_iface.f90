@@ -10,6 +10,8 @@ module pomgpu_iface
   type(c_ptr), save :: pom_ctx = c_null_ptr
   ! which forcing files the library reads itself (set by pomgpu_open_forcing_files' caller; pom_gpu_main's advance_hot looks at them)
   logical, save :: pom_frc_sfrc = .false., pom_frc_lbry = .false., pom_frc_clim = .false.
+  ! the water files <wrk_pth>in/<netcdf_file>.water.NNNN.nc are registered (pomgpu_open_forcing_files found .water.0000.nc): `water` runs
+  logical, save :: pom_frc_water = .false.
   ! the init / clim file holds z levels (pomgpu_set_z_inputs): cold_start_files and pomgpu_open_forcing_files pass the two on
   logical, save :: pom_init_on_z = .false., pom_clim_on_z = .false.
   ! temp, salt of the lbry file are on z levels (pomgpu_set_z_lateral): pomgpu_open_forcing_files passes it on
@@ -94,6 +96,18 @@ module pomgpu_iface
     end function
     integer(c_int) function pomgpu_set_forcing_files(ctx, sfrc, lbry, clim, meta) bind(C, name='pomgpu_set_forcing_files')
       import; type(c_ptr), value :: ctx, sfrc, lbry, clim; type(pomgpu_file_meta) :: meta   ! any path may be c_null_ptr
+    end function
+    integer(c_int) function pomgpu_set_water_record(ctx, n, w) bind(C, name='pomgpu_set_water_record')
+      import; type(c_ptr), value :: ctx, w; integer(c_int), value :: n   ! n >= 0
+    end function
+    integer(c_int) function pomgpu_set_water_files(ctx, prefix, meta) bind(C, name='pomgpu_set_water_files')
+      import; type(c_ptr), value :: ctx, prefix; type(pomgpu_file_meta) :: meta   ! <prefix>.water.NNNN.nc
+    end function
+    integer(c_int) function pomgpu_set_water(ctx, on) bind(C, name='pomgpu_set_water')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: on
+    end function
+    integer(c_int) function pomgpu_set_surface_sss(ctx, on) bind(C, name='pomgpu_set_surface_sss')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: on
     end function
     integer(c_int) function pomgpu_set_restore_rate_record(ctx, n, tau) bind(C, name='pomgpu_set_restore_rate_record')
       import; type(c_ptr), value :: ctx, tau; integer(c_int), value :: n
@@ -190,6 +204,7 @@ module pomgpu_iface
   procedure(pomgpu_noarg), bind(C, name='pomgpu_baropg_mcc') :: pomgpu_baropg_mcc
   procedure(pomgpu_noarg), bind(C, name='pomgpu_wind') :: pomgpu_wind
   procedure(pomgpu_noarg), bind(C, name='pomgpu_heat') :: pomgpu_heat
+  procedure(pomgpu_noarg), bind(C, name='pomgpu_water') :: pomgpu_water
   procedure(pomgpu_noarg), bind(C, name='pomgpu_surface') :: pomgpu_surface
   procedure(pomgpu_noarg), bind(C, name='pomgpu_lateral_bc') :: pomgpu_lateral_bc
   procedure(pomgpu_noarg), bind(C, name='pomgpu_profq') :: pomgpu_profq

@@ -103,6 +103,36 @@ class PomGpu:
                 b = np.ascontiguousarray(recs[n - 1][1], dtype=np.float64)
                 self._chk(self.L.pomgpu_set_forcing_record(self.h, kind, n, self._p(a), self._p(b)), "set_forcing_record")
 
+    def set_water_records(self, first: int = 0, count: int = 4):
+        """pomgpu_set_water_record: hand records first..first+count-1 of st.water_records (a dict n -> (jm, im) array, n >= 0: what
+        read_water_pnetcdf(n, ...) would deliver) to the library, which keeps the last four; the first one switches water on"""
+        recs = getattr(self.st, "water_records", {})
+        for n in range(first, first + count):
+            if n in recs:
+                w = np.ascontiguousarray(recs[n], dtype=np.float64)
+                if w.shape != (self.st.jm, self.st.im):
+                    raise ValueError(f"set_water_records: record {n} is {w.shape}, not (jm, im) = {(self.st.jm, self.st.im)}")
+                self._chk(self.L.pomgpu_set_water_record(self.h, n, self._p(w)), "set_water_record")
+
+    def set_water_files(self, prefix, im_global=None, jm_global=None):
+        """pomgpu_set_water_files: from now on water takes record n from <prefix>.water.NNNN.nc (one record per file, `w`), on the
+        device; switches water on.  This tile's patch starts at (i_off+1, j_off+1) of the global grid, as in set_forcing_files."""
+        st = self.st
+        m = _lib.FileMeta(b"", b"", im_global or st.im, jm_global or st.jm, st.i_off + 1, st.j_off + 1, 0, None)
+        self._chk(self.L.pomgpu_set_water_files(self.h, None if prefix is None else str(prefix).encode(), ctypes.byref(m)), "set_water_files")
+
+    def set_water(self, on: bool = True):
+        """pomgpu_set_water: advance / run / surface_forcing call water (on) or leave wssurf alone (off)"""
+        self._chk(self.L.pomgpu_set_water(self.h, 1 if on else 0), "set_water")
+
+    def water(self):
+        """pomgpu_water (bounds_forcing.f:986-1020) for the current iint and time"""
+        self.call("water")
+
+    def set_surface_sss(self, on: bool = True):
+        """pomgpu_set_surface_sss: surface also sets ssurf from the record's SSS (bounds_forcing.f:979 uncommented)"""
+        self._chk(self.L.pomgpu_set_surface_sss(self.h, 1 if on else 0), "set_surface_sss")
+
     def set_lateral_records(self, first: int = 1, count: int = 4):
         """hand records first..first+count-1 of st.lateral_records (20 arrays each, see pomgpu.h) to the library"""
         recs = getattr(self.st, "lateral_records", [])

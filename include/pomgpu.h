@@ -145,7 +145,32 @@ int pomgpu_set_forcing_record(pomgpu_ctx *ctx, int kind, int n, const double *a,
 int pomgpu_wind(pomgpu_ctx *ctx);              /* bounds_forcing.f:871-912 */
 int pomgpu_heat(pomgpu_ctx *ctx);              /* bounds_forcing.f:915-960 */
 int pomgpu_surface(pomgpu_ctx *ctx);           /* bounds_forcing.f:963-983 */
-int pomgpu_surface_forcing(pomgpu_ctx *ctx);   /* advance.f:77-93: wind, heat, surface */
+int pomgpu_surface_forcing(pomgpu_ctx *ctx);   /* advance.f:77-93: wind, heat, [water,] surface */
+/* ":979 ssurf(1:im,1:jm) = sss", which the reference keeps commented: on != 0 makes pomgpu_surface load ssurf from the record's second
+ * field (SSS of the sfrc file, `b` of a kind-2 record) beside tsurf -- what proft's salt solve reads at nbcs = 3.  Off (the default):
+ * ssurf is never written. */
+int pomgpu_set_surface_sss(pomgpu_ctx *ctx, int on);
+
+/* ---- water: the fresh-water flux wssurf (bounds_forcing.f:986-1020; the call at advance.f:89 is commented in the reference) -------------
+ * proft's salt solve reads wssurf at nbcs = 1 (solver.f:1566-1574, advance.f:440).  pomgpu_water restates `water` as written: twater = 1.
+ * day, iwater = int(86400 / dti); at iint == 1 record iint / iwater goes into wssurff; when iint == 1 or mod(iint, iwater) == 0, wssurfb =
+ * wssurff over (1:im, 1:jm) and record (iint + iwater) / iwater goes into wssurff; then wssurf = fold * wssurfb + fnew * wssurff with fnew
+ * = time / twater - int(time / twater), fold = 1. - fnew.  Three differences from wind and heat: (1) cont_bry is not in the schedule;
+ * (2) the record number carries no "+ 1" -- records count from 0, which the first step reads unless dti is a day or more; (3) there is
+ * no "iint /= iend" guard: a run whose last step is a multiple of iwater needs one more record.  The record is neither converted nor
+ * tapered.  Off by default: the first pomgpu_set_water_record or pomgpu_set_water_files switches it on, pomgpu_set_water(ctx, 0) off
+ * again.  While on, pomgpu_surface_forcing calls pomgpu_water between heat and surface, and pomgpu_advance / pomgpu_run call it alone
+ * where no surface source is registered.  iwater < 1 and a record that cannot be had: POMGPU_EINVAL, error_status = 1, before any mirror or record
+ * slot is written (the shift is not made either).
+ * Records: pomgpu_set_water_record hands over the one (im,jm) field read_water_pnetcdf(n, ...) (io_pnetcdf.F:3227-3272) would deliver, n
+ * >= 0, the last four are kept; or pomgpu_set_water_files names <prefix>.water.NNNN.nc -- the reference's '(a,''in/'',a,''.water.'',
+ * i4.4,''.nc'')' with prefix = <wrk_pth>in/<netcdf_file> -- each file ONE record: `w` as (jm_global, im_global), found by name, NC_FLOAT
+ * or NC_DOUBLE, other dimensions and variables tolerated.  The file of record n is opened when the schedule asks for it, checked like
+ * every other file this library reads, its band unpacked by the kernel of the surface records, and closed; n > 9999 has no file name.
+ * Every rank reads its own window (meta's i0, j0): no message round.  The setter is refused once files are registered. */
+int pomgpu_set_water_record(pomgpu_ctx *ctx, int n, const double *w);   /* pomgpu_set_water_files: declared beside pomgpu_set_forcing_files */
+int pomgpu_set_water(pomgpu_ctx *ctx, int on);
+int pomgpu_water(pomgpu_ctx *ctx);             /* bounds_forcing.f:986-1020 */
 
 /* lateral_bc on the device (bounds_forcing.f:593-868): records every 1/24 day, the same shift / load /
  * interpolate pattern on the open-boundary arrays of `bdry`, plus the depth integrals uab?f, vab?f, uabe, uabw,
@@ -427,9 +452,12 @@ int pomgpu_set_lateral_sides(pomgpu_ctx *ctx, int sides);
 int pomgpu_set_forcing_files(pomgpu_ctx *ctx, const char *sfrc, const char *lbry, const char *clim, const pomgpu_file_meta *meta);
 /* the restore rate's file: see pomgpu_set_restore_rate_record above */
 int pomgpu_set_restore_rate_file(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta);
+/* the water files: see pomgpu_water above */
+int pomgpu_set_water_files(pomgpu_ctx *ctx, const char *prefix, const pomgpu_file_meta *meta);
 
 /* One internal step for the current blkcon.iint: get_time, [surface_forcing, lateral_bc -- once the host has named
- * forcing files or supplied forcing / lateral records, see above; skipped otherwise: constant forcing], lateral_viscosity,
+ * forcing files or supplied forcing / lateral records, see above; skipped otherwise: constant forcing; water inside surface_forcing, or
+ * alone where no surface source is registered, once water is on], lateral_viscosity,
  * mode_interaction, isplit x mode_external, mode_internal, check_velocity (advance.f:6-59 minus print and
  * output, which stay on the host).  Does not synchronise: a record fetched from a file holds the host for its preads only. */
 int pomgpu_advance(pomgpu_ctx *ctx);

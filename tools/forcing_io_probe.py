@@ -13,7 +13,11 @@ fraction of their pages was resident (mincore) before the first and after the la
     python tools/forcing_io_probe.py [--grid 1024x1024x40] [--dir /scratch] [--turns 3] [--out profiles/forcing_read_1024x1024x40.json]
     python tools/forcing_io_probe.py --lbry-z [--ks 33] [--out profiles/forcing_read_lbry_z_1024x1024x40.json]
     python tools/forcing_io_probe.py --sides 15 [--lbry-z] [--out profiles/forcing_read_lbry_sides_1024x1024x40.json]
+    python tools/forcing_io_probe.py --water --grid 2048x1536x50 [--out profiles/water_forcing_probe.json]
     python tools/forcing_io_probe.py --check      (no GPU: arguments, paths and free space only; reports no time)
+
+--water: a job of its own (water_probe below): one water fetch beside a wind fetch of the same build, and the step with water on and off
+in one context.
 
 --lbry-z: a third context of the same job takes its lateral records from an lbry file whose temp / salt lines are on ks z levels
 (PomGpu.set_z_inputs(lbry=True)): its fetch steps stand beside the sigma file's, with the bare pread of the bytes it reads, and one more
@@ -37,8 +41,84 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 PERIOD, LPERIOD = 60, 20                                         # steps between surface / lateral record changes at dti = 180 s
 
 
+def water_probe(args, im, jm, kb, where):
+    """--water: one context with an sfrc file and the water files registered.  (1) at iint = 1 wind and water each fetch two records
+    (wind: two planes a record, water: one): `wind` and `water` alone, host clock around call + sync, against the same calls at iint = 2,
+    which fetch nothing.  (2) the step with water on and off, alternating in ONE context (the --ab idea of tools/tile_probe.py): `ab_turns`
+    turns of `ab_steps` steps each way, none of which fetches.  (3) a few steps with every kernel bracketed: k_frc_interp1's own time."""
+    import numpy as np
+    import forcing_expect as fx
+    import water_expect as wx
+    from extpom_amd.cases import make_case
+    from extpom_amd.model import PomGpu
+    out = dict(tool="forcing_io_probe --water", grid=f"{im}x{jm}x{kb}", case=args.case)
+    st = make_case(args.case, im, jm, kb, dte=6.0, isplit=30)     # dti = 180 s: iwater = 480, the surface records change every 60 steps
+    tmp = tempfile.mkdtemp(prefix="water_probe_", dir=where)
+    try:
+        sfrc = fx.write_sfrc(os.path.join(tmp, "probe.sfrc.nc"), fx.raw_sfrc(st, 2))
+        prefix = os.path.join(tmp, "probe")
+        wx.write_all(prefix, wx.raw_water(st, (0, 1)))
+        g = PomGpu(st, device=0)
+        g.set_forcing_files(sfrc=sfrc)
+        g.set_water_files(prefix)
+
+        def timed(fn):
+            g.sync()
+            t = time.perf_counter()
+            fn()
+            g.sync()
+            return round((time.perf_counter() - t) * 1e3, 3)
+
+        def at(iint):
+            g.set_con(iint=iint)
+            g.call("get_time")
+
+        at(1)
+        out["wind_two_fetches_ms"] = timed(lambda: g.call("wind"))
+        out["water_two_fetches_ms"] = timed(lambda: g.water())
+        at(2)
+        out["wind_no_fetch_ms"] = timed(lambda: g.call("wind"))
+        out["water_no_fetch_ms"] = timed(lambda: g.water())
+        out["fetch_bytes"] = {"wind": 2 * 2 * 8 * im * jm, "water": 2 * 8 * im * jm}
+        at(1)                                                     # heat and surface too: every field's "b" and "f" generation is in place
+        g.call("heat")
+        g.call("surface")
+        g.set_con(iint=1)
+        g.run(2)                                                  # warm: steps 2, 3
+        on, off = [], []
+        for _ in range(args.ab_turns):
+            g.set_water(True)
+            on.append(round(timed(lambda: g.run(args.ab_steps)) / args.ab_steps, 4))
+            g.set_water(False)
+            off.append(round(timed(lambda: g.run(args.ab_steps)) / args.ab_steps, 4))
+        out["step_ms_water_on"], out["step_ms_water_off"] = on, off
+        out["step_ms_on_minus_off_median"] = round(float(np.median(on) - np.median(off)), 4)
+        out["step_ms_off_spread"] = round(max(off) - min(off), 4)
+        g.set_water(True)
+        g.prof_begin()
+        g.run(3)
+        prof = g.prof_end()
+        out["kernels_ms"] = {k: [prof[k][0], round(prof[k][1] / max(prof[k][0], 1), 5)] for k in ("k_frc_interp1", "k_frc_interp", "phase_step") if k in prof}
+        out["interp1_bytes"] = 3 * 8 * im * jm
+        g.download()
+        out["error_status"], out["iint"] = int(st.error_status), int(st.iint)
+        out["wssurf_nonzero"] = bool(st.wssurf.any())
+        g.close()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    print(json.dumps(out))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--water", action="store_true", help="the water fetch beside a wind fetch, and the step with water on and off")
+    ap.add_argument("--ab-turns", type=int, default=4)
+    ap.add_argument("--ab-steps", type=int, default=5)
     ap.add_argument("--grid", default="1024x1024x40")
     ap.add_argument("--case", default="basin")
     ap.add_argument("--dir", default=None, help="where the files go (default: the temporary directory)")
@@ -68,6 +148,8 @@ def main():
         out["checked"] = "arguments and paths only: no time is reported without a GPU"
         print(json.dumps(out))
         return 0
+    if args.water:
+        return water_probe(args, im, jm, kb, where)
 
     import numpy as np
     from scipy.io import netcdf_file
