@@ -501,6 +501,47 @@ template <int TAU> __device__ __forceinline__ void c_ts_update(const KP &P, cons
 }
 // (Tried: 7 levels per wavefront with the next level's operands in flight, as k_aam_pair now does -- 4.08 against 3.90 ms: this kernel's
 // 2.5 M one-level wavefronts at 8 waves per SIMD already keep its 17 passes moving at 5.5 TB/s; the chunked form holds 110 VGPRs, 4 waves.)
+// ---- passive tracers (pomgpu_set_tracers): the tail of the tracer stage for NF fields in ONE pass -- bcond(4)'s mask on (1:im, 1:jm,
+// 1:kbm1) (bounds_forcing.f:233-240), the filter and the rotation f = f + .5*smoth*(ff + fb - 2.*f); fb = f; f = ff on the whole arrays
+// (advance.f:444-449 for a field that is not t or s), with advt2's in-place round trip of fb (solver.f:691,715) where the advection left
+// it (rt), as k_ts_update does for T and S.  Level kb takes the filter without the mask.  No restore_interior, no dens.
+template <int NF> struct TrUpds { TrUpd u[NF]; };
+template <int NF> __device__ __forceinline__ void c_tr_update(const KP &P, const int i, const int j, const int k, const TrUpds<NF> &A, int rt) {
+  const bool msk = (i <= P.im && j <= P.jm && k <= P.kbm1);
+  const double m = F2(fsm, i, j);
+#pragma unroll
+  for (int f = 0; f < NF; f++) {
+    const TrUpd &u = A.u[f];
+    double ff = G3(u.ff, i, j, k);
+    if (msk) ff = ff * m;
+    double fb = G3(u.fb, i, j, k);
+    if (rt) {
+      const double fc = G3(u.fc, i, j, k);
+      fb = (fb - fc) + fc;
+    }
+    const double f0 = G3(u.f, i, j, k);
+    G3(u.fb, i, j, k) = f0 + .5 * P.smoth * (ff + fb - 2. * f0);
+    G3(u.f, i, j, k) = ff;
+  }
+}
+template <int NF> __global__ void k_tr_update(KP P, TrUpds<NF> A, int rt) {
+  MARCH3(c_tr_update<NF>(P, i, j, k, A, rt))
+}
+// step 2 of the tracer stage: ff = ff + dti2 * (q - lam * fb) on (1:im, 1:jm, 1:kbm1); four roundings (the build contracts nothing), a
+// missing q is +0.0.  fc: advt2's round trip of fb is still to come (k_tr_update) and is applied to what is loaded here.  Launched only
+// for a tracer that has a source array or a decay rate
+__device__ __forceinline__ void c_tr_source(const KP &P, const int i, const int j, const int k, double *ff, const double *fb, const double *fc, const double *q, double lam) {
+  if (k > P.kbm1 || i > P.im || j > P.jm) return;
+  double x = G3(fb, i, j, k);
+  if (fc) { const double y = G3(fc, i, j, k); x = (x - y) + y; }
+  const double a = lam * x;
+  const double b = (q ? (double)G3(q, i, j, k) : 0.) - a;
+  const double d = P.dti2 * b;
+  G3(ff, i, j, k) = (double)G3(ff, i, j, k) + d;
+}
+__global__ void k_tr_source(KP P, double *ff, const double *fb, const double *fc, const double *q, double lam) {
+  MARCH3(c_tr_source(P, i, j, k, ff, fb, fc, q, lam))
+}
 __device__ __forceinline__ void c_mask_ts(const KP &P, const int i, const int j, const int k);
 __global__ void k_mask_ts(KP P) {   // the mask of bcond(4) alone
   MARCH3(c_mask_ts(P, i, j, k))
@@ -961,6 +1002,18 @@ void launch_ts_update(pomgpu_ctx *c, double fold, double fnew, int rt, int store
 }
 void launch_restore_fields(pomgpu_ctx *c, double fold, double fnew) { LAUNCH(c, k_restore_fields, gridm(c->P), blk2(), c->P, fold, fnew); }
 void launch_mask_ts(pomgpu_ctx *c) { LAUNCH(c, k_mask_ts, gridm(c->P), blk2(), c->P); }
+void launch_tr_update(pomgpu_ctx *c, const TrUpd *u, int nf, int rt) {
+  if (nf == 2) {
+    TrUpds<2> A; A.u[0] = u[0]; A.u[1] = u[1];
+    LAUNCHN(c, "k_tr_update2", (k_tr_update<2>), gridm(c->P), blk2(), c->P, A, rt);
+  } else {
+    TrUpds<1> A; A.u[0] = u[0];
+    LAUNCHN(c, "k_tr_update", (k_tr_update<1>), gridm(c->P), blk2(), c->P, A, rt);
+  }
+}
+void launch_tr_source(pomgpu_ctx *c, double *ff, const double *fb, const double *fc, const double *q, double lam) {
+  LAUNCH(c, k_tr_source, gridm(c->P), blk2(), c->P, ff, fb, fc, q, lam);
+}
 void launch_mask_uv(pomgpu_ctx *c) { LAUNCH(c, k_mask_uv, gridm(c->P), blk2(), c->P); }
 void launch_mask_w(pomgpu_ctx *c) { LAUNCH(c, k_mask_w, gridm(c->P), blk2(), c->P); }
 void launch_restore(pomgpu_ctx *c, double fold, double fnew) { LAUNCH(c, k_restore, gridm(c->P), blk2(), c->P, fold, fnew); }

@@ -88,6 +88,42 @@ __global__ void k_bcond4_edges(KP P) {
   F3(vf, i, j, k) = sv;
 }
 
+// bcond(4)'s T lines for NF passive tracers on explicit pointers (pomgpu_set_tracers): ff for uf, f for t, be bw bn bs for tbe tbw tbn tbs.
+// Same cells, same corner rule, same u, v (uvm_ld) as k_bcond4_edges; the velocity terms are formed once for the NF fields.
+template <int NF> struct TrEdges { TrEdge e[NF]; };
+template <int NF> __global__ void k_tr_edges(KP P, TrEdges<NF> A) {
+  EDGE_CELL(1)
+  if (k > P.kbm1) return;
+  const bool vert = (k != 1 && k != P.kbm1);
+  // the cell's own index, the interior neighbour's, and the boundary value's offset inside its array
+  const int ii = line == 0 ? 2 : (line == 1 ? P.imm1 : i), ji = line == 2 ? 2 : (line == 3 ? P.jmm1 : j);
+  double u1;
+  if (line == 1) u1 = 2. * uvm_ld<0>(P, P.im, j, k) * P.dti / (F2(dx, P.im, j) + F2(dx, P.imm1, j));
+  else if (line == 0) u1 = 2. * uvm_ld<0>(P, 2, j, k) * P.dti / (F2(dx, 1, j) + F2(dx, 2, j));
+  else if (line == 2) u1 = 2. * uvm_ld<1>(P, i, 2, k) * P.dti / (F2(dy, i, 1) + F2(dy, i, 2));
+  else u1 = 2. * uvm_ld<1>(P, i, P.jm, k) * P.dti / (F2(dy, i, P.jm) + F2(dy, i, P.jmm1));
+  const bool inflow = (line == 1 || line == 3) ? (u1 <= 0.) : (u1 >= 0.);
+  double wm = 0.;
+  if (!inflow && vert) wm = .5 * (F3(w, ii, ji, k) + F3(w, ii, ji, k + 1)) * P.dti / ((F1(zz, k - 1) - F1(zz, k + 1)) * F2(dt, ii, ji));
+  const size_t ob = line < 2 ? (size_t)(k - 1) * P.jml + (size_t)(j - 1) : (size_t)(k - 1) * P.iml + (size_t)(i - 1);
+#pragma unroll
+  for (int f = 0; f < NF; f++) {
+    const TrEdge &e = A.e[f];
+    const double *bp = line == 0 ? e.bw : (line == 1 ? e.be : (line == 2 ? e.bs : e.bn));
+    const double tc = G3(e.f, i, j, k);
+    double tv;
+    if (inflow) {
+      // east, north: t - u1*(tb - t); west, south: t - u1*(t - tb)
+      tv = (line == 1 || line == 3) ? tc - u1 * (bp[ob] - tc) : tc - u1 * (tc - bp[ob]);
+    } else {
+      const double tn = G3(e.f, ii, ji, k);
+      tv = (line == 1 || line == 3) ? tc - u1 * (tc - tn) : tc - u1 * (tn - tc);
+      if (vert) tv = tv - wm * (G3(e.f, ii, ji, k - 1) - G3(e.f, ii, ji, k + 1));
+    }
+    G3(e.ff, i, j, k) = tv;
+  }
+}
+
 // bcond(6): upstream q2, q2l on the open edges (uf = q2, vf = q2l), k = 1..kb -- :261-313, with the mask of :315-322
 // applied here (uf*fsm + 1.e-10 on the value in registers): stored first and masked by a later kernel, the fp32-storage
 // build rounded these cells twice.  The later mask (c_mask_q, c_q_filter) skips them (bcond6_edge_cell).
@@ -290,6 +326,19 @@ void launch_bcond4_edges(pomgpu_ctx *c) {
   if (!(P.W || P.E || P.S || P.N)) return;
   const int len = P.im > P.jm ? P.im : P.jm;
   LAUNCH(c, k_bcond4_edges, dim3((len + 63) / 64, 4, P.kbm1), dim3(64, 1, 1), c->P);
+}
+void launch_tr_edges(pomgpu_ctx *c, const TrEdge *e, int nf) {
+  const KP &P = c->P;
+  if (!(P.W || P.E || P.S || P.N)) return;
+  const int len = P.im > P.jm ? P.im : P.jm;
+  const dim3 grid((len + 63) / 64, 4, P.kbm1), blk(64, 1, 1);
+  if (nf == 2) {
+    TrEdges<2> A; A.e[0] = e[0]; A.e[1] = e[1];
+    LAUNCHN(c, "k_tr_edges2", (k_tr_edges<2>), grid, blk, c->P, A);
+  } else {
+    TrEdges<1> A; A.e[0] = e[0];
+    LAUNCHN(c, "k_tr_edges", (k_tr_edges<1>), grid, blk, c->P, A);
+  }
 }
 void launch_bcond6_edges(pomgpu_ctx *c) {
   const KP &P = c->P;

@@ -975,6 +975,9 @@ void launch_advuv_col(pomgpu_ctx *c) {
 void launch_advt2_rows(pomgpu_ctx *c, const double *fb, const double *f, const double *fc, double *ff) {
   {
     TFields A; A.fb[0] = A.fb[1] = fb; A.f[0] = A.f[1] = f; A.fcl[0] = A.fcl[1] = fc; A.ff[0] = A.ff[1] = ff;
+#if POMGPU_UVM_ONLOAD   // an odd passive tracer on one tile: u, v still lack the depth-mean correction (the T / S pair never comes here with KP::uvm up)
+    if (c->P.uvm) { LAUNCHN(c, "k_advt2_col", (k_advt2_col<1, true>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A); return; }
+#endif
     LAUNCHN(c, "k_advt2_col", (k_advt2_col<1>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A);
   }
 }

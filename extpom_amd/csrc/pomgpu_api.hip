@@ -162,6 +162,7 @@ static void sync_scalars(pomgpu_ctx *c) {
   P.cb_profq = pow((double)15.8f * 100., (double)(2.f / 3.f));
 }
 
+static void tracers_free(pomgpu_ctx *c);
 // ---- life cycle -------------------------------------------------------------------------------
 // a digest of the library's sources, put in by the build (__graft_entry__.build_hip): measurements kept in profiles/ carry it, and
 // bench.py only quotes a stored counter value (roofline.traffic) for the build it was taken from
@@ -278,7 +279,9 @@ static bool w_fused(const pomgpu_ctx *c) {
 static bool uvm_onload(const pomgpu_ctx *c) {
   const pom_blkcon &k = c->con;
   return POMGPU_UVM_ONLOAD && w_fused(c) && uv_fused(c) && c->uvm_valid && !SW(c, UVMEAN_PASS) &&
-         (k.mode == 4 || (k.nadv == 2 && c->P.nitera == 1 && !SW(c, ADVT2_SINGLE)));
+         (k.mode == 4 || (k.nadv == 2 && c->P.nitera == 1 && !SW(c, ADVT2_SINGLE))) &&
+         // passive tracers are advected in mode 4 too, and with nadv 1 or nitera > 1 by kernels that read u, v as they are in memory
+         (!c->ntr || (k.nadv == 2 && c->P.nitera == 1));
 }
 // may k_profq of a step that another step of the same pomgpu_run follows keep l and dtef out of memory (launch_profq, store_ld = 0)?
 // Nothing on the device reads them back and the next step's profq rewrites both whole, so the question is only who can look between
@@ -467,6 +470,7 @@ extern "C" void pomgpu_destroy(pomgpu_ctx *c) {
   for (int k = 0; k < 3; k++) for (int sl = 0; sl < 4; sl++) { (void)hipFree(c->frc_dev[k][sl][0]); (void)hipFree(c->frc_dev[k][sl][1]); }
   for (int sl = 0; sl < 4; sl++) { (void)hipFree(c->lat_dev[sl]); (void)hipFree(c->wat_dev[sl]); }
   (void)hipFree(c->mean_acc);
+  tracers_free(c);
   ProfState *ps = PS(c);
   if (ps) {
     for (auto &p : ps->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -1709,6 +1713,77 @@ extern "C" int pomgpu_mode_external(pomgpu_ctx *c) {
 }
 // wr (solver.f:2024-2067) and its exchange (:2055) on the side stream: nobody on the hot path reads wr (a diagnostic for the
 // output file), so realvertvl itself may run there as well (with_kernel: beside the NEXT step's external substeps, below)
+// ---- passive tracers (include/pomgpu.h) ---------------------------------------------------------------------------
+// The stage mode_internal runs between dens (advance.f:454) and advu (:459) while tracers are registered: per tracer the lines the
+// reference runs for T -- advt1 / advt2, the exchange of :436, proft, bcond(4), the filter and rotation -- plus a source / decay term
+// behind the advection.  It reads u v w aam kh etb etf as they stand there (u, v through the UM forms while KP::uvm is up) and writes
+// nothing but the tracers' own arrays.  With the one-pass advection (nadv 2, nitera 1) tracers 2p-1, 2p share k_advt2_col<2>, one lane of
+// proft where launch_proft2 takes the pair, k_tr_edges<2> and k_tr_update<2>; an odd one, nadv 1 and nitera > 1 go one by one
+// (POMGPU_TR_NOPAIR, read here: every tracer one by one).  fb's round trip (solver.f:691,715) is deferred to k_tr_update as k_ts_update
+// does for T and S; k_tr_source, which reads trb in between, applies it to what it loads.
+// Message rounds, the library's own exchange (lib_x): the one-pass advection's solver.f:728 and advance.f:436 have nothing written on a
+// ghost line in between that the neighbour does not write alike (the source is pointwise and runs on ghost lines too), so ONE round
+// carries trf of all tracers (xch takes eight arrays); nitera > 1 adds smol_adif's nitera rounds and :728 per tracer (seq_advt2).
+static void xchv(pomgpu_ctx *c, double *const *ptr, const int *nz, int count) {
+  if (c->exch) c->exch(c->exch_user, ptr, nz, count);
+}
+static int tracer_stage(pomgpu_ctx *c, bool lib_x) {
+  KP &P = c->P;
+  const pom_blkcon &k = c->con;
+  const int ntr = c->ntr;
+  if (k.nadv != 1 && k.nadv != 2) return fail(c, POMGPU_EINVAL, "Error: invalid value for nadv");
+  const bool one_pass = k.nadv == 2 && P.nitera == 1;
+  const bool pairs = one_pass && !SW(c, ADVT2_SINGLE) && !SW(c, TR_NOPAIR);
+  const int rt = k.nadv == 2;                                 // advt2's round trip of trb rides in k_tr_update
+  // 1. the advection
+  for (int n = 0; n < ntr;) {
+    pomgpu_ctx::pomgpu_tracer &a = c->trc[n];
+    if (pairs && n + 1 < ntr) {
+      pomgpu_ctx::pomgpu_tracer &b = c->trc[n + 1];
+      launch_advt2x2_col(c, a.trb, a.tr, a.clim, a.trf, b.trb, b.tr, b.clim, b.trf);
+      if (!lib_x) { xch(c, 1, a.trf, P.kbm1); xch(c, 1, b.trf, P.kbm1); }   // solver.f:728
+      launch_copy_kb(c, a.trb, b.trb);                        // :618
+      n += 2;
+      continue;
+    }
+    if (k.nadv == 1) seq_advt1(c, a.trb, a.tr, a.clim, a.trf);
+    else if (one_pass) {
+      launch_advt2_rows(c, a.trb, a.tr, a.clim, a.trf);       // (HEA, HFA: mode_internal's launch_coef_eta)
+      if (!lib_x) xch(c, 1, a.trf, P.kbm1);                   // :728
+      launch_copy_kb(c, a.trb);                               // :618
+    } else seq_advt2(c, a.trb, a.tr, a.clim, a.trf, true);
+    n += 1;
+  }
+  // 2. source and decay
+  for (int n = 0; n < ntr; n++) {
+    const pomgpu_ctx::pomgpu_tracer &a = c->trc[n];
+    if (a.q || a.lam != 0.) launch_tr_source(c, a.trf, a.trb, rt ? a.clim : NULL, a.q, a.lam);
+  }
+  // 3. advance.f:436
+  {
+    double *ptr[POMGPU_TRMAX];
+    int nz[POMGPU_TRMAX];
+    for (int n = 0; n < ntr; n++) { ptr[n] = c->trc[n].trf; nz[n] = P.kbm1; }
+    xchv(c, ptr, nz, ntr);
+  }
+  side_wait(c, SIDE_RQ);                                      // proft's ghost columns need kh of the ghost lines
+  // 4. - 6. proft, bcond(4), the filter and rotation
+  for (int n = 0; n < ntr;) {
+    const pomgpu_ctx::pomgpu_tracer &a = c->trc[n];
+    const int nf = (pairs && n + 1 < ntr) ? 2 : 1;
+    const pomgpu_ctx::pomgpu_tracer &b = c->trc[n + nf - 1];
+    if (nf == 1 || !launch_proft2(c, a.trf, a.wsurf, a.surf, a.nbc, b.trf, b.wsurf, b.surf, b.nbc)) {
+      launch_proft(c, a.trf, a.wsurf, a.surf, a.nbc);
+      if (nf == 2) launch_proft(c, b.trf, b.wsurf, b.surf, b.nbc);
+    }
+    const TrEdge e[2] = {{a.trf, a.tr, a.bd[0], a.bd[1], a.bd[2], a.bd[3]}, {b.trf, b.tr, b.bd[0], b.bd[1], b.bd[2], b.bd[3]}};
+    launch_tr_edges(c, e, nf);
+    const TrUpd u[2] = {{a.trf, a.clim, a.tr, a.trb}, {b.trf, b.clim, b.tr, b.trb}};
+    launch_tr_update(c, u, nf, rt);
+    n += nf;
+  }
+  return POMGPU_OK;
+}
 static int wr_on_side(pomgpu_ctx *c, int with_kernel) {
   const KP &P = c->P;
   side_wait(c, SIDE_WR);                                      // at most one piece of side work outstanding per event
@@ -1841,6 +1916,10 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
         const int rct = rim_round(c, SIDE_RTS, at, nt, 5);
         if (rct) return rct;
       }
+    }
+    if (c->ntr) {                                             // the passive tracers: behind :454, in front of :459, mode 3 and mode 4 alike
+      const int rct = tracer_stage(c, lib_x);
+      if (rct) return rct;
     }
     side_wait(c, SIDE_RQ);                                    // profu / profv average km with the neighbour line's
     const bool fuse = uv_fused(c);                            // :461-462 and the interior of :469-514 in one kernel (one tile)
@@ -2169,6 +2248,132 @@ extern "C" int pomgpu_set_mean_output(pomgpu_ctx *c, int on) {
   HIPCHK(c, hipMemsetAsync(c->mean_acc, 0, cur * sizeof(double), c->stream));   // +0.0 everywhere, behind whatever still accumulates
   return POMGPU_OK;
 }
+// ---- passive tracers: the state (include/pomgpu.h; the stage: tracer_stage above) ---------------------------------------------------------
+static void tracers_free(pomgpu_ctx *c) {
+  for (int n = 0; n < POMGPU_TRMAX; n++) {
+    pomgpu_ctx::pomgpu_tracer &t = c->trc[n];
+    (void)hipFree(t.trb); (void)hipFree(t.tr); (void)hipFree(t.trf); (void)hipFree(t.q); (void)hipFree(t.wsurf); (void)hipFree(t.surf);
+    if (t.clim != c->tr_zero3) (void)hipFree(t.clim);
+    for (int d = 0; d < 4; d++) (void)hipFree(t.bd[d]);
+    memset(&t, 0, sizeof t);
+  }
+  (void)hipFree(c->tr_zero3);
+  c->tr_zero3 = NULL;
+  c->ntr = 0;
+}
+// doubles of array `which` of a tracer (enum pomgpu_tracer_array), 0 = no such array
+static size_t tracer_len(const pomgpu_ctx *c, int which) {
+  const KP &P = c->P;
+  switch (which) {
+    case POMGPU_TR_TRB: case POMGPU_TR_TR: case POMGPU_TR_CLIM: case POMGPU_TR_SOURCE: return P.n3;
+    case POMGPU_TR_WSURF: case POMGPU_TR_SURF: return P.n2;
+    case POMGPU_TR_BE: case POMGPU_TR_BW: return (size_t)P.kb * P.jml;
+    case POMGPU_TR_BN: case POMGPU_TR_BS: return (size_t)P.kb * P.iml;
+    default: return 0;
+  }
+}
+static double **tracer_slot(pomgpu_ctx *c, int n, int which) {
+  pomgpu_ctx::pomgpu_tracer &t = c->trc[n - 1];
+  switch (which) {
+    case POMGPU_TR_TRB: return &t.trb;
+    case POMGPU_TR_TR: return &t.tr;
+    case POMGPU_TR_CLIM: return &t.clim;
+    case POMGPU_TR_SOURCE: return &t.q;
+    case POMGPU_TR_WSURF: return &t.wsurf;
+    case POMGPU_TR_SURF: return &t.surf;
+    case POMGPU_TR_BE: return &t.bd[0];
+    case POMGPU_TR_BW: return &t.bd[1];
+    case POMGPU_TR_BN: return &t.bd[2];
+    default: return &t.bd[3];
+  }
+}
+static int tracer_zeros(pomgpu_ctx *c, double **p, size_t n) {
+  if (!*p && hipMalloc((void **)p, n * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    *p = NULL;
+    return fail(c, POMGPU_ENOMEM, "set_tracers: no memory for a tracer array (%zu MB)", n * sizeof(double) >> 20);
+  }
+  HIPCHK(c, hipMemsetAsync(*p, 0, n * sizeof(double), c->stream));
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_tracer_count(pomgpu_ctx *c) { return c ? c->ntr : 0; }
+extern "C" int pomgpu_set_tracers(pomgpu_ctx *c, int n) {
+  if (c) { F32_REFUSE(c, "set_tracers"); }
+  NEED_RAW(c);
+  if (c->flags & POMGPU_CTX_2D) return fail(c, POMGPU_EINVAL, "set_tracers: a context with 3-D arrays");
+  if (n < 0 || n > POMGPU_MAXTRACERS) return fail(c, POMGPU_EINVAL, "set_tracers: %d tracers asked for, 0..%d are possible", n, POMGPU_MAXTRACERS);
+  if (c->ntr) HIPCHK(c, hipStreamSynchronize(c->stream));     // arrays are about to be freed: behind the steps that still use them
+  if (n != c->ntr) tracers_free(c);                           // another number: the arrays go
+  if (!n) return POMGPU_OK;
+  int rc;
+  if ((rc = tracer_zeros(c, &c->tr_zero3, c->P.n3))) { tracers_free(c); return rc; }
+  for (int t = 1; t <= n; t++) {
+    pomgpu_ctx::pomgpu_tracer &T = c->trc[t - 1];
+    if (T.clim && T.clim != c->tr_zero3) (void)hipFree(T.clim);   // a kept allocation: an own clim or q goes back to the default
+    (void)hipFree(T.q);
+    T.clim = c->tr_zero3; T.q = NULL; T.nbc = 1; T.lam = 0.;
+    static const int own[] = {POMGPU_TR_TRB, POMGPU_TR_TR, POMGPU_TR_WSURF, POMGPU_TR_SURF, POMGPU_TR_BE, POMGPU_TR_BW, POMGPU_TR_BN, POMGPU_TR_BS};
+    for (int q = 0; q < 8; q++)
+      if ((rc = tracer_zeros(c, tracer_slot(c, t, own[q]), tracer_len(c, own[q])))) { tracers_free(c); return rc; }
+    if ((rc = tracer_zeros(c, &T.trf, c->P.n3))) { tracers_free(c); return rc; }
+  }
+  c->ntr = n;
+  return POMGPU_OK;
+}
+static int tracer_args(pomgpu_ctx *c, const char *what, int n, int which, bool has_which = true) {
+  if (!c->ntr) return fail(c, POMGPU_EINVAL, "%s: no tracers are registered (pomgpu_set_tracers)", what);
+  if (n < 1 || n > c->ntr) return fail(c, POMGPU_EINVAL, "%s: tracer %d, 1..%d are registered", what, n, c->ntr);
+  if (has_which && !tracer_len(c, which)) return fail(c, POMGPU_EINVAL, "%s: %d names no tracer array (enum pomgpu_tracer_array)", what, which);
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_tracer_set(pomgpu_ctx *c, int n, int nbc, double lam) {
+  if (c) { F32_REFUSE(c, "tracer_set"); }
+  NEED_RAW(c);
+  int rc = tracer_args(c, "tracer_set", n, 0, false);
+  if (rc) return rc;
+  if (nbc != 1 && nbc != 3)
+    return fail(c, POMGPU_EINVAL, "tracer_set: nbc = %d; a tracer takes 1 (the flux wtrsurf) or 3 (the value trsurf), the short-wave forms 2 and 4 are T's", nbc);
+  c->trc[n - 1].nbc = nbc; c->trc[n - 1].lam = lam;
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_tracer_upload(pomgpu_ctx *c, int n, int which, const double *host) {
+  if (c) { F32_REFUSE(c, "tracer_upload"); }
+  NEED_RAW(c);
+  int rc = tracer_args(c, "tracer_upload", n, which);
+  if (rc) return rc;
+  double **slot = tracer_slot(c, n, which);
+  const size_t len = tracer_len(c, which);
+  const bool opt = which == POMGPU_TR_CLIM || which == POMGPU_TR_SOURCE;
+  if (!host && !opt) return fail(c, POMGPU_EINVAL, "tracer_upload: no host array");
+  if (opt) {                                                  // own array on first upload; NULL: back to the default
+    double *def = which == POMGPU_TR_CLIM ? c->tr_zero3 : NULL;
+    if (!host) {
+      if (*slot != def) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(*slot); *slot = def; }
+      return POMGPU_OK;
+    }
+    if (*slot == def) {
+      double *p = NULL;
+      if (hipMalloc((void **)&p, len * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return fail(c, POMGPU_ENOMEM, "tracer_upload: no memory for the array (%zu MB)", len * sizeof(double) >> 20); }
+      *slot = p;
+    }
+  }
+  HIPCHK(c, hipMemcpyAsync(*slot, host, len * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));                 // the host array is the caller's again
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_tracer_download(pomgpu_ctx *c, int n, int which, double *host) {
+  if (c) { F32_REFUSE(c, "tracer_download"); }
+  NEED_RAW(c);
+  int rc = tracer_args(c, "tracer_download", n, which);
+  if (rc) return rc;
+  if (!host) return fail(c, POMGPU_EINVAL, "tracer_download: no host array");
+  const double *src = *tracer_slot(c, n, which);
+  const size_t len = tracer_len(c, which);
+  if (!src) { memset(host, 0, len * sizeof(double)); return POMGPU_OK; }   // no source array: zeros
+  HIPCHK(c, hipMemcpyAsync(host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return POMGPU_OK;
+}
 static int advance(pomgpu_ctx *c, int more_steps_follow);
 extern "C" int pomgpu_advance(pomgpu_ctx *c) { return advance(c, 0); }
 static int advance(pomgpu_ctx *c, int more_steps_follow) {    // advance.f:6-59
@@ -2285,6 +2490,8 @@ extern "C" int pomgpu_tune_placement(pomgpu_ctx *c, int steps, int max_try, doub
   if (kept) *kept = 0;
   if (c->mean_acc)                                            // the trial steps are real steps: they would be accumulated
     return fail(c, POMGPU_EINVAL, "tune_placement: the time-mean output is on and the trial steps would count -- tune first, switch the mean on afterwards");
+  if (c->ntr)                                                 // ... and would move the tracers
+    return fail(c, POMGPU_EINVAL, "tune_placement: passive tracers are registered and the trial steps would move them -- tune first, register tracers afterwards");
 #ifdef POMGPU_EMU
   (void)steps; (void)max_try; (void)ms_out; (void)front_mib_out; (void)pad_mib_out;
   return POMGPU_OK;

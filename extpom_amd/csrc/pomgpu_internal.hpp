@@ -20,6 +20,7 @@
 #define POMGPU_NSCR2 8     // 2-D scratch arrays
 #define POMGPU_NCOEF2 25   // derived 2-D coefficient arrays
 #define POMGPU_MAXREC 8
+#define POMGPU_TRMAX 8     // passive tracers per context (POMGPU_MAXTRACERS, include/pomgpu.h)
 #define POMGPU_KBMAX 128   // per-column private arrays in the tridiagonal kernels
 #define POMGPU_CTX_2D 1
 // bits of the device error word (pomgpu_ctx::d_err)
@@ -580,7 +581,7 @@ static inline dim3 grid2_halo(const KP &P) { return dim3((P.iml + 61) / 62, (P.j
   X(PROFQ_NOPACE) X(COL_STRIP) X(BAND_BYTES) X(PAD3) X(IO_SYNC) X(ADVCT_SPLIT) X(ADVQ_EXCHANGE) X(PROD_FULL) X(QFILTER_SPLIT) \
   X(NO_OVERLAP) X(NO_SIDE_COMM) X(WR_MAIN) X(WIDE_W) X(WIDE_FULL) X(DEBUG_ALLOC) X(TEST_SPLIT_FAIL_RANK)  \
   X(WR_NODEFER) X(EXT_RING_FIRST) X(TUNE_FORCE) X(RIM_MAIN) X(RIM_RESULTS_MAIN) X(SUM2D_OFF) X(ADVCT_ROWS4) X(ADVCT_ROWS8) \
-  X(IO_CHUNK_KB) X(UV_NOFUSE) X(W_NOFUSE) X(UVMEAN_PASS) X(PROFT_TWIN) X(LD_EAGER)
+  X(IO_CHUNK_KB) X(UV_NOFUSE) X(W_NOFUSE) X(UVMEAN_PASS) X(PROFT_TWIN) X(LD_EAGER) X(TR_NOPAIR)
 enum pomgpu_sw {
 #define POMGPU_SW_(name) SW_##name,
   POMGPU_SWITCHES(POMGPU_SW_)
@@ -780,6 +781,12 @@ struct pomgpu_ctx {
   double *mean_acc;
   size_t mean_off[9];
   int mean_count;
+  // passive tracers (pomgpu_set_tracers, include/pomgpu.h): ntr of them, each with its own trb, tr, work array trf (level kb stays +0.0),
+  // surface and boundary arrays; clim / q are the tracer's own once uploaded, else tr_zero3 (one shared all-zero array) / NULL.
+  // bd: trbe, trbw (kb x jml), trbn, trbs (kb x iml).  mode_internal runs their stage between dens and advu (tracer_stage, pomgpu_api.hip)
+  int ntr;
+  struct pomgpu_tracer { double *trb, *tr, *trf, *clim, *q, *wsurf, *surf, *bd[4]; int nbc; double lam; } trc[POMGPU_TRMAX];
+  double *tr_zero3;
   char err[512];
 };
 // The register-resident column kernels (k_vert.hip: their level loops are unrolled for a template bound, with_kbt) serve this context's
@@ -919,6 +926,9 @@ void launch_advt2_diff(pomgpu_ctx *c, const double *fb, const double *fc, double
 void launch_ts_update(pomgpu_ctx *c, double fold, double fnew, int rt, int store_rst);   // uses c->tau_known / tau_val
 void launch_restore_fields(pomgpu_ctx *c, double fold, double fnew);
 void launch_mask_ts(pomgpu_ctx *c);
+// passive tracers: bcond(4)'s mask, the filter and the rotation for one field or a pair (rt: with advt2's deferred fb round trip)
+struct TrUpd { const double *ff, *fc; double *f, *fb; };
+void launch_tr_update(pomgpu_ctx *c, const TrUpd *u, int nf, int rt);
 void launch_mask_uv(pomgpu_ctx *c);
 void launch_mask_w(pomgpu_ctx *c);
 void launch_restore(pomgpu_ctx *c, double fold, double fnew);
@@ -944,12 +954,16 @@ void launch_uv_filter(pomgpu_ctx *c, int own = 0);   // own: the ghost lines are
 void launch_coef_static(pomgpu_ctx *c);
 void launch_coef_dt(pomgpu_ctx *c);
 void launch_coef_eta(pomgpu_ctx *c, int uvm = 0);   // uvm: C2_UCOR, C2_VCOR as well (mode_internal)
-void launch_advt2_rows(pomgpu_ctx *c, const double *fb, const double *f, const double *fc, double *ff);
+void launch_advt2_rows(pomgpu_ctx *c, const double *fb, const double *f, const double *fc, double *ff);   // KP::uvm: the UM form
 void launch_advq_col(pomgpu_ctx *c, const double *q, const double *qb, double *qf, int zero_else);
 // k_bc.hip
 void launch_bcond4_edges(pomgpu_ctx *c);
 void launch_bcond6_edges(pomgpu_ctx *c);
 void launch_bcondorl3(pomgpu_ctx *c);
+// passive tracers: bcond(4)'s lines for one field or a pair on explicit pointers (be, bw: kb x jml; bn, bs: kb x iml), and the pointwise source
+struct TrEdge { double *ff; const double *f, *be, *bw, *bn, *bs; };
+void launch_tr_edges(pomgpu_ctx *c, const TrEdge *e, int nf);
+void launch_tr_source(pomgpu_ctx *c, double *ff, const double *fb, const double *fc, const double *q, double lam);   // fc: fb's round trip applied on load
 int launch_halo_pack(pomgpu_ctx *c, double *const *dev, const int *nz, int count, int dir, double *to_lo, double *to_hi);
 int launch_halo_pack8(pomgpu_ctx *c, double *const *dev, const int *nz, int count, double *const *to);
 int launch_halo_unpack8(pomgpu_ctx *c, double *const *dev, const int *nz, int count, const double *const *from);

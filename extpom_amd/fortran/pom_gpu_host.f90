@@ -177,6 +177,46 @@ subroutine pom_surface_sss(on)
   if (pomgpu_set_surface_sss(pom_ctx, merge(1_c_int, 0_c_int, on)) /= 0) error_status = 1
 end subroutine
 
+! Passive tracers (no counterpart in the reference; include/pomgpu.h): pom_tracers(n) after pomgpu_upload_state -- and after
+! pomgpu_tune_placement, which refuses while tracers are registered -- gives the context n tracers, all zero; mode_internal then carries
+! them with the flow.  pom_tracer_put / pom_tracer_get move one array of tracer n (which: 0 trb 1 tr 2 clim 3 source 4 wsurf 5 surf
+! 6 be 7 bw 8 bn 9 bs, shaped like tb, wtsurf, tbe, tbn); pom_tracer_set: nbc 1 (the flux) or 3 (the surface value), the decay rate in 1/s.
+! Tracers are not in the output or restart files: a host checkpoints trb and tr through pom_tracer_get / pom_tracer_put.
+subroutine pom_tracers(n)
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  integer, intent(in) :: n
+  if (pomgpu_set_tracers(pom_ctx, int(n, c_int)) /= 0) error_status = 1
+end subroutine
+
+subroutine pom_tracer_put(n, which, a)
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  integer, intent(in) :: n, which
+  double precision, intent(in), target :: a(*)
+  if (pomgpu_tracer_upload(pom_ctx, int(n, c_int), int(which, c_int), c_loc(a)) /= 0) error_status = 1
+end subroutine
+
+subroutine pom_tracer_get(n, which, a)
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  integer, intent(in) :: n, which
+  double precision, intent(out), target :: a(*)
+  if (pomgpu_tracer_download(pom_ctx, int(n, c_int), int(which, c_int), c_loc(a)) /= 0) error_status = 1
+end subroutine
+
+subroutine pom_tracer_set(n, nbc, lam)
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  integer, intent(in) :: n, nbc
+  double precision, intent(in) :: lam
+  if (pomgpu_tracer_set(pom_ctx, int(n, c_int), int(nbc, c_int), real(lam, c_double)) /= 0) error_status = 1
+end subroutine
+
 subroutine mean_accumulate
   use pomgpu_iface
   implicit none

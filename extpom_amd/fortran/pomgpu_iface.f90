@@ -133,6 +133,22 @@ module pomgpu_iface
     integer(c_int) function pomgpu_mean_download(ctx, is3d, slot, host) bind(C, name='pomgpu_mean_download')
       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: is3d, slot
     end function
+    ! passive tracers (include/pomgpu.h): which = enum pomgpu_tracer_array, 0 trb 1 tr 2 clim 3 source 4 wsurf 5 surf 6 be 7 bw 8 bn 9 bs
+    integer(c_int) function pomgpu_set_tracers(ctx, n) bind(C, name='pomgpu_set_tracers')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: n
+    end function
+    integer(c_int) function pomgpu_tracer_count(ctx) bind(C, name='pomgpu_tracer_count')
+      import; type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function pomgpu_tracer_upload(ctx, n, which, host) bind(C, name='pomgpu_tracer_upload')
+      import; type(c_ptr), value :: ctx, host; integer(c_int), value :: n, which
+    end function
+    integer(c_int) function pomgpu_tracer_download(ctx, n, which, host) bind(C, name='pomgpu_tracer_download')
+      import; type(c_ptr), value :: ctx, host; integer(c_int), value :: n, which
+    end function
+    integer(c_int) function pomgpu_tracer_set(ctx, n, nbc, lam) bind(C, name='pomgpu_tracer_set')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: n, nbc; real(c_double), value :: lam
+    end function
     integer(c_int) function pomgpu_write_restart(ctx, path, meta) bind(C, name='pomgpu_write_restart')
       import; type(c_ptr), value :: ctx, path; type(pomgpu_file_meta) :: meta
     end function

@@ -108,6 +108,11 @@ _SIGS = {
     "pomgpu_mean_accumulate": (_I, [_P]),
     "pomgpu_mean_count": (_I, [_P]),
     "pomgpu_mean_download": (_I, [_P, _I, _I, _P]),
+    "pomgpu_set_tracers": (_I, [_P, _I]),
+    "pomgpu_tracer_count": (_I, [_P]),
+    "pomgpu_tracer_upload": (_I, [_P, _I, _I, _P]),
+    "pomgpu_tracer_download": (_I, [_P, _I, _I, _P]),
+    "pomgpu_tracer_set": (_I, [_P, _I, _I, ctypes.c_double]),
     "pomgpu_write_restart": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
     "pomgpu_read_restart": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "pomgpu_set_forcing_files": (_I, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),

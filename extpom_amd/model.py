@@ -297,6 +297,48 @@ class PomGpu:
         self._chk(self.L.pomgpu_mean_download(self.h, 1 if is3d else 0, P3[name] if is3d else P2[name], self._p(out)), "mean_download")
         return out
 
+    # ---- passive tracers (pomgpu.h "passive tracers") ------------------------------------------
+    TRACER_ARRAYS = {"trb": 0, "tr": 1, "clim": 2, "source": 3, "wsurf": 4, "surf": 5, "be": 6, "bw": 7, "bn": 8, "bs": 9}
+
+    def tracer_shape(self, name: str):
+        """shape of a tracer array on the host: trb tr clim source as tb, wsurf surf as wtsurf, be bw as tbe, bn bs as tbn"""
+        st = self.st
+        if name in ("trb", "tr", "clim", "source"):
+            return (st.kb, st.jm_local, st.im_local)
+        if name in ("wsurf", "surf"):
+            return (st.jm_local, st.im_local)
+        if name in ("be", "bw"):
+            return (st.kb, st.jm_local)
+        if name in ("bn", "bs"):
+            return (st.kb, st.im_local)
+        raise PomGpuError(f"tracer array {name!r}: one of {' '.join(self.TRACER_ARRAYS)}")
+
+    def set_tracers(self, n: int):
+        """pomgpu_set_tracers: n passive tracers (0..8), every array of theirs +0.0, nbc 1, no decay, no source; 0 frees them"""
+        self._chk(self.L.pomgpu_set_tracers(self.h, int(n)), "set_tracers")
+
+    def tracer_count(self) -> int:
+        return int(self.L.pomgpu_tracer_count(self.h))
+
+    def tracer_upload(self, n: int, name: str, a):
+        """array `name` (TRACER_ARRAYS) of tracer n (1-based); a=None returns clim / source to the default"""
+        if a is None:
+            self._chk(self.L.pomgpu_tracer_upload(self.h, int(n), self.TRACER_ARRAYS[name], None), "tracer_upload")
+            return
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != self.tracer_shape(name):
+            raise ValueError(f"tracer_upload: {name} is {a.shape}, not {self.tracer_shape(name)}")
+        self._chk(self.L.pomgpu_tracer_upload(self.h, int(n), self.TRACER_ARRAYS[name], self._p(a)), "tracer_upload")
+
+    def tracer_download(self, n: int, name: str):
+        out = np.empty(self.tracer_shape(name))
+        self._chk(self.L.pomgpu_tracer_download(self.h, int(n), self.TRACER_ARRAYS[name], self._p(out)), "tracer_download")
+        return out
+
+    def set_tracer(self, n: int, nbc: int = 1, decay: float = 0.0):
+        """pomgpu_tracer_set: surface condition 1 (the flux wsurf) or 3 (the value surf), and the decay rate in 1/s"""
+        self._chk(self.L.pomgpu_tracer_set(self.h, int(n), int(nbc), float(decay)), "tracer_set")
+
     def read_restart(self, path, im_global=None, jm_global=None):
         """read_restart_pnetcdf (io_pnetcdf.F:2420-2768) without PnetCDF: this tile's patch of the 37 restart fields from a classic
         NetCDF file straight into the device mirrors, d and dt formed from them, time0 = time = the file's time (and cont_bry, if it

@@ -541,6 +541,42 @@ int pomgpu_mean_count(pomgpu_ctx *ctx);
 int pomgpu_mean_download(pomgpu_ctx *ctx, int is3d, int slot, double *host);
 int pomgpu_write_output_mean(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta);
 
+/* ---- passive tracers (no counterpart in the reference; optional, off by default: with none registered every byte and every launch is as
+ * without them) ------------------------------------------------------------------------------------------------------------------------
+ * Up to POMGPU_MAXTRACERS fields that the flow carries and mixes as it does T and S -- dye, age, a first-order decaying constituent --
+ * and that never act on the flow: with tracers registered every other array keeps the bits it has without them.  The reference's users
+ * add such a field by repeating the advt / proft / bcond(4) / filter lines of mode_internal for it; that is what the library does, per
+ * tracer n = 1..ntr, inside pomgpu_mode_internal whenever the 3-D body runs (advance.f:362; mode 3 and mode 4), behind advance.f:454 and
+ * in front of :459, with the run's own nadv nitera tprni smoth umol dti2 and the u v w aam kh etb etf of that moment:
+ *   1. advt1 / advt2(trb, tr, trclim, trf) as for T, level kb of trb (tr) and the fb - fclim + fclim round trip included;
+ *   2. only with a source array or lam != 0: trf = trf + dti2 * (q - lam * trb) on (1:im, 1:jm, 1:kbm1), four separate fp64 operations;
+ *   3. the exchange of advance.f:436;   4. proft(trf, wtrsurf, trsurf, nbc);
+ *   5. bcond(4)'s lines for T with trf, tr, trb[ewns] in place of uf, t, tb[ewns], and its mask on levels 1..kbm1;
+ *   6. tr = tr + .5*smoth*(trf + trb - 2.*tr); trb = tr; tr = trf on the whole arrays.  No restore_interior, no dens.
+ * The work array trf is the library's own; its level kb is +0.0.  Tracers are not in the output, restart or mean files (their schemas are
+ * the reference's): a host checkpoints through pomgpu_tracer_download and _upload of TRB and TR.  pomgpu_upload, pomgpu_cold_start and
+ * pomgpu_read_restart do not touch them.
+ * pomgpu_set_tracers: n > 0 allocates n tracers (or keeps the allocation of a context that has n already) and sets every array of theirs
+ * to +0.0, nbc to 1, lam to 0, no source; n == 0 frees them.  POMGPU_EINVAL: n outside 0..POMGPU_MAXTRACERS, the fp32-storage variants, a
+ * 2-D-only context.
+ * pomgpu_tracer_upload / _download: array `which` of tracer n (1-based), HOST doubles in the shape of the array it stands for: TRB TR
+ * CLIM SOURCE as tb (n3 doubles), WSURF SURF as wtsurf (n2), BE BW as tbe (jm_local x kb), BN BS as tbn (im_local x kb).  Uploading CLIM or
+ * SOURCE gives the tracer an array of its own; a NULL host for either returns it to the default (the shared zero array / no source), and
+ * downloading a default delivers zeros.  POMGPU_EINVAL: no tracers registered, n outside 1..ntr, an unknown `which`, a NULL host otherwise.
+ * pomgpu_tracer_set: the surface condition (1: the flux wtrsurf, 3: the value trsurf; 2 and 4, the short-wave forms, are refused) and the
+ * decay rate lam (1/s).  pomgpu_tracer_count: the number registered.
+ * pomgpu_tune_placement refuses while tracers are registered -- its trial steps are real steps and would move them. */
+#define POMGPU_MAXTRACERS 8
+enum pomgpu_tracer_array {
+  POMGPU_TR_TRB = 0, POMGPU_TR_TR = 1, POMGPU_TR_CLIM = 2, POMGPU_TR_SOURCE = 3, POMGPU_TR_WSURF = 4, POMGPU_TR_SURF = 5,
+  POMGPU_TR_BE = 6, POMGPU_TR_BW = 7, POMGPU_TR_BN = 8, POMGPU_TR_BS = 9
+};
+int pomgpu_set_tracers(pomgpu_ctx *ctx, int n);
+int pomgpu_tracer_count(pomgpu_ctx *ctx);
+int pomgpu_tracer_upload(pomgpu_ctx *ctx, int n, int which, const double *host);
+int pomgpu_tracer_download(pomgpu_ctx *ctx, int n, int which, double *host);
+int pomgpu_tracer_set(pomgpu_ctx *ctx, int n, int nbc, double lam);
+
 /* ---- the hot path: kernels (solver.f, bounds_forcing.f), device-resident ---------------- */
 int pomgpu_advave(pomgpu_ctx *ctx);              /* solver.f:6-198   */
 int pomgpu_advct(pomgpu_ctx *ctx);               /* solver.f:201-408 */
