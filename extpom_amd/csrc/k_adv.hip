@@ -445,15 +445,18 @@ __device__ __forceinline__ double dens_point(const KP &P, double si, double ti, 
 // TAU: 1 = taurstrb, taurstrf hold the values tau_b, tau_f everywhere (pomgpu_ctx::tau_known): not read
 //      2 (k_ts_update_same) = a rate field whose two arrays hold the same bits wherever this kernel looks (pomgpu_ctx::tau_same, the steady sponge): taurstrf
 //          alone is read and stands for both.  The arithmetic stays fold*x + fnew*x: that is not x.
-template <int TAU> __device__ __forceinline__ void c_ts_update(const KP &P, const int i, const int j, const int k, double fold, double fnew, int rt, int store_rst, double tau_b, double tau_f);
-template <int TAU> __global__ void k_ts_update(KP P, double fold, double fnew, int rt, int store_rst, double tau_b, double tau_f) {
-  MARCH3(c_ts_update<TAU>(P, i, j, k, fold, fnew, rt, store_rst, tau_b, tau_f))
+// rtf (with rt; NULL = not valid): the words k_advt2_col<2, *, true> left in this same mode_internal (RT_WORD, pomgpu_internal.hpp) -- tclim, sclim are
+// loaded and the round trip applied only where the cell's bit is set, and at level kb, which has no word (copy_kb leaves values there
+// that the advection never held); elsewhere tb, sb are used as loaded, which is what the round trip would have given
+template <int TAU> __device__ __forceinline__ void c_ts_update(const KP &P, const int i, const int j, const int k, double fold, double fnew, int rt, int store_rst, double tau_b, double tau_f, const unsigned long long *rtf);
+template <int TAU> __global__ void k_ts_update(KP P, double fold, double fnew, int rt, int store_rst, double tau_b, double tau_f, const unsigned long long *rtf) {
+  MARCH3(c_ts_update<TAU>(P, i, j, k, fold, fnew, rt, store_rst, tau_b, tau_f, rtf))
 }
 // TAU = 2 under a kernel name of its own: profiles and ISA listings tell it from the two forms above by name
-__global__ void k_ts_update_same(KP P, double fold, double fnew, int rt, int store_rst) {
-  MARCH3(c_ts_update<2>(P, i, j, k, fold, fnew, rt, store_rst, 0., 0.))
+__global__ void k_ts_update_same(KP P, double fold, double fnew, int rt, int store_rst, const unsigned long long *rtf) {
+  MARCH3(c_ts_update<2>(P, i, j, k, fold, fnew, rt, store_rst, 0., 0., rtf))
 }
-template <int TAU> __device__ __forceinline__ void c_ts_update(const KP &P, const int i, const int j, const int k, double fold, double fnew, int rt, int store_rst, double tau_b, double tau_f) {
+template <int TAU> __device__ __forceinline__ void c_ts_update(const KP &P, const int i, const int j, const int k, double fold, double fnew, int rt, int store_rst, double tau_b, double tau_f, const unsigned long long *rtf) {
   // pomgpu_ct: fp32 in the fp32-arithmetic variant (pomgpu_internal.hpp) -- all but dens, which takes the widened t, s
   const bool act = (i <= P.im && j <= P.jm), lev = (k <= P.kbm1);
   const pomgpu_ct m = F2(fsm, i, j);
@@ -463,7 +466,9 @@ template <int TAU> __device__ __forceinline__ void c_ts_update(const KP &P, cons
     vf = vf * m;                                                       // filter; advu/advv rewrite both arrays next (advance.f:459-460)
   }
   pomgpu_ct tb = F3(tb, i, j, k), sb = F3(sb, i, j, k);
-  if (rt) {                                                            // fb = fb-fclim ... fb = fb+fclim
+  bool rtc = rt != 0;
+  if (rtc && rtf && lev) rtc = ((rtf[RT_WORD(P, i, j, k)] >> RT_BIT(i)) & 1ull) != 0;   // (rt, rtf, lev: the same for the whole wavefront)
+  if (rtc) {                                                           // fb = fb-fclim ... fb = fb+fclim
     const pomgpu_ct tc = F3(tclim, i, j, k), sc = F3(sclim, i, j, k);
     tb = (tb - tc) + tc;
     sb = (sb - sc) + sc;
@@ -992,13 +997,20 @@ void launch_mask3(pomgpu_ctx *c, double *a, const double *m2) { LAUNCH(c, k_mask
 void launch_smol(pomgpu_ctx *c, const double *ff) { LAUNCH(c, k_smol, gridm(c->P), blk2(), c->P, ff); }
 void launch_copy3(pomgpu_ctx *c, double *dst, const double *src) { LAUNCH(c, k_copy3, gridm(c->P), blk2(), c->P, dst, src); }
 void launch_advt2_diff(pomgpu_ctx *c, const double *fb, const double *fc, double *ff) { LAUNCH(c, k_advt2_diff, gridm(c->P), blk2(), c->P, fb, fc, ff); }
-void launch_ts_update(pomgpu_ctx *c, double fold, double fnew, int rt, int store_rst) {
+// rt_flags: the words of this step's launch_advt2x2_col are valid (pomgpu_api.hip decides); ts_rt_flags of the event profile counts the
+// launches that read them, a count without events as profq_ld_store
+void launch_ts_update(pomgpu_ctx *c, double fold, double fnew, int rt, int store_rst, int rt_flags) {
+  const unsigned long long *rtf = (rt && rt_flags) ? c->rt_words : NULL;
+  if (rtf && c->prof_on) {
+    const int s = pomgpu_prof_slot(c, "ts_rt_flags");
+    if (s >= 0) (c->parent ? c->parent : c)->prof[s].launches++;
+  }
   if (c->tau_known[0] && c->tau_known[1] && !c->tau_handed && !SW(c, TAU_ARRAYS))
-    LAUNCHN(c, "k_ts_update", (k_ts_update<1>), gridm(c->P), blk2(), c->P, fold, fnew, rt, store_rst, c->tau_val[0], c->tau_val[1]);
+    LAUNCHN(c, "k_ts_update", (k_ts_update<1>), gridm(c->P), blk2(), c->P, fold, fnew, rt, store_rst, c->tau_val[0], c->tau_val[1], rtf);
   else if (c->tau_same && !c->tau_handed && !SW(c, TAU_ARRAYS))
-    LAUNCH(c, k_ts_update_same, gridm(c->P), blk2(), c->P, fold, fnew, rt, store_rst);
+    LAUNCH(c, k_ts_update_same, gridm(c->P), blk2(), c->P, fold, fnew, rt, store_rst, rtf);
   else
-    LAUNCHN(c, "k_ts_update", (k_ts_update<0>), gridm(c->P), blk2(), c->P, fold, fnew, rt, store_rst, 0., 0.);
+    LAUNCHN(c, "k_ts_update", (k_ts_update<0>), gridm(c->P), blk2(), c->P, fold, fnew, rt, store_rst, 0., 0., rtf);
 }
 void launch_restore_fields(pomgpu_ctx *c, double fold, double fnew) { LAUNCH(c, k_restore_fields, gridm(c->P), blk2(), c->P, fold, fnew); }
 void launch_mask_ts(pomgpu_ctx *c) { LAUNCH(c, k_mask_ts, gridm(c->P), blk2(), c->P); }

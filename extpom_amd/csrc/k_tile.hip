@@ -86,7 +86,8 @@ struct FaceT { pomgpu_ct adv, dif; };
 // in x/y (was 4) and 1 in z (was 2).
 // NF = 2 advances T and S in ONE pass (advance.f:431-432 calls advt2 twice): u, v, w, aam and the face
 // coefficients are read once for both fields.
-struct TFields { const double *fb[2], *f[2], *fcl[2]; double *ff[2]; };
+// rtf (RTF launches alone, the last member: the others keep their place in the kernel's arguments): see k_advt2_col
+struct TFields { const double *fb[2], *f[2], *fcl[2]; double *ff[2]; unsigned long long *rtf; };
 // Operands of a level.  Shared with the rows above and below through the workgroup's LDS slab (RowShare,
 // pomgpu_internal.hpp), in this order: fb[0..NF-1], fclim[0..NF-1], aam, v; this row only: u, w.
 // c: the wavefront's own row, h: its share of the two rows outside the workgroup.
@@ -122,7 +123,14 @@ __device__ __forceinline__ FaceT advt2_face(const pomgpu_ct tprni, const CoefT &
 // UM: u, v in memory still lack the depth-mean correction of advance.f:365-393 (KP::uvm, uvm_fix in pomgpu_internal.hpp): applied to
 // u of the own column and to v before it enters the slab -- the own row's with the lane's coefficients, the share of a row outside the
 // workgroup with that row's; the east face travels through the lane shift as before.  Every level this kernel loads is <= kbm1.
-template <int NF, bool UM = false>
+// RTF (the T / S launch of mode_internal alone, launch_advt2x2_col): where does fb's in-place round trip through fb - fclim
+// (solver.f:691,715), which k_ts_update applies to what it loads, change a bit?  The lane that owns a column holds both operands of
+// every level 1..kbm1 and forms fb - fclim anyway: (fb - fclim) + fclim is compared with fb bit for bit, the wavefront's 64 answers
+// (T's or S's) are one lane mask, and lane 0 stores that word to A.rtf -- one per (level, row, 62-column block), bit = lane,
+// RT_WORD below.  k_ts_update reads tclim, sclim only where a bit is set (by Sterbenz's lemma fb - fclim is exact for fclim/2 <= fb <=
+// 2 fclim: a field next to its climatology sets none).  The store follows the loop's discipline: every lane, every iteration, the
+// offset selected.  The emulated build, one lane at a time, ORs its bit into the word its block's first owned lane has started.
+template <int NF, bool UM = false, bool RTF = false>
 __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
   constexpr int NS = 2 * NF + 2, NH = ROWSHARE_SLOTS(NS), AM = 2 * NF, VV = 2 * NF + 1;
   HALO_XCD_DECODE_R(LDS_ROWS)                                           // a workgroup outside the grid leaves as a whole
@@ -159,6 +167,9 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
   for (int q = 0; q < NH; q++) mh[q] = UM ? rowshare_uvm<1, NS, LDS_ROWS>(P, S, q, VV, j0w, i) : uvm_none();
   const unsigned oc = BOFF2(i, jc), lvb = LVB;
   const unsigned ost = in ? oc : BOFF_NONE;
+  const int rt_nbx = RT_NBX(P);
+  const BufA brtf = buf2_of((const double *)A.rtf, RTF ? (size_t)P.kbm1 * P.jml * rt_nbx : 0);
+  const unsigned ortf = (RTF && jrow && lane == 0) ? (unsigned)((jc - 1) * rt_nbx + (i0 - lane) / 62) * 8u : BOFF_NONE, lvrtf = (unsigned)(P.jml * rt_nbx) * 8u;
 #ifndef POMGPU_EMU
   __shared__ pomgpu_ct slab[2][NS][ROWSHARE_ROWS][64];
 #else
@@ -205,6 +216,21 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
     const pomgpu_ct am_w = halo_w(am_c, [&] { return F3(aam, iw, jc, L); });
     InvDc dzk; dzk.b = dzk.y = 0.;
     if (L >= 2) { dzk.b = F1(dz, L - 1); dzk.y = R1(dz, L - 1); }
+    if constexpr (RTF) {                                    // cur holds level min(L, kbm1); padding and halo lanes answer 0
+      bool ch = false;
+#pragma unroll
+      for (int f = 0; f < NF; f++) ch = ch || rt_changes(cur.c[f], cur.c[NF + f]);
+      const unsigned lvw = (unsigned)WAVE_UNIFORM(L - 1) * lvrtf;
+#ifndef POMGPU_EMU
+      bst2u(brtf, L <= kbm1 ? ortf : BOFF_NONE, lvw, __ballot(icol && ch));
+#else
+      if (L <= kbm1) {
+        unsigned long long &wd = A.rtf[RT_WORD(P, i, jc, L)];
+        wd = (lane == 1 ? 0ull : wd) | ((unsigned long long)ch << lane);
+      }
+      (void)brtf; (void)ortf; (void)lvw;
+#endif
+    }
 #pragma unroll
     for (int f = 0; f < NF; f++) {
       const pomgpu_ct fb_c = cur.c[f], fc_c = cur.c[NF + f];
@@ -974,16 +1000,24 @@ void launch_advuv_col(pomgpu_ctx *c) {
 }
 void launch_advt2_rows(pomgpu_ctx *c, const double *fb, const double *f, const double *fc, double *ff) {
   {
-    TFields A; A.fb[0] = A.fb[1] = fb; A.f[0] = A.f[1] = f; A.fcl[0] = A.fcl[1] = fc; A.ff[0] = A.ff[1] = ff;
+    TFields A; A.fb[0] = A.fb[1] = fb; A.f[0] = A.f[1] = f; A.fcl[0] = A.fcl[1] = fc; A.ff[0] = A.ff[1] = ff; A.rtf = NULL;
 #if POMGPU_UVM_ONLOAD   // an odd passive tracer on one tile: u, v still lack the depth-mean correction (the T / S pair never comes here with KP::uvm up)
     if (c->P.uvm) { LAUNCHN(c, "k_advt2_col", (k_advt2_col<1, true>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A); return; }
 #endif
     LAUNCHN(c, "k_advt2_col", (k_advt2_col<1>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A);
   }
 }
+// rtf (the T / S pair of mode_internal on one tile; NULL: passive tracers, tiles): where the round trip of tb, sb changes bits (RTF)
 void launch_advt2x2_col(pomgpu_ctx *c, const double *tb, const double *t, const double *tc, double *tf, const double *sb, const double *s_,
-                        const double *sc, double *sf) {
-  TFields A; A.fb[0] = tb; A.f[0] = t; A.fcl[0] = tc; A.ff[0] = tf; A.fb[1] = sb; A.f[1] = s_; A.fcl[1] = sc; A.ff[1] = sf;
+                        const double *sc, double *sf, unsigned long long *rtf) {
+  TFields A; A.fb[0] = tb; A.f[0] = t; A.fcl[0] = tc; A.ff[0] = tf; A.fb[1] = sb; A.f[1] = s_; A.fcl[1] = sc; A.ff[1] = sf; A.rtf = rtf;
+  if (rtf) {
+#if POMGPU_UVM_ONLOAD
+    if (c->P.uvm) { LAUNCHN(c, "k_advt2x2_col", (k_advt2_col<2, true, true>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A); return; }
+#endif
+    LAUNCHN(c, "k_advt2x2_col", (k_advt2_col<2, false, true>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A);
+    return;
+  }
 #if POMGPU_UVM_ONLOAD
   if (c->P.uvm) { LAUNCHN(c, "k_advt2x2_col", (k_advt2_col<2, true>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A); return; }
 #endif

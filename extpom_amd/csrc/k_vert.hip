@@ -95,7 +95,10 @@ __global__ void k_baropg(KP P, int sum2d) {
 #define BPG_ROWS 16                                         /* kbench, one context: 2 rows 1.40, 4 1.30, 8 1.24, 16 1.15 ms; one thread per column (k_baropg) 1.32 */
 #endif
 static_assert(COL_WX == 1, "k_baropg_rs / k_vertvl_rs take threadIdx.y as the row inside the workgroup: one wavefront per workgroup row");
-__global__ void __launch_bounds__(64 * BPG_ROWS) k_baropg_rs(KP P, int sum2d) {
+// rtcol (NULL: nobody asks): does rho's round trip through rho - rmean (solver.f:854,937), which k_profq applies to what it loads while
+// pomgpu_ctx::rho_rt_pending, change a bit anywhere in this column's levels 1..kbm1?  The owning lane holds both operands and their
+// difference at every level; one answer per column goes to the plane behind the loop (rows and columns no lane owns: never read)
+__global__ void __launch_bounds__(64 * BPG_ROWS) k_baropg_rs(KP P, int sum2d, unsigned *rtcol) {
   HALO_XCD_DECODE_R(BPG_ROWS)
   const int r = WAVE_UNIFORM((int)threadIdx.y);
   const bool jvalid = j <= P.jml;
@@ -128,10 +131,12 @@ __global__ void __launch_bounds__(64 * BPG_ROWS) k_baropg_rs(KP P, int sum2d) {
     L.rho_s = bld(brho, osh, lv); L.rm_s = bld(brm, osh, lv);
   };
   double rc0 = 0., rw0 = 0., rs0 = 0., ax = 0., ay = 0., rx = 0., ry = 0.;
+  bool rtch = false;
   auto step = [&](const int k, const Lev &cur, Lev &nxt) {
     const int par = k & 1;
     load(nxt, k + 2 <= kbm1 ? k + 2 : kbm1);                // two levels ahead: in flight during this iteration and the next
     const double rc = cur.rho - cur.rm;
+    rtch = rtch || rt_changes(cur.rho, cur.rm);
 #ifndef POMGPU_EMU
     slab[par][r + 1][lane] = rc;
     if (r == 0) slab[par][0][lane] = cur.rho_s - cur.rm_s;
@@ -170,6 +175,7 @@ __global__ void __launch_bounds__(64 * BPG_ROWS) k_baropg_rs(KP P, int sum2d) {
     if (k + 2 <= kbm1) step(k + 2, rc_, rb);
   }
   if (!own) return;
+  if (rtcol) rtcol[(size_t)(jc - 1) * P.iml + (i - 1)] = rtch ? 1u : 0u;
   if (in) {
     if (sum2d) { F2(drx2d, i, jc) = rx; F2(dry2d, i, jc) = ry; }
     F3(drhox, i, jc, P.kb) = P.ramp * F3(drhox, i, jc, P.kb);                                 // :928-935, k=kb
@@ -549,7 +555,9 @@ template <int FP, int FF, int ROWS, int LD = 1>
 // jfirst, jlast: the rows this launch covers (1..jm: everything).  On tiles whose ghost lines are filled by a message round behind this
 // kernel (pomgpu_api.hip, rim round Rq) the ghost rows are left out: a 2048x194 tile is 25 row blocks x 32 = 800 workgroups for the 768 that
 // are resident at once -- a fourth, nearly empty round -- and 24 x 32 = 768 without its two ghost rows
-__global__ void __launch_bounds__(64 * ROWS) k_profq(KP P, int rho_rt_pace, int jfirst, int jlast) {
+// rho_rt_pace & 4: rtcol holds k_baropg_rs's answers for the rho and rmean now in memory (pomgpu_ctx::rho_rt_cols) -- rmean is requested, and the round trip
+// applied, only in the columns where it changes a bit (cells holding -0.0: masked columns); elsewhere rho is used as loaded
+__global__ void __launch_bounds__(64 * ROWS) k_profq(KP P, int rho_rt_pace, int jfirst, int jlast, const unsigned *rtcol) {
 #ifndef POMGPU_EMU
   // 8-row workgroups (one per CU): 19 levels = 152 KB.  NOT 20 = the whole 160 KB: a library that merely CONTAINS a kernel with
   // 163840 bytes of LDS made processes that share one GPU (tests, rehearsals: bench.py --gpus 4 on one card) run one after the
@@ -631,7 +639,10 @@ __global__ void __launch_bounds__(64 * ROWS) k_profq(KP P, int rho_rt_pace, int 
   const unsigned o_abs = ffil ? BOFF_NONE : oc;             // |q2b|, |q2lb| on the way down: rewritten on the way up where the filter is fused
   const unsigned o_fil = ffil ? oc : BOFF_NONE, o_uv = ffil ? BOFF_NONE : oc;
   const unsigned o_pr = (FP == 0 || (FP == 2 && !pin)) ? oc : BOFF_NONE;
-  const unsigned o_rm = rho_rt ? oc : BOFF_NONE;            // rmean is requested only where it is used (outside the buffer: no traffic)
+  // rmean is requested only where it is used (outside the buffer: no traffic).  The walks ask o_rm, not a flag of their own, whether this
+  // lane's rho makes the round trip: <1, 1, 8> has no register left for one
+  unsigned o_rm = rho_rt ? oc : BOFF_NONE;
+  if (rho_rt_pace & 4) o_rm = (rho_rt && rtcol[(size_t)(j - 1) * P.iml + (i - 1)]) ? oc : BOFF_NONE;
   // boundary values of the two solves -- :1296-1297, :1417-1425
   // (the peeled walk forms them where it holds their operand, two column-resident values less: vbot at level kbm1 from that level's
   // q2, ufbot from the level kb it loads last -- the walk down stores neither q2 nor level kb of uf)
@@ -665,7 +676,7 @@ __global__ void __launch_bounds__(64 * ROWS) k_profq(KP P, int rho_rt_pace, int 
     const double kqp = cur.kq1;
     // ---- level-local quantities
     double cck = 0., rhok = 0.;
-    if (k <= kbm1) { cck = profq_cc_v(P, cur.t, cur.s, hij, k); rhok = rho_rt ? (cur.rho - cur.rm) + cur.rm : cur.rho; }
+    if (k <= kbm1) { cck = profq_cc_v(P, cur.t, cur.s, hij, k); rhok = (o_rm != BOFF_NONE) ? (cur.rho - cur.rm) + cur.rm : cur.rho; }
     double q2b = cur.q2b;
     double l, gh = 0.;
     double uck = 0., uek = 0., vck = 0., vnk = 0., bg = 0.;
@@ -800,7 +811,7 @@ __global__ void __launch_bounds__(64 * ROWS) k_profq(KP P, int rho_rt_pace, int 
     const double kqp = cur.kq1;
     // ---- level-local quantities
     double cck = 0., rhok = 0.;
-    if (PH != PH_KB) { cck = profq_cc_v(P, cur.t, cur.s, hij, k); rhok = rho_rt ? (cur.rho - cur.rm) + cur.rm : cur.rho; }
+    if (PH != PH_KB) { cck = profq_cc_v(P, cur.t, cur.s, hij, k); rhok = (o_rm != BOFF_NONE) ? (cur.rho - cur.rm) + cur.rm : cur.rho; }
     double q2b = cur.q2b;
     double l, gh = 0.;
     double uck = 0., uek = 0., vck = 0., vnk = 0., bg = 0.;
@@ -1887,9 +1898,11 @@ static inline dim3 colgrid(const KP &P) { return dim3((P.iml + 63) / 64, (P.jml 
 // baropg, vertvl: four paced rows per workgroup (same-context A/B against 2 unpaced rows: -2..-3 %; 8 rows: +3 % on baropg)
 #define COLV_G(P) dim3(((P).iml + 63) / 64, ((P).jml + 3) / 4, 1)
 #define COLV_B dim3(64, 4, 1)
-void launch_baropg(pomgpu_ctx *c, int sum2d) {
-  if (SW(c, BAROPG_CELLS)) { LAUNCH(c, k_baropg, COLV_G(c->P), COLV_B, c->P, sum2d); return; }   // developer switch: one thread per column, six loads per level
-  LAUNCHN(c, "k_baropg", k_baropg_rs, grid1_halo_r(c->P, BPG_ROWS), blk_col_r(BPG_ROWS), c->P, sum2d);
+// rtcol: the plane that takes "rho's round trip changes bits in this column" (k_baropg_rs alone: returns whether it was written)
+int launch_baropg(pomgpu_ctx *c, int sum2d, unsigned *rtcol) {
+  if (SW(c, BAROPG_CELLS)) { LAUNCH(c, k_baropg, COLV_G(c->P), COLV_B, c->P, sum2d); return 0; }   // developer switch: one thread per column, six loads per level
+  LAUNCHN(c, "k_baropg", k_baropg_rs, grid1_halo_r(c->P, BPG_ROWS), blk_col_r(BPG_ROWS), c->P, sum2d, rtcol);
+  return rtcol != NULL;
 }
 void launch_baropg_mcc(pomgpu_ctx *c, int sum2d) { LAUNCH(c, k_baropg_mcc, colgrid(c->P), colblk(), c->P, sum2d); }
 void launch_order_pack(pomgpu_ctx *c, double *send_e, double *send_n) {
@@ -1940,11 +1953,18 @@ void launch_profq(pomgpu_ctx *c, int fuse_prod, int fuse_filter, int rho_rt, int
   // (a 514x769 tile of an 8-tile split: 3.4 per CU, k_profq 1.27 -> 1.22 ms, the tile's step 7.15 -> 6.9)
   // (developer switches: POMGPU_PROFQ_ROWS8 / _ROWS2 force a shape, POMGPU_PROFQ_NOPACE drops the barrier)
   const int rows8 = !SW(c, PROFQ_ROWS2) && (SW(c, PROFQ_ROWS8) || (long)((c->P.iml + 63) / 64) * ((c->P.jml + 7) / 8) >= 3 * 256);
-  rho_rt = (rho_rt ? 1 : 0) | (SW(c, PROFQ_NOPACE) ? 0 : 2);
+  // the column plane of k_baropg_rs, while it is valid (pomgpu_ctx::rho_rt_cols; POMGPU_RT_LOAD, read here: rmean in every column as before);
+  // profq_rm_flags counts the launches that read it, a count without events
+  const int cols = rho_rt && c->rho_rt_cols && !SW(c, RT_LOAD);
+  if (cols && c->prof_on) {
+    const int s = pomgpu_prof_slot(c, "profq_rm_flags");
+    if (s >= 0) (c->parent ? c->parent : c)->prof[s].launches++;
+  }
+  rho_rt = (rho_rt ? 1 : 0) | (SW(c, PROFQ_NOPACE) ? 0 : 2) | (cols ? 4 : 0);
 #define PQ(FP, FF, LD)                                                                                                                   \
   do {                                                                                                                                   \
-    if (rows8) LAUNCHN(c, "k_profq", (k_profq<FP, FF, PROFQ_BIG, LD>), dim3((c->P.iml + 63) / 64, (nrows + PROFQ_BIG - 1) / PROFQ_BIG, 1), dim3(64, PROFQ_BIG, 1), c->P, rho_rt, jfirst, jlast); \
-    else LAUNCHN(c, "k_profq", (k_profq<FP, FF, 2, LD>), dim3((c->P.iml + 63) / 64, (nrows + 1) / 2, 1), dim3(64, 2, 1), c->P, rho_rt, jfirst, jlast);       \
+    if (rows8) LAUNCHN(c, "k_profq", (k_profq<FP, FF, PROFQ_BIG, LD>), dim3((c->P.iml + 63) / 64, (nrows + PROFQ_BIG - 1) / PROFQ_BIG, 1), dim3(64, PROFQ_BIG, 1), c->P, rho_rt, jfirst, jlast, c->rt_cols); \
+    else LAUNCHN(c, "k_profq", (k_profq<FP, FF, 2, LD>), dim3((c->P.iml + 63) / 64, (nrows + 1) / 2, 1), dim3(64, 2, 1), c->P, rho_rt, jfirst, jlast, c->rt_cols); \
   } while (0)
   if (fuse_filter) { if (fuse_prod == 0) PQ(0, 1, 1); else if (fuse_prod == 1) { if (ld) PQ(1, 1, 1); else PQ(1, 1, 0); } else PQ(2, 1, 1); }
   else { if (fuse_prod == 0) PQ(0, 0, 1); else if (fuse_prod == 1) PQ(1, 0, 1); else PQ(2, 0, 1); }

@@ -232,7 +232,7 @@ static void ext_buffers(pomgpu_ctx *c) {
 // rho's deferred round trip (levels 1..kbm1; level kb was done when it was deferred)
 static void rho_materialize(pomgpu_ctx *c) {
   if (!c->rho_rt_pending || (c->flags & POMGPU_CTX_2D)) return;
-  c->rho_rt_pending = 0;
+  c->rho_rt_pending = c->rho_rt_cols = 0;
   launch_roundtrip(c, SLOT3(c, P3_rho), SLOT3(c, P3_rmean), 2);
 }
 static void side_join(pomgpu_ctx *c);
@@ -283,6 +283,10 @@ static bool uvm_onload(const pomgpu_ctx *c) {
          // passive tracers are advected in mode 4 too, and with nadv 1 or nitera > 1 by kernels that read u, v as they are in memory
          (!c->ntr || (k.nadv == 2 && c->P.nitera == 1));
 }
+// may a round trip be read only where it changes bits (rt_words, rt_cols)?  One tile alone: no exchange hook, no transport, no wide halo,
+// no parent, not 2-D -- and no address handed out (pomgpu_device_2d / _3d: writes the library cannot see, as for wr).  POMGPU_RT_LOAD is
+// read where the consumers are launched
+static bool rt_one_tile(const pomgpu_ctx *c) { return !c->exch && !c->tp.on && !c->wide.on && !c->parent && !(c->flags & POMGPU_CTX_2D) && !c->wr_eager; }
 // may k_profq of a step that another step of the same pomgpu_run follows keep l and dtef out of memory (launch_profq, store_ld = 0)?
 // Nothing on the device reads them back and the next step's profq rewrites both whole, so the question is only who can look between
 // the two: nobody on one tile whose mirrors only the library reads (as for wr).  No lazy state comes with it -- they cannot be formed
@@ -406,6 +410,10 @@ static int ctx_create(pomgpu_ctx **out, const pomgpu_dims *d, int device, void *
   for (int n = 0; n < POMGPU_NSCR3 && !only2d; n++) alloc(&P.s3[n], P.n3);
   for (int n = 0; n < POMGPU_NSCR2; n++) alloc(&P.s2[n], P.n2);
   for (int n = 0; n < 2 && !only2d; n++) alloc(&c->uvb_bot[n], P.n2);
+  if (!only2d) {                                              // round trips read only where bits change: 8 bytes per (level <= kbm1, row, 62 columns), 4 per column
+    double *m = NULL; alloc(&m, (size_t)(P.kb > 1 ? P.kb - 1 : 1) * P.jml * RT_NBX(P)); c->rt_words = (unsigned long long *)m;
+    m = NULL; alloc(&m, (P.n2 + 1) / 2); c->rt_cols = (unsigned *)m;
+  }
   for (int n = 0; n < POMGPU_NCOEF2; n++) alloc(&P.c2[n], P.n2);
   alloc(&c->alt2[0], (size_t)POMGPU_NGEN * P.n2);              // ONE block: a kernel reaches the whole set through one buffer descriptor (k_ext_march2)
   for (int n = 1; n < POMGPU_NGEN && ok; n++) c->alt2[n] = c->alt2[0] + (size_t)n * P.n2;
@@ -461,6 +469,7 @@ extern "C" void pomgpu_destroy(pomgpu_ctx *c) {
   for (int n = 0; n < POMGPU_NSCR3; n++) (void)hipFree(P.s3[n]);
   for (int n = 0; n < POMGPU_NSCR2; n++) (void)hipFree(P.s2[n]);
   (void)hipFree(c->uvb_bot[0]); (void)hipFree(c->uvb_bot[1]);
+  (void)hipFree(c->rt_words); (void)hipFree(c->rt_cols);
   for (int n = 0; n < POMGPU_NCOEF2; n++) (void)hipFree(P.c2[n]);
   (void)hipFree(c->alt2[0]); (void)hipFree(c->alt3[0]);         // one block each
   (void)hipFree(P.m8);
@@ -829,17 +838,19 @@ static void seq_advct(pomgpu_ctx *c, int sum2d = 0, int defer_xch = 0) {   // so
 // the stored rho by a rounding.  Before dens rewrites rho at the end of the same step only profq reads it, so the three
 // array passes of k_roundtrip are replaced by one extra read of rmean inside k_profq; level kb, which dens does not
 // write, makes its round trip here.  Anything else that wants rho first gets it materialised (rho_materialize).
-static void seq_rho_roundtrip(pomgpu_ctx *c, int defer_rt) {
+// cols: k_baropg_rs has just written the column plane for this rho, rmean (rt_cols)
+static void seq_rho_roundtrip(pomgpu_ctx *c, int defer_rt, int cols = 0) {
   if (defer_rt) {
     launch_roundtrip_level(c, D3(c, rho), D3(c, rmean), c->P.kb);
     c->rho_rt_pending = 1;
+    c->rho_rt_cols = cols;
   } else {
     launch_roundtrip(c, D3(c, rho), D3(c, rmean), 0);
   }
 }
 static void seq_baropg(pomgpu_ctx *c, int sum2d = 0, int defer_rt = 0) {        // solver.f:848-940
-  launch_baropg(c, sum2d);
-  seq_rho_roundtrip(c, defer_rt);                             // :854 + :937
+  const int cols = launch_baropg(c, sum2d, (defer_rt && rt_one_tile(c)) ? c->rt_cols : NULL);
+  seq_rho_roundtrip(c, defer_rt, cols);                       // :854 + :937
 }
 static void seq_baropg_mcc(pomgpu_ctx *c, int sum2d = 0, int defer_rt = 0) {    // solver.f:943-1159
   KP &P = c->P;
@@ -1101,6 +1112,7 @@ int pomgpu_materialize(pomgpu_ctx *c) {
 // those slots (none of them is a mask or a taurstr array; upload_3d invalidates nothing else)
 void pomgpu_mirrors_written(pomgpu_ctx *c) {
   c->uvm_valid = 0;                                           // u, v are the file's now
+  c->rho_rt_cols = 0;                                         // ... and rho (the reader has materialised a pending round trip before it wrote: no plane can be valid here)
   c->wide.static_done = 0;
   early_invalidate(c);
   refresh_coefs(c);
@@ -1874,12 +1886,14 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
     }
     side_wait(c, SIDE_RW);                                    // the tracer advection and advu / advv read w's ghost lines
     if (k.mode != 4) {
+      bool ts_flags = false;                                  // rt_words are this step's: the one-pass T / S advection alone writes them
       if (k.nadv == 1) {
         seq_advt1(c, D3(c, tb), D3(c, t), D3(c, tclim), D3(c, uf));
         seq_advt1(c, D3(c, sb), D3(c, s), D3(c, sclim), D3(c, vf));
       } else if (k.nadv == 2) {
         if (P.nitera == 1 && !SW(c, ADVT2_SINGLE)) {   // T and S in one pass (HEA, HFA: launch_coef_eta above -- etb, etf have not changed since)
-          launch_advt2x2_col(c, D3(c, tb), D3(c, t), D3(c, tclim), D3(c, uf), D3(c, sb), D3(c, s), D3(c, sclim), D3(c, vf));
+          ts_flags = rt_one_tile(c);                            // ... and says where the round trip of tb, sb changes bits, for k_ts_update below
+          launch_advt2x2_col(c, D3(c, tb), D3(c, t), D3(c, tclim), D3(c, uf), D3(c, sb), D3(c, s), D3(c, sclim), D3(c, vf), ts_flags ? c->rt_words : NULL);
           // solver.f:728 exchanges T, then S; advance.f:436-437 below exchanges both again with nothing written
           // in between: the library's own exchange serves the three points in that one round
           if (!lib_x) xch(c, 1, D3(c, uf), P.kbm1);             // solver.f:728 (T)
@@ -1907,8 +1921,8 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
       double fold, fnew;
       int rc = restore_prepare(c, &fold, &fnew);              // :452 (record handling)
       if (rc) return rc;
-      launch_ts_update(c, fold, fnew, k.nadv == 2, 0);        // :444-454 in one pass; trstr/srstr/taurstr on demand
-      c->rho_rt_pending = 0;                                  // dens has rewritten rho(1..kbm1)
+      launch_ts_update(c, fold, fnew, k.nadv == 2, 0, ts_flags && !SW(c, RT_LOAD));   // :444-454 in one pass; trstr/srstr/taurstr on demand
+      c->rho_rt_pending = c->rho_rt_cols = 0;                 // dens has rewritten rho(1..kbm1)
       c->rst_pending = 1; c->rst_fold = fold; c->rst_fnew = fnew;
       if (rts) {
         double *at[5] = {D3(c, t), D3(c, tb), D3(c, s), D3(c, sb), D3(c, rho)};

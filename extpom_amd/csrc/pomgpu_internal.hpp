@@ -372,6 +372,38 @@ static inline BufA buf2_of(const double *p, size_t) { BufA b; b.p = (double *)p;
 static inline double bld2(const BufA &b, unsigned voff, unsigned soff) { return voff >= 0xFFFFFFF0u ? 0. : b.p[((size_t)voff + soff) >> 3]; }
 static inline void bst2(const BufA &b, unsigned voff, unsigned soff, double x) { if (voff < 0xFFFFFFF0u) b.p[((size_t)voff + soff) >> 3] = x; }
 #endif
+// ---- round trips read only where bits change (k_advt2_col<2, *, true> -> k_ts_update, k_baropg_rs -> k_profq) ----------
+// The reference subtracts a climatology in place and adds it back (tb, sb with tclim, sclim: solver.f:691,715; rho with rmean: :854,
+// :937); the library applies (x - y) + y to what a later kernel loads, and that kernel needs y for nothing else.  The earlier kernel
+// that holds both operands says where the round trip changes a bit; everywhere else the later one takes x as loaded and leaves y alone.
+// T / S: one 64-bit word per (level <= kbm1, row, block of 62 columns), bit = the column's lane in k_advt2_col's halo-lane wavefront
+// (HALO_XCD_DECODE_R: i = 62 * bx + lane, lanes 1..62), T's and S's answers ORed.
+#define RT_NBX(P) (((P).iml + 61) / 62)
+#define RT_WORD(P, i, j, k) ((size_t)((k) - 1) * (P).jml * RT_NBX(P) + (size_t)((j) - 1) * RT_NBX(P) + (size_t)(((i) - 1) / 62))
+#define RT_BIT(i) (((i) - 1) % 62 + 1)
+__device__ __forceinline__ bool rt_changes(double x, double y) {
+  const double rt = (x - y) + y;
+#ifndef POMGPU_EMU
+  return __double_as_longlong(rt) != __double_as_longlong(x);
+#else
+  return memcmp(&rt, &x, sizeof x) != 0;
+#endif
+}
+__device__ __forceinline__ bool rt_changes(float x, float y) {
+  const float rt = (x - y) + y;
+#ifndef POMGPU_EMU
+  return __float_as_uint(rt) != __float_as_uint(x);
+#else
+  return memcmp(&rt, &x, sizeof x) != 0;
+#endif
+}
+#ifndef POMGPU_EMU
+__device__ __forceinline__ void bst2u(const BufA &b, unsigned voff, unsigned soff, unsigned long long x) {
+  pomgpu_u32x2 v;
+  v.x = (unsigned)x; v.y = (unsigned)(x >> 32);
+  __builtin_amdgcn_raw_buffer_store_b64(v, b.r, (int)voff, (int)soff, 0);
+}
+#endif
 // per-lane offset of a lane that must not store: outside every descriptor, the hardware drops the access (loads return 0;
 // tools/micro/buf_oob.hip).  A branch around a store or load inside a software-pipelined loop costs far more than the
 // wasted lanes: where the paths join the compiler no longer knows how many memory operations are outstanding and waits
@@ -581,7 +613,7 @@ static inline dim3 grid2_halo(const KP &P) { return dim3((P.iml + 61) / 62, (P.j
   X(PROFQ_NOPACE) X(COL_STRIP) X(BAND_BYTES) X(PAD3) X(IO_SYNC) X(ADVCT_SPLIT) X(ADVQ_EXCHANGE) X(PROD_FULL) X(QFILTER_SPLIT) \
   X(NO_OVERLAP) X(NO_SIDE_COMM) X(WR_MAIN) X(WIDE_W) X(WIDE_FULL) X(DEBUG_ALLOC) X(TEST_SPLIT_FAIL_RANK)  \
   X(WR_NODEFER) X(EXT_RING_FIRST) X(TUNE_FORCE) X(RIM_MAIN) X(RIM_RESULTS_MAIN) X(SUM2D_OFF) X(ADVCT_ROWS4) X(ADVCT_ROWS8) \
-  X(IO_CHUNK_KB) X(UV_NOFUSE) X(W_NOFUSE) X(UVMEAN_PASS) X(PROFT_TWIN) X(LD_EAGER) X(TR_NOPAIR)
+  X(IO_CHUNK_KB) X(UV_NOFUSE) X(W_NOFUSE) X(UVMEAN_PASS) X(PROFT_TWIN) X(LD_EAGER) X(TR_NOPAIR) X(RT_LOAD)
 enum pomgpu_sw {
 #define POMGPU_SW_(name) SW_##name,
   POMGPU_SWITCHES(POMGPU_SW_)
@@ -725,6 +757,15 @@ struct pomgpu_ctx {
   // rho's round trip through rho - rmean (baropg, solver.f:854,937) has not been stored for levels 1..kbm1: inside
   // pomgpu_advance its only reader before dens rewrites rho is k_profq, which applies it to what it loads
   int rho_rt_pending;
+  // Round trips read only where bits change (above RT_NBX; one tile, POMGPU_RT_LOAD reads everywhere as before).
+  // rt_words: k_advt2_col<2, *, true>'s words for tb, sb -- valid from a launch_advt2x2_col to the launch_ts_update of the same mode_internal,
+  // between which nothing writes tb, sb, tclim, sclim at levels <= kbm1 (copy_kb writes level kb, bcond4 uf, vf); no state survives the call.
+  // rt_cols: k_baropg_rs's plane for rho, one answer per column; rho_rt_cols: it describes the rho and rmean now in memory -- set with
+  // rho_rt_pending where that kernel ran, dropped wherever rho_rt_pending is (rho_materialize: uploads, downloads, handed-out addresses,
+  // stand-alone entry points, the restart reader, the placement tuner; dens at the end of the step)
+  unsigned long long *rt_words;
+  unsigned *rt_cols;
+  int rho_rt_cols;
   int rst_pending;           // trstr/srstr/taurstr of the last step exist only as (rst_fold, rst_fnew) weights
   double rst_fold, rst_fnew;
   // wr of the last step has not been formed (one tile, no exchange of any kind: mode_internal ends without realvertvl).  wr is a
@@ -871,7 +912,7 @@ void launch_advct_edge(pomgpu_ctx *c, double *to_e, double *to_n);
 void launch_advct_fix(pomgpu_ctx *c, const double *from_w, const double *from_s);
 void launch_advct_fix2d(pomgpu_ctx *c, int west, int south);
 void launch_advt2x2_col(pomgpu_ctx *c, const double *tb, const double *t, const double *tc, double *tf, const double *sb, const double *s_,
-                        const double *sc, double *sf);
+                        const double *sc, double *sf, unsigned long long *rtf = NULL);
 void launch_advq2_col(pomgpu_ctx *c, const double *q, const double *qb, double *qf, const double *ql, const double *qlb, double *qlf, int zero_else);
 #if POMGPU_W_FUSE
 void launch_advq2w_col(pomgpu_ctx *c, const double *q, const double *qb, double *qf, const double *ql, const double *qlb, double *qlf, int zero_else);
@@ -923,7 +964,7 @@ void launch_mask3(pomgpu_ctx *c, double *a, const double *m2);
 void launch_smol(pomgpu_ctx *c, const double *ff);
 void launch_copy3(pomgpu_ctx *c, double *dst, const double *src);
 void launch_advt2_diff(pomgpu_ctx *c, const double *fb, const double *fc, double *ff);
-void launch_ts_update(pomgpu_ctx *c, double fold, double fnew, int rt, int store_rst);   // uses c->tau_known / tau_val
+void launch_ts_update(pomgpu_ctx *c, double fold, double fnew, int rt, int store_rst, int rt_flags = 0);   // uses c->tau_known / tau_val; rt_flags: c->rt_words are this step's
 void launch_restore_fields(pomgpu_ctx *c, double fold, double fnew);
 void launch_mask_ts(pomgpu_ctx *c);
 // passive tracers: bcond(4)'s mask, the filter and the rotation for one field or a pair (rt: with advt2's deferred fb round trip)
@@ -937,7 +978,7 @@ void launch_restore_load(pomgpu_ctx *c, const double *tr, const double *sr, doub
 void launch_dens(pomgpu_ctx *c, const double *si, const double *ti, double *rhoo);
 void launch_realvertvl(pomgpu_ctx *c, int etf_is_et = 0);   // etf_is_et: read et where solver.f:2052 reads etf (a pending wr, pomgpu_ctx::wr_pending)
 // k_vert.hip
-void launch_baropg(pomgpu_ctx *c, int sum2d);
+int launch_baropg(pomgpu_ctx *c, int sum2d, unsigned *rtcol = NULL);   // returns whether rtcol was written (k_baropg_rs)
 void launch_baropg_mcc(pomgpu_ctx *c, int sum2d);
 void launch_order_pack(pomgpu_ctx *c, double *send_e, double *send_n);
 void launch_int_uvmean(pomgpu_ctx *c);
