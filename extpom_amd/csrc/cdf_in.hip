@@ -1,9 +1,12 @@
-// cdf_in.hip -- a whole state from files WITHOUT PnetCDF: pomgpu_read_restart (the restart file back) and pomgpu_cold_start (the reference's
-// grid, init and clim files), with pomgpu_set_z_inputs / pomgpu_set_z_lateral, which say what is on z levels.  Both readers parse the
+// cdf_in.hip -- a whole state from files WITHOUT PnetCDF: pomgpu_read_restart (the restart file back), pomgpu_read_tracers (the passive
+// tracers' own file) and pomgpu_cold_start (the reference's grid, init and clim files), with pomgpu_set_z_inputs / pomgpu_set_z_lateral,
+// which say what is on z levels.  The readers parse the
 // headers and check every variable before the first mirror changes, then send raw big-endian bands through the pinned buffers of
 // cdf_io.hpp to the device on a copy stream of their own, a kernel behind each copy; the forcing records are frc_files.hip's.
 #include <fcntl.h>
 #include <sys/stat.h>
+
+#include <cstdio>
 
 #include "cdf_io.hpp"
 #define fail pomgpu_fail
@@ -99,6 +102,120 @@ extern "C" int pomgpu_read_restart(pomgpu_ctx *c, const char *path, const pomgpu
   if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, POMGPU_EHIP, "read_restart: %s: synchronise failed", path);
   if (time0_out) *time0_out = sc[1];
   if (iint_out) *iint_out = sc[0];
+  return POMGPU_OK;
+}
+
+// ---- the tracers' file back (pomgpu_read_tracers, include/pomgpu.h; the writer: cdf_out.hip) ------------------------------------------
+// k_cdf_unpack's lane mapping with up to three destinations: the staged value's bytes are reversed once and stored to d0 and, where they
+// are given, d1 and d2 -- trNN into tr, and into trb / trf of a file that has no trbNN / trfNN: no second read, no device-to-device copy.
+// The two pointers are kernel arguments: the branches around their stores are uniform
+__global__ void k_tr_unpack(double *d0, double *d1, double *d2, const void *src, int im, int jm, size_t dl, int dp, int rows, int pitch, int c0) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x), j = (int)(blockIdx.y * blockDim.y + threadIdx.y), k = (int)blockIdx.z;
+  if (i >= im || j >= jm) return;
+  const double x = CdfRaw<double>::get(src, ((size_t)k * rows + j) * (size_t)pitch + (size_t)(c0 + i));
+  const size_t e = (size_t)k * dl + (size_t)j * dp + i;
+  d0[e] = x;
+  if (d1) d1[e] = x;
+  if (d2) d2[e] = x;
+}
+
+extern "C" int pomgpu_read_tracers(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m, double *time_out, double *iint_out) {
+#ifdef POMGPU_STORE_F32
+  if (c) return fail(c, POMGPU_EINVAL, "read_tracers: not in the fp32-storage variant (3-D arrays are not doubles there)");
+#endif
+  if (!c || !path || !m) return POMGPU_EINVAL;
+  (void)hipSetDevice(c->device);
+  if (c->flags & POMGPU_CTX_2D) return fail(c, POMGPU_EINVAL, "read_tracers: a context with 3-D arrays");
+  if (!c->ntr) return fail(c, POMGPU_EINVAL, "read_tracers: no tracers are registered (pomgpu_set_tracers)");
+  { const int rcw = pomgpu_io_wait(c); if (rcw) return rcw; }  // the file may be the one this context is still writing
+  const KP &P = c->P;
+  if (!tile_fits(m, P, 0, 0, 0, 0))
+    return fail(c, POMGPU_EINVAL, "read_tracers: %s: the tile (%d..%d, %d..%d) does not fit the global grid %d x %d", path, m->i0, m->i0 + P.im - 1,
+                m->j0, m->j0 + P.jm - 1, m->im_global, m->jm_global);
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return fail(c, POMGPU_EINVAL, "read_tracers: cannot open %s", path);
+  struct stat sb;
+  if (fstat(fd, &sb)) { (void)close(fd); return fail(c, POMGPU_EINVAL, "read_tracers: cannot stat %s", path); }
+  const uint64_t fsize = (uint64_t)sb.st_size;
+  RHeader H;
+  {
+    std::string what;
+    const int rc = read_header(fd, fsize, H, what);
+    if (rc == -2) { (void)close(fd); return fail(c, POMGPU_EINVAL, "read_tracers: I/O error on %s (header)", path); }
+    if (rc < 0) { (void)close(fd); return fail(c, POMGPU_EINVAL, "read_tracers: %s is not a tracer file this library reads: %s", path, what.c_str()); }
+  }
+  auto refuse = [&](const std::string &why) { (void)close(fd); return fail(c, POMGPU_EINVAL, "read_tracers: %s: %s", path, why.c_str()); };
+  const uint64_t img = (uint64_t)m->im_global, jmg = (uint64_t)m->jm_global;
+  const int ntr = c->ntr;
+  auto nn = [](const char *stem, int n) { char b[32]; snprintf(b, sizeof b, "%s%02d", stem, n); return std::string(b); };
+  // one value of an optional scalar variable: 0 = absent, 1 = read into *x, -1 = refused (why)
+  auto scalar = [&](const std::string &name, double *x, std::string &why) {
+    if (!find_var(H, name.c_str())) return 0;
+    const RVar *v = NULL;
+    why = check_var(H, fsize, name.c_str(), VarWant::fixed(NC_ONLY_DOUBLE, {}, VarWant::ONE_VALUE), &v);
+    if (!why.empty()) return -1;
+    uint64_t u;
+    if (pread_all(fd, &u, 8, v->begin)) { why = "I/O error (" + name + ")"; return -1; }
+    u = __builtin_bswap64(u);
+    memcpy(x, &u, 8);
+    return 1;
+  };
+  // ---- every variable, and every scalar's value, before anything changes ----
+  struct TItem { const RVar *v; double *d[3]; };
+  std::vector<TItem> items;
+  int nbc[POMGPU_TRMAX], has_set[POMGPU_TRMAX];
+  double lam[POMGPU_TRMAX], sc[2] = {0., 0.};                    // time, iint
+  {
+    std::string why;
+    if (scalar("time", &sc[0], why) < 0 || scalar("iint", &sc[1], why) < 0) return refuse(why);
+    const std::vector<uint64_t> want = {(uint64_t)P.kb, jmg, img};
+    for (int n = 1; n <= ntr; n++) {
+      pomgpu_ctx::pomgpu_tracer &t = c->trc[n - 1];
+      const RVar *v = NULL, *vb = NULL, *vf = NULL;
+      why = check_var(H, fsize, nn("tr", n).c_str(), VarWant::fixed(NC_ONLY_DOUBLE, want), &v);
+      if (why.empty() && find_var(H, nn("trb", n).c_str())) why = check_var(H, fsize, nn("trb", n).c_str(), VarWant::fixed(NC_ONLY_DOUBLE, want), &vb);
+      if (why.empty() && find_var(H, nn("trf", n).c_str())) why = check_var(H, fsize, nn("trf", n).c_str(), VarWant::fixed(NC_ONLY_DOUBLE, want), &vf);
+      if (!why.empty()) return refuse(why);
+      items.push_back({v, {t.tr, vb ? NULL : t.trb, vf ? NULL : t.trf}});
+      if (vb) items.push_back({vb, {t.trb, NULL, NULL}});
+      if (vf) items.push_back({vf, {t.trf, NULL, NULL}});
+      double xn = (double)t.nbc;
+      lam[n - 1] = t.lam;
+      const int hn = scalar(nn("nbc", n), &xn, why), hl = hn < 0 ? -1 : scalar(nn("lam", n), &lam[n - 1], why);
+      if (hn < 0 || hl < 0) return refuse(why);
+      if (xn != 1. && xn != 3.)
+        return refuse("variable " + nn("nbc", n) + " holds " + std::to_string(xn) + "; a tracer takes 1 (the flux wtrsurf) or 3 (the value trsurf)");
+      nbc[n - 1] = (int)xn;
+      has_set[n - 1] = hn > 0 || hl > 0;
+    }
+  }
+  // ---- from here on the tracers change ----
+  for (int n = 1; n <= ntr; n++) if (has_set[n - 1]) { c->trc[n - 1].nbc = nbc[n - 1]; c->trc[n - 1].lam = lam[n - 1]; }
+  int bad = 0;
+  const size_t band = (size_t)P.jm * (size_t)img * 8;           // bytes of one level's band
+  BandReader R;
+  if (R.open(c, io_run_bytes(c, band, band * (size_t)P.kb)) || hipStreamSynchronize(c->stream) != hipSuccess) bad = 2;   // the steps that still use the tracers precede the first store below
+  const hipStream_t cur0 = c->cur;
+  c->cur = R.own;                                                // LAUNCH goes to the copy stream: each kernel behind the copy that feeds it
+  const dim3 grid((unsigned)((P.im + 63) / 64), (unsigned)((P.jm + 3) / 4), 1);
+  for (const TItem &it : items) {
+    if (bad) break;
+    bad = read_levels(c, R, fd, it.v->begin + (uint64_t)(m->j0 - 1) * img * 8, band, jmg * img * 8, P.kb, [&](int k0, int nl) {
+      const size_t o = (size_t)k0 * P.n2;
+      LAUNCH(c, k_tr_unpack, dim3(grid.x, grid.y, (unsigned)nl), blk2(), it.d[0] + o, it.d[1] ? it.d[1] + o : (double *)NULL, it.d[2] ? it.d[2] + o : (double *)NULL,
+             (const void *)R.stage, P.im, P.jm, P.n2, P.iml, P.jm, (int)img, m->i0 - 1);
+    });
+  }
+  c->cur = cur0;
+  if (hipStreamSynchronize(R.own) != hipSuccess && !bad) bad = 2;
+  R.release();
+  (void)close(fd);
+  if (bad || c->launch_err) {
+    if (bad == 2) (void)hipGetLastError();
+    return fail(c, bad == 1 ? POMGPU_EINVAL : POMGPU_EHIP, bad == 1 ? "read_tracers: I/O error on %s (the tracers are unspecified)" : "read_tracers: a HIP call failed while reading %s (the tracers are unspecified)", path);
+  }
+  if (time_out) *time_out = sc[0];
+  if (iint_out) *iint_out = sc[1];
   return POMGPU_OK;
 }
 

@@ -1,5 +1,6 @@
 // cdf_out.hip -- the writer: the output and restart files of the reference WITHOUT PnetCDF.  Host code plus device-to-host copies; the
-// only kernels are the two of the time-mean output at the end of the file (k_mean_accum, k_mean_snapshot).  The readers are cdf_in.hip
+// only kernels are the two of the time-mean output (k_mean_accum, k_mean_snapshot); the passive tracers' files and means (pomgpu_write_tracers)
+// are at the end of the file.  The readers are cdf_in.hip
 // (restart, cold start) and frc_files.hip (forcing records).
 // io_pnetcdf.F writes NetCDF "64-bit offset" files
 // (nf_64bit_offset = CDF-2) through the parallel library: write_output_pnetcdf (:57-410) and
@@ -17,6 +18,7 @@
 #include <unistd.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -37,6 +39,8 @@ struct Var {
   Src src; int slot; int nlev;    // slot: blk1d / blk2d / blk3d member; nlev: levels written (3-D), values (1-D)
   double value;                   // SCALAR
   uint64_t begin;
+  const double *dev;              // VOLUME3D outside blk3d (a tracer's array): the device address; NULL = the slot's mirror
+  int tmean;                      // the tracer (0-based) whose mean accumulator supplies the values in a tracer mean file, -1 = none
 };
 struct Spec { std::vector<std::pair<std::string, int>> dims; std::vector<Att> gatts; std::vector<Var> vars; };
 
@@ -74,7 +78,7 @@ std::string header(Spec &S) {
 }
 Var mk(const char *name, std::vector<int> dims, const char *long_name, const char *units, const char *coords, Src src, int slot, int nlev,
        double value = 0.) {
-  Var v; v.name = name; v.dims = dims; v.src = src; v.slot = slot; v.nlev = nlev; v.value = value; v.begin = 0;
+  Var v; v.name = name; v.dims = dims; v.src = src; v.slot = slot; v.nlev = nlev; v.value = value; v.begin = 0; v.dev = NULL; v.tmean = -1;
   v.atts.push_back({"long_name", long_name}); v.atts.push_back({"units", units});
   if (coords) v.atts.push_back({"coordinates", coords});
   return v;
@@ -176,10 +180,13 @@ static int mean_field(const Var &v) {                                 // which o
   return -1;
 }
 static void launch_mean_snapshot(pomgpu_ctx *c, double *const *dst, const size_t *nout);
-// mean != 0 (pomgpu_write_output_mean): the nine fields come from the accumulators -- k_mean_snapshot stores acc / count into the snapshot
-// and +0.0 into acc in one pass, on the kernels' stream -- and the count returns to 0
+static void launch_tracer_mean_snapshot(pomgpu_ctx *c, double *const *dst, const size_t *nout);
+// mean == 1 (pomgpu_write_output_mean): the nine fields come from the accumulators -- k_mean_snapshot stores acc / count into the snapshot
+// and +0.0 into acc in one pass, on the kernels' stream -- and the count returns to 0.  mean == 2 (pomgpu_write_tracers, the mean kind):
+// the same for the variables that name a tracer (Var::tmean), from the tracers' accumulators and with the tracers' count
 static int write_file(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m, Spec &S, int mean = 0) {
   const KP &P = c->P;
+  auto mean_of = [&](const Var &v) { return mean == 2 ? v.tmean : (mean ? mean_field(v) : -1); };   // which accumulator supplies v, -1 = none
   if (!tile_fits(m, P, 0, 0, 0, 0))
     return fail(c, POMGPU_EINVAL, "write: the tile (%d..%d, %d..%d) does not fit the global grid %d x %d", m->i0, m->i0 + P.im - 1, m->j0,
                 m->j0 + P.jm - 1, m->im_global, m->jm_global);
@@ -219,7 +226,7 @@ static int write_file(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m
 #else
   if (async && hipMalloc((void **)&J->snap, total * sizeof(double)) != hipSuccess) { J->snap = NULL; (void)hipGetLastError(); async = false; }
 #endif
-  auto dev_of = [&](const Var &v) { return v.src == PLANE2D ? P.b2 + (size_t)v.slot * P.n2 : P.b3 + (size_t)v.slot * P.a3; };
+  auto dev_of = [&](const Var &v) { return v.dev ? v.dev : (v.src == PLANE2D ? P.b2 + (size_t)v.slot * P.n2 : P.b3 + (size_t)v.slot * P.a3); };
   // the means: where each of the nine lands in `base` (the snapshot, or on the synchronous path a buffer for the nine alone), one launch
   double *mdst[MEAN_NF] = {NULL};
   size_t mout[MEAN_NF] = {0};
@@ -227,18 +234,18 @@ static int write_file(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m
     size_t o = 0;
     for (const Var &v : S.vars) {
       const size_t n = var_doubles(*J, v);
-      const int q = mean_field(v);
+      const int q = mean_of(v);
       if (q >= 0 && n) { mdst[q] = base + o; mout[q] = n; }
       if (q >= 0 || !nine_only) o += n;
     }
-    launch_mean_snapshot(c, mdst, mout);
-    c->mean_count = 0;
+    if (mean == 2) { launch_tracer_mean_snapshot(c, mdst, mout); c->trmean_count = 0; }
+    else { launch_mean_snapshot(c, mdst, mout); c->mean_count = 0; }
   };
   if (!async) {                                                        // the synchronous path: variable by variable through pageable memory
     double *nine = NULL;
     if (mean && !bad) {
       size_t tot9 = 0;
-      for (const Var &v : S.vars) if (mean_field(v) >= 0) tot9 += var_doubles(*J, v);
+      for (const Var &v : S.vars) if (mean_of(v) >= 0) tot9 += var_doubles(*J, v);
       if (hipMalloc((void **)&nine, (tot9 ? tot9 : 1) * sizeof(double)) != hipSuccess) { nine = NULL; (void)hipGetLastError(); bad = 1; }
       else take_means(nine, true);
     }
@@ -246,7 +253,7 @@ static int write_file(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m
       const size_t n = var_doubles(*J, v);
       if (bad || !n) continue;
       host.resize(n);
-      const int q = mean ? mean_field(v) : -1;
+      const int q = mean_of(v);
       if (hipMemcpyAsync(host.data(), q >= 0 ? mdst[q] : dev_of(v), sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
           hipStreamSynchronize(c->stream) != hipSuccess) { bad = 1; break; }
       bad |= put_var(*J, v, host.data(), tmp);
@@ -263,7 +270,7 @@ static int write_file(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m
   for (const Var &v : S.vars) {                                        // the snapshot, on the kernels' stream
     const size_t n = var_doubles(*J, v);
     if (!n) continue;
-    if (!(mean && mean_field(v) >= 0) &&
+    if (mean_of(v) < 0 &&
         hipMemcpyAsync(J->snap + off, dev_of(v), n * sizeof(double), hipMemcpyDeviceToDevice, c->stream) != hipSuccess) bad = 1;
     off += n;
   }
@@ -528,6 +535,100 @@ extern "C" int pomgpu_write_output_mean(pomgpu_ctx *c, const char *path, const p
   Spec S;
   output_spec(c, m, S);
   return write_file(c, path, m, S, 1);
+}
+
+// ---- the tracers' files (include/pomgpu.h: pomgpu_write_tracers; no counterpart in the reference) -----------------------------------
+// The tracers' time mean is the nine fields' machinery with a table of its own: k_mean_accum once more per step, blockIdx.y the tracer
+// (ONE added launch per step while the mean is on and tracers are registered, whatever their number), and k_mean_snapshot for the mean
+// file.  A tracer's arrays and its accumulator are allocations of their own and 16-byte aligned alike (pomgpu_ctx::trmean_stride is
+// even), so the accumulation takes the 16-byte form; an odd n3 leaves the one tail element.
+static_assert(POMGPU_TRMAX <= MEAN_NF, "the tracers' table is a MeanTab");
+static dim3 tracer_mean_grid(const pomgpu_ctx *c) { return dim3((unsigned)((c->P.n3 + MEAN_WG - 1) / MEAN_WG), (unsigned)c->ntr, 1); }
+static void tracer_mean_tab(const pomgpu_ctx *c, MeanTab &T) {
+  for (int q = 0; q < MEAN_NF; q++) {
+    const bool on = q < c->ntr;
+    T.j[q].x = on ? c->trc[q].tr : NULL; T.j[q].acc = on ? c->trmean_acc + (size_t)q * c->trmean_stride : NULL; T.j[q].dst = T.j[q].acc;
+    T.j[q].n = on ? (unsigned)c->P.n3 : 0u; T.j[q].nout = 0;
+  }
+  T.cnt = 0.;
+}
+void launch_tracer_mean_accum(pomgpu_ctx *c) {
+  MeanTab T;
+  tracer_mean_tab(c, T);
+  LAUNCH(c, k_mean_accum, tracer_mean_grid(c), dim3(256), T);
+}
+static void launch_tracer_mean_snapshot(pomgpu_ctx *c, double *const *dst, const size_t *nout) {
+  MeanTab T;
+  tracer_mean_tab(c, T);
+  for (int q = 0; q < c->ntr; q++) if (dst[q]) { T.j[q].dst = dst[q]; T.j[q].nout = (unsigned)nout[q]; }
+  T.cnt = (double)c->trmean_count;
+  LAUNCH(c, k_mean_snapshot, tracer_mean_grid(c), dim3(256), T);
+}
+extern "C" int pomgpu_write_tracers(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m, int kind, const double *trstats) {
+#ifdef POMGPU_STORE_F32
+  if (c) return pomgpu_fail(c, POMGPU_EINVAL, "write_tracers: not in the fp32-storage variant (3-D arrays are not doubles there)");
+#endif
+  if (!c || !path || !m) return POMGPU_EINVAL;
+  if (!c->ntr) return fail(c, POMGPU_EINVAL, "write_tracers: no tracers are registered (pomgpu_set_tracers)");
+  if (kind != POMGPU_TRFILE_RESTART && kind != POMGPU_TRFILE_OUTPUT && kind != POMGPU_TRFILE_OUTPUT_MEAN)
+    return fail(c, POMGPU_EINVAL, "write_tracers: kind = %d; POMGPU_TRFILE_RESTART (0), _OUTPUT (1) or _OUTPUT_MEAN (2)", kind);
+  const bool mean = kind == POMGPU_TRFILE_OUTPUT_MEAN;
+  if (mean && !c->trmean_acc) return fail(c, POMGPU_EINVAL, "write_tracers: the time-mean output is off (pomgpu_set_mean_output)");
+  if (mean && c->trmean_count < 1)
+    return fail(c, POMGPU_EINVAL, "write_tracers: no step has been accumulated since the switch, pomgpu_set_tracers or the last mean file -- %s is not written", path);
+  (void)hipSetDevice(c->device);
+  const KP &P = c->P;
+  const int ntr = c->ntr;
+  const std::string since = std::string("days since ") + (m->time_start ? m->time_start : "");
+  auto nn = [](const char *stem, int n) { char b[32]; snprintf(b, sizeof b, "%s%02d", stem, n); return std::string(b); };
+  auto volume = [&](const std::string &name, std::vector<int> dims, const std::string &ln, const char *co, const double *dev, int nlev, int tmean) {
+    Var v = mk(name.c_str(), dims, ln.c_str(), "tracer units", co, VOLUME3D, -1, nlev);
+    v.dev = dev; v.tmean = tmean;
+    return v;
+  };
+  Spec S;
+  if (kind == POMGPU_TRFILE_RESTART) {
+    S.dims = {{"time", 1}, {"z", P.kb}, {"y", m->jm_global}, {"x", m->im_global}};
+    S.gatts = {{"title", m->title ? m->title : ""}, {"description", "tracer restart file"}};
+    const int T = 0, Z = 1, Y = 2, X = 3;
+    S.vars.push_back(mk("iint", {}, "i_internal", "model internal step number", NULL, SCALAR, 0, 0, (double)c->con.iint));
+    S.vars.push_back(mk("time", {T}, "time", since.c_str(), NULL, SCALAR, 0, 0, c->con.time));
+    S.vars.push_back(mk("ntr", {}, "number of passive tracers", "dimensionless", NULL, SCALAR, 0, 0, (double)ntr));
+    for (int n = 1; n <= ntr; n++) {
+      S.vars.push_back(mk(nn("nbc", n).c_str(), {}, ("surface condition of tracer " + nn("", n)).c_str(), "1: flux, 3: value", NULL, SCALAR, 0, 0, (double)c->trc[n - 1].nbc));
+      S.vars.push_back(mk(nn("lam", n).c_str(), {}, ("decay rate of tracer " + nn("", n)).c_str(), "1/sec", NULL, SCALAR, 0, 0, c->trc[n - 1].lam));
+    }
+    for (int n = 1; n <= ntr; n++) {
+      const pomgpu_ctx::pomgpu_tracer &t = c->trc[n - 1];
+      S.vars.push_back(volume(nn("tr", n), {Z, Y, X}, "passive tracer " + nn("", n), "east_e north_e zz", t.tr, P.kb, -1));
+      S.vars.push_back(volume(nn("trb", n), {Z, Y, X}, "passive tracer " + nn("", n) + " at time -dt", "east_e north_e zz", t.trb, P.kb, -1));
+      S.vars.push_back(volume(nn("trf", n), {Z, Y, X}, "work array of passive tracer " + nn("", n), "east_e north_e zz", t.trf, P.kb, -1));
+    }
+    return write_file(c, path, m, S);
+  }
+  double st[4 * POMGPU_TRMAX];
+  if (trstats) memcpy(st, trstats, 4 * (size_t)ntr * sizeof(double));   // the caller's rank-reduced values
+  else { const int rcs = pomgpu_tracer_stats(c, st); if (rcs) return rcs; }
+  S.dims = {{"time", 1}, {"z", P.kb}, {"zz", P.kbm1}, {"y", m->jm_global}, {"x", m->im_global}};
+  S.gatts = {{"title", m->title ? m->title : ""}, {"description", "tracer output file"}};
+  const int T = 0, Z = 1, ZZ = 2, Y = 3, X = 4;
+  S.vars.push_back(mk("time", {T}, "time", since.c_str(), NULL, SCALAR, 0, 0, c->con.time));
+  for (int n = 1; n <= ntr; n++) {
+    static const char *const stem[4] = {"tot", "avg", "min", "max"};
+    static const char *const what[4] = {"domain inventory", "domain average", "minimum", "maximum"};
+    static const char *const unit[4] = {"tracer units metre^3", "tracer units", "tracer units", "tracer units"};
+    for (int q = 0; q < 4; q++)
+      S.vars.push_back(mk(nn(stem[q], n).c_str(), {T}, (std::string(what[q]) + " of tracer " + nn("", n)).c_str(), unit[q], NULL, SCALAR, 0, 0, st[4 * (n - 1) + q]));
+  }
+  S.vars.push_back(mk("z", {Z}, "sigma of cell face", "sigma_level", NULL, LEVELS1D, P1_z, P.kb));
+  S.vars.back().atts.push_back({"standard_name", "ocean_sigma_coordinate"});
+  S.vars.back().atts.push_back({"formula_terms", "sigma: z eta: elb depth: h"});
+  S.vars.push_back(mk("zz", {ZZ}, "sigma of cell centre", "sigma_level", NULL, LEVELS1D, P1_zz, P.kbm1));
+  S.vars.back().atts.push_back({"standard_name", "ocean_sigma_coordinate"});
+  S.vars.back().atts.push_back({"formula_terms", "sigma: zz eta: elb depth: h"});
+  for (int n = 1; n <= ntr; n++)
+    S.vars.push_back(volume(nn("tr", n), {T, ZZ, Y, X}, "passive tracer " + nn("", n), "east_e north_e zz", c->trc[n - 1].tr, P.kbm1, n - 1));
+  return write_file(c, path, m, S, mean ? 2 : 0);
 }
 
 // A source list from before the readers moved out names this file for writer and readers alike.  Every list of the project names the

@@ -135,6 +135,109 @@ void launch_domain_stats(pomgpu_ctx *c, double *out_dev) {
   LAUNCH(c, k_domain_stats, dim3(nb), dim3(256), c->P, c->P.s2[7]);          // 2048 x 7 partials fit one 2-D scratch plane (>= 25 cells checked at create)
   LAUNCH(c, k_domain_stats_fin, dim3(1), dim3(256), (const double *)c->P.s2[7], nb, out_dev);
 }
+// ---------------------------------------------------------------------------------------------
+// pomgpu_tracer_stats (include/pomgpu.h): the inventory of every registered tracer in ONE pass over the columns, in the shape of
+// k_domain_stats -- a strided share of the columns per lane, the wavefront shuffle tree, four partials in LDS, one finishing workgroup, no
+// atomics: same launch, same bits.  Per tracer tot = sum trb * dvol with domain_stats' dvol = dx*dy*fsm * dt * dz(k) on its cells
+// (2:imm1 x 2:jmm1, k = 1..kbm1), so that tile sums add up under the host's rank reduction as sum(tb*dvol) does, and min / max of tr over
+// the cells of (1:im, 1:jm, 1:kbm1) with fsm != 0, which are exact whatever the tree's shape.  vtot comes out of the same pass:
+// avg = tot / vtot.  A value's place q says how it is combined: 0 vtot (sum); 1 + 3t, 2 + 3t, 3 + 3t: tot (sum), min, max of tracer t.
+// The loops over the tracers are unrolled to POMGPU_TRMAX with the count as a predicate: every value stays in a register.
+#define TRS_NV (1 + 3 * POMGPU_TRMAX)
+struct TrStatTab { const double *trb[POMGPU_TRMAX], *tr[POMGPU_TRMAX]; int ntr; };
+__device__ __forceinline__ double trs_op(int q, double x, double y) {
+  const int kind = q == 0 ? 0 : (q - 1) % 3;
+  return kind == 0 ? x + y : (kind == 1 ? (y < x ? y : x) : (y > x ? y : x));
+}
+__device__ __forceinline__ double trs_unit(int q) { return (q == 0 || (q - 1) % 3 == 0) ? 0. : ((q - 1) % 3 == 1 ? __DBL_MAX__ : -__DBL_MAX__); }
+__device__ __forceinline__ void trs_block(double (&a)[TRS_NV], double (*part)[TRS_NV]) {   // result in thread 0
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < TRS_NV; q++)
+    for (int off = 32; off > 0; off >>= 1) a[q] = trs_op(q, a[q], __shfl_down(a[q], off, 64));
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < TRS_NV; q++) part[wave][q] = a[q];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < TRS_NV; q++) a[q] = trs_op(q, trs_op(q, trs_op(q, part[0][q], part[1][q]), part[2][q]), part[3][q]);
+  }
+}
+__global__ void __launch_bounds__(256) k_tracer_stats(KP P, TrStatTab T, double *partial) {
+  __shared__ double part[4][TRS_NV];
+  double a[TRS_NV];
+#pragma unroll
+  for (int q = 0; q < TRS_NV; q++) a[q] = trs_unit(q);
+  const unsigned total = (unsigned)P.im * (unsigned)P.jm;       // a level's cells: 32 bits hold them (pomgpu_create: an array is under 4 GiB)
+  for (unsigned n = blockIdx.x * blockDim.x + threadIdx.x; n < total; n += gridDim.x * blockDim.x) {
+    const int j = (int)(n / (unsigned)P.im) + 1, i = (int)(n % (unsigned)P.im) + 1;
+    const bool inner = i >= 2 && i <= P.imm1 && j >= 2 && j <= P.jmm1;
+    const double fs = F2(fsm, i, j);
+    const bool wet = fs != 0.;
+    if (!inner && !wet) continue;
+    const double darea = F2(dx, i, j) * F2(dy, i, j) * fs, dtc = F2(dt, i, j);
+    if (inner)
+      for (int k = 1; k <= P.kbm1; k++) a[0] = a[0] + darea * dtc * F1(dz, k);
+    // tracer by tracer down the column: two of the sixteen array addresses are in use at a time
+#pragma unroll
+    for (int t = 0; t < POMGPU_TRMAX; t++)
+      if (t < T.ntr) {
+        const double *pb = T.trb[t] + IX2(i, j), *px = T.tr[t] + IX2(i, j);
+        double tot = a[1 + 3 * t], mn = a[2 + 3 * t], mx = a[3 + 3 * t];
+        for (int k = 1; k <= P.kbm1; k++) {
+          const double dvol = darea * dtc * F1(dz, k);
+          const size_t e = (size_t)(k - 1) * P.n2;
+          if (inner) tot = tot + pb[e] * dvol;
+          if (wet) {
+            const double x = px[e];
+            mn = x < mn ? x : mn;
+            mx = x > mx ? x : mx;
+          }
+        }
+        a[1 + 3 * t] = tot; a[2 + 3 * t] = mn; a[3 + 3 * t] = mx;
+      }
+  }
+  trs_block(a, part);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < TRS_NV; q++) partial[(size_t)blockIdx.x * TRS_NV + q] = a[q];
+  }
+}
+__global__ void __launch_bounds__(256) k_tracer_stats_fin(const double *partial, int nb, int ntr, double *out) {
+  __shared__ double part[4][TRS_NV];
+  double a[TRS_NV];
+#pragma unroll
+  for (int q = 0; q < TRS_NV; q++) a[q] = trs_unit(q);
+  for (int b = threadIdx.x; b < nb; b += blockDim.x) {
+#pragma unroll
+    for (int q = 0; q < TRS_NV; q++) a[q] = trs_op(q, a[q], partial[(size_t)b * TRS_NV + q]);
+  }
+  trs_block(a, part);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int t = 0; t < POMGPU_TRMAX; t++)
+      if (t < ntr) {
+        out[4 * t] = a[1 + 3 * t];
+        out[4 * t + 1] = a[0] != 0. ? a[1 + 3 * t] / a[0] : 0.;
+        out[4 * t + 2] = a[2 + 3 * t];
+        out[4 * t + 3] = a[3 + 3 * t];
+      }
+  }
+}
+void launch_tracer_stats(pomgpu_ctx *c, double *out_dev) {
+  const long long total = (long long)c->P.im * c->P.jm;
+  int nb = (int)((total + 255) / 256);
+  if (nb > 2048) nb = 2048;
+  if (nb < 1) nb = 1;
+  TrStatTab T;
+  for (int t = 0; t < POMGPU_TRMAX; t++) { T.trb[t] = t < c->ntr ? c->trc[t].trb : NULL; T.tr[t] = t < c->ntr ? c->trc[t].tr : NULL; }
+  T.ntr = c->ntr;
+  // nb x 25 partials fit one 2-D scratch plane: nb = 1 needs 25 cells (checked at create), beyond that 25 per 256 cells
+  LAUNCH(c, k_tracer_stats, dim3(nb), dim3(256), c->P, T, c->P.s2[7]);
+  LAUNCH(c, k_tracer_stats_fin, dim3(1), dim3(256), (const double *)c->P.s2[7], nb, c->ntr, out_dev);
+}
 void launch_check_velocity(pomgpu_ctx *c) {
   const long long total = (long long)c->P.im * c->P.jm;
   int nb = (int)((total + 256 * 8 - 1) / (256 * 8));

@@ -2222,6 +2222,10 @@ static int mean_accumulate(pomgpu_ctx *c) {
   const double *x[9] = {P.x2[X2_uab], P.x2[X2_vab], P.x2[X2_elb], D3(c, u), D3(c, v), D3(c, t), D3(c, s), D3(c, rho), D3(c, w)};
   launch_mean_accum(c, x);
   c->mean_count += 1;
+  if (c->trmean_acc) {                                        // the tracers: tr is final when mode_internal returns (k_tr_update), its ghost
+    launch_tracer_mean_accum(c);                              // lines travelled on this stream.  ONE more launch of k_mean_accum per step
+    c->trmean_count += 1;
+  }
   return POMGPU_OK;
 }
 extern "C" int pomgpu_mean_accumulate(pomgpu_ctx *c) {
@@ -2230,6 +2234,23 @@ extern "C" int pomgpu_mean_accumulate(pomgpu_ctx *c) {
   return mean_accumulate(c);
 }
 extern "C" int pomgpu_mean_count(pomgpu_ctx *c) { return c && c->mean_acc ? c->mean_count : -1; }
+// The tracers' accumulators exist if and only if the mean is on and tracers are registered: both switches end here.  They are created
+// anew at +0.0 with count 0 -- pomgpu_set_mean_output(1) zeroes every sum, pomgpu_set_tracers(n > 0) zeroes the tracers themselves -- and
+// the nine fields' accumulators and count are not looked at
+static void trmean_free(pomgpu_ctx *c) {
+  if (c->trmean_acc) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->trmean_acc); }
+  c->trmean_acc = NULL; c->trmean_stride = 0; c->trmean_count = 0;
+}
+static int trmean_reset(pomgpu_ctx *c) {
+  trmean_free(c);
+  if (!c->mean_acc || !c->ntr) return POMGPU_OK;
+  const size_t stride = c->P.n3 + (c->P.n3 & 1), total = stride * (size_t)c->ntr;
+  double *acc = NULL;
+  if (hipMalloc((void **)&acc, total * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return fail(c, POMGPU_ENOMEM, "no memory for the tracers' mean accumulators (%zu MB)", total * sizeof(double) >> 20); }
+  c->trmean_acc = acc; c->trmean_stride = stride;
+  HIPCHK(c, hipMemsetAsync(acc, 0, total * sizeof(double), c->stream));
+  return POMGPU_OK;
+}
 extern "C" int pomgpu_set_mean_output(pomgpu_ctx *c, int on) {
 #ifdef POMGPU_STORE_F32
   if (c) return fail(c, POMGPU_EINVAL, "set_mean_output: not in the fp32-storage variant (download and write from the host)");
@@ -2240,6 +2261,7 @@ extern "C" int pomgpu_set_mean_output(pomgpu_ctx *c, int on) {
   if (!on) {
     if (c->mean_acc) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->mean_acc); }
     c->mean_acc = NULL; c->mean_count = 0;
+    trmean_free(c);
     return POMGPU_OK;
   }
   // nine accumulators in one allocation, each n2 / n3 doubles: a 3-D one starts on a 16-byte boundary exactly where its mirror does
@@ -2260,7 +2282,7 @@ extern "C" int pomgpu_set_mean_output(pomgpu_ctx *c, int on) {
   for (int q = 0; q < 9; q++) c->mean_off[q] = off[q];
   c->mean_count = 0;
   HIPCHK(c, hipMemsetAsync(c->mean_acc, 0, cur * sizeof(double), c->stream));   // +0.0 everywhere, behind whatever still accumulates
-  return POMGPU_OK;
+  return trmean_reset(c);                                     // and the tracers registered now
 }
 // ---- passive tracers: the state (include/pomgpu.h; the stage: tracer_stage above) ---------------------------------------------------------
 static void tracers_free(pomgpu_ctx *c) {
@@ -2274,6 +2296,9 @@ static void tracers_free(pomgpu_ctx *c) {
   (void)hipFree(c->tr_zero3);
   c->tr_zero3 = NULL;
   c->ntr = 0;
+  trmean_free(c);
+  (void)hipFree(c->d_trstats);
+  c->d_trstats = NULL;
 }
 // doubles of array `which` of a tracer (enum pomgpu_tracer_array), 0 = no such array
 static size_t tracer_len(const pomgpu_ctx *c, int which) {
@@ -2332,7 +2357,7 @@ extern "C" int pomgpu_set_tracers(pomgpu_ctx *c, int n) {
     if ((rc = tracer_zeros(c, &T.trf, c->P.n3))) { tracers_free(c); return rc; }
   }
   c->ntr = n;
-  return POMGPU_OK;
+  return trmean_reset(c);                                     // with the mean on: sums of +0.0 and count 0 for the tracers that are +0.0 now
 }
 static int tracer_args(pomgpu_ctx *c, const char *what, int n, int which, bool has_which = true) {
   if (!c->ntr) return fail(c, POMGPU_EINVAL, "%s: no tracers are registered (pomgpu_set_tracers)", what);
@@ -2386,6 +2411,68 @@ extern "C" int pomgpu_tracer_download(pomgpu_ctx *c, int n, int which, double *h
   if (!src) { memset(host, 0, len * sizeof(double)); return POMGPU_OK; }   // no source array: zeros
   HIPCHK(c, hipMemcpyAsync(host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_tracer_get(pomgpu_ctx *c, int n, int *nbc, double *lam) {
+  if (c) { F32_REFUSE(c, "tracer_get"); }
+  NEED_RAW(c);
+  int rc = tracer_args(c, "tracer_get", n, 0, false);
+  if (rc) return rc;
+  if (nbc) *nbc = c->trc[n - 1].nbc;
+  if (lam) *lam = c->trc[n - 1].lam;
+  return POMGPU_OK;
+}
+// the inventory: tot avg min max per tracer (k_reduce.hip: k_tracer_stats, two launches for all tracers).  The host emulation has no lanes
+// to shuffle between and forms the same four numbers here, the sums in scan order
+extern "C" int pomgpu_tracer_stats(pomgpu_ctx *c, double *out) {
+  if (c) { F32_REFUSE(c, "tracer_stats"); }
+  NEED(c);
+  if (!c->ntr) return fail(c, POMGPU_EINVAL, "tracer_stats: no tracers are registered (pomgpu_set_tracers)");
+  if (!out) return fail(c, POMGPU_EINVAL, "tracer_stats: no host array");
+  if (!c->d_trstats && hipMalloc((void **)&c->d_trstats, 4 * POMGPU_TRMAX * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    c->d_trstats = NULL;
+    return fail(c, POMGPU_ENOMEM, "tracer_stats: no memory for the result");
+  }
+#ifndef POMGPU_EMU
+  launch_tracer_stats(c, c->d_trstats);
+#else
+  {
+    const KP &P = c->P;
+    for (int t = 0; t < c->ntr; t++) {
+      double vt = 0., tot = 0., mn = __DBL_MAX__, mx = -__DBL_MAX__;
+      for (int j = 1; j <= P.jm; j++)
+        for (int i = 1; i <= P.im; i++) {
+          const bool inner = i >= 2 && i <= P.imm1 && j >= 2 && j <= P.jmm1;
+          const double fs = F2(fsm, i, j), darea = F2(dx, i, j) * F2(dy, i, j) * fs, dtc = F2(dt, i, j);
+          for (int k = 1; k <= P.kbm1; k++) {
+            const double dvol = darea * dtc * F1(dz, k), x = c->trc[t].tr[IX3(i, j, k)];
+            if (inner) { vt = vt + dvol; tot = tot + c->trc[t].trb[IX3(i, j, k)] * dvol; }
+            if (fs != 0.) { mn = x < mn ? x : mn; mx = x > mx ? x : mx; }
+          }
+        }
+      c->d_trstats[4 * t] = tot; c->d_trstats[4 * t + 1] = vt != 0. ? tot / vt : 0.; c->d_trstats[4 * t + 2] = mn; c->d_trstats[4 * t + 3] = mx;
+    }
+  }
+#endif
+  HIPCHK(c, hipMemcpyAsync(out, c->d_trstats, 4 * (size_t)c->ntr * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_tracer_mean_count(pomgpu_ctx *c) { return c && c->trmean_acc ? c->trmean_count : -1; }
+extern "C" int pomgpu_tracer_mean_download(pomgpu_ctx *c, int n, double *host) {
+  if (c) { F32_REFUSE(c, "tracer_mean_download"); }
+  NEED_RAW(c);
+  int rc = tracer_args(c, "tracer_mean_download", n, 0, false);
+  if (rc) return rc;
+  if (!host) return fail(c, POMGPU_EINVAL, "tracer_mean_download: no host array");
+  if (!c->trmean_acc) return fail(c, POMGPU_EINVAL, "tracer_mean_download: the time-mean output is off (pomgpu_set_mean_output)");
+  if (c->trmean_count < 1) return fail(c, POMGPU_EINVAL, "tracer_mean_download: no step has been accumulated since the switch, pomgpu_set_tracers or the last mean file");
+  const size_t len = c->P.n3;
+  HIPCHK(c, hipMemcpyAsync(host, c->trmean_acc + (size_t)(n - 1) * c->trmean_stride, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const double cnt = (double)c->trmean_count;
+  for (size_t e = 0; e < len; e++) host[e] = host[e] / cnt;    // the division k_mean_snapshot makes
   return POMGPU_OK;
 }
 static int advance(pomgpu_ctx *c, int more_steps_follow);

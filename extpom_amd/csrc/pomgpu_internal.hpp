@@ -828,6 +828,13 @@ struct pomgpu_ctx {
   int ntr;
   struct pomgpu_tracer { double *trb, *tr, *trf, *clim, *q, *wsurf, *surf, *bd[4]; int nbc; double lam; } trc[POMGPU_TRMAX];
   double *tr_zero3;
+  // the tracers' time mean (pomgpu_api.hip: trmean_alloc): one fp64 accumulator of n3 doubles per tracer, trmean_stride doubles apart
+  // (n3 rounded up to even: each is 16-byte aligned, as tr is) in one allocation, and a count of their own.  They exist if and only if the
+  // mean is on and ntr > 0.  d_trstats: pomgpu_tracer_stats' result on the device (4 x POMGPU_TRMAX doubles), allocated at its first call
+  double *trmean_acc;
+  size_t trmean_stride;
+  int trmean_count;
+  double *d_trstats;
   char err[512];
 };
 // The register-resident column kernels (k_vert.hip: their level loops are unrolled for a template bound, with_kbt) serve this context's
@@ -1052,7 +1059,11 @@ void launch_ztosig_edges(pomgpu_ctx *c, double *t);
 int launch_ztosig_line(pomgpu_ctx *c, int edge, const double *zs, int ks, const double *src, double *out);
 // cdf_out.hip: the time-mean output.  launch_mean_accum: acc = acc + x for the nine fields in one launch, x[q] where field q lives now
 void launch_mean_accum(pomgpu_ctx *c, const double *const *x);
+// the same kernel once more with the tracers' table: trmean_acc[n] = trmean_acc[n] + tr[n] for every registered tracer, ONE launch
+void launch_tracer_mean_accum(pomgpu_ctx *c);
 // k_reduce.hip
+// pomgpu_tracer_stats: tot avg min max of every registered tracer into out_dev (4 x ntr doubles), two launches (not in the host emulation)
+void launch_tracer_stats(pomgpu_ctx *c, double *out_dev);
 // pomgpu_math_probe: n values per operand in device memory, one per lane (gpow15: k_adv.hip; divi, proft_rad_q: k_vert.hip)
 void launch_probe_gpow15(pomgpu_ctx *c, long n, const double *x, double *out);
 void launch_probe_divi(pomgpu_ctx *c, long n, const double *a, const double *b, double *out, int f32);

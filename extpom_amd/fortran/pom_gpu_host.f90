@@ -181,7 +181,8 @@ end subroutine
 ! pomgpu_tune_placement, which refuses while tracers are registered -- gives the context n tracers, all zero; mode_internal then carries
 ! them with the flow.  pom_tracer_put / pom_tracer_get move one array of tracer n (which: 0 trb 1 tr 2 clim 3 source 4 wsurf 5 surf
 ! 6 be 7 bw 8 bn 9 bs, shaped like tb, wtsurf, tbe, tbn); pom_tracer_set: nbc 1 (the flux) or 3 (the surface value), the decay rate in 1/s.
-! Tracers are not in the output or restart files: a host checkpoints trb and tr through pom_tracer_get / pom_tracer_put.
+! Tracers are not in the reference's output or restart files: they have files of their own, write_tracers_pnetcdf and
+! read_tracers_pnetcdf (pom_gpu_io.f90).  pom_tracer_stats: the inventory, out(1:4, n) = tot avg min max of tracer n on THIS rank's tile.
 subroutine pom_tracers(n)
   use pomgpu_iface
   implicit none
@@ -215,6 +216,14 @@ subroutine pom_tracer_set(n, nbc, lam)
   integer, intent(in) :: n, nbc
   double precision, intent(in) :: lam
   if (pomgpu_tracer_set(pom_ctx, int(n, c_int), int(nbc, c_int), real(lam, c_double)) /= 0) error_status = 1
+end subroutine
+
+subroutine pom_tracer_stats(out)
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  double precision, intent(out), target :: out(4, *)
+  if (pomgpu_tracer_stats(pom_ctx, c_loc(out)) /= 0) error_status = 1
 end subroutine
 
 subroutine mean_accumulate

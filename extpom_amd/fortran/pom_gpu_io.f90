@@ -4,6 +4,7 @@
 ! (pomgpu_write_output / pomgpu_write_restart); every rank writes its patch, rank 0 creates the file first.  With the time-mean output on
 ! (pom_output_mean, pom_gpu_host.f90) write_output_pnetcdf writes the same file with the means of its nine time-dependent fields.
 ! read_restart_pnetcdf reads such a file (or one PnetCDF wrote) back into the device state and the COMMON blocks.
+! write_tracers_pnetcdf / read_tracers_pnetcdf are the same for the passive tracers' own files (pomgpu_write_tracers, pomgpu_read_tracers).
 ! cold_start_files is initialize.f:24-36 (initialize_arrays, read_grid, initial_conditions, update_initial, bottom_friction) from the
 ! reference's grid, init and clim files (pomgpu_cold_start).
 ! Link instead of the reference's two writers and its restart reader.  pomgpu_barrier_mpi is the integrator's one-liner
@@ -118,6 +119,112 @@ subroutine read_restart_pnetcdf
   rc = pomgpu_get_con(pom_ctx, c_loc(alpha))       ! time0, time, cont_bry
   if (rc /= 0) error_status = 1
   call pomgpu_download_state
+end subroutine
+
+! The tracers' files (no counterpart in the reference; include/pomgpu.h: pomgpu_write_tracers).  kind 0: the restart kind,
+! <wrk_pth>out/<netcdf_file>.tracer.rst.nc, joined before return as write_restart_pnetcdf's file is; kind 1 / 2: the output kind / its
+! time-mean form, <wrk_pth>out/<netcdf_file>.tracer.<nnnn>.nc with write_output_pnetcdf's counter.  pomgpu_write_file's two passes: rank 0
+! lays the file out, a barrier, everybody else writes.  The statistics are rank-reduced as the reference reduces its own: tot with
+! sum0d_mpi and avg = tot / vtot with domain_stats' vtot, min and max with pomgpu_minmax0d_mpi (pom_gpu_mpi.f90; an identity on one rank).
+! Nothing happens without tracers.
+subroutine write_tracers_pnetcdf(kind)
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  integer, intent(in) :: kind
+  type(pomgpu_file_meta) :: m
+  character(len=400) :: fname
+  character(kind=c_char, len=401), target :: cname
+  character(kind=c_char, len=41), target :: ctitle
+  character(kind=c_char, len=27), target :: cstart
+  real(c_double), target :: ts(4, 8)
+  double precision :: vtot, atot, mtot, stot, tavg, savg, eavg, ekin
+  type(c_ptr) :: pts
+  integer(c_int) :: rc
+  integer :: pass, nprint, n, ntr
+  ntr = pomgpu_tracer_count(pom_ctx)
+  if (ntr <= 0) return
+  if (kind == 0) then
+    write(fname, '(a,''out/'',a,''.tracer.rst.nc'')') trim(wrk_pth), trim(netcdf_file)
+  else
+    nprint = (iint+int(time0*86400./dti))/iprint
+    write(fname, '(a,''out/'',a,''.tracer.'',i4.4,''.nc'')') trim(wrk_pth), trim(netcdf_file), nprint
+  end if
+  cname = trim(fname)//c_null_char
+  ctitle = trim(title)//c_null_char
+  cstart = trim(time_start)//c_null_char
+  call pomgpu_push_con
+  pts = c_null_ptr
+  if (kind /= 0) then
+    call domain_stats(vtot, atot, mtot, stot, tavg, savg, eavg, ekin)   ! rank-reduced vtot
+    if (pomgpu_tracer_stats(pom_ctx, c_loc(ts)) /= 0) error_status = 1
+    do n = 1, ntr
+      call sum0d_mpi(ts(1, n), master_task)
+      call pomgpu_minmax0d_mpi(ts(3, n), ts(4, n), master_task)
+      if (vtot /= 0.d0) then
+        ts(2, n) = ts(1, n) / vtot
+      else
+        ts(2, n) = 0.d0
+      end if
+    end do
+    pts = c_loc(ts)
+  end if
+  if (my_task == 0) write(*,'(/''writing file '',a)') trim(fname)
+  m%title = c_loc(ctitle); m%time_start = c_loc(cstart); m%stats = c_null_ptr
+  m%im_global = im_global; m%jm_global = jm_global
+  m%i0 = i_global(1); m%j0 = j_global(1)
+  do pass = 1, 2                                  ! rank 0 lays the file out, then everybody else writes
+    m%create = 0
+    if (pass == 1 .and. my_task == 0) m%create = 1
+    if ((pass == 1) .eqv. (my_task == 0)) then
+      rc = pomgpu_write_tracers(pom_ctx, c_loc(cname), m, int(kind, c_int), pts)
+      if (rc /= 0) error_status = 1
+    end if
+    call pomgpu_barrier_mpi
+  end do
+  if (kind == 0) then                             ! a restart file is whole when this routine returns
+    if (pomgpu_io_wait(pom_ctx) /= 0) error_status = 1
+    call pomgpu_barrier_mpi
+  end if
+end subroutine
+
+! <wrk_pth>in/<netcdf_file>.tracer.nc, where it exists, into the registered tracers (pomgpu_read_tracers): every rank reads its own patch,
+! ghost lines included; a file with trNN alone is an initial file.  Call it after pom_tracers.  A refusal is printed as the restart
+! reader's is and sets error_status.
+subroutine read_tracers_pnetcdf
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  type(pomgpu_file_meta) :: m
+  character(len=400) :: fname
+  character(kind=c_char, len=401), target :: cname
+  character(kind=c_char), pointer :: msg(:)
+  type(c_ptr) :: pm
+  integer(c_int) :: rc
+  integer :: n
+  logical :: there
+  write(fname, '(a,''in/'',a,''.tracer.nc'')') trim(wrk_pth), trim(netcdf_file)
+  inquire(file=trim(fname), exist=there)
+  if (.not. there) return
+  cname = trim(fname)//c_null_char
+  if (my_task == 0) write(*,'(/''reading file '',a)') trim(fname)
+  m%title = c_null_ptr; m%time_start = c_null_ptr; m%stats = c_null_ptr; m%create = 0
+  m%im_global = im_global; m%jm_global = jm_global
+  m%i0 = i_global(1); m%j0 = j_global(1)
+  rc = pomgpu_read_tracers(pom_ctx, c_loc(cname), m, c_null_ptr, c_null_ptr)
+  if (rc /= 0) then
+    error_status = 1
+    pm = pomgpu_last_error(pom_ctx)                ! names the file and the cause
+    if (c_associated(pm)) then
+      call c_f_pointer(pm, msg, (/512/))
+      n = 0
+      do while (n < 511)
+        if (msg(n+1) == c_null_char) exit
+        n = n + 1
+      end do
+      write(*,'(/i4,''] Error: read_tracers_pnetcdf: '',511a1)') my_task, msg(1:n)
+    end if
+  end if
 end subroutine
 
 ! initialize.f:24-36 without PnetCDF: what initialize does between read_input and the restart reader -- initialize_arrays, read_grid,

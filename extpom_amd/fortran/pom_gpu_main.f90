@@ -23,6 +23,11 @@
 !                                                                <wrk_pth>out/<netcdf_file>.<nnnn>.nc with the means since the last one;
 !                                                                beside the other two, in any order)
 !        ... --cold | --cold-z <state.out> <nsteps> --sss      (surface sets ssurf from the record's SSS: bounds_forcing.f:979 uncommented)
+!        ... --cold | --cold-z <state.out> <nsteps> --tracers <n>     (n passive tracers, pom_tracers: read from <wrk_pth>in/<netcdf_file>.tracer.nc
+!                                                                      where it exists; wherever an output file is written,
+!                                                                      <wrk_pth>out/<netcdf_file>.tracer.<nnnn>.nc beside it -- the mean kind under
+!                                                                      --mean --; <wrk_pth>out/<netcdf_file>.tracer.rst.nc at the end of the run;
+!                                                                      beside the other flags, in any order)
 ! The water files <wrk_pth>in/<netcdf_file>.water.NNNN.nc need no flag: they are registered when record 0000's exists.
 program pom_gpu_main
   use pomgpu_iface
@@ -30,7 +35,7 @@ program pom_gpu_main
   include 'pom.h'
   namelist/pom_nml/ title,wrk_pth,netcdf_file,mode,nadv,nitera,sw,npg,dte,isplit,time_start,nread_rst, &
                     read_rst_file,cont_bry,write_rst,write_rst_file,days,prtd1,prtd2,swtch,ntp,nbct,nbcs
-  integer :: nsteps, nrec, n, rc, n2, n3, nbd
+  integer :: nsteps, nrec, n, rc, n2, n3, nbd, ntrac
   double precision :: vtot, atot, mtot, stot, tavg, savg, eavg, ekin
   double precision, allocatable, target :: tr(:,:,:,:), sr(:,:,:,:)
   character(len=256) :: fin, fout, arg3
@@ -43,7 +48,7 @@ program pom_gpu_main
   nbd = 8*jm_local + 8*im_local + (12+12+6+6)*0   ! filled below
   nbd = 20*jm_local + 20*im_local + 18*jm_local*kb + 18*im_local*kb   ! bdry: 20 J, 20 I... see pom_layout.h
   cold = trim(fin) == '--cold' .or. trim(fin) == '--cold-z'
-  mean = .false.; sss = .false.
+  mean = .false.; sss = .false.; ntrac = 0
   if (trim(fin) == '--cold-z') then         ! the init and the clim file are on z levels (initialize.f:410-422)
     pom_init_on_z = .true.; pom_clim_on_z = .true.
   end if
@@ -60,6 +65,11 @@ program pom_gpu_main
         n = n + 1
         call get_command_argument(n, arg3)
         read(arg3, *) pom_lbry_sides
+      end if
+      if (trim(arg3) == '--tracers') then
+        n = n + 1
+        call get_command_argument(n, arg3)
+        read(arg3, *) ntrac
       end if
       n = n + 1
     end do
@@ -113,15 +123,23 @@ program pom_gpu_main
       rc = pomgpu_set_restore_record(pom_ctx, int(n, c_int), c_loc(tr(1,1,1,n)), c_loc(sr(1,1,1,n)))
     end do
   end if
+  if (ntrac > 0) then                        ! before the mean is switched on: its accumulators are made for the tracers registered then
+    call pom_tracers(ntrac)
+    call read_tracers_pnetcdf                ! <wrk_pth>in/<netcdf_file>.tracer.nc, where it exists
+  end if
   if (mean) call pom_output_mean(.true.)
   if (sss) call pom_surface_sss(.true.)
   do n = 1, nsteps                          ! pom.f:17-19
     iint = iint + 1
     call advance_hot
     if (pom_mean_on .and. iprint > 0) then   ! advance.f:35-38: the mean file in the snapshot's place (Fortran does not short-circuit: iprint is tested first)
-      if (mod(iint, iprint) == 0) call write_output_pnetcdf
+      if (mod(iint, iprint) == 0) then
+        call write_output_pnetcdf
+        if (ntrac > 0) call write_tracers_pnetcdf(2)   ! the tracers' means, beside the nine fields'
+      end if
     end if
   end do
+  if (ntrac > 0) call write_tracers_pnetcdf(0)   ! <wrk_pth>out/<netcdf_file>.tracer.rst.nc: trb, tr and the work array trf
   if (pom_mean_on) call pom_output_mean(.false.)
   my_task = 0; master_task = 0
   call domain_stats(vtot, atot, mtot, stot, tavg, savg, eavg, ekin)   ! print_section's sums, no state download needed
@@ -178,6 +196,11 @@ subroutine bcast0d_mpi(work, from)
   implicit none
   double precision work
   integer from
+end subroutine
+subroutine pomgpu_minmax0d_mpi(mn, mx, to)
+  implicit none
+  double precision mn, mx
+  integer to
 end subroutine
 subroutine pomgpu_barrier_mpi               ! pom_gpu_io.f90's barrier between ranks: one task, nothing to wait for
 end subroutine

@@ -3,8 +3,8 @@
 ! found (:34-122) are handed to the library's MPI mover (libpomgpu_mpi.so, extpom_amd/csrc/mpi_mover.c) -- from then on the
 ! library packs, moves and unpacks at every exchange point of the hot path by itself, and the 2-D external mode runs on a
 ! wide-halo copy of the tile.  The scalar reductions print_section / the output writers need (sum0d_mpi, bcast0d_mpi,
-! parallel_mpi.f:482-513) and the barrier between the ranks' writes into one file are plain MPI calls on pom_comm; an
-! integrator who keeps the reference's parallel_mpi.f links ITS sum0d_mpi / bcast0d_mpi instead of these two.
+! parallel_mpi.f:482-513; pomgpu_minmax0d_mpi for the tracers' files) and the barrier between the ranks' writes into one file are plain
+! MPI calls on pom_comm; an integrator who keeps the reference's parallel_mpi.f links ITS sum0d_mpi / bcast0d_mpi instead of these two.
 subroutine pomgpu_host_connect_mpi
   use pomgpu_iface
   implicit none
@@ -50,6 +50,19 @@ subroutine bcast0d_mpi(work, from)
   double precision work
   integer from, ierr
   call mpi_bcast(work, 1, mpi_double_precision, from, pom_comm, ierr)
+end subroutine
+
+! the minimum of mn and the maximum of mx over the ranks, on rank `to` (write_tracers_pnetcdf: the tracers' min and max)
+subroutine pomgpu_minmax0d_mpi(mn, mx, to)
+  implicit none
+  include 'mpif.h'
+  include 'pom.h'
+  double precision mn, mx, tmp
+  integer to, ierr
+  call mpi_reduce(mn, tmp, 1, mpi_double_precision, mpi_min, to, pom_comm, ierr)
+  if (my_task == to) mn = tmp
+  call mpi_reduce(mx, tmp, 1, mpi_double_precision, mpi_max, to, pom_comm, ierr)
+  if (my_task == to) mx = tmp
 end subroutine
 
 subroutine pomgpu_barrier_mpi

@@ -149,6 +149,26 @@ module pomgpu_iface
     integer(c_int) function pomgpu_tracer_set(ctx, n, nbc, lam) bind(C, name='pomgpu_tracer_set')
       import; type(c_ptr), value :: ctx; integer(c_int), value :: n, nbc; real(c_double), value :: lam
     end function
+    ! the tracers' files, means and inventory (include/pomgpu.h): kind 0 restart, 1 output, 2 output mean; trstats: 4 x ntr rank-reduced
+    ! values (tot avg min max per tracer) or c_null_ptr; time_out / iint_out may be c_null_ptr
+    integer(c_int) function pomgpu_write_tracers(ctx, path, meta, kind, trstats) bind(C, name='pomgpu_write_tracers')
+      import; type(c_ptr), value :: ctx, path, trstats; type(pomgpu_file_meta) :: meta; integer(c_int), value :: kind
+    end function
+    integer(c_int) function pomgpu_read_tracers(ctx, path, meta, time_out, iint_out) bind(C, name='pomgpu_read_tracers')
+      import; type(c_ptr), value :: ctx, path, time_out, iint_out; type(pomgpu_file_meta) :: meta
+    end function
+    integer(c_int) function pomgpu_tracer_stats(ctx, out) bind(C, name='pomgpu_tracer_stats')
+      import; type(c_ptr), value :: ctx, out   ! out(4, ntr)
+    end function
+    integer(c_int) function pomgpu_tracer_get(ctx, n, nbc, lam) bind(C, name='pomgpu_tracer_get')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: n; integer(c_int) :: nbc; real(c_double) :: lam
+    end function
+    integer(c_int) function pomgpu_tracer_mean_count(ctx) bind(C, name='pomgpu_tracer_mean_count')
+      import; type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function pomgpu_tracer_mean_download(ctx, n, host) bind(C, name='pomgpu_tracer_mean_download')
+      import; type(c_ptr), value :: ctx, host; integer(c_int), value :: n
+    end function
     integer(c_int) function pomgpu_write_restart(ctx, path, meta) bind(C, name='pomgpu_write_restart')
       import; type(c_ptr), value :: ctx, path; type(pomgpu_file_meta) :: meta
     end function

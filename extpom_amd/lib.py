@@ -113,6 +113,12 @@ _SIGS = {
     "pomgpu_tracer_upload": (_I, [_P, _I, _I, _P]),
     "pomgpu_tracer_download": (_I, [_P, _I, _I, _P]),
     "pomgpu_tracer_set": (_I, [_P, _I, _I, ctypes.c_double]),
+    "pomgpu_tracer_get": (_I, [_P, _I, ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_double)]),
+    "pomgpu_tracer_stats": (_I, [_P, ctypes.POINTER(ctypes.c_double)]),
+    "pomgpu_tracer_mean_count": (_I, [_P]),
+    "pomgpu_tracer_mean_download": (_I, [_P, _I, _P]),
+    "pomgpu_write_tracers": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta), _I, ctypes.POINTER(ctypes.c_double)]),
+    "pomgpu_read_tracers": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "pomgpu_write_restart": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
     "pomgpu_read_restart": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "pomgpu_set_forcing_files": (_I, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),

@@ -263,13 +263,26 @@ class PomGpu:
         self._chk(self.L.pomgpu_domain_stats(self.h, out, 1 if sums_only else 0), "domain_stats")
         return tuple(out)
 
-    def write_file(self, kind, path, title="", time_start="", im_global=None, jm_global=None, create=True, stats=None):
+    TRACER_FILE_KINDS = {"tracer_restart": 0, "tracer_output": 1, "tracer_output_mean": 2}
+
+    def write_file(self, kind, path, title="", time_start="", im_global=None, jm_global=None, create=True, stats=None, trstats=None):
         """kind = "output" | "restart": the reference's NetCDF (CDF-2) files without PnetCDF (io_pnetcdf.F:57-410,
         :1661-2083); this tile's patch at (i_off+1, j_off+1) of the global grid.  kind = "output_mean": the output file with the
-        time means of uab vab elb u v t s rho w since set_mean_output or the last such file in place of their values now"""
+        time means of uab vab elb u v t s rho w since set_mean_output or the last such file in place of their values now.
+        kind = "tracer_restart" | "tracer_output" | "tracer_output_mean": the tracers' own files (pomgpu_write_tracers); trstats: the
+        rank-reduced (ntr, 4) statistics of the two output kinds, None = this tile's own"""
         st = self.st
         m = _lib.FileMeta(title.encode(), time_start.encode(), im_global or st.im, jm_global or st.jm, st.i_off + 1, st.j_off + 1,
                           1 if create else 0, (ctypes.c_double * 8)(*stats) if stats is not None else None)
+        if kind in self.TRACER_FILE_KINDS:
+            ts = None
+            if trstats is not None:
+                flat = [float(x) for x in np.asarray(trstats, dtype=np.float64).ravel()]
+                if len(flat) != 4 * self.tracer_count():
+                    raise ValueError(f"write_file: trstats holds {len(flat)} values, not 4 x {self.tracer_count()}")
+                ts = (ctypes.c_double * len(flat))(*flat)
+            self._chk(self.L.pomgpu_write_tracers(self.h, str(path).encode(), ctypes.byref(m), self.TRACER_FILE_KINDS[kind], ts), "write_" + kind)
+            return
         fn = {"output": self.L.pomgpu_write_output, "output_mean": self.L.pomgpu_write_output_mean, "restart": self.L.pomgpu_write_restart}[kind]
         self._chk(fn(self.h, str(path).encode(), ctypes.byref(m)), "write_" + kind)
 
@@ -338,6 +351,37 @@ class PomGpu:
     def set_tracer(self, n: int, nbc: int = 1, decay: float = 0.0):
         """pomgpu_tracer_set: surface condition 1 (the flux wsurf) or 3 (the value surf), and the decay rate in 1/s"""
         self._chk(self.L.pomgpu_tracer_set(self.h, int(n), int(nbc), float(decay)), "tracer_set")
+
+    def tracer_get(self, n: int):
+        """pomgpu_tracer_get: (nbc, decay) of tracer n as set_tracer or a tracer file left them"""
+        nbc, lam = ctypes.c_int(), ctypes.c_double()
+        self._chk(self.L.pomgpu_tracer_get(self.h, int(n), ctypes.byref(nbc), ctypes.byref(lam)), "tracer_get")
+        return nbc.value, lam.value
+
+    def tracer_stats(self):
+        """pomgpu_tracer_stats: (ntr, 4) -- tot avg min max per tracer, reduced on the device; tot is this tile's share of the inventory"""
+        out = np.empty((self.tracer_count(), 4))
+        self._chk(self.L.pomgpu_tracer_stats(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "tracer_stats")
+        return out
+
+    def tracer_mean_count(self) -> int:
+        """steps accumulated into the tracers' means; -1 unless the mean is on and tracers are registered"""
+        return int(self.L.pomgpu_tracer_mean_count(self.h))
+
+    def tracer_mean(self, n: int):
+        """pomgpu_tracer_mean_download: accumulator / count of tracer n, shaped like tr; resets nothing"""
+        out = np.empty(self.tracer_shape("tr"))
+        self._chk(self.L.pomgpu_tracer_mean_download(self.h, int(n), self._p(out)), "tracer_mean_download")
+        return out
+
+    def read_tracers(self, path, im_global=None, jm_global=None):
+        """pomgpu_read_tracers: this tile's patch of trNN (and trbNN, trfNN, nbcNN, lamNN where the file has them) of every registered
+        tracer from a classic NetCDF file straight into the device arrays.  Returns (time, iint) of the file, applied to nothing."""
+        st = self.st
+        m = _lib.FileMeta(b"", b"", im_global or st.im, jm_global or st.jm, st.i_off + 1, st.j_off + 1, 0, None)
+        t, ii = ctypes.c_double(), ctypes.c_double()
+        self._chk(self.L.pomgpu_read_tracers(self.h, str(path).encode(), ctypes.byref(m), ctypes.byref(t), ctypes.byref(ii)), "read_tracers")
+        return t.value, ii.value
 
     def read_restart(self, path, im_global=None, jm_global=None):
         """read_restart_pnetcdf (io_pnetcdf.F:2420-2768) without PnetCDF: this tile's patch of the 37 restart fields from a classic

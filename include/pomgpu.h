@@ -554,8 +554,8 @@ int pomgpu_write_output_mean(pomgpu_ctx *ctx, const char *path, const pomgpu_fil
  *   5. bcond(4)'s lines for T with trf, tr, trb[ewns] in place of uf, t, tb[ewns], and its mask on levels 1..kbm1;
  *   6. tr = tr + .5*smoth*(trf + trb - 2.*tr); trb = tr; tr = trf on the whole arrays.  No restore_interior, no dens.
  * The work array trf is the library's own; its level kb is +0.0.  Tracers are not in the output, restart or mean files (their schemas are
- * the reference's): a host checkpoints through pomgpu_tracer_download and _upload of TRB and TR.  pomgpu_upload, pomgpu_cold_start and
- * pomgpu_read_restart do not touch them.
+ * the reference's): they have a file family of their own, below (pomgpu_write_tracers, pomgpu_read_tracers).  pomgpu_upload,
+ * pomgpu_cold_start and pomgpu_read_restart do not touch them.
  * pomgpu_set_tracers: n > 0 allocates n tracers (or keeps the allocation of a context that has n already) and sets every array of theirs
  * to +0.0, nbc to 1, lam to 0, no source; n == 0 frees them.  POMGPU_EINVAL: n outside 0..POMGPU_MAXTRACERS, the fp32-storage variants, a
  * 2-D-only context.
@@ -576,6 +576,53 @@ int pomgpu_tracer_count(pomgpu_ctx *ctx);
 int pomgpu_tracer_upload(pomgpu_ctx *ctx, int n, int which, const double *host);
 int pomgpu_tracer_download(pomgpu_ctx *ctx, int n, int which, double *host);
 int pomgpu_tracer_set(pomgpu_ctx *ctx, int n, int nbc, double lam);
+/* ---- tracer files, means and inventory (off unless called: with no tracers registered, or with these entry points unused, every byte
+ * and every launch is as without them) ----------------------------------------------------------------------------------------------------
+ * pomgpu_tracer_get: nbc and lam of tracer n as pomgpu_tracer_set (or a file) left them; either pointer may be NULL.
+ * pomgpu_tracer_stats: the inventory, out[4 * (n-1) + 0..3] = tot avg min max of tracer n, reduced on the device in one pass over the
+ * columns for all tracers (two launches, a fixed-shape tree, no atomics: same launch, same bits).  tot = sum trb * dx*dy*fsm*dt*dz(k) over
+ * 2:imm1 x 2:jmm1, k = 1..kbm1 -- domain_stats' sum(tb*dvol) with trb in tb's place, so tile sums add up under the host's rank reduction;
+ * avg = tot / vtot with vtot from the same pass (0 where vtot is 0); min, max of tr over the cells of (1:im, 1:jm, 1:kbm1) with fsm != 0.
+ * Time mean: while the mean is on (pomgpu_set_mean_output) AND tracers are registered the library keeps one more fp64 accumulator of n3
+ * doubles per tracer, with a count of their own.  pomgpu_set_mean_output(1) creates and zeroes them for the tracers registered then;
+ * pomgpu_set_tracers(n > 0) while the mean is on creates them anew at +0.0 with count 0 (it zeroes the tracers themselves) and leaves the
+ * nine fields' sums and count alone; pomgpu_set_tracers(0) and pomgpu_set_mean_output(0) free them.  pomgpu_mean_accumulate -- called by
+ * pomgpu_advance / pomgpu_run as before -- adds tr of every tracer with ONE fp64 add per cell: the nine fields' kernel launched once more
+ * with the tracers' table, i.e. ONE added launch per step whatever the number of tracers, and none without tracers or with the mean off.
+ * pomgpu_tracer_mean_count: steps accumulated, -1 while there are no tracer accumulators.  pomgpu_tracer_mean_download: acc / (double)count
+ * of tracer n, n3 doubles shaped like tr; resets nothing; POMGPU_EINVAL at count 0 or without accumulators.
+ * pomgpu_write_tracers: one CDF-2 file of `kind`, laid out and written as pomgpu_write_output writes (meta->create, every rank its patch,
+ * asynchronous, joined by pomgpu_io_wait); NN is the tracer number, two digits; everything is NC_DOUBLE.
+ *   POMGPU_TRFILE_RESTART  description "tracer restart file"; dimensions time = 1, z = kb, y, x; iint (scalar), time {time}, ntr (scalar);
+ *     nbcNN, lamNN (scalars) per tracer; then per tracer trNN, trbNN, trfNN (z, y, x), all kb levels, as pomgpu_tracer_download shows them
+ *     and trf straight from the work array: trf survives between steps unmasked and smol_adif reads its edge lines when nitera > 1, so
+ *     trb and tr alone are not the state of the run.
+ *   POMGPU_TRFILE_OUTPUT  description "tracer output file"; the output file's dimensions time, z, zz, y, x; time; per tracer totNN avgNN
+ *     minNN maxNN {time}; z, zz; per tracer trNN (time, zz, y, x).  trstats: 4 * ntr rank-reduced values in pomgpu_tracer_stats' order,
+ *     as meta->stats is for the output file; NULL: this tile's own.
+ *   POMGPU_TRFILE_OUTPUT_MEAN  the same file with acc / count in place of trNN: one kernel pass stores the quotient into the snapshot and
+ *     +0.0 into the accumulator, the tracers' count returns to 0; `time` and the statistics are as of the call.  Count 0 or no accumulators:
+ *     POMGPU_EINVAL, no file touched, nothing changed.
+ * POMGPU_EINVAL too: no tracers registered, an unknown kind, a tile that does not fit the global grid, the fp32-storage variants.
+ * pomgpu_read_tracers: a classic NetCDF file (CDF-1 or CDF-2) into the registered tracers; variables are found BY NAME, order, extra
+ * variables and attributes do not matter.  For n = 1..ntr trNN is required: NC_DOUBLE, not a record variable, (kb, jm_global, im_global).
+ * trbNN / trfNN are optional and an absent one takes trNN's values (a file with trNN alone is an initial file any tool can write); a
+ * present one must have trNN's type and shape.  nbcNN / lamNN are optional and applied as pomgpu_tracer_set would; nbc other than 1 or 3 is
+ * refused.  Tracers of the file beyond ntr are ignored.  The tile's (im, jm) patch at (i0, j0) lands in X(1:im, 1:jm, 1:kb); cells
+ * beyond keep what they held; clim source wsurf surf be bw bn bs, the flow and every accumulator are not touched.  *time_out / *iint_out
+ * (either may be NULL) return the file's `time` / `iint`, 0 where absent; they are applied to nothing.  The data path is
+ * pomgpu_read_restart's -- pinned bands, a copy stream -- with one kernel behind each copy that reverses the staged bytes once and stores
+ * them to one, two or three arrays.  No message round: on tiles every rank reads its own patch, ghost lines included.  Every refusal
+ * comes BEFORE any array changes, with POMGPU_EINVAL, error_status = 1 and the cause in pomgpu_last_error: no tracers registered; a
+ * required variable absent, of another type or shape, or a record variable; a file shorter than a variable's begin + size; any other
+ * magic (CDF-5, HDF5); a tile that does not fit the global grid; the fp32-storage variants; a 2-D-only context. */
+enum { POMGPU_TRFILE_RESTART = 0, POMGPU_TRFILE_OUTPUT = 1, POMGPU_TRFILE_OUTPUT_MEAN = 2 };
+int pomgpu_write_tracers(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta, int kind, const double *trstats);
+int pomgpu_read_tracers(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta, double *time_out, double *iint_out);
+int pomgpu_tracer_stats(pomgpu_ctx *ctx, double *out);            /* 4 * ntr doubles: tot avg min max per tracer */
+int pomgpu_tracer_get(pomgpu_ctx *ctx, int n, int *nbc, double *lam);
+int pomgpu_tracer_mean_count(pomgpu_ctx *ctx);                    /* -1: no tracer accumulators */
+int pomgpu_tracer_mean_download(pomgpu_ctx *ctx, int n, double *host);   /* acc / count, n3 doubles */
 
 /* ---- the hot path: kernels (solver.f, bounds_forcing.f), device-resident ---------------- */
 int pomgpu_advave(pomgpu_ctx *ctx);              /* solver.f:6-198   */
