@@ -410,6 +410,13 @@ __global__ void k_copy3(KP P, double *dst, const double *src) {
 __device__ __forceinline__ void c_copy3(const KP &P, const int i, const int j, const int k, double *dst, const double *src) {
   G3(dst, i, j, k) = G3(src, i, j, k);
 }
+// aam_canonical (pomgpu_api.hip): what k_advct_col<*, true> wrote of aam -- levels 1..kbm1 -- from the spare array back into the slot
+__device__ __forceinline__ void c_aam_copy(const KP &P, const int i, const int j, const int k, double *dst, const double *src) {
+  if (k <= P.kbm1) G3(dst, i, j, k) = G3(src, i, j, k);
+}
+__global__ void k_aam_copy(KP P, double *dst, const double *src) {
+  MARCH3(c_aam_copy(P, i, j, k, dst, src))
+}
 __device__ __forceinline__ double advt2_xdiff(const KP &P, const double *fb, const double *fc, int i, int j, int k) {
   const double am = 0.5 * (aam_(i, j, k) + aam_(i - 1, j, k));
   return -am * (h_(i, j) + h_(i - 1, j)) * P.tprni *
@@ -876,16 +883,7 @@ __device__ __forceinline__ double aam_point(const KP &P, double dx, double dy, d
          sqrt(sq((u_e - u_c) / dx) + sq((v_n - v_c) / dy) +
               .5 * sq(.25 * (u_n + u_ne - u_s - u_se) / dy + .25 * (v_e + v_ne - v_w - v_nw) / dx));
 }
-// the same with the four divisions by dx, dy through divi() (their reciprocals from k_coef_static: correctly rounded quotients, the same
-// bits -- pomgpu_internal.hpp).  The counters put k_aam_pair on its arithmetic, not on memory (profiles/round3_pmc_kernels.txt: VALU
-// 0.13 of every wave's cycles at 8 waves per SIMD): 8 division macros (~69 cycles each) + 2 square roots per lane; forming the
-// reciprocals in the kernel (round 2) only moved the divisions.
-__device__ __forceinline__ double aam_point_r(const KP &P, const InvD &dx, const InvD &dy, double u_c, double u_e, double u_n, double u_ne, double u_s,
-                                              double u_se, double v_c, double v_n, double v_e, double v_ne, double v_w, double v_nw) {
-  return P.horcon * dx.b * dy.b *
-         sqrt(sq(divi(u_e - u_c, dx)) + sq(divi(v_n - v_c, dy)) +
-              .5 * sq(divi(.25 * (u_n + u_ne - u_s - u_se), dy) + divi(.25 * (v_e + v_ne - v_w - v_nw), dx)));
-}
+// aam_point_r, the same with the four divisions by dx, dy through divi(): pomgpu_internal.hpp (k_advct_col<*, true> forms aam with it too)
 // AAM_KCH levels per wavefront, the operands of level k+1 requested while level k is worked on: one level per wavefront was 1.3 M
 // wavefronts of seven loads, ~600 cycles of dependent fp64 and two stores each -- 4.0 TB/s of real traffic, bound by that chain at
 // 8 waves per SIMD (neither memory nor arithmetic: the divisions through reciprocals bought 1.3 %).
@@ -996,6 +994,7 @@ void launch_advt2_step(pomgpu_ctx *c, const double *fbmem, const double *f, cons
 void launch_mask3(pomgpu_ctx *c, double *a, const double *m2) { LAUNCH(c, k_mask3, gridm(c->P), blk2(), c->P, a, m2); }
 void launch_smol(pomgpu_ctx *c, const double *ff) { LAUNCH(c, k_smol, gridm(c->P), blk2(), c->P, ff); }
 void launch_copy3(pomgpu_ctx *c, double *dst, const double *src) { LAUNCH(c, k_copy3, gridm(c->P), blk2(), c->P, dst, src); }
+void launch_aam_copy(pomgpu_ctx *c, double *dst, const double *src) { LAUNCH(c, k_aam_copy, gridm(c->P), blk2(), c->P, dst, src); }
 void launch_advt2_diff(pomgpu_ctx *c, const double *fb, const double *fc, double *ff) { LAUNCH(c, k_advt2_diff, gridm(c->P), blk2(), c->P, fb, fc, ff); }
 // rt_flags: the words of this step's launch_advt2x2_col are valid (pomgpu_api.hip decides); ts_rt_flags of the event profile counts the
 // launches that read them, a count without events as profq_ld_store

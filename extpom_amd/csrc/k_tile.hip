@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
   const double *ps[NS];
 #pragma unroll
   for (int f = 0; f < NF; f++) { ps[f] = A.fb[f]; ps[NF + f] = A.fcl[f]; bff[f] = BUF3(A.ff[f]); }
-  ps[AM] = A3(aam); ps[VV] = A3(v); bo[0] = BUF3(A3(u)); bo[1] = BUF3(A3(w));
+  ps[AM] = P.aamc; ps[VV] = A3(v); bo[0] = BUF3(A3(u)); bo[1] = BUF3(A3(w));
 #pragma unroll
   for (int x = 0; x < NS; x++) bs[x] = BUF3(ps[x]);
   const RowShare<NS> S = rowshare_setup<NS>(P, r, j, j0w, i);
@@ -213,7 +213,7 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
     nb.s[VV] = uvm_fix(nb.s[VV], uvm_of<1>(P, i, js)); nb.n[VV] = uvm_fix(nb.n[VV], uvm_of<1>(P, i, jn));
 #endif
     const pomgpu_ct am_c = cur.c[AM], u_c = uvm_fix(cur.o[0], mu), w_c = cur.o[1];
-    const pomgpu_ct am_w = halo_w(am_c, [&] { return F3(aam, iw, jc, L); });
+    const pomgpu_ct am_w = halo_w(am_c, [&] { return G3(P.aamc, iw, jc, L); });
     InvDc dzk; dzk.b = dzk.y = 0.;
     if (L >= 2) { dzk.b = F1(dz, L - 1); dzk.y = R1(dz, L - 1); }
     if constexpr (RTF) {                                    // cur holds level min(L, kbm1); padding and halo lanes answer 0
@@ -242,7 +242,7 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advt2_col(KP P, TFields A) {
         const FaceT xw = advt2_face(tprni, cw, u_c, fb_c, fb_w, fc_c, fc_w, am_c, am_w);
         auto east = [&] {                                   // emulation only: the east face from memory
           return advt2_face(tprni, coef_x(P, ie, jc), uvm_ld<0>(P, ie, jc, L), G3(A.fb[f], ie, jc, L), fb_c, G3(A.fcl[f], ie, jc, L), fc_c,
-                            F3(aam, ie, jc, L), am_c);
+                            G3(P.aamc, ie, jc, L), am_c);
         };
         FaceT xe;
         xe.adv = halo_e(xw.adv, [&] { return east().adv; });
@@ -345,7 +345,7 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
   const double *ps[NS];
 #pragma unroll
   for (int f = 0; f < NF; f++) { ps[f] = A.q[f]; ps[NF + f] = A.qb[f]; bqf[f] = BUF3(A.qf[f]); }
-  ps[AM] = A3(aam); ps[VV] = A3(v); bo[0] = BUF3(A3(u)); bo[1] = BUF3(A3(w));
+  ps[AM] = P.aamc; ps[VV] = A3(v); bo[0] = BUF3(A3(u)); bo[1] = BUF3(A3(w));
 #pragma unroll
   for (int x = 0; x < NS; x++) bs[x] = BUF3(ps[x]);
   const RowShare<NS> S = rowshare_setup<NS>(P, r, j, j0w, i);
@@ -417,7 +417,7 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
 #endif
     const pomgpu_ct am_c = cur.c[AM];
     const pomgpu_ct am_s = nb.s[AM], am_n = nb.n[AM], v_n = nb.n[VV];
-    const pomgpu_ct am_w = halo_w(am_c, [&] { return F3(aam, iw, jc, L); });
+    const pomgpu_ct am_w = halo_w(am_c, [&] { return G3(P.aamc, iw, jc, L); });
     pomgpu_ct w_c, ue_c = 0.;
     if constexpr (WF) {
       ue_c = halo_e(u_c, [&] { return uvm_ld<0>(P, ie, jc, L); });
@@ -444,8 +444,8 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
         const pomgpu_ct xw = advq_face(cw, q_c, q_w, u_c, u_m, am_c, am_w, am_m, am_w_prv, qb_c, qb_w);
         xw_c = xw;
         xe_c = halo_e(xw, [&] {                             // emulation only: the east face from memory
-          return advq_face(coefq_x(P, ie, jc), G3(A.q[f], ie, jc, L), q_c, uvm_ld<0>(P, ie, jc, L), uvm_ld<0>(P, ie, jc, L - 1), F3(aam, ie, jc, L), am_c,
-                           F3(aam, ie, jc, L - 1), am_m, G3(A.qb[f], ie, jc, L), qb_c);
+          return advq_face(coefq_x(P, ie, jc), G3(A.q[f], ie, jc, L), q_c, uvm_ld<0>(P, ie, jc, L), uvm_ld<0>(P, ie, jc, L - 1), G3(P.aamc, ie, jc, L), am_c,
+                           G3(P.aamc, ie, jc, L - 1), am_m, G3(A.qb[f], ie, jc, L), qb_c);
         });
         ys_c = advq_face(cs, q_c, nb.s[f], v_c, v_m, am_c, am_s, am_m, ams_m, qb_c, nb.s[NF + f]);
         yn_c = advq_face(cn, nb.n[f], q_c, v_n, vn_m, am_n, am_c, amn_m, am_m, nb.n[NF + f], qb_c);
@@ -501,33 +501,34 @@ __global__ void __launch_bounds__(64 * LDS_ROWS) k_advq_col(KP P, QFields A, int
 // no lane ever needs a mid-iteration fallback load (vmcnt is in-order) and no flux is evaluated
 // from memory.  Wave w covers columns 62w .. 62w+63.
 // the same quantities evaluated from memory (emulation fallbacks only); i, j inside the tile
-__device__ double advct_xf_mem(const KP &P, int i, int j, int k) {                 // x-eq. xflux, 2<=j
+// am: the array that holds the aam being read (its slot, or the spare array while k_advct_col<*, true> reads it there)
+__device__ double advct_xf_mem(const KP &P, const double *am, int i, int j, int k) {                 // x-eq. xflux, 2<=j
   if (i < 2 || i > P.imm1) return 0.;
   double xf = .125 * (K2(DTSX, i + 1, j) * F3(u, i + 1, j, k) + K2(DTSX, i, j) * F3(u, i, j, k)) * (F3(u, i + 1, j, k) + F3(u, i, j, k));
-  xf = xf - F2(dt, i, j) * F3(aam, i, j, k) * 2. * (F3(ub, i + 1, j, k) - F3(ub, i, j, k)) / F2(dx, i, j);
+  xf = xf - F2(dt, i, j) * G3(am, i, j, k) * 2. * (F3(ub, i + 1, j, k) - F3(ub, i, j, k)) / F2(dx, i, j);
   return F2(dy, i, j) * xf;
 }
 __device__ double advct_curv_mem(const KP &P, int i, int j, int k) {
   if (i < 2 || i > P.imm1 || j < 2 || j > P.jmm1) return 0.;
   return .25 * ((F3(v, i, j + 1, k) + F3(v, i, j, k)) * K2(CVA, i, j) - (F3(u, i + 1, j, k) + F3(u, i, j, k)) * K2(CVB, i, j)) / F2(art, i, j);
 }
-__device__ double advct_xg_mem(const KP &P, int i, int j, int k) {                 // y-eq. xflux at corner (i,j), 2<=i, 2<=j<=jmm1
+__device__ double advct_xg_mem(const KP &P, const double *am, int i, int j, int k) {                 // y-eq. xflux at corner (i,j), 2<=i, 2<=j<=jmm1
   double xg = .125 * (K2(DTSX, i, j) * F3(u, i, j, k) + K2(DTSX, i, j - 1) * F3(u, i, j - 1, k)) * (F3(v, i, j, k) + F3(v, i - 1, j, k));
-  const double dtaam = .25 * K2(DT4, i, j) * (F3(aam, i, j, k) + F3(aam, i - 1, j, k) + F3(aam, i, j - 1, k) + F3(aam, i - 1, j - 1, k));
+  const double dtaam = .25 * K2(DT4, i, j) * (G3(am, i, j, k) + G3(am, i - 1, j, k) + G3(am, i, j - 1, k) + G3(am, i - 1, j - 1, k));
   const double dy4 = K2(DY4, i, j);
   xg = xg - dtaam * ((F3(ub, i, j, k) - F3(ub, i, j - 1, k)) / dy4 + (F3(vb, i, j, k) - F3(vb, i - 1, j, k)) / K2(DX4, i, j));
   return .25 * dy4 * xg;
 }
-__device__ double advct_yf_mem(const KP &P, int i, int j, int k) {                 // x-eq. yflux at corner (i,j), 2<=i<=imm1, 2<=j
+__device__ double advct_yf_mem(const KP &P, const double *am, int i, int j, int k) {                 // x-eq. yflux at corner (i,j), 2<=i<=imm1, 2<=j
   double yf = .125 * (K2(DTSY, i, j) * F3(v, i, j, k) + K2(DTSY, i - 1, j) * F3(v, i - 1, j, k)) * (F3(u, i, j, k) + F3(u, i, j - 1, k));
-  const double dtaam = .25 * K2(DT4, i, j) * (F3(aam, i, j, k) + F3(aam, i - 1, j, k) + F3(aam, i, j - 1, k) + F3(aam, i - 1, j - 1, k));
+  const double dtaam = .25 * K2(DT4, i, j) * (G3(am, i, j, k) + G3(am, i - 1, j, k) + G3(am, i, j - 1, k) + G3(am, i - 1, j - 1, k));
   const double dx4 = K2(DX4, i, j);
   yf = yf - dtaam * ((F3(ub, i, j, k) - F3(ub, i, j - 1, k)) / K2(DY4, i, j) + (F3(vb, i, j, k) - F3(vb, i - 1, j, k)) / dx4);
   return .25 * dx4 * yf;
 }
-__device__ double advct_yg_mem(const KP &P, int i, int j, int k) {                 // y-eq. yflux at the centre of (i,j), 2<=i, 2<=j<=jmm1
+__device__ double advct_yg_mem(const KP &P, const double *am, int i, int j, int k) {                 // y-eq. yflux at the centre of (i,j), 2<=i, 2<=j<=jmm1
   double yg = .125 * (K2(DTSY, i, j + 1) * F3(v, i, j + 1, k) + K2(DTSY, i, j) * F3(v, i, j, k)) * (F3(v, i, j + 1, k) + F3(v, i, j, k));
-  yg = yg - F2(dt, i, j) * F3(aam, i, j, k) * 2. * (F3(vb, i, j + 1, k) - F3(vb, i, j, k)) / F2(dy, i, j);
+  yg = yg - F2(dt, i, j) * G3(am, i, j, k) * 2. * (F3(vb, i, j + 1, k) - F3(vb, i, j, k)) / F2(dy, i, j);
   return F2(dx, i, j) * yg;
 }
 // advct on tiles without exchanging whole intermediate arrays.  What a tile cannot form itself is little: advx(2,j)
@@ -543,12 +544,12 @@ __global__ void k_advct_edge(KP P, double *to_e, double *to_n) {
   if (to_e && t <= P.jm) {
     const size_t o = (size_t)(k - 1) * P.jm + (size_t)(t - 1);
     to_e[o] = advct_curv_mem(P, P.imm1, t, k);
-    to_e[(size_t)P.kbm1 * P.jm + o] = t >= 2 ? advct_xf_mem(P, P.imm1, t, k) : 0.;
+    to_e[(size_t)P.kbm1 * P.jm + o] = t >= 2 ? advct_xf_mem(P, A3(aam), P.imm1, t, k) : 0.;
   }
   if (to_n && t <= P.im) {
     const size_t o = (size_t)(k - 1) * P.im + (size_t)(t - 1);
     to_n[o] = advct_curv_mem(P, t, P.jmm1, k);
-    to_n[(size_t)P.kbm1 * P.im + o] = t >= 2 ? advct_yg_mem(P, t, P.jmm1, k) : 0.;
+    to_n[(size_t)P.kbm1 * P.im + o] = t >= 2 ? advct_yg_mem(P, A3(aam), t, P.jmm1, k) : 0.;
   }
 }
 __global__ void k_advct_fix(KP P, const double *from_w, const double *from_s) {
@@ -558,7 +559,7 @@ __global__ void k_advct_fix(KP P, const double *from_w, const double *from_s) {
     const int j = t;
     const size_t o = (size_t)(k - 1) * P.jm + (size_t)(j - 1);
     const double cv_w = from_w[o], xf_w = from_w[(size_t)P.kbm1 * P.jm + o];
-    const double xf = advct_xf_mem(P, 2, j, k), yf_n = advct_yf_mem(P, 2, j + 1, k), yf_c = advct_yf_mem(P, 2, j, k);
+    const double xf = advct_xf_mem(P, A3(aam), 2, j, k), yf_n = advct_yf_mem(P, A3(aam), 2, j + 1, k), yf_c = advct_yf_mem(P, A3(aam), 2, j, k);
     const double cv = advct_curv_mem(P, 2, j, k);
     const double ctx = cv * F2(dt, 2, j) * (F3(v, 2, j + 1, k) + F3(v, 2, j, k));
     const double ctx_w = cv_w * F2(dt, 1, j) * (F3(v, 1, j + 1, k) + F3(v, 1, j, k));
@@ -570,7 +571,7 @@ __global__ void k_advct_fix(KP P, const double *from_w, const double *from_s) {
     const int i = t;
     const size_t o = (size_t)(k - 1) * P.im + (size_t)(i - 1);
     const double cv_s = from_s[o], yg_s = from_s[(size_t)P.kbm1 * P.im + o];
-    const double xg_e = advct_xg_mem(P, i + 1, 2, k), xg = advct_xg_mem(P, i, 2, k), yg_c = advct_yg_mem(P, i, 2, k);
+    const double xg_e = advct_xg_mem(P, A3(aam), i + 1, 2, k), xg = advct_xg_mem(P, A3(aam), i, 2, k), yg_c = advct_yg_mem(P, A3(aam), i, 2, k);
     const double cv = advct_curv_mem(P, i, 2, k);
     double ay = xg_e - xg + yg_c - yg_s;                                                         // :374-378
     ay = ay + F2(arv, i, 2) * .25 * (cv * F2(dt, i, 2) * (F3(u, i + 1, 2, k) + F3(u, i, 2, k)) +
@@ -585,9 +586,15 @@ __global__ void k_advct_fix(KP P, const double *from_w, const double *from_s) {
 // advance.f:365-372 forms at the head of mode_internal -- nothing writes u, v between here and there -- in that loop's order, fp64
 // ROWS rows per workgroup: 8 (LDS_ROWS) on large grids; 4 on low tiles, where a launch is only three or four rounds of workgroups and two
 // workgroups per compute unit leave the last round fuller (launch_advct_col)
+// AAM (one tile, lateral_viscosity's aam_fused; never in the fp32-arithmetic variant, POMGPU_AAM_FUSE): iteration k also forms the NEW
+// aam(i,j,k) of advance.f:122-136 from the raw u, v it holds -- three more east shifts: u(i+1,j+1), v(i+1,j), v(i+1,j+1) -- with
+// aam_point_r (pomgpu_internal.hpp, the expression k_aam_pair evaluates), and stores it to aam_w, which is never the array being read
+// (ps[AM] = KP::aamc): this launch reads the old aam of rows and columns other workgroups own.  Every owned cell of levels 1..kbm1 is
+// stored, the rim rows and columns with the old value as loaded, so that aam_w is the whole current aam afterwards.  aam2d (advance.f:
+// 158-168) is one more running sum, of the value as stored (rounded to the storage type), in k_vint's order, fp64 in every build.
 template <int ROWS> struct LevCaT { pomgpu_ct c[5], h[(2 * 5 + ROWS - 1) / ROWS]; };
-template <int ROWS>
-__global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
+template <int ROWS, bool AAM = false>
+__global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d, double *aam_w) {
   constexpr int NS = 5, NH = (2 * NS + ROWS - 1) / ROWS, U = 0, V = 1, UB = 2, VB = 3, AM = 4;
   typedef LevCaT<ROWS> LevCa;
   HALO_XCD_DECODE_R(ROWS)                                               // i0: 1-based column of this lane (0 for the very first halo lane)
@@ -612,6 +619,7 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
 #if POMGPU_UVM_ONLOAD
   double su2 = 0., sv2 = 0.;
 #endif
+  double am2 = 0.;                                          // AAM: sum_k aam(k)*dz(k) of the new aam
   // column-resident coefficients
   const pomgpu_ct dtsx_c = K2(DTSX, i, jc), dtsx_s = K2(DTSX, i, js);
   const pomgpu_ct dtsx_e = halo_e(dtsx_c, [&] { return K2(DTSX, ie, jc); });
@@ -631,15 +639,16 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
   const bool srow = (jc - 1 >= 2);                          // row j-1 carries y-eq. fluxes / curv
   const bool curvx = (i0 >= (P.W ? 3 : 2)), curvy = (jc >= (P.S ? 3 : 2));
   BufA bs[NS], bh[NH];
-  const double *ps[NS] = {A3(u), A3(v), A3(ub), A3(vb), A3(aam)};
+  const double *ps[NS] = {A3(u), A3(v), A3(ub), A3(vb), AAM ? P.aamc : A3(aam)};
 #pragma unroll
   for (int x = 0; x < NS; x++) bs[x] = BUF3(ps[x]);
-  const BufA bax = BUF3(A3(advx)), bay = BUF3(A3(advy));
+  const BufA bax = BUF3(A3(advx)), bay = BUF3(A3(advy)), baw = BUF3(AAM ? aam_w : A3(advx));
   const RowShare<NS, ROWS> S = rowshare_setup<NS, ROWS>(P, r, j, j0w, i);
 #pragma unroll
   for (int q = 0; q < NH; q++) bh[q] = BUF3(rowshare_pick<NS>(ps, S.hop[q]));
   const unsigned oc = BOFF2(i, jc), lvb = LVB;
   const unsigned ost = (out && jrow) ? oc : BOFF_NONE;      // rim rows are zeroed after the loop
+  const unsigned osta = out ? oc : BOFF_NONE;               // AAM: every owned cell, rim rows included
 #ifndef POMGPU_EMU
   __shared__ pomgpu_ct slab[2][NS][ROWS + 3][64];
 #else
@@ -678,9 +687,9 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
     const pomgpu_ct v_nw = halo_w(v_n, [&] { return F3(v, iw, jn, k); });
     const pomgpu_ct vb_w = halo_w(vb_c, [&] { return F3(vb, iw, jc, k); });
     const pomgpu_ct vb_nw = halo_w(vb_n, [&] { return F3(vb, iw, jn, k); });
-    const pomgpu_ct am_w = halo_w(am_c, [&] { return F3(aam, iw, jc, k); });
-    const pomgpu_ct am_sw = halo_w(am_s, [&] { return F3(aam, iw, js, k); });
-    const pomgpu_ct am_nw = halo_w(am_n, [&] { return F3(aam, iw, jn, k); });
+    const pomgpu_ct am_w = halo_w(am_c, [&] { return G3(ps[AM], iw, jc, k); });
+    const pomgpu_ct am_sw = halo_w(am_s, [&] { return G3(ps[AM], iw, js, k); });
+    const pomgpu_ct am_nw = halo_w(am_n, [&] { return G3(ps[AM], iw, jn, k); });
     // x-equation xflux at the cell centre (:233-239, :257-262, :275); 0 outside 2..imm1
     pomgpu_ct xf = 0., cv = 0.;
     if (iin) {
@@ -690,7 +699,7 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
       cv = divi(CT(.25) * ((v_n + v_c) * cva_c - (u_e + u_c) * cvb_c), art_c);                     // :217-227
     }
     const pomgpu_ct ctx = cv * dt_c * (v_n + v_c);                                                // :296-297
-    const pomgpu_ct xf_w = halo_w(xf, [&] { return advct_xf_mem(P, i - 1, jc, k); });
+    const pomgpu_ct xf_w = halo_w(xf, [&] { return advct_xf_mem(P, ps[AM], i - 1, jc, k); });
     const pomgpu_ct ctx_w = halo_w(ctx, [&] {
       return advct_curv_mem(P, i - 1, jc, k) * F2(dt, i - 1, jc) * (F3(v, i - 1, jc + 1, k) + F3(v, i - 1, jc, k));
     });
@@ -703,7 +712,7 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
     pomgpu_ct xg = CT(.125) * (dtsx_c * u_c + dtsx_s * u_s) * (v_c + v_w);                            // :322-328
     xg = xg - dtaam * br;                                                                      // :348-353
     xg = CT(.25) * dy4_c.b * xg;                                                                   // :363-364
-    const pomgpu_ct xg_e = halo_e(xg, [&] { return advct_xg_mem(P, i + 1, jc, k); });
+    const pomgpu_ct xg_e = halo_e(xg, [&] { return advct_xg_mem(P, ps[AM], i + 1, jc, k); });
     // corner (i,j+1): y-flux of the x-equation only
     const pomgpu_ct dtaam_n = CT(.25) * dt4_n * (am_n + am_nw + am_c + am_w);
     pomgpu_ct yf_n = CT(.125) * (dtsy_n * v_n + dtsy_nw * v_nw) * (u_n + u_c);
@@ -737,6 +746,17 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
     su2 = su2 + (double)u_c * dzk;                                                             // advance.f:365-372
     sv2 = sv2 + (double)v_c * dzk;
 #endif
+#if POMGPU_AAM_FUSE
+    if constexpr (AAM) {                                                                       // advance.f:122-136, :158-168
+      const double u_ne = halo_e(u_n, [&] { return F3(u, ie, jn, k); });
+      const double v_e = halo_e(v_c, [&] { return F3(v, ie, jc, k); });
+      const double v_ne = halo_e(v_n, [&] { return F3(v, ie, jn, k); });
+      double an = am_c;                                     // off the interior: the old value, as loaded
+      if (in) an = aam_point_r(P, idx_c, idy_c, u_c, u_e, u_n, u_ne, u_s, u_se, v_c, v_n, v_e, v_ne, v_w, v_nw);
+      bstc(baw, osta, lv, an);
+      am2 = am2 + (double)(pomgpu_st)an * dzk;              // the value as stored: what k_vint would read back
+    }
+#endif
   };
   LevCa ra, rb;
 #ifdef POMGPU_EMU
@@ -755,6 +775,12 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
     for (int k = 1; k <= kbm1; k++) { su2 = su2 + (double)F3(u, i, jc, k) * F1(dz, k); sv2 = sv2 + (double)F3(v, i, jc, k) * F1(dz, k); }
   }
 #endif
+  if (AAM && !jrow)                                         // ... nor its copy of the old aam and its share of aam2d
+    for (int k = 1; k <= kbm1; k++) {
+      const double an = bldc(bs[AM], oc, (unsigned)(k - 1) * lvb);
+      bstc(baw, osta, (unsigned)(k - 1) * lvb, an);
+      am2 = am2 + (double)(pomgpu_st)an * F1(dz, k);
+    }
 #endif
 #if POMGPU_UVM_ONLOAD
   if (out && (sum2d & 2)) { K2(USUM, i, jc) = su2; K2(VSUM, i, jc) = sv2; }
@@ -766,6 +792,7 @@ __global__ void __launch_bounds__(64 * ROWS) k_advct_col(KP P, int sum2d) {
       for (int k = 1; k <= kb; k++) { F3(advx, i, jc, k) = 0.; F3(advy, i, jc, k) = 0.; }
     }
     if (sum2d & 1) { F2(adx2d, i, jc) = jrow ? ax2 : 0.; F2(ady2d, i, jc) = jrow ? ay2 : 0.; }
+    if (AAM) F2(aam2d, i, jc) = (i <= P.im && jc <= P.jm) ? am2 : 0.;   // the cells and values k_vint(only_aam) writes
   }
 #ifdef POMGPU_WGTIME
   __syncthreads();
@@ -953,12 +980,24 @@ void launch_advq2w_col(pomgpu_ctx *c, const double *q, const double *qb, double 
   LAUNCHN(c, "k_advq2_col", (k_advq_col<2, true>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, A, zero_else);
 }
 #endif
-void launch_advct_col(pomgpu_ctx *c, int sum2d) {
+// aam_w (lateral_viscosity, aam_fused): the march also forms the new aam into aam_w and leaves aam2d; advct_aam_fused of the event profile
+// counts these launches, a count without events as profq_ld_store
+void launch_advct_col(pomgpu_ctx *c, int sum2d, double *aam_w) {
   // low tiles (a tile of an 8- or 4-tile split of 2048x1536): 4-row workgroups, two per compute unit
   const bool rows4 = SW(c, ADVCT_ROWS4) || (!SW(c, ADVCT_ROWS8) && c->P.jml <= 400 && c->exch);
   sum2d = (sum2d ? 1 : 0) | (POMGPU_UVM_ONLOAD && !c->exch && !c->tp.on && !c->wide.on && !(c->flags & POMGPU_CTX_2D) ? 2 : 0);   // bit 1: the depth sums of u, v (one tile)
-  if (rows4) LAUNCHN(c, "k_advct_col", (k_advct_col<4>), grid1_halo_r(c->P, 4), blk_col_r(4), c->P, sum2d);
-  else LAUNCHN(c, "k_advct_col", (k_advct_col<LDS_ROWS>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, sum2d);
+#if POMGPU_AAM_FUSE
+  if (aam_w) {                                              // one tile only: the 4-row shape is for low tiles
+    if (c->prof_on) {
+      const int s = pomgpu_prof_slot(c, "advct_aam_fused");
+      if (s >= 0) (c->parent ? c->parent : c)->prof[s].launches++;
+    }
+    LAUNCHN(c, "k_advct_col", (k_advct_col<LDS_ROWS, true>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, sum2d, aam_w);
+    return;
+  }
+#endif
+  if (rows4) LAUNCHN(c, "k_advct_col", (k_advct_col<4>), grid1_halo_r(c->P, 4), blk_col_r(4), c->P, sum2d, (double *)NULL);
+  else LAUNCHN(c, "k_advct_col", (k_advct_col<LDS_ROWS>), grid1_halo_r(c->P, LDS_ROWS), blk_col_r(LDS_ROWS), c->P, sum2d, (double *)NULL);
 }
 // with sum2d the column kernel has left adx2d, ady2d (advance.f:152-168) from its own advx(2,:), advy(:,2): redo the
 // two lines from the corrected values, in the column kernel's order of summation

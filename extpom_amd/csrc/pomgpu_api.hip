@@ -309,6 +309,35 @@ static bool next_step_fetches_record(const pomgpu_ctx *c) {
   return (c->frc_on && (isrf < 1 || next % isrf == 0)) || (c->lat_on && (ibc < 1 || next % ibc == 0)) ||
          (c->wat_on && (iwater < 1 || (k.iint + 1) % iwater == 0));
 }
+// ---- the two homes of aam (k_advct_col<*, true>, k_tile.hip) ----------------------------------------
+// aam_parity == 0: the current aam is in its blk3d slot; == 1: its levels 1..kbm1 are in aam_spare (level kb and whatever the march
+// does not write are never read from the spare).  KP::aamc names the current one for the column kernels of mode_internal
+// (k_advq_col, k_advt2_col) and the next k_advct_col; aam_canonical() copies it back into the slot for everybody else.
+static void aam_buffers(pomgpu_ctx *c) {
+  KP &P = c->P;
+  P.aamc = (c->aam_parity && c->aam_spare) ? c->aam_spare : (P.b3 ? P.b3 + (size_t)P3_aam * P.a3 : NULL);
+}
+static void aam_canonical(pomgpu_ctx *c) {
+  if (!c->aam_parity) return;
+  (void)hipSetDevice(c->device);
+  launch_aam_copy(c, SLOT3(c, P3_aam), c->aam_spare);
+  c->aam_parity = 0;
+  aam_buffers(c);
+}
+// may lateral_viscosity form aam and aam2d inside advct's march instead of launching k_aam_pair / k_aam and k_vint?  One tile whose mirrors
+// only the library reads (as for wr), with the 3-D part on (mode 2 has no aam).  POMGPU_AAM_NOFUSE (read here, at launch time) keeps the
+// pair; the fp32-arithmetic variant keeps it at build time (POMGPU_AAM_FUSE).  The spare array is allocated here the first time
+static bool aam_fused(pomgpu_ctx *c) {
+  if (!POMGPU_AAM_FUSE || c->exch || c->tp.on || c->wide.on || c->parent || (c->flags & POMGPU_CTX_2D) || c->wr_eager || c->P.mode == 2 ||
+      SW(c, AAM_NOFUSE) || c->aam_spare_failed)
+    return false;
+  if (!c->aam_spare) {
+    const size_t bytes = c->P.n3 * sizeof(pomgpu_st);
+    if (hipMalloc((void **)&c->aam_spare, bytes) != hipSuccess) { (void)hipGetLastError(); c->aam_spare = NULL; c->aam_spare_failed = 1; return false; }
+    (void)hipMemsetAsync(c->aam_spare, 0, bytes, c->stream);
+  }
+  return true;
+}
 static void uvf_materialize(pomgpu_ctx *c) {
   if (!c->uvf_pending) return;
   c->uvf_pending = 0;
@@ -320,6 +349,7 @@ static void restore_materialize(pomgpu_ctx *c) {
   rho_materialize(c);
   pomgpu_wr_materialize(c);
   uvf_materialize(c);
+  aam_canonical(c);
   if (!c->rst_pending) return;
   c->rst_pending = 0;
   launch_restore_fields(c, c->rst_fold, c->rst_fnew);
@@ -441,6 +471,7 @@ static int ctx_create(pomgpu_ctx **out, const pomgpu_dims *d, int device, void *
   c->ext_parity = 0;
   c->rst_pending = 0;
   ext_buffers(c);
+  aam_buffers(c);
   (void)hipStreamSynchronize(c->stream);
   *out = c;
   return POMGPU_OK;
@@ -470,6 +501,7 @@ extern "C" void pomgpu_destroy(pomgpu_ctx *c) {
   for (int n = 0; n < POMGPU_NSCR2; n++) (void)hipFree(P.s2[n]);
   (void)hipFree(c->uvb_bot[0]); (void)hipFree(c->uvb_bot[1]);
   (void)hipFree(c->rt_words); (void)hipFree(c->rt_cols);
+  (void)hipFree(c->aam_spare);
   for (int n = 0; n < POMGPU_NCOEF2; n++) (void)hipFree(P.c2[n]);
   (void)hipFree(c->alt2[0]); (void)hipFree(c->alt3[0]);         // one block each
   (void)hipFree(P.m8);
@@ -505,6 +537,7 @@ extern "C" int pomgpu_debug_switch(pomgpu_ctx *c, const char *name, const char *
       pomgpu_ctx *two[2] = {c, c->wide.x};
       for (pomgpu_ctx *t : two)
         if (t) { t->sw.on[n] = value ? 1 : 0; t->sw.val[n] = value ? atol(value) : 0; }
+      if (n == SW_AAM_NOFUSE) aam_canonical(c);               // the pair reads and writes aam in its slot
       return POMGPU_OK;
     }
   return fail(c, POMGPU_EINVAL, "debug_switch: no switch named %s", name);
@@ -799,10 +832,10 @@ static void seq_advave(pomgpu_ctx *c) {                       // solver.f:6-198
     launch_advave_m2b(c);
   }
 }
-static void seq_advct(pomgpu_ctx *c, int sum2d = 0, int defer_xch = 0) {   // solver.f:201-408
+static void seq_advct(pomgpu_ctx *c, int sum2d = 0, int defer_xch = 0, double *aam_w = NULL) {   // solver.f:201-408
   KP &P = c->P;
   if (!c->exch) {                                             // one tile: nothing to exchange, fluxes stay in registers
-    launch_advct_col(c, sum2d);
+    launch_advct_col(c, sum2d, aam_w);                        // aam_w (lateral_viscosity): the new aam and aam2d as well
     c->uvm_valid = POMGPU_UVM_ONLOAD && !c->tp.on && !c->wide.on && !(c->flags & POMGPU_CTX_2D);   // ... and the depth sums of u, v are left for mode_internal
     return;
   }
@@ -1146,6 +1179,7 @@ static int lateral_viscosity(pomgpu_ctx *c, int sum2d, int defer_rt = 0) {      
   side_wait(c, SIDE_RTS);                                     // rho's ghost lines (rim round Rts of the step before; posted ahead of R8 on the same stream)
   rho_materialize(c);                                         // a deferred round trip no step has consumed (baropg reads rho)
   KP &P = c->P;
+  c->aam2d_done = 0;
   if (P.mode != 2) {
     const bool lib_x = c->tp.on && c->exch && !SW(c, ADVCT_SPLIT);
     auto pressure_gradient = [&]() {
@@ -1161,9 +1195,14 @@ static int lateral_viscosity(pomgpu_ctx *c, int sum2d, int defer_rt = 0) {      
     const bool pg_first = c->side_ev[SIDE_R8].pending != 0;
     if (pg_first) pressure_gradient();
     side_wait(c, SIDE_R8);
-    seq_advct(c, sum2d, lib_x);                               // lib_x: advx, advy travel with aam below
+    // aam and aam2d out of advct's march (one tile, inside a whole step: sum2d; the routine-by-routine entry points keep the pair).  The
+    // march reads the current aam and writes the other buffer; the parity flips behind it
+    const bool fuse = sum2d && aam_fused(c);
+    if (!fuse) aam_canonical(c);                              // k_advct_col<*, false>, advct_a/b/c, k_aam_pair / k_aam work on the slot
+    seq_advct(c, sum2d, lib_x, fuse ? (c->aam_parity ? SLOT3(c, P3_aam) : c->aam_spare) : NULL);   // lib_x: advx, advy travel with aam below
     if (!pg_first) pressure_gradient();
-    launch_aam(c);
+    if (fuse) { c->aam_parity ^= 1; aam_buffers(c); c->aam2d_done = 1; }
+    else launch_aam(c);
     if (lib_x && sum2d && rim_side(c)) {                      // rim round R2: solver.f:315,405 + :137 on the side stream
       double *arr[3] = {D3(c, advx), D3(c, advy), D3(c, aam)};
       const int nz[3] = {P.kb, P.kb, P.kbm1};
@@ -1199,13 +1238,15 @@ static int mode_interaction(pomgpu_ctx *c, int sums_done) {   // advance.f:144-2
   if (c->wide.on) {                                           // one wide exchange instead of ~180 narrow ones
     // :152-168; while rim round R2 is in flight aam's ghost lines are not there yet: this launch leaves aam2d's alone, the side stream
     // fills them behind the round (lateral_viscosity)
-    if (c->P.mode != 2) launch_vint(c, sums_done, sums_done && c->side_ev[SIDE_R2].pending ? 1 : 0);
+    if (c->P.mode != 2) { aam_canonical(c); launch_vint(c, sums_done, sums_done && c->side_ev[SIDE_R2].pending ? 1 : 0); }
     return wide_begin(c);                                     // :170-199 on the extended tile
   }
   if (c->P.mode != 2) {
-    launch_vint(c, sums_done);
+    // :152-168.  aam2d_done: this step's march has left all five integrals (lateral_viscosity); whoever comes here without it reads aam in its slot
+    if (!(sums_done && c->aam2d_done)) { aam_canonical(c); launch_vint(c, sums_done); }
     seq_advave(c);
   }
+  c->aam2d_done = 0;
   launch_modeint_tail(c);
   xch(c, 2, D2(c, utf), 1, D2(c, vtf), 1);                    // :198-199
   return POMGPU_OK;
@@ -1820,6 +1861,9 @@ static int mode_internal(pomgpu_ctx *c, int defer_wr) {       // advance.f:356-5
   side_wait(c, SIDE_R8);                                      // (a step whose lateral_viscosity did not run: nothing else has waited)
   if ((k.iint != 1 || k.time0 != 0.) && k.mode != 2) {
     c->uvf_pending = 0;                                       // u, v change now and advq rewrites uf, vf whole: nobody has asked for the copy
+    // the row-sharing column kernels (k_advq_col, k_advt2_col) read the current aam wherever it lives (KP::aamc); the other advection
+    // kernels -- advt1, smol_adif's advt2, the flux / step pair of ADVQ_EXCHANGE -- read the slot
+    if (!(k.nadv == 2 && P.nitera == 1) || (c->exch && SW(c, ADVQ_EXCHANGE))) aam_canonical(c);
     // :365-393 as a pass over u, v -- or applied by every kernel below to what it loads of them, u, v staying raw in memory until the
     // filter overwrites them (uvm_onload; KP::uvm tells the kernels, and is down again when this function returns)
     struct UvmScope { pomgpu_ctx *c; ~UvmScope() { c->P.uvm = 0; c->uvm_valid = 0; } } uvm_scope{c};
@@ -2569,6 +2613,7 @@ static int tune_relayout(pomgpu_ctx *c, TuneLay to) {
     }
     return POMGPU_OK;
   };
+  aam_canonical(c);                                           // the trial steps between two moves may have left aam in its spare array
   const TuneLay cur = {c->tune_front, c->P.a3};
   int rc = POMGPU_OK;
   if ((to.f >= cur.f && to.a >= cur.a) || (to.f <= cur.f && to.a <= cur.a)) rc = one_way(cur, to);
@@ -2583,6 +2628,7 @@ static int tune_relayout(pomgpu_ctx *c, TuneLay to) {
   P.a3 = to.a;
   P.b3 = c->tune_block + to.f;
   for (int n = 0; n < POMGPU_NSCR3; n++) P.s3[n] = P.b3 + (size_t)POM_NBLK3D * P.a3 + (size_t)n * P.n3;
+  aam_buffers(c);
   return POMGPU_OK;
 }
 extern "C" int pomgpu_tune_placement(pomgpu_ctx *c, int steps, int max_try, double *ms_out, long *front_mib_out, long *pad_mib_out, int *ntried, int *kept) {
@@ -2635,6 +2681,7 @@ extern "C" int pomgpu_tune_placement(pomgpu_ctx *c, int steps, int max_try, doub
     c->tune_amax = amax;
     P.b3 = blk;
     for (int n = 0; n < POMGPU_NSCR3; n++) P.s3[n] = blk + (size_t)POM_NBLK3D * a0 + (size_t)n * P.n3;
+    aam_buffers(c);
   }
   // (start offset in units of two arrays, wider distance?) in the order they are tried
   static const int KS[20][2] = {{0, 0}, {3, 0}, {10, 0}, {0, 1}, {3, 1}, {10, 1}, {5, 0}, {5, 1}, {2, 0}, {1, 0}, {7, 0}, {4, 0}, {7, 1}, {2, 1}, {15, 0}, {20, 0}, {25, 0}, {30, 0}, {15, 1}, {20, 1}};

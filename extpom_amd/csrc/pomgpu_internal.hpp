@@ -60,6 +60,9 @@ struct KP {
   // 1 while u, v in memory still lack the depth-mean correction of advance.f:365-393 and every kernel that loads them applies it
   // (uvm_fix below; mode_internal on one tile, between the external mode and the velocity filter).  0 everywhere else
   int uvm;
+  // where the current aam lives: its blk3d slot, or the context's spare array after a k_advct_col<*, true> that left the new values there
+  // (pomgpu_ctx::aam_parity, aam_buffers).  The column kernels of mode_internal read aam through it; everybody else reads the slot
+  const double *aamc;
 };
 enum pomgpu_x2 { X2_ua, X2_va, X2_d, X2_el, X2_elb, X2_uab, X2_vab };
 
@@ -109,6 +112,13 @@ typedef double pomgpu_ct;
 #define POMGPU_UVM_ONLOAD 0
 #else
 #define POMGPU_UVM_ONLOAD 1
+#endif
+// aam (advance.f:122-136) and aam2d (:158-168) formed inside k_advct_col's march bring fp64 divisions, a square root and a fp64 running
+// sum into a stencil kernel: the fp32-arithmetic variant keeps k_aam and k_vint, as it keeps vertvl.
+#ifdef POMGPU_COMPUTE_F32
+#define POMGPU_AAM_FUSE 0
+#else
+#define POMGPU_AAM_FUSE 1
 #endif
 #ifdef POMGPU_STORE_F32
 struct Ref3 {
@@ -530,6 +540,17 @@ __device__ __forceinline__ float divi(float a, const InvDT<float> &d) {
 static inline double divi(double a, const InvD &d) { return a / d.b; }
 static inline float divi(float a, const InvDT<float> &d) { return a / d.b; }
 #endif
+// Smagorinsky viscosity of one cell (advance.f:122-136) with the four divisions by dx, dy through divi() (correctly rounded quotients,
+// the same bits as the reference's divisions).  k_aam_pair (k_adv.hip) and k_advct_col<*, true> (k_tile.hip) share this one definition.
+// The counters put k_aam_pair on its arithmetic, not on memory (profiles/round3_pmc_kernels.txt: VALU 0.13 of every wave's cycles at 8
+// waves per SIMD): 8 division macros (~69 cycles each) + 2 square roots per lane; forming the reciprocals in the kernel (round 2) only
+// moved the divisions.
+__device__ __forceinline__ double aam_point_r(const KP &P, const InvD &dx, const InvD &dy, double u_c, double u_e, double u_n, double u_ne, double u_s,
+                                              double u_se, double v_c, double v_n, double v_e, double v_ne, double v_w, double v_nw) {
+  return P.horcon * dx.b * dy.b *
+         sqrt(sq(divi(u_e - u_c, dx)) + sq(divi(v_n - v_c, dy)) +
+              .5 * sq(divi(.25 * (u_n + u_ne - u_s - u_se), dy) + divi(.25 * (v_e + v_ne - v_w - v_nw), dx)));
+}
 // XCD-aware placement of the column kernels' workgroups (64 x 4 columns each).  Workgroups are dealt
 // to the 8 XCDs round-robin in linear-id order, and every XCD has its own 4 MiB L2.  A plain
 // (bx, by) grid therefore puts vertically adjacent workgroups on different XCDs and each re-fetches
@@ -613,7 +634,7 @@ static inline dim3 grid2_halo(const KP &P) { return dim3((P.iml + 61) / 62, (P.j
   X(PROFQ_NOPACE) X(COL_STRIP) X(BAND_BYTES) X(PAD3) X(IO_SYNC) X(ADVCT_SPLIT) X(ADVQ_EXCHANGE) X(PROD_FULL) X(QFILTER_SPLIT) \
   X(NO_OVERLAP) X(NO_SIDE_COMM) X(WR_MAIN) X(WIDE_W) X(WIDE_FULL) X(DEBUG_ALLOC) X(TEST_SPLIT_FAIL_RANK)  \
   X(WR_NODEFER) X(EXT_RING_FIRST) X(TUNE_FORCE) X(RIM_MAIN) X(RIM_RESULTS_MAIN) X(SUM2D_OFF) X(ADVCT_ROWS4) X(ADVCT_ROWS8) \
-  X(IO_CHUNK_KB) X(UV_NOFUSE) X(W_NOFUSE) X(UVMEAN_PASS) X(PROFT_TWIN) X(LD_EAGER) X(TR_NOPAIR) X(RT_LOAD)
+  X(IO_CHUNK_KB) X(UV_NOFUSE) X(W_NOFUSE) X(UVMEAN_PASS) X(PROFT_TWIN) X(LD_EAGER) X(TR_NOPAIR) X(RT_LOAD) X(AAM_NOFUSE)
 enum pomgpu_sw {
 #define POMGPU_SW_(name) SW_##name,
   POMGPU_SWITCHES(POMGPU_SW_)
@@ -781,6 +802,13 @@ struct pomgpu_ctx {
   // u, v since.  Dropped by everything that may write them from outside the step (restore_materialize: uploads, downloads, handed-out
   // addresses, the stand-alone entry points; the restart reader) and by mode_internal itself, whose filter rewrites u, v.
   int uvm_valid;
+  // The two homes of aam (k_advct_col<*, true> forms the new aam while it reads the old one of neighbour rows and columns, so it stores
+  // to the array it does not read).  aam_spare: one 3-D array of the storage type, allocated the first time the fused march is taken
+  // (aam_spare_failed: the allocation was refused once; the context keeps k_aam / k_vint for good).  aam_parity == 1: levels 1..kbm1 of the
+  // current aam are in the spare, KP::aamc points there, and aam_canonical (pomgpu_api.hip) copies them back for whoever reads the slot.
+  // aam2d_done: the march of this step's lateral_viscosity has left aam2d as well; mode_interaction launches no k_vint and drops it
+  double *aam_spare;
+  int aam_parity, aam_spare_failed, aam2d_done;
   double *uvb_bot[2];        // level kbm1 of ub, vb as they were before that kernel: its bottom friction reads neighbour columns others rewrite
   int wr_eager;              // pomgpu_device_2d / _3d has handed out an address: reads and writes the library cannot see -- wr at the end of every step from then on
   double *d_vel;             // device: vamax, then (imax,jmax) as two doubles' worth of ints
@@ -914,7 +942,7 @@ void launch_advave_a(pomgpu_ctx *c);
 void launch_advave_b(pomgpu_ctx *c);
 void launch_advave_c(pomgpu_ctx *c);
 void launch_advave_fused(pomgpu_ctx *c);
-void launch_advct_col(pomgpu_ctx *c, int sum2d);
+void launch_advct_col(pomgpu_ctx *c, int sum2d, double *aam_w = NULL);   // aam_w: also form the new aam there, and aam2d (one tile)
 void launch_advct_edge(pomgpu_ctx *c, double *to_e, double *to_n);
 void launch_advct_fix(pomgpu_ctx *c, const double *from_w, const double *from_s);
 void launch_advct_fix2d(pomgpu_ctx *c, int west, int south);
@@ -970,6 +998,7 @@ void launch_advt2_step(pomgpu_ctx *c, const double *fbmem, const double *f, cons
 void launch_mask3(pomgpu_ctx *c, double *a, const double *m2);
 void launch_smol(pomgpu_ctx *c, const double *ff);
 void launch_copy3(pomgpu_ctx *c, double *dst, const double *src);
+void launch_aam_copy(pomgpu_ctx *c, double *dst, const double *src);   // levels 1..kbm1 of (1:iml, 1:jml): aam from its spare array back into its slot
 void launch_advt2_diff(pomgpu_ctx *c, const double *fb, const double *fc, double *ff);
 void launch_ts_update(pomgpu_ctx *c, double fold, double fnew, int rt, int store_rst, int rt_flags = 0);   // uses c->tau_known / tau_val; rt_flags: c->rt_words are this step's
 void launch_restore_fields(pomgpu_ctx *c, double fold, double fnew);
