@@ -219,6 +219,69 @@ extern "C" int pomgpu_read_tracers(pomgpu_ctx *c, const char *path, const pomgpu
   return POMGPU_OK;
 }
 
+// ---- the float file back (pomgpu_read_floats, include/pomgpu.h; the writer: cdf_out.hip) -------------------------------------------------
+// 1-D arrays of a few bytes a float: read and byte-swapped on the host, then registered as pomgpu_float_upload registers host arrays
+extern "C" int pomgpu_read_floats(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m, double *time_out, double *iint_out) {
+#ifdef POMGPU_STORE_F32
+  if (c) return fail(c, POMGPU_EINVAL, "read_floats: not in the fp32-storage variant (3-D arrays are not doubles there)");
+#endif
+  if (!c || !path || !m) return POMGPU_EINVAL;
+  (void)hipSetDevice(c->device);
+  if (c->flags & POMGPU_CTX_2D) return fail(c, POMGPU_EINVAL, "read_floats: a context with 3-D arrays");
+  { const int rcw = pomgpu_io_wait(c); if (rcw) return rcw; }
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return fail(c, POMGPU_EINVAL, "read_floats: cannot open %s", path);
+  struct stat sb;
+  if (fstat(fd, &sb)) { (void)close(fd); return fail(c, POMGPU_EINVAL, "read_floats: cannot stat %s", path); }
+  const uint64_t fsize = (uint64_t)sb.st_size;
+  RHeader H;
+  {
+    std::string what;
+    const int rc = read_header(fd, fsize, H, what);
+    if (rc == -2) { (void)close(fd); return fail(c, POMGPU_EINVAL, "read_floats: I/O error on %s (header)", path); }
+    if (rc < 0) { (void)close(fd); return fail(c, POMGPU_EINVAL, "read_floats: %s is not a float file this library reads: %s", path, what.c_str()); }
+  }
+  auto refuse = [&](const std::string &why) { (void)close(fd); return fail(c, POMGPU_EINVAL, "read_floats: %s: %s", path, why.c_str()); };
+  // ---- every variable and every value before anything changes ----
+  const RVar *vx = find_var(H, "x");
+  if (!vx) return refuse("variable x is absent");
+  if (vx->dimids.size() != 1) return refuse("variable x has the dimension lengths " + lengths_of(H, *vx) + ", wanted one dimension");
+  const uint64_t N = H.dimlen[vx->dimids[0]];
+  if (N == 0) return refuse("variable x is a record variable (unlimited dimension)");
+  if (N > (uint64_t)POMGPU_MAXFLOATS) return refuse("the file holds " + std::to_string(N) + " floats, 0.." + std::to_string(POMGPU_MAXFLOATS) + " are possible");
+  static const char *const DN[3] = {"x", "y", "sig"}, *const INAMES[3] = {"status", "kind", "id"};
+  const RVar *dv[3] = {NULL, NULL, NULL}, *iv[3] = {NULL, NULL, NULL}, *v_time = NULL, *v_iint = NULL;
+  std::string why;
+  for (int q = 0; q < 3 && why.empty(); q++) why = check_var(H, fsize, DN[q], VarWant::fixed(NC_ONLY_DOUBLE, {N}), &dv[q]);
+  for (int q = 0; q < 3 && why.empty(); q++) if (find_var(H, INAMES[q])) why = check_var(H, fsize, INAMES[q], VarWant::fixed(1u << 4, {N}), &iv[q]);
+  if (why.empty() && find_var(H, "time")) why = check_var(H, fsize, "time", VarWant::fixed(NC_ONLY_DOUBLE, {}, VarWant::ONE_VALUE), &v_time);
+  if (why.empty() && find_var(H, "iint")) why = check_var(H, fsize, "iint", VarWant::fixed(NC_ONLY_DOUBLE, {}, VarWant::ONE_VALUE), &v_iint);
+  if (!why.empty()) return refuse(why);
+  std::vector<double> dbl(3 * (size_t)N);
+  std::vector<int> itg(3 * (size_t)N);
+  double sc[2] = {0., 0.};                                       // time, iint
+  for (int q = 0; q < 3; q++) {
+    if (pread_all(fd, dbl.data() + (size_t)q * N, 8 * (size_t)N, dv[q]->begin)) return refuse(std::string("I/O error (") + DN[q] + ")");
+    if (iv[q] && pread_all(fd, itg.data() + (size_t)q * N, 4 * (size_t)N, iv[q]->begin)) return refuse(std::string("I/O error (") + INAMES[q] + ")");
+  }
+  for (int q = 0; q < 2; q++) {
+    const RVar *v = q ? v_iint : v_time;
+    if (v && pread_all(fd, &sc[q], 8, v->begin)) return refuse("I/O error (time, iint)");
+  }
+  (void)close(fd);
+  auto swap8 = [](double *p, size_t n) { for (size_t e = 0; e < n; e++) { uint64_t u; memcpy(&u, p + e, 8); u = __builtin_bswap64(u); memcpy(p + e, &u, 8); } };
+  swap8(dbl.data(), dbl.size());
+  swap8(sc, 2);
+  for (size_t e = 0; e < itg.size(); e++) itg[e] = (int)__builtin_bswap32((uint32_t)itg[e]);
+  // ---- from here on the float set changes (pomgpu_float_register makes the context's own refusals first) ----
+  const int rc = pomgpu_float_register(c, "read_floats", (int)N, dbl.data(), dbl.data() + N, dbl.data() + 2 * N, iv[1] ? itg.data() + N : NULL,
+                                       iv[2] ? itg.data() + 2 * N : NULL, iv[0] ? itg.data() : NULL);
+  if (rc) return rc;
+  if (time_out) *time_out = sc[0];
+  if (iint_out) *iint_out = sc[1];
+  return POMGPU_OK;
+}
+
 // ---- a cold start from the reference's input files (pomgpu_cold_start) ---------------------------------------------------------------
 // initialize.f:24-36 after read_input: initialize_arrays, read_grid (read_grid_pnetcdf io_pnetcdf.F:2085-2263, initialize.f:317-389),
 // initial_conditions (read_initial_ts_pnetcdf :2771-2842, read_clim_ts_pnetcdf :2845-2909, initialize.f:392-463), update_initial

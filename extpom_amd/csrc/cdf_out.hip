@@ -631,6 +631,72 @@ extern "C" int pomgpu_write_tracers(pomgpu_ctx *c, const char *path, const pomgp
   return write_file(c, path, m, S, mean ? 2 : 0);
 }
 
+// ---- the float file (include/pomgpu.h: pomgpu_write_floats; no counterpart in the reference) ------------------------------------------------
+// Output and checkpoint of the Lagrangian floats in one: the state (x y sig status kind id) and what pomgpu_float_sample shows of it.  One
+// dimension, eight NC_DOUBLE and three NC_INT variables; no tile writes a patch, the arrays are the whole file.  Written synchronously, behind
+// whatever file is still in flight: 68 bytes a float, a million floats are 68 MB
+extern "C" int pomgpu_write_floats(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m) {
+#ifdef POMGPU_STORE_F32
+  if (c) return pomgpu_fail(c, POMGPU_EINVAL, "write_floats: not in the fp32-storage variant (3-D arrays are not doubles there)");
+#endif
+  if (!c || !path || !m) return POMGPU_EINVAL;
+  if (!c->nflt) return fail(c, POMGPU_EINVAL, "write_floats: no floats are registered (pomgpu_float_upload)");
+  (void)hipSetDevice(c->device);
+  { const int rcw = pomgpu_io_wait(c); if (rcw) return rcw; }
+  const size_t N = (size_t)c->nflt;
+  std::vector<double> dbl(8 * N);                              // x y sig, then lon lat depth t s
+  std::vector<int> itg(3 * N);                                 // status kind id
+  int rc = pomgpu_float_download(c, dbl.data(), dbl.data() + N, dbl.data() + 2 * N, itg.data(), itg.data() + N, itg.data() + 2 * N);
+  if (!rc) rc = pomgpu_float_sample(c, dbl.data() + 3 * N);
+  if (rc) return rc;
+  static const struct { const char *name, *long_name, *units; } DV[8] = {
+      {"x", "index coordinate along i (cell centre i at x = i)", "grid cells"}, {"y", "index coordinate along j (cell centre j at y = j)", "grid cells"},
+      {"sig", "sigma", "sigma_level"}, {"lon", "longitude", "degree"}, {"lat", "latitude", "degree"}, {"depth", "height relative to the resting surface", "metre"},
+      {"t", "potential temperature of the containing column", "K"}, {"s", "salinity of the containing column", "PSS"}};
+  static const struct { const char *name, *long_name, *units; } IV[3] = {
+      {"status", "0 active, 1 exited, 2 lost", "dimensionless"}, {"kind", "0 follows w, 1 keeps its sigma", "dimensionless"}, {"id", "the caller's number", "dimensionless"}};
+  const std::string since = std::string("days since ") + (m->time_start ? m->time_start : "");
+  uint64_t begin[13] = {0};
+  std::string h;
+  for (int pass = 0; pass < 2; pass++) {                         // pass 0 measures, pass 1 has the offsets (as header() above)
+    h.assign("CDF\002", 4);
+    put32(h, 0);
+    put32(h, 0x0A); put32(h, 1); putname(h, "nfloat"); put32(h, (uint32_t)N);
+    putatts(h, {{"title", m->title ? m->title : ""}, {"description", "float file"}});
+    put32(h, 0x0B); put32(h, 13);
+    auto var = [&](const char *name, bool vec, const char *ln, const std::string &un, uint32_t type, int q) {
+      putname(h, name); put32(h, vec ? 1 : 0);
+      if (vec) put32(h, 0);
+      putatts(h, {{"long_name", ln}, {"units", un}});
+      put32(h, type);
+      const uint64_t nb = (vec ? N : 1) * (type == 6 ? 8 : 4);
+      put32(h, (uint32_t)((nb + 3) & ~(uint64_t)3)); put64(h, begin[q]);
+    };
+    var("iint", false, "i_internal", "model internal step number", 6, 0);
+    var("time", false, "time", since, 6, 1);
+    for (int q = 0; q < 8; q++) var(DV[q].name, true, DV[q].long_name, DV[q].units, 6, 2 + q);
+    for (int q = 0; q < 3; q++) var(IV[q].name, true, IV[q].long_name, IV[q].units, 4, 10 + q);
+    uint64_t off = h.size();
+    for (int q = 0; q < 13; q++) { begin[q] = off; off += q < 2 ? 8 : (q < 10 ? 8 * N : 4 * N); }
+  }
+  const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+  if (fd < 0) return fail(c, POMGPU_EINVAL, "write_floats: cannot open %s", path);
+  auto put_bytes = [&](const void *src, size_t bytes, uint64_t off) {
+    const char *p = (const char *)src;
+    while (bytes) { const ssize_t w = pwrite(fd, p, bytes, (off_t)off); if (w <= 0) return 1; p += w; off += (uint64_t)w; bytes -= (size_t)w; }
+    return 0;
+  };
+  std::vector<uint64_t> tmp;
+  int bad = put_bytes(h.data(), h.size(), 0);
+  const double sc[2] = {(double)c->con.iint, c->con.time};
+  for (int q = 0; q < 2 && !bad; q++) bad = write_be(fd, &sc[q], 1, begin[q], tmp);
+  for (int q = 0; q < 8 && !bad; q++) bad = write_be(fd, dbl.data() + (size_t)q * N, N, begin[2 + q], tmp);
+  for (size_t e = 0; e < itg.size(); e++) itg[e] = (int)__builtin_bswap32((uint32_t)itg[e]);
+  for (int q = 0; q < 3 && !bad; q++) bad = put_bytes(itg.data() + (size_t)q * N, 4 * N, begin[10 + q]);
+  if (close(fd)) bad = 1;
+  return bad ? fail(c, POMGPU_EINVAL, "write_floats: I/O error on %s", path) : POMGPU_OK;
+}
+
 // A source list from before the readers moved out names this file for writer and readers alike.  Every list of the project names the
 // four units and says so with POMGPU_FILE_UNITS (the device build needs no word: it has no such old list); a host build without it still
 // gets the readers, through here.

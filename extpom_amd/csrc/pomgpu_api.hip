@@ -10,6 +10,7 @@
 #include <vector>
 #include "pomgpu.h"
 #include "pomgpu_internal.hpp"
+#include "k_float.hpp"
 
 struct ProfPair { int slot; hipEvent_t a, b; };
 struct ProfState { std::vector<ProfPair> pending; std::vector<ProfPair> free_; char filter[64]; };
@@ -163,6 +164,7 @@ static void sync_scalars(pomgpu_ctx *c) {
 }
 
 static void tracers_free(pomgpu_ctx *c);
+static void floats_free(pomgpu_ctx *c);
 // ---- life cycle -------------------------------------------------------------------------------
 // a digest of the library's sources, put in by the build (__graft_entry__.build_hip): measurements kept in profiles/ carry it, and
 // bench.py only quotes a stored counter value (roofline.traffic) for the build it was taken from
@@ -512,6 +514,7 @@ extern "C" void pomgpu_destroy(pomgpu_ctx *c) {
   for (int sl = 0; sl < 4; sl++) { (void)hipFree(c->lat_dev[sl]); (void)hipFree(c->wat_dev[sl]); }
   (void)hipFree(c->mean_acc);
   tracers_free(c);
+  floats_free(c);
   ProfState *ps = PS(c);
   if (ps) {
     for (auto &p : ps->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -2519,6 +2522,109 @@ extern "C" int pomgpu_tracer_mean_download(pomgpu_ctx *c, int n, double *host) {
   for (size_t e = 0; e < len; e++) host[e] = host[e] / cnt;    // the division k_mean_snapshot makes
   return POMGPU_OK;
 }
+// ---- Lagrangian floats (include/pomgpu.h; the kernels: k_float.hpp) -------------------------------------------------------------------------
+// The step reads u v w dt dx dy fsm z zz as pomgpu_download would show them: what mean_accumulate completes first is what this stage needs
+// complete, and in the step's own order it finds nothing to do.  No lazily kept array is formed: wr, uf / vf, the restore fields and aam's
+// spare home are not among the operands
+static void float_stage(pomgpu_ctx *c) {
+  ext_flush_deferred(c);
+  wide_flush(c);
+  side_wait(c, SIDE_RW); side_wait(c, SIDE_R8); side_wait(c, SIDE_RTS);
+  launch_float_step(c);
+}
+static void floats_free(pomgpu_ctx *c) {
+  (void)hipFree(c->flt_x); (void)hipFree(c->flt_y); (void)hipFree(c->flt_s); (void)hipFree(c->flt_smp);
+  (void)hipFree(c->flt_status); (void)hipFree(c->flt_kind); (void)hipFree(c->flt_id);
+  c->flt_x = c->flt_y = c->flt_s = c->flt_smp = NULL;
+  c->flt_status = c->flt_kind = c->flt_id = NULL;
+  c->nflt = 0;
+}
+// what pomgpu_float_upload and pomgpu_read_floats (cdf_in.hip) share: every refusal, then the new arrays, then the old ones go.  status:
+// a float whose entry is not ACTIVE keeps it over the admission's verdict (a checkpoint); NULL: the admission decides alone
+int pomgpu_float_register(pomgpu_ctx *c, const char *what, int n, const double *x, const double *y, const double *sig, const int *kind, const int *id,
+                          const int *status) {
+  NEED_RAW(c);
+  if (n < 0 || n > POMGPU_MAXFLOATS) return fail(c, POMGPU_EINVAL, "%s: %d floats asked for, 0..%d are possible", what, n, POMGPU_MAXFLOATS);
+  if (n && (!x || !y || !sig)) return fail(c, POMGPU_EINVAL, "%s: no host array for x, y or sig", what);
+  const KP &P = c->P;
+  if (!(P.W && P.E && P.S && P.N) || c->parent)
+    return fail(c, POMGPU_EINVAL, "%s: this context is a tile with neighbours; floats live on a single tile, moving them between ranks takes a message round a step that the library does not have", what);
+  if (c->flags & POMGPU_CTX_2D) return fail(c, POMGPU_EINVAL, "%s: a context with 3-D arrays", what);
+  if (c->nflt) HIPCHK(c, hipStreamSynchronize(c->stream));     // the steps that still use the old arrays
+  if (!n) { floats_free(c); return POMGPU_OK; }
+  const size_t N = (size_t)n;
+  double *d[3] = {NULL, NULL, NULL};
+  int *q[3] = {NULL, NULL, NULL}, *keep = NULL;
+  bool ok = true;
+  for (int a = 0; a < 3 && ok; a++) ok = hipMalloc((void **)&d[a], N * sizeof(double)) == hipSuccess && hipMalloc((void **)&q[a], N * sizeof(int)) == hipSuccess;
+  if (ok && status) ok = hipMalloc((void **)&keep, N * sizeof(int)) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    for (int a = 0; a < 3; a++) { (void)hipFree(d[a]); (void)hipFree(q[a]); }
+    (void)hipFree(keep);
+    return fail(c, POMGPU_ENOMEM, "%s: no memory for %d floats", what, n);
+  }
+  floats_free(c);                                             // from here on the float set changes
+  c->flt_x = d[0]; c->flt_y = d[1]; c->flt_s = d[2]; c->flt_status = q[0]; c->flt_kind = q[1]; c->flt_id = q[2];
+  c->nflt = n;
+  std::vector<int> iota;
+  if (!id) { iota.resize(N); for (size_t e = 0; e < N; e++) iota[e] = (int)e; id = iota.data(); }
+  int rc = POMGPU_OK;
+  auto put = [&](void *dst, const void *src, size_t bytes) { if (!rc && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = POMGPU_EHIP; };
+  put(c->flt_x, x, N * sizeof(double)); put(c->flt_y, y, N * sizeof(double)); put(c->flt_s, sig, N * sizeof(double));
+  put(c->flt_id, id, N * sizeof(int));
+  if (kind) put(c->flt_kind, kind, N * sizeof(int));
+  else if (hipMemsetAsync(c->flt_kind, 0, N * sizeof(int), c->stream) != hipSuccess) rc = POMGPU_EHIP;
+  if (keep) put(keep, status, N * sizeof(int));
+  if (!rc) launch_float_admit(c, keep);
+  if (hipStreamSynchronize(c->stream) != hipSuccess) rc = POMGPU_EHIP;   // the host arrays are the caller's again
+  (void)hipFree(keep);
+  if (rc) { floats_free(c); return fail(c, POMGPU_EHIP, "%s: a HIP call failed while the floats were copied; none are registered", what); }
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_float_upload(pomgpu_ctx *c, int n, const double *x, const double *y, const double *sig, const int *kind, const int *id) {
+  if (c) { F32_REFUSE(c, "float_upload"); }
+  return pomgpu_float_register(c, "float_upload", n, x, y, sig, kind, id, NULL);
+}
+extern "C" int pomgpu_float_count(pomgpu_ctx *c) { return c ? c->nflt : 0; }
+extern "C" int pomgpu_float_download(pomgpu_ctx *c, double *x, double *y, double *sig, int *status, int *kind, int *id) {
+  if (c) { F32_REFUSE(c, "float_download"); }
+  NEED_RAW(c);
+  if (!c->nflt) return POMGPU_OK;
+  const size_t N = (size_t)c->nflt;
+  if (x) HIPCHK(c, hipMemcpyAsync(x, c->flt_x, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (y) HIPCHK(c, hipMemcpyAsync(y, c->flt_y, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (sig) HIPCHK(c, hipMemcpyAsync(sig, c->flt_s, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (status) HIPCHK(c, hipMemcpyAsync(status, c->flt_status, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (kind) HIPCHK(c, hipMemcpyAsync(kind, c->flt_kind, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (id) HIPCHK(c, hipMemcpyAsync(id, c->flt_id, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_float_step(pomgpu_ctx *c) {
+  if (c) { F32_REFUSE(c, "float_step"); }
+  NEED_RAW(c);
+  if (!c->nflt) return fail(c, POMGPU_EINVAL, "float_step: no floats are registered (pomgpu_float_upload)");
+  float_stage(c);
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_float_sample(pomgpu_ctx *c, double *out) {
+  if (c) { F32_REFUSE(c, "float_sample"); }
+  NEED_RAW(c);
+  if (!c->nflt) return fail(c, POMGPU_EINVAL, "float_sample: no floats are registered (pomgpu_float_upload)");
+  if (!out) return fail(c, POMGPU_EINVAL, "float_sample: no host array");
+  const size_t bytes = 5 * (size_t)c->nflt * sizeof(double);
+  if (!c->flt_smp && hipMalloc((void **)&c->flt_smp, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    c->flt_smp = NULL;
+    return fail(c, POMGPU_ENOMEM, "float_sample: no memory for the result (%zu MB)", bytes >> 20);
+  }
+  { const int rcm = pomgpu_materialize(c); if (rcm) return rcm; }   // t s et dt as pomgpu_download would show them
+  launch_float_sample(c, c->flt_smp);
+  HIPCHK(c, hipMemcpyAsync(out, c->flt_smp, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return POMGPU_OK;
+}
 static int advance(pomgpu_ctx *c, int more_steps_follow);
 extern "C" int pomgpu_advance(pomgpu_ctx *c) { return advance(c, 0); }
 static int advance(pomgpu_ctx *c, int more_steps_follow) {    // advance.f:6-59
@@ -2556,8 +2662,10 @@ static int advance(pomgpu_ctx *c, int more_steps_follow) {    // advance.f:6-59
   }
   prof_phase_close(c, ph_ext, "phase_external");
   c->con.iext = c->con.isplit + 1;
+  const bool body = (c->con.iint != 1 || c->con.time0 != 0.) && c->con.mode != 2;   // mode_internal runs its 3-D part (advance.f:362)
   if ((rc = mode_internal(c, more_steps_follow))) return rc;
   if (c->mean_acc && (rc = mean_accumulate(c))) return rc;    // the time-mean output, where advance.f:38 writes
+  if (c->nflt && body) float_stage(c);                        // the floats move with the u, v, w this step has left: ONE launch
   launch_check_velocity(c);   // result stays on the device; error flag is merged at the next get_con
   prof_phase_close(c, ph_step, "phase_step");
   return POMGPU_OK;
@@ -2639,6 +2747,8 @@ extern "C" int pomgpu_tune_placement(pomgpu_ctx *c, int steps, int max_try, doub
     return fail(c, POMGPU_EINVAL, "tune_placement: the time-mean output is on and the trial steps would count -- tune first, switch the mean on afterwards");
   if (c->ntr)                                                 // ... and would move the tracers
     return fail(c, POMGPU_EINVAL, "tune_placement: passive tracers are registered and the trial steps would move them -- tune first, register tracers afterwards");
+  if (c->nflt)                                                // ... and the floats
+    return fail(c, POMGPU_EINVAL, "tune_placement: floats are registered and the trial steps would move them -- tune first, upload floats afterwards");
 #ifdef POMGPU_EMU
   (void)steps; (void)max_try; (void)ms_out; (void)front_mib_out; (void)pad_mib_out;
   return POMGPU_OK;

@@ -863,6 +863,13 @@ struct pomgpu_ctx {
   size_t trmean_stride;
   int trmean_count;
   double *d_trstats;
+  // Lagrangian floats (pomgpu_float_upload, include/pomgpu.h; the kernels: k_float.hpp): nflt of them as a structure of arrays, three of
+  // doubles (x, y in index coordinates of the grid, sigma) and three of ints (status, kind, id), each its own allocation of nflt elements.
+  // advance runs their step behind mean_accumulate in every step whose 3-D body ran.  flt_smp: pomgpu_float_sample's result on the device
+  // (5 x nflt doubles), allocated at its first call and freed with the floats.  nflt == 0: no array exists, no launch is made
+  int nflt;
+  double *flt_x, *flt_y, *flt_s, *flt_smp;
+  int *flt_status, *flt_kind, *flt_id;
   char err[512];
 };
 // The register-resident column kernels (k_vert.hip: their level loops are unrolled for a template bound, with_kbt) serve this context's
@@ -1056,7 +1063,10 @@ int pomgpu_tp_reserve(pomgpu_ctx *c, const size_t *need);                       
 int pomgpu_tp_reserve2(pomgpu_ctx *c, const size_t *need);                      // ... those of the side stream
 void pomgpu_wr_materialize(pomgpu_ctx *c);                                      // a pending wr formed now (pomgpu_api.hip); part of pomgpu_materialize
 int pomgpu_materialize(pomgpu_ctx *c);                                          // every lazily kept array up to date in the mirrors (pomgpu_api.hip)
-void pomgpu_mirrors_written(pomgpu_ctx *c);                                     // the restart reader has written blk2d / blk3d mirrors on the device: what pomgpu_upload_2d / _3d invalidate (pomgpu_api.hip)
+// n floats from host arrays, as pomgpu_float_upload registers them (pomgpu_api.hip); `what` names the caller in a refusal; status: entries other
+// than ACTIVE are kept over the admission's verdict (pomgpu_read_floats, cdf_in.hip), NULL = none
+int pomgpu_float_register(pomgpu_ctx *c, const char *what, int n, const double *x, const double *y, const double *sig, const int *kind, const int *id, const int *status);
+void pomgpu_mirrors_written(pomgpu_ctx *c);                                    // the restart reader has written blk2d / blk3d mirrors on the device: what pomgpu_upload_2d / _3d invalidate (pomgpu_api.hip)
 void pomgpu_cold_tail(pomgpu_ctx *c, void (*update_initial)(pomgpu_ctx *), void (*sums)(pomgpu_ctx *));   // pomgpu_cold_start's 3-D tail in the reference's order (pomgpu_api.hip): dens twice, update_initial, baropg by npg, drx2d dry2d; then what pomgpu_upload invalidates
 int pomgpu_side_stream(pomgpu_ctx *c);                                          // create the side stream and its events (pomgpu_api.hip); 1 = there
 int pomgpu_tp_side_ok(pomgpu_ctx *c);                                           // can rounds run on the side stream (second communicator / callback mover)?

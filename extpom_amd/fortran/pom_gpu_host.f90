@@ -234,6 +234,41 @@ subroutine mean_accumulate
   if (pomgpu_mean_accumulate(pom_ctx) /= 0) error_status = 1
 end subroutine
 
+! Lagrangian floats (no counterpart in the reference; include/pomgpu.h): pom_floats_put after pomgpu_upload_state -- and after
+! pomgpu_tune_placement, which refuses while floats are registered -- registers n floats at the index coordinates x, y (the centre of cell
+! (i, j) is x = i, y = j) and sigma sig, kind 0 following w and 1 keeping its sigma, id the caller's number; n = 0 frees them.
+! pom_floats_get brings the six arrays back (status: 0 active, 1 exited, 2 lost).  float_step is the floats' stage for a host that strings
+! the routines together: call it after mode_internal and mean_accumulate; nothing happens without floats, nor in a step whose
+! mode_internal skipped its 3-D part (advance.f:362: the first step of a run from rest, mode 2).  Floats have a file of their own,
+! write_floats_pnetcdf and read_floats_pnetcdf (pom_gpu_io.f90).  One tile only: a context with neighbours refuses them.
+subroutine pom_floats_put(n, x, y, sig, kind, id)
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  integer, intent(in) :: n
+  double precision, intent(in), target :: x(*), y(*), sig(*)
+  integer(c_int), intent(in), target :: kind(*), id(*)
+  if (pomgpu_float_upload(pom_ctx, int(n, c_int), c_loc(x), c_loc(y), c_loc(sig), c_loc(kind), c_loc(id)) /= 0) error_status = 1
+end subroutine
+
+subroutine pom_floats_get(x, y, sig, status, kind, id)
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  double precision, intent(out), target :: x(*), y(*), sig(*)
+  integer(c_int), intent(out), target :: status(*), kind(*), id(*)
+  if (pomgpu_float_download(pom_ctx, c_loc(x), c_loc(y), c_loc(sig), c_loc(status), c_loc(kind), c_loc(id)) /= 0) error_status = 1
+end subroutine
+
+subroutine float_step
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  if (pomgpu_float_count(pom_ctx) <= 0) return
+  if ((iint == 1 .and. time0 == 0.d0) .or. mode == 2) return
+  if (pomgpu_float_step(pom_ctx) /= 0) error_status = 1
+end subroutine
+
 subroutine check_velocity
   use pomgpu_iface
   implicit none

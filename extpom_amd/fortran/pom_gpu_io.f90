@@ -227,6 +227,77 @@ subroutine read_tracers_pnetcdf
   end if
 end subroutine
 
+! The float file (no counterpart in the reference; include/pomgpu.h: pomgpu_write_floats): state and samples of the Lagrangian floats,
+! output and checkpoint in one.  kind 0: <wrk_pth>out/<netcdf_file>.floats.rst.nc; kind 1: <wrk_pth>out/<netcdf_file>.floats.<nnnn>.nc with
+! write_output_pnetcdf's counter.  Floats live on one tile: rank 0 writes the whole file, synchronously.  Nothing happens without floats.
+subroutine write_floats_pnetcdf(kind)
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  integer, intent(in) :: kind
+  type(pomgpu_file_meta) :: m
+  character(len=400) :: fname
+  character(kind=c_char, len=401), target :: cname
+  character(kind=c_char, len=41), target :: ctitle
+  character(kind=c_char, len=27), target :: cstart
+  integer :: nprint
+  if (pomgpu_float_count(pom_ctx) <= 0) return
+  if (kind == 0) then
+    write(fname, '(a,''out/'',a,''.floats.rst.nc'')') trim(wrk_pth), trim(netcdf_file)
+  else
+    nprint = (iint+int(time0*86400./dti))/iprint
+    write(fname, '(a,''out/'',a,''.floats.'',i4.4,''.nc'')') trim(wrk_pth), trim(netcdf_file), nprint
+  end if
+  cname = trim(fname)//c_null_char
+  ctitle = trim(title)//c_null_char
+  cstart = trim(time_start)//c_null_char
+  call pomgpu_push_con
+  if (my_task == 0) write(*,'(/''writing file '',a)') trim(fname)
+  m%title = c_loc(ctitle); m%time_start = c_loc(cstart); m%stats = c_null_ptr; m%create = 1
+  m%im_global = im_global; m%jm_global = jm_global
+  m%i0 = i_global(1); m%j0 = j_global(1)
+  if (pomgpu_write_floats(pom_ctx, c_loc(cname), m) /= 0) error_status = 1
+end subroutine
+
+! <wrk_pth>in/<netcdf_file>.floats.nc, where it exists, registered as pom_floats_put would (pomgpu_read_floats): x y sig are required,
+! status kind id optional -- a file with x y sig alone is an initial file any tool can write.  A refusal is printed as the restart reader's
+! is and sets error_status.
+subroutine read_floats_pnetcdf
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  type(pomgpu_file_meta) :: m
+  character(len=400) :: fname
+  character(kind=c_char, len=401), target :: cname
+  character(kind=c_char), pointer :: msg(:)
+  type(c_ptr) :: pm
+  integer(c_int) :: rc
+  integer :: n
+  logical :: there
+  write(fname, '(a,''in/'',a,''.floats.nc'')') trim(wrk_pth), trim(netcdf_file)
+  inquire(file=trim(fname), exist=there)
+  if (.not. there) return
+  cname = trim(fname)//c_null_char
+  if (my_task == 0) write(*,'(/''reading file '',a)') trim(fname)
+  m%title = c_null_ptr; m%time_start = c_null_ptr; m%stats = c_null_ptr; m%create = 0
+  m%im_global = im_global; m%jm_global = jm_global
+  m%i0 = i_global(1); m%j0 = j_global(1)
+  rc = pomgpu_read_floats(pom_ctx, c_loc(cname), m, c_null_ptr, c_null_ptr)
+  if (rc /= 0) then
+    error_status = 1
+    pm = pomgpu_last_error(pom_ctx)                ! names the file and the cause
+    if (c_associated(pm)) then
+      call c_f_pointer(pm, msg, (/512/))
+      n = 0
+      do while (n < 511)
+        if (msg(n+1) == c_null_char) exit
+        n = n + 1
+      end do
+      write(*,'(/i4,''] Error: read_floats_pnetcdf: '',511a1)') my_task, msg(1:n)
+    end if
+  end if
+end subroutine
+
 ! initialize.f:24-36 without PnetCDF: what initialize does between read_input and the restart reader -- initialize_arrays, read_grid,
 ! initial_conditions, update_initial, bottom_friction -- on the device, from <wrk_pth>in/<netcdf_file>.grid.nc, .init.nc and .clim.nc
 ! (the names of io_pnetcdf.F:2102, :2790, :2865).  Call it after read_input and pomgpu_upload_state (blkcon holds the run's constants;

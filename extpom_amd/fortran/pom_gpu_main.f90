@@ -28,6 +28,9 @@
 !                                                                      <wrk_pth>out/<netcdf_file>.tracer.<nnnn>.nc beside it -- the mean kind under
 !                                                                      --mean --; <wrk_pth>out/<netcdf_file>.tracer.rst.nc at the end of the run;
 !                                                                      beside the other flags, in any order)
+!        ... --cold | --cold-z <state.out> <nsteps> --floats   (Lagrangian floats: registered from <wrk_pth>in/<netcdf_file>.floats.nc where it
+!                                                                exists; wherever an output file is written, <wrk_pth>out/<netcdf_file>.floats.<nnnn>.nc
+!                                                                beside it; <wrk_pth>out/<netcdf_file>.floats.rst.nc at the end of the run)
 ! The water files <wrk_pth>in/<netcdf_file>.water.NNNN.nc need no flag: they are registered when record 0000's exists.
 program pom_gpu_main
   use pomgpu_iface
@@ -39,7 +42,7 @@ program pom_gpu_main
   double precision :: vtot, atot, mtot, stot, tavg, savg, eavg, ekin
   double precision, allocatable, target :: tr(:,:,:,:), sr(:,:,:,:)
   character(len=256) :: fin, fout, arg3
-  logical :: cold, mean, sss
+  logical :: cold, mean, sss, floats
 
   call get_command_argument(1, fin)
   call get_command_argument(2, fout)
@@ -48,7 +51,7 @@ program pom_gpu_main
   nbd = 8*jm_local + 8*im_local + (12+12+6+6)*0   ! filled below
   nbd = 20*jm_local + 20*im_local + 18*jm_local*kb + 18*im_local*kb   ! bdry: 20 J, 20 I... see pom_layout.h
   cold = trim(fin) == '--cold' .or. trim(fin) == '--cold-z'
-  mean = .false.; sss = .false.; ntrac = 0
+  mean = .false.; sss = .false.; ntrac = 0; floats = .false.
   if (trim(fin) == '--cold-z') then         ! the init and the clim file are on z levels (initialize.f:410-422)
     pom_init_on_z = .true.; pom_clim_on_z = .true.
   end if
@@ -61,6 +64,7 @@ program pom_gpu_main
       if (trim(arg3) == '--lbry-z') pom_lbry_on_z = .true.
       if (trim(arg3) == '--mean') mean = .true.
       if (trim(arg3) == '--sss') sss = .true.
+      if (trim(arg3) == '--floats') floats = .true.
       if (trim(arg3) == '--lbry-sides') then
         n = n + 1
         call get_command_argument(n, arg3)
@@ -127,6 +131,7 @@ program pom_gpu_main
     call pom_tracers(ntrac)
     call read_tracers_pnetcdf                ! <wrk_pth>in/<netcdf_file>.tracer.nc, where it exists
   end if
+  if (floats) call read_floats_pnetcdf       ! <wrk_pth>in/<netcdf_file>.floats.nc, where it exists
   if (mean) call pom_output_mean(.true.)
   if (sss) call pom_surface_sss(.true.)
   do n = 1, nsteps                          ! pom.f:17-19
@@ -136,10 +141,12 @@ program pom_gpu_main
       if (mod(iint, iprint) == 0) then
         call write_output_pnetcdf
         if (ntrac > 0) call write_tracers_pnetcdf(2)   ! the tracers' means, beside the nine fields'
+        if (floats) call write_floats_pnetcdf(1)       ! the floats as they are now, beside it
       end if
     end if
   end do
   if (ntrac > 0) call write_tracers_pnetcdf(0)   ! <wrk_pth>out/<netcdf_file>.tracer.rst.nc: trb, tr and the work array trf
+  if (floats) call write_floats_pnetcdf(0)       ! <wrk_pth>out/<netcdf_file>.floats.rst.nc: output and checkpoint in one
   if (pom_mean_on) call pom_output_mean(.false.)
   my_task = 0; master_task = 0
   call domain_stats(vtot, atot, mtot, stot, tavg, savg, eavg, ekin)   ! print_section's sums, no state download needed
@@ -183,6 +190,7 @@ subroutine advance_hot
   end do
   call mode_internal
   call mean_accumulate                       ! the time-mean output, where advance.f:38 writes (nothing while it is off)
+  call float_step                            ! the Lagrangian floats (nothing without them)
   call check_velocity
 end subroutine
 

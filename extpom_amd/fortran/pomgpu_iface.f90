@@ -169,6 +169,26 @@ module pomgpu_iface
     integer(c_int) function pomgpu_tracer_mean_download(ctx, n, host) bind(C, name='pomgpu_tracer_mean_download')
       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: n
     end function
+    ! Lagrangian floats (include/pomgpu.h): x y sig doubles, status kind id integers, n of each; kind / id may be c_null_ptr on upload, any
+    ! pointer on download; the float file is output and checkpoint in one
+    integer(c_int) function pomgpu_float_upload(ctx, n, x, y, sig, kind, id) bind(C, name='pomgpu_float_upload')
+      import; type(c_ptr), value :: ctx, x, y, sig, kind, id; integer(c_int), value :: n
+    end function
+    integer(c_int) function pomgpu_float_count(ctx) bind(C, name='pomgpu_float_count')
+      import; type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function pomgpu_float_download(ctx, x, y, sig, status, kind, id) bind(C, name='pomgpu_float_download')
+      import; type(c_ptr), value :: ctx, x, y, sig, status, kind, id
+    end function
+    integer(c_int) function pomgpu_float_sample(ctx, out) bind(C, name='pomgpu_float_sample')
+      import; type(c_ptr), value :: ctx, out   ! out(n, 5): lon lat depth t s
+    end function
+    integer(c_int) function pomgpu_write_floats(ctx, path, meta) bind(C, name='pomgpu_write_floats')
+      import; type(c_ptr), value :: ctx, path; type(pomgpu_file_meta) :: meta
+    end function
+    integer(c_int) function pomgpu_read_floats(ctx, path, meta, time_out, iint_out) bind(C, name='pomgpu_read_floats')
+      import; type(c_ptr), value :: ctx, path, time_out, iint_out; type(pomgpu_file_meta) :: meta
+    end function
     integer(c_int) function pomgpu_write_restart(ctx, path, meta) bind(C, name='pomgpu_write_restart')
       import; type(c_ptr), value :: ctx, path; type(pomgpu_file_meta) :: meta
     end function
@@ -232,6 +252,7 @@ module pomgpu_iface
   procedure(pomgpu_noarg), bind(C, name='pomgpu_mode_external') :: pomgpu_mode_external
   procedure(pomgpu_noarg), bind(C, name='pomgpu_mode_internal') :: pomgpu_mode_internal
   procedure(pomgpu_noarg), bind(C, name='pomgpu_mean_accumulate') :: pomgpu_mean_accumulate
+  procedure(pomgpu_noarg), bind(C, name='pomgpu_float_step') :: pomgpu_float_step
   procedure(pomgpu_noarg), bind(C, name='pomgpu_advave') :: pomgpu_advave
   procedure(pomgpu_noarg), bind(C, name='pomgpu_advct') :: pomgpu_advct
   procedure(pomgpu_noarg), bind(C, name='pomgpu_advu') :: pomgpu_advu

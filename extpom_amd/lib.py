@@ -119,7 +119,14 @@ _SIGS = {
     "pomgpu_tracer_mean_download": (_I, [_P, _I, _P]),
     "pomgpu_write_tracers": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta), _I, ctypes.POINTER(ctypes.c_double)]),
     "pomgpu_read_tracers": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
-    "pomgpu_write_restart": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
+    "pomgpu_float_upload": (_I, [_P, _I, _P, _P, _P, _P, _P]),
+    "pomgpu_float_count": (_I, [_P]),
+    "pomgpu_float_download": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "pomgpu_float_step": (_I, [_P]),
+    "pomgpu_float_sample": (_I, [_P, _P]),
+    "pomgpu_write_floats": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
+    "pomgpu_read_floats": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "pomgpu_write_restart":(_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
     "pomgpu_read_restart": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "pomgpu_set_forcing_files": (_I, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
     "pomgpu_cold_start": (_I, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(FileMeta), ctypes.POINTER(ColdInfo)]),

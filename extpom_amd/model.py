@@ -270,10 +270,14 @@ class PomGpu:
         :1661-2083); this tile's patch at (i_off+1, j_off+1) of the global grid.  kind = "output_mean": the output file with the
         time means of uab vab elb u v t s rho w since set_mean_output or the last such file in place of their values now.
         kind = "tracer_restart" | "tracer_output" | "tracer_output_mean": the tracers' own files (pomgpu_write_tracers); trstats: the
-        rank-reduced (ntr, 4) statistics of the two output kinds, None = this tile's own"""
+        rank-reduced (ntr, 4) statistics of the two output kinds, None = this tile's own.  kind = "floats": the float file
+        (pomgpu_write_floats), output and checkpoint of the Lagrangian floats in one"""
         st = self.st
         m = _lib.FileMeta(title.encode(), time_start.encode(), im_global or st.im, jm_global or st.jm, st.i_off + 1, st.j_off + 1,
                           1 if create else 0, (ctypes.c_double * 8)(*stats) if stats is not None else None)
+        if kind == "floats":
+            self._chk(self.L.pomgpu_write_floats(self.h, str(path).encode(), ctypes.byref(m)), "write_floats")
+            return
         if kind in self.TRACER_FILE_KINDS:
             ts = None
             if trstats is not None:
@@ -381,6 +385,60 @@ class PomGpu:
         m = _lib.FileMeta(b"", b"", im_global or st.im, jm_global or st.jm, st.i_off + 1, st.j_off + 1, 0, None)
         t, ii = ctypes.c_double(), ctypes.c_double()
         self._chk(self.L.pomgpu_read_tracers(self.h, str(path).encode(), ctypes.byref(m), ctypes.byref(t), ctypes.byref(ii)), "read_tracers")
+        return t.value, ii.value
+
+    # ---- Lagrangian floats (pomgpu.h "Lagrangian floats") ---------------------------------------
+    FLOAT_ACTIVE, FLOAT_EXITED, FLOAT_LOST = 0, 1, 2
+    FLOAT_SAMPLES = ("lon", "lat", "depth", "t", "s")
+
+    def set_floats(self, x, y, sig, kind=None, ids=None, sort=False):
+        """pomgpu_float_upload: floats at the index coordinates x, y (cell centre (i, j) at x = i, y = j) and sigma sig; kind 0 follows w,
+        1 keeps its sigma (None: all 0); ids: the caller's numbers (None: 0..n-1).  Empty arrays free the floats.  sort=True orders them
+        by containing cell (jc * im + ic, stable) so that neighbours in memory gather from neighbouring cells; ids keep the caller's
+        numbering.  Floats drift a few hundredths of a cell a step: a host re-sorts at output times if it wants to."""
+        x, y, sig = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (x, y, sig))
+        n = x.size
+        if y.size != n or sig.size != n:
+            raise ValueError(f"set_floats: x, y, sig hold {x.size}, {y.size}, {sig.size} values")
+        kind = np.zeros(n, dtype=np.int32) if kind is None else np.ascontiguousarray(kind, dtype=np.int32).ravel()
+        ids = np.arange(n, dtype=np.int32) if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        if kind.size != n or ids.size != n:
+            raise ValueError(f"set_floats: kind, ids hold {kind.size}, {ids.size} values, not {n}")
+        if sort and n:
+            with np.errstate(invalid="ignore"):
+                ic = np.clip(np.floor(np.nan_to_num(x, nan=0.0) + 0.5), 1, self.st.im)
+                jc = np.clip(np.floor(np.nan_to_num(y, nan=0.0) + 0.5), 1, self.st.jm)
+            order = np.argsort(jc * self.st.im + ic, kind="stable")
+            x, y, sig, kind, ids = (np.ascontiguousarray(a[order]) for a in (x, y, sig, kind, ids))
+        self._chk(self.L.pomgpu_float_upload(self.h, n, self._p(x), self._p(y), self._p(sig), self._p(kind), self._p(ids)), "float_upload")
+
+    def float_count(self) -> int:
+        return int(self.L.pomgpu_float_count(self.h))
+
+    def floats(self) -> dict:
+        """pomgpu_float_download: {"x", "y", "sig" (float64), "status", "kind", "id" (int32)}"""
+        n = self.float_count()
+        out = {k: np.empty(n) for k in ("x", "y", "sig")}
+        out.update({k: np.empty(n, dtype=np.int32) for k in ("status", "kind", "id")})
+        self._chk(self.L.pomgpu_float_download(self.h, *[self._p(out[k]) for k in ("x", "y", "sig", "status", "kind", "id")]), "float_download")
+        return out
+
+    def float_step(self):
+        """pomgpu_float_step: the floats' stage alone, for a host that strings the routines together (advance and run do it themselves)"""
+        self._chk(self.L.pomgpu_float_step(self.h), "float_step")
+
+    def float_sample(self) -> dict:
+        """pomgpu_float_sample: {"lon", "lat", "depth", "t", "s"} of every float, whatever its status"""
+        out = np.empty((5, max(self.float_count(), 1)))
+        self._chk(self.L.pomgpu_float_sample(self.h, self._p(out)), "float_sample")
+        return {k: out[q].copy() for q, k in enumerate(self.FLOAT_SAMPLES)}
+
+    def read_floats(self, path):
+        """pomgpu_read_floats: registers the floats of a float file (x y sig required; status kind id where the file has them) as
+        set_floats would.  Returns (time, iint) of the file, applied to nothing."""
+        m = _lib.FileMeta(b"", b"", self.st.im, self.st.jm, 1, 1, 0, None)
+        t, ii = ctypes.c_double(), ctypes.c_double()
+        self._chk(self.L.pomgpu_read_floats(self.h, str(path).encode(), ctypes.byref(m), ctypes.byref(t), ctypes.byref(ii)), "read_floats")
         return t.value, ii.value
 
     def read_restart(self, path, im_global=None, jm_global=None):

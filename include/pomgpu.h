@@ -624,6 +624,63 @@ int pomgpu_tracer_get(pomgpu_ctx *ctx, int n, int *nbc, double *lam);
 int pomgpu_tracer_mean_count(pomgpu_ctx *ctx);                    /* -1: no tracer accumulators */
 int pomgpu_tracer_mean_download(pomgpu_ctx *ctx, int n, double *host);   /* acc / count, n3 doubles */
 
+/* ---- Lagrangian floats (no counterpart in the reference; optional, off by default: with none registered every byte and every launch is as
+ * without them, and with some every other array keeps its bits) -----------------------------------------------------------------------------
+ * Water parcels that the model's own u, v, w of every internal step carry: surface drifters, larval or spill trajectories.  A float is
+ *   x, y    index coordinates of the grid: the centre of cell (i, j) is x = i, y = j; u(i,j,k) sits at (i - 0.5, j), v(i,j,k) at (i, j - 0.5),
+ *           w and t at (i, j);
+ *   sig     sigma in [-1, 0];
+ *   status  POMGPU_FLOAT_ACTIVE, _EXITED (it left 2..im-1 x 2..jm-1; the position is where it left) or _LOST (a position that was not
+ *           finite, or admitted on land);   kind  0 follows w, 1 keeps its sigma (a surface drifter is sig = 0, kind = 1);
+ *   id      an int the library carries and never reads.
+ * The state is a structure of arrays: three arrays of n doubles and three of n ints, n <= POMGPU_MAXFLOATS.
+ * Interpolation.  L(p, q, f) = p + f * (q - p).  A field point's horizontal cell: for u xs = x + 0.5, i0 = floor(xs), fx = xs - i0,
+ * j0 = floor(y), fy = y - j0; for v the same with y + 0.5; for cell-centre fields floor(x), floor(y); i1 = i0 + 1, j1 = j0 + 1.  Every
+ * coordinate is limited to [0, im + 1] ([0, jm + 1]) by fmax then fmin before it becomes an integer and every index to 1..im (1..jm) after
+ * the fractions are formed, so no position or velocity addresses memory outside the arrays.  Vertically u v t s live on zz: level 1 alone
+ * for sig >= zz(1), level kbm1 alone for sig <= zz(kbm1), else the k with zz(k) >= sig > zz(k+1) and fz = (zz(k) - sig) / (zz(k) - zz(k+1));
+ * w lives on z: the k in 1..kbm1 with z(k) >= sig > z(k+1) and the same fz with z.  A value is L in i, then in j, per level, then in k.
+ * The velocity in index space is V(x, y, sig) = (U / DXU, V / DYV, W / D): DXU the bilinear interpolant, over u's four corners, of
+ * 0.5 * (dx(i,j) + dx(max(i-1,1),j)), DYV likewise of dy and j - 1 over v's, D that of dt at cell centres (w is the sigma velocity).
+ * The step, for ACTIVE floats, is one midpoint step of length dti with the fields frozen:
+ *   (a1,b1,c1) = V(x,y,sig); xm = x + .5*dti*a1, ym alike, sm = sig + .5*dti*c1 (kind 1: sig) limited to [-1, 0]; (a2,b2,c2) = V(xm,ym,sm);
+ *   xn = x + dti*a2, yn alike, sn = sig + dti*c2 (kind 1: sig); sn > 0 reflects to -sn, sn < -1 to -2 - sn, then sn is limited to [-1, 0].
+ * Then, in this order: xn, yn or sn (as summed, before its limits) not finite: LOST, position kept; the containing cell (floor(xn + 0.5),
+ * floor(yn + 0.5)) outside 2..im-1 x 2..jm-1: EXITED, xn yn sn stored; fsm of that cell 0: x, y kept, sig = sn, the float stays active and
+ * tries again; otherwise xn yn sn stored.  pomgpu_advance / pomgpu_run make the step behind pomgpu_mean_accumulate and in front of
+ * check_velocity in every step whose 3-D body ran (mode 3 and 4, not the first step of a run from rest; in mode 2 floats rest), with u v
+ * w dt as that step left them: ONE launch (k_float_step) per step, none without floats.  pomgpu_float_step is the stage alone, for a host
+ * that strings the routines together (after pomgpu_mode_internal and pomgpu_mean_accumulate).
+ * pomgpu_float_upload: n floats from host arrays; kind NULL = all 0, id NULL = 0..n-1; n == 0 frees them.  The positions are admitted by
+ * the step's classification: not finite or on land LOST, outside EXITED.  Replaces whatever was registered.
+ * pomgpu_float_download: any pointer may be NULL.  pomgpu_float_count: the number registered.
+ * pomgpu_float_sample: out[q * n + f], q = 0..4: lon lat depth t s of float f, whatever its status -- lon, lat bilinear in east_e, north_e
+ * at cell centres; depth = et + sig * dt of the containing cell (indices limited like every index); t, s from that cell's column alone,
+ * linear in sigma on zz as above, so that land zeros never mix in.
+ * pomgpu_write_floats: one CDF-2 file, description "float file": dimension nfloat; iint, time (scalars, NC_DOUBLE); x y sig lon lat depth
+ * t s (nfloat) NC_DOUBLE; status kind id (nfloat) NC_INT.  Output and checkpoint in one; written synchronously (68 MB for a million
+ * floats) behind pomgpu_io_wait.  meta->title and time_start are used, the tile members are not.
+ * pomgpu_read_floats: registers the floats of a classic file (CDF-1 or CDF-2) as pomgpu_float_upload would.  x y sig are found by name and
+ * required: NC_DOUBLE, one shared 1-D length, not record variables, inside the file; status kind id are optional (NC_INT, that length),
+ * anything else is ignored: a file with x y sig alone is an initial file any tool can write.  A stored status other than ACTIVE is kept
+ * over the admission's verdict.  *time_out / *iint_out (either may be NULL) return the file's `time` / `iint`, 0 where absent, applied to
+ * nothing.
+ * Refused with POMGPU_EINVAL, error_status = 1 and the cause in pomgpu_last_error, before anything changes: n outside 0..POMGPU_MAXFLOATS;
+ * a NULL position array; a context with any neighbour in pomgpu_dims -- floats live on a single tile, moving them between ranks takes a
+ * message round a step; the fp32-storage variants; a 2-D-only context; step, sample or write with no floats registered; for the reader
+ * also a file it cannot open, any other magic, a required variable absent, of another type or shape, a record variable or one that
+ * reaches beyond the file, more than POMGPU_MAXFLOATS floats.  pomgpu_tune_placement refuses while floats are registered -- its trial
+ * steps are real steps and would move them.  pomgpu_upload, pomgpu_cold_start and pomgpu_read_restart do not touch the floats. */
+#define POMGPU_MAXFLOATS (1 << 26)
+enum { POMGPU_FLOAT_ACTIVE = 0, POMGPU_FLOAT_EXITED = 1, POMGPU_FLOAT_LOST = 2 };
+int pomgpu_float_upload(pomgpu_ctx *ctx, int n, const double *x, const double *y, const double *sig, const int *kind, const int *id);
+int pomgpu_float_count(pomgpu_ctx *ctx);
+int pomgpu_float_download(pomgpu_ctx *ctx, double *x, double *y, double *sig, int *status, int *kind, int *id);
+int pomgpu_float_step(pomgpu_ctx *ctx);
+int pomgpu_float_sample(pomgpu_ctx *ctx, double *out5n);
+int pomgpu_write_floats(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta);
+int pomgpu_read_floats(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta, double *time_out, double *iint_out);
+
 /* ---- the hot path: kernels (solver.f, bounds_forcing.f), device-resident ---------------- */
 int pomgpu_advave(pomgpu_ctx *ctx);              /* solver.f:6-198   */
 int pomgpu_advct(pomgpu_ctx *ctx);               /* solver.f:201-408 */
