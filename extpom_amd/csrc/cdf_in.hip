@@ -6,6 +6,7 @@
 #include <fcntl.h>
 #include <sys/stat.h>
 
+#include <cmath>
 #include <cstdio>
 
 #include "cdf_io.hpp"
@@ -280,6 +281,75 @@ extern "C" int pomgpu_read_floats(pomgpu_ctx *c, const char *path, const pomgpu_
   if (time_out) *time_out = sc[0];
   if (iint_out) *iint_out = sc[1];
   return POMGPU_OK;
+}
+
+// ---- the tide file (pomgpu_set_tide_file, include/pomgpu.h) ---------------------------------------------------------------------------------
+// omega(ncon) and, per side that has them, el_amp.<side> el_pha.<side> [un_amp.<side> un_pha.<side>], (ncon, jm_global | im_global), NC_DOUBLE,
+// found by name; every variable is checked before anything changes.  A few lines: read and byte-swapped on the host, converted as the
+// Python layer converts (C = A cos g, S = A sin g, g in degrees) and registered through pomgpu_set_tides, which makes its own refusals
+extern "C" int pomgpu_set_tide_file(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m) {
+#ifdef POMGPU_STORE_F32
+  if (c) return fail(c, POMGPU_EINVAL, "set_tide_file: not in the fp32-storage variant (3-D arrays are not doubles there)");
+#endif
+  if (!c || !path || !m) return POMGPU_EINVAL;
+  (void)hipSetDevice(c->device);
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return fail(c, POMGPU_EINVAL, "set_tide_file: cannot open %s", path);
+  struct stat sb;
+  if (fstat(fd, &sb)) { (void)close(fd); return fail(c, POMGPU_EINVAL, "set_tide_file: cannot stat %s", path); }
+  const uint64_t fsize = (uint64_t)sb.st_size;
+  RHeader H;
+  {
+    std::string what;
+    const int rc = read_header(fd, fsize, H, what);
+    if (rc == -2) { (void)close(fd); return fail(c, POMGPU_EINVAL, "set_tide_file: I/O error on %s (header)", path); }
+    if (rc < 0) { (void)close(fd); return fail(c, POMGPU_EINVAL, "set_tide_file: %s is not a tide file this library reads: %s", path, what.c_str()); }
+  }
+  auto refuse = [&](const std::string &why) { (void)close(fd); return fail(c, POMGPU_EINVAL, "set_tide_file: %s: %s", path, why.c_str()); };
+  const RVar *vo = find_var(H, "omega");
+  if (!vo) return refuse("variable omega is absent");
+  if (vo->dimids.size() != 1) return refuse("variable omega has the dimension lengths " + lengths_of(H, *vo) + ", wanted one dimension");
+  const uint64_t NC = H.dimlen[vo->dimids[0]];
+  if (NC < 1 || NC > (uint64_t)POMGPU_MAXTIDES) return refuse("the file holds " + std::to_string(NC) + " constituents, 1.." + std::to_string(POMGPU_MAXTIDES) + " are possible");
+  std::string why = check_var(H, fsize, "omega", VarWant::fixed(NC_ONLY_DOUBLE, {NC}), &vo);
+  static const char *const SIDE[4] = {"east", "south", "west", "north"}, *const STEM[4] = {"el_amp", "el_pha", "un_amp", "un_pha"};
+  const RVar *lv[4][4] = {};
+  int sides = 0;
+  for (int s = 0; s < 4 && why.empty(); s++) {
+    const uint64_t n = (uint64_t)((s == 0 || s == 2) ? m->jm_global : m->im_global);
+    bool have[4];
+    for (int q = 0; q < 4; q++) have[q] = find_var(H, (std::string(STEM[q]) + "." + SIDE[s]).c_str()) != NULL;
+    if (have[0] != have[1] || have[2] != have[3]) { why = std::string("the ") + SIDE[s] + " side has an amplitude without its phase, or a phase without its amplitude"; break; }
+    if (have[2] && !have[0]) { why = std::string("the ") + SIDE[s] + " side has un lines and no el lines"; break; }
+    for (int q = 0; q < 4 && why.empty(); q++)
+      if (have[q]) why = check_var(H, fsize, (std::string(STEM[q]) + "." + SIDE[s]).c_str(), VarWant::fixed(NC_ONLY_DOUBLE, {NC, n}), &lv[s][q]);
+    if (have[0]) sides |= 1 << s;
+  }
+  if (!why.empty()) return refuse(why);
+  auto swap8 = [](double *p, size_t n) { for (size_t e = 0; e < n; e++) { uint64_t u; memcpy(&u, p + e, 8); u = __builtin_bswap64(u); memcpy(p + e, &u, 8); } };
+  std::vector<double> omega((size_t)NC);
+  if (pread_all(fd, omega.data(), 8 * (size_t)NC, vo->begin)) return refuse("I/O error (omega)");
+  swap8(omega.data(), omega.size());
+  std::vector<double> buf[4][4];
+  const double *lines[16] = {};
+  for (int s = 0; s < 4; s++) {
+    const size_t n = (size_t)NC * (size_t)((s == 0 || s == 2) ? m->jm_global : m->im_global);
+    for (int q0 = 0; q0 < 4; q0 += 2) {
+      if (!lv[s][q0]) continue;
+      std::vector<double> amp(n), pha(n);
+      if (pread_all(fd, amp.data(), 8 * n, lv[s][q0]->begin) || pread_all(fd, pha.data(), 8 * n, lv[s][q0 + 1]->begin)) return refuse(std::string("I/O error (") + SIDE[s] + ")");
+      swap8(amp.data(), n); swap8(pha.data(), n);
+      buf[s][q0].resize(n); buf[s][q0 + 1].resize(n);
+      for (size_t e = 0; e < n; e++) {
+        const double g = pha[e] * (3.14159265358979323846 / 180.);
+        buf[s][q0][e] = amp[e] * cos(g);
+        buf[s][q0 + 1][e] = amp[e] * sin(g);
+      }
+      lines[4 * s + q0] = buf[s][q0].data(); lines[4 * s + q0 + 1] = buf[s][q0 + 1].data();
+    }
+  }
+  (void)close(fd);
+  return pomgpu_set_tides(c, (int)NC, omega.data(), sides, lines, m);   // from here on the table changes; its own refusals come first
 }
 
 // ---- a cold start from the reference's input files (pomgpu_cold_start) ---------------------------------------------------------------

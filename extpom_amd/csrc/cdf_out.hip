@@ -31,7 +31,7 @@
 
 namespace {
 struct Att { std::string name, text; };
-enum Src { SCALAR, LEVELS1D, PLANE2D, VOLUME3D };
+enum Src { SCALAR, LEVELS1D, PLANE2D, VOLUME3D, VALUES1D };
 struct Var {
   std::string name;
   std::vector<int> dims;          // dimension ids, slowest first (file order)
@@ -41,6 +41,7 @@ struct Var {
   uint64_t begin;
   const double *dev;              // VOLUME3D outside blk3d (a tracer's array): the device address; NULL = the slot's mirror
   int tmean;                      // the tracer (0-based) whose mean accumulator supplies the values in a tracer mean file, -1 = none
+  std::vector<double> vals;       // VALUES1D: the values of a 1-D variable the caller holds on the host (the harmonics file's omega)
 };
 struct Spec { std::vector<std::pair<std::string, int>> dims; std::vector<Att> gatts; std::vector<Var> vars; };
 
@@ -217,6 +218,7 @@ static int write_file(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m
     if (bad) break;
     if (v.src == SCALAR) { if (m->create) bad |= write_be(fd, &v.value, 1, v.begin, tmp); continue; }
     if (v.src == LEVELS1D && m->create) bad |= write_be(fd, J->b1.data() + (size_t)v.slot * P.kb, (size_t)v.nlev, v.begin, tmp);
+    if (v.src == VALUES1D && m->create) bad |= write_be(fd, v.vals.data(), v.vals.size(), v.begin, tmp);
   }
   size_t total = 0;
   for (const Var &v : S.vars) total += var_doubles(*J, v);
@@ -629,6 +631,49 @@ extern "C" int pomgpu_write_tracers(pomgpu_ctx *c, const char *path, const pomgp
   for (int n = 1; n <= ntr; n++)
     S.vars.push_back(volume(nn("tr", n), {T, ZZ, Y, X}, "passive tracer " + nn("", n), "east_e north_e zz", c->trc[n - 1].tr, P.kbm1, n - 1));
   return write_file(c, path, m, S, mean ? 2 : 0);
+}
+
+// ---- the harmonics file (include/pomgpu.h: pomgpu_write_harmonics; no counterpart in the reference) -----------------------------------------
+// omega(ncon), count, t_first, t_last and per field of elb uab vab <f>_mean(y,x), <f>_amp(ncon,y,x), <f>_pha(ncon,y,x): the planes
+// pomgpu_harmonic_planes leaves on the device go through the patch writer like any array of a tile.  Writing resets nothing
+extern "C" int pomgpu_write_harmonics(pomgpu_ctx *c, const char *path, const pomgpu_file_meta *m) {
+#ifdef POMGPU_STORE_F32
+  if (c) return pomgpu_fail(c, POMGPU_EINVAL, "write_harmonics: not in the fp32-storage variant (3-D arrays are not doubles there)");
+#endif
+  if (!c || !path || !m) return POMGPU_EINVAL;
+  (void)hipSetDevice(c->device);
+  { const int rcw = pomgpu_io_wait(c); if (rcw) return rcw; }  // the planes are rewritten below: no file may still be reading them
+  const double *planes = NULL;
+  { const int rcp = pomgpu_harmonic_planes(c, &planes); if (rcp) return rcp; }
+  const KP &P = c->P;
+  const int nc = c->ntide;
+  Spec S;
+  S.dims = {{"ncon", nc}, {"y", m->jm_global}, {"x", m->im_global}};
+  S.gatts = {{"title", m->title ? m->title : ""}, {"description", "harmonics file"}};
+  const int N = 0, Y = 1, X = 2;
+  Var om = mk("omega", {N}, "angular frequency of the constituent", "radian/sec", NULL, VALUES1D, 0, nc);
+  om.vals.assign(c->tide_omega, c->tide_omega + nc);
+  S.vars.push_back(om);
+  S.vars.push_back(mk("count", {}, "samples in the sums", "dimensionless", NULL, SCALAR, 0, 0, (double)c->harm_count));
+  S.vars.push_back(mk("t_first", {}, "time of the first sample", "sec", NULL, SCALAR, 0, 0, c->harm_t[0]));
+  S.vars.push_back(mk("t_last", {}, "time of the last sample", "sec", NULL, SCALAR, 0, 0, c->harm_t[1]));
+  static const struct { const char *n, *ln, *u, *co; } F[3] = {{"elb", "surface elevation", "metre", "east_e north_e"}, {"uab", "depth-averaged u", "metre/sec", "east_u north_u"},
+                                                               {"vab", "depth-averaged v", "metre/sec", "east_v north_v"}};
+  const size_t np = 1 + 2 * (size_t)nc;
+  for (int f = 0; f < 3; f++) {
+    const double *base = planes + (size_t)f * np * P.n2;
+    const std::string n = F[f].n, ln = F[f].ln;
+    Var a = mk((n + "_mean").c_str(), {Y, X}, ("mean of " + ln).c_str(), F[f].u, F[f].co, PLANE2D, -1, 1);
+    a.dev = base;
+    S.vars.push_back(a);
+    Var b = mk((n + "_amp").c_str(), {N, Y, X}, ("amplitude of " + ln).c_str(), F[f].u, F[f].co, VOLUME3D, -1, nc);
+    b.dev = base + P.n2;
+    S.vars.push_back(b);
+    Var g = mk((n + "_pha").c_str(), {N, Y, X}, ("phase g of " + ln + ", A cos(omega t - g)").c_str(), "degree", F[f].co, VOLUME3D, -1, nc);
+    g.dev = base + (1 + (size_t)nc) * P.n2;
+    S.vars.push_back(g);
+  }
+  return write_file(c, path, m, S);
 }
 
 // ---- the float file (include/pomgpu.h: pomgpu_write_floats; no counterpart in the reference) ------------------------------------------------

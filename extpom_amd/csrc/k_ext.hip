@@ -427,6 +427,21 @@ __device__ __forceinline__ double vaf_interior(const KP &P, int i, int j, double
       ((F2(h, i, j) + ec + F2(h, i, j - 1) + es) * F2(arv, i, j));                            // :282-286
   return v;
 }
+// The tide of an open boundary (pomgpu_set_tides, include/pomgpu.h): what bcond(2) reads as the elevation e and the depth-mean NORMAL velocity
+// un of point a of side `side` (0 west, 1 east: a = j; 2 south, 3 north: a = i) gets constituent c's elC*cw + elS*sw and unC*cw + unS*sw added,
+// c = 0..ntide-1 in that order, with the host's phasors of substep P.iext.  The stored boundary arrays are not written.  No tide: e, un as loaded
+__device__ __forceinline__ void tide_add(const KP &P, int side, int a, double &e, double &un) {
+  const int bit = side == 0 ? 4 : (side == 1 ? 1 : (side == 2 ? 2 : 8));   // POMGPU_SIDE_WEST, _EAST, _SOUTH, _NORTH
+  if (!P.ntide || !(P.tide_sides & bit)) return;
+  const int ld = side < 2 ? P.tide_ldj : P.tide_ldi;
+  const double *L = (side < 2 ? P.tide_j : P.tide_i) + (size_t)(side & 1) * P.ntide * 4 * ld + (size_t)(a - 1);
+  const double *ph = P.tide_ph + (size_t)(P.iext - 1) * P.ntide * 2;
+  for (int c = 0; c < P.ntide; c++, L += 4 * ld) {
+    const double cw = ph[2 * c], sw = ph[2 * c + 1];
+    e = e + (L[0] * cw + L[ld] * sw);
+    un = un + (L[2 * ld] * cw + L[3 * ld] * sw);
+  }
+}
 // the open-boundary values of bcond(2); `interior` = 0 skips the advance.f formulas (bcond alone)
 // adu, adv: advua(i,j), advva(i,j)
 __device__ __forceinline__ void uvaf_cell(const KP &P, int i, int j, int interior, double ec, double ew, double es, double adu, double adv,
@@ -439,21 +454,29 @@ __device__ __forceinline__ void uvaf_cell(const KP &P, int i, int j, int interio
   }
   if (P.W && jin && (i == 1 || i == 2)) {                                                 // :47-53
     if (i == 1) v = BD1(vabw, j);
-    u = BD1(uabw, j) - P.rfw * sqrt(P.grav / d_(2, j)) * (el_(2, j) - BD1(elw, j));
+    double e = BD1(elw, j), un = BD1(uabw, j);
+    tide_add(P, 0, j, e, un);
+    u = un - P.rfw * sqrt(P.grav / d_(2, j)) * (el_(2, j) - e);
     u = P.ramp * u;
   }
   if (P.E && jin && i == P.im) {                                                          // :56-61
-    u = BD1(uabe, j) + P.rfe * sqrt(P.grav / d_(P.imm1, j)) * (el_(P.imm1, j) - BD1(ele, j));
+    double e = BD1(ele, j), un = BD1(uabe, j);
+    tide_add(P, 1, j, e, un);
+    u = un + P.rfe * sqrt(P.grav / d_(P.imm1, j)) * (el_(P.imm1, j) - e);
     u = P.ramp * u;
     v = BD1(vabe, j);
   }
   if (P.S && iin && (j == 1 || j == 2)) {                                                 // :64-70
     if (j == 1) u = BD1(uabs, i);
-    v = BD1(vabs, i) - P.rfs * sqrt(P.grav / d_(i, 2)) * (el_(i, 2) - BD1(els, i));
+    double e = BD1(els, i), un = BD1(vabs, i);
+    tide_add(P, 2, i, e, un);
+    v = un - P.rfs * sqrt(P.grav / d_(i, 2)) * (el_(i, 2) - e);
     v = P.ramp * v;
   }
   if (P.N && iin && j == P.jm) {                                                          // :73-78
-    v = BD1(vabn, i) + P.rfn * sqrt(P.grav / d_(i, P.jmm1)) * (el_(i, P.jmm1) - BD1(eln, i));
+    double e = BD1(eln, i), un = BD1(vabn, i);
+    tide_add(P, 3, i, e, un);
+    v = un + P.rfn * sqrt(P.grav / d_(i, P.jmm1)) * (el_(i, P.jmm1) - e);
     v = P.ramp * v;
     u = BD1(uabn, i);
   }
@@ -557,21 +580,29 @@ __device__ __forceinline__ void uvaf_cell_nb(const KP &P, int i, int j, double e
   double u = ucalc ? u1 : u0, v = vcalc ? v1 : v0;
   if (P.W && jin && (i == 1 || i == 2)) {                                                 // :47-53
     if (i == 1) v = BD1(vabw, j);
-    u = BD1(uabw, j) - P.rfw * sqrt(P.grav / d_(2, j)) * (el_(2, j) - BD1(elw, j));
+    double e = BD1(elw, j), un = BD1(uabw, j);
+    tide_add(P, 0, j, e, un);
+    u = un - P.rfw * sqrt(P.grav / d_(2, j)) * (el_(2, j) - e);
     u = P.ramp * u;
   }
   if (P.E && jin && i == P.im) {                                                          // :56-61
-    u = BD1(uabe, j) + P.rfe * sqrt(P.grav / d_(P.imm1, j)) * (el_(P.imm1, j) - BD1(ele, j));
+    double e = BD1(ele, j), un = BD1(uabe, j);
+    tide_add(P, 1, j, e, un);
+    u = un + P.rfe * sqrt(P.grav / d_(P.imm1, j)) * (el_(P.imm1, j) - e);
     u = P.ramp * u;
     v = BD1(vabe, j);
   }
   if (P.S && iin && (j == 1 || j == 2)) {                                                 // :64-70
     if (j == 1) u = BD1(uabs, i);
-    v = BD1(vabs, i) - P.rfs * sqrt(P.grav / d_(i, 2)) * (el_(i, 2) - BD1(els, i));
+    double e = BD1(els, i), un = BD1(vabs, i);
+    tide_add(P, 2, i, e, un);
+    v = un - P.rfs * sqrt(P.grav / d_(i, 2)) * (el_(i, 2) - e);
     v = P.ramp * v;
   }
   if (P.N && iin && j == P.jm) {                                                          // :73-78
-    v = BD1(vabn, i) + P.rfn * sqrt(P.grav / d_(i, P.jmm1)) * (el_(i, P.jmm1) - BD1(eln, i));
+    double e = BD1(eln, i), un = BD1(vabn, i);
+    tide_add(P, 3, i, e, un);
+    v = un + P.rfn * sqrt(P.grav / d_(i, P.jmm1)) * (el_(i, P.jmm1) - e);
     v = P.ramp * v;
     u = BD1(uabn, i);
   }

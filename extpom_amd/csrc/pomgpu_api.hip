@@ -11,6 +11,7 @@
 #include "pomgpu.h"
 #include "pomgpu_internal.hpp"
 #include "k_float.hpp"
+#include "k_tide.hpp"
 
 struct ProfPair { int slot; hipEvent_t a, b; };
 struct ProfState { std::vector<ProfPair> pending; std::vector<ProfPair> free_; char filter[64]; };
@@ -165,6 +166,10 @@ static void sync_scalars(pomgpu_ctx *c) {
 
 static void tracers_free(pomgpu_ctx *c);
 static void floats_free(pomgpu_ctx *c);
+static void tides_free(pomgpu_ctx *c);
+static int tide_table(pomgpu_ctx *c);
+static int tide_widen(pomgpu_ctx *c);
+static int harm_accumulate(pomgpu_ctx *c);
 // ---- life cycle -------------------------------------------------------------------------------
 // a digest of the library's sources, put in by the build (__graft_entry__.build_hip): measurements kept in profiles/ carry it, and
 // bench.py only quotes a stored counter value (roofline.traffic) for the build it was taken from
@@ -515,6 +520,7 @@ extern "C" void pomgpu_destroy(pomgpu_ctx *c) {
   (void)hipFree(c->mean_acc);
   tracers_free(c);
   floats_free(c);
+  tides_free(c);
   ProfState *ps = PS(c);
   if (ps) {
     for (auto &p : ps->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -1266,6 +1272,7 @@ static KP row_window(const KP &P, int lo, int hi) {
   for (int n = 0; n < POMGPU_NCOEF2; n++) if (Q.c2[n]) Q.c2[n] += sh;
   for (int n = 0; n < POMGPU_NGEN; n++) { Q.x2[n] += sh; Q.y2[n] += sh; }
   if (Q.m8) Q.m8 += sh;
+  if (Q.tide_j) Q.tide_j += lo;                               // the tide's j-indexed lines, like the boundary values below
   int s = 0;
 #define BD_(name, shape) Q.bdoff[s++] += BDW_##shape;
 #define BDW_J ((size_t)lo)
@@ -1676,6 +1683,7 @@ extern "C" int pomgpu_set_wide_external(pomgpu_ctx *c, int on, int min_im, int m
     Wd.split = 1;
   }
   Wd.static_done = 0;
+  if ((rc = tide_widen(c))) { wide_free(c); return rc; }      // the extended tile's stretch of the tide's lines, cut from the global ones
   Wd.on = 1;
   return POMGPU_OK;
 }
@@ -1752,6 +1760,11 @@ static void ext_flush_deferred(pomgpu_ctx *c) {
 extern "C" int pomgpu_mode_external(pomgpu_ctx *c) {
   NEED_RAW(c);
   const int iext = c->con.iext;
+  if (c->ntide) {                                             // the step's phasors, once per iint; the table has isplit substeps
+    if (iext < 1 || iext > c->con.isplit) return fail(c, POMGPU_EINVAL, "mode_external with a tide: iext = %d is not a substep of 1..%d", iext, c->con.isplit);
+    const int rct = tide_table(c);
+    if (rct) return rct;
+  }
   if (c->ext_deferred) {
     if (iext == c->ext_deferred + 1) {
       const int first = c->ext_deferred;
@@ -2625,6 +2638,295 @@ extern "C" int pomgpu_float_sample(pomgpu_ctx *c, double *out) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return POMGPU_OK;
 }
+// ---- tides (include/pomgpu.h "tides"; tide_add in k_ext.hip, the other kernels: k_tide.hpp) -------------------------------------------------
+static void tide_phasors(const pomgpu_ctx *c, double t, double *out) {
+  for (int q = 0; q < c->ntide; q++) { out[2 * q] = cos(c->tide_omega[q] * t); out[2 * q + 1] = sin(c->tide_omega[q] * t); }
+}
+static double tide_time(const pom_blkcon &k, int iint, int iext) {
+  return (k.time0 * 86400. + k.dti * (double)(iint - 1)) + k.dte * (double)iext;
+}
+// the coefficient lines of context t (the tile, or its extended tile `off` cells further west / south) cut out of the global lines and put on
+// the device; KP's members set.  0 or a pomgpu_status; nothing changes on failure
+static int tide_cut(pomgpu_ctx *c, pomgpu_ctx *t, int ox, int oy, int sides) {
+  KP &P = t->P;
+  const int nc = c->ntide, ldj = P.jml, ldi = P.iml;
+  const size_t nj = (size_t)2 * nc * 4 * ldj, ni = (size_t)2 * nc * 4 * ldi;
+  std::vector<double> h(nj + ni, 0.);
+  for (int side = 0; side < 4; side++) {
+    const bool alongj = side < 2;
+    const int ld = alongj ? ldj : ldi, len = alongj ? P.jm : P.im, ng = alongj ? c->tide_g[1] : c->tide_g[0];
+    const int g0 = (alongj ? c->tide_g[3] - oy : c->tide_g[2] - ox) - 1;      // global index (0-based) of the context's point 1
+    for (int q = 0; q < 4; q++) {
+      const double *src = c->tide_host[side][q];
+      if (!src) continue;
+      for (int k = 0; k < nc; k++) {
+        double *dst = h.data() + (alongj ? 0 : nj) + ((size_t)((side & 1) * nc + k) * 4 + q) * ld;
+        for (int a = 0; a < len; a++) dst[a] = src[(size_t)k * ng + g0 + a];
+      }
+    }
+  }
+  double *dev = NULL;
+  if (hipMalloc((void **)&dev, h.size() * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return fail(c, POMGPU_ENOMEM, "set_tides: no memory for the coefficient lines"); }
+  if (hipMemcpyAsync(dev, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+    (void)hipFree(dev);
+    return fail(c, POMGPU_EHIP, "set_tides: the coefficient lines could not be copied");
+  }
+  (void)hipFree(t->tide_dev);
+  t->tide_dev = dev;
+  P.ntide = nc; P.tide_sides = sides; P.tide_ldj = ldj; P.tide_ldi = ldi;
+  P.tide_j = dev; P.tide_i = dev + nj;
+  P.tide_ph = c->tide_tab;
+  return POMGPU_OK;
+}
+static void tide_off(pomgpu_ctx *t) {
+  KP &P = t->P;
+  P.ntide = P.tide_sides = P.tide_ldj = P.tide_ldi = 0;
+  P.tide_ph = P.tide_j = P.tide_i = NULL;
+  (void)hipFree(t->tide_dev);
+  t->tide_dev = NULL;
+}
+static void harm_free(pomgpu_ctx *c) {
+  if (c->harm_acc) (void)hipStreamSynchronize(c->stream);
+  (void)hipFree(c->harm_acc); (void)hipFree(c->harm_coef); (void)hipFree(c->harm_file);
+  c->harm_acc = c->harm_coef = c->harm_file = NULL;
+  c->harm_on = c->harm_count = 0; c->harm_every = 1;
+}
+static void tides_free(pomgpu_ctx *c) {
+  harm_free(c);
+  tide_off(c);
+  if (c->wide.x) tide_off(c->wide.x);
+  for (int s = 0; s < 4; s++) for (int q = 0; q < 4; q++) { free(c->tide_host[s][q]); c->tide_host[s][q] = NULL; }
+  (void)hipFree(c->tide_tab);
+  c->tide_tab = NULL; c->tide_tab_cap = 0; c->tide_key_ok = 0;
+  c->ntide = 0;
+}
+// is the stretch of a context of n points that begins `off` points before the tile's inside the global line of ng points?
+static bool tide_inside(int g1, int off, int n, int ng) { return g1 - off >= 1 && g1 - off - 1 + n <= ng; }
+// the extended tile of the wide-halo mode takes the table of its tile (pomgpu_set_wide_external, behind ctx_create)
+static int tide_widen(pomgpu_ctx *c) {
+  if (!c->ntide || !c->wide.x) return POMGPU_OK;
+  const pomgpu_wide &Wd = c->wide;
+  if (!tide_inside(c->tide_g[2], Wd.ox, Wd.x->P.im, c->tide_g[0]) || !tide_inside(c->tide_g[3], Wd.oy, Wd.x->P.jm, c->tide_g[1]))
+    return fail(c, POMGPU_EINVAL, "tides: the extended tile's stretch lies outside the global line (%d x %d from %d, %d of %d x %d)", Wd.x->P.im, Wd.x->P.jm,
+                c->tide_g[2] - Wd.ox, c->tide_g[3] - Wd.oy, c->tide_g[0], c->tide_g[1]);
+  return tide_cut(c, Wd.x, Wd.ox, Wd.oy, c->P.tide_sides);
+}
+extern "C" int pomgpu_set_tides(pomgpu_ctx *c, int nc, const double *omega, int sides, const double *const *lines, const pomgpu_file_meta *meta) {
+  if (c) { F32_REFUSE(c, "set_tides"); }
+  NEED_HOT(c);
+  if (c->flags & POMGPU_CTX_2D) return fail(c, POMGPU_EINVAL, "set_tides: the table belongs to the tile's context, not to its extended tile");   // (no public way makes such a context: no test)
+  if (nc < 0 || nc > POMGPU_MAXTIDES) return fail(c, POMGPU_EINVAL, "set_tides: %d constituents asked for, 0..%d are possible", nc, POMGPU_MAXTIDES);
+  if (!nc) { HIPCHK(c, hipStreamSynchronize(c->stream)); tides_free(c); return POMGPU_OK; }
+  if (!omega || !meta) return fail(c, POMGPU_EINVAL, "set_tides: no omega or no meta");
+  if (sides & ~15) return fail(c, POMGPU_EINVAL, "set_tides: sides = %d is not a set of POMGPU_SIDE_* bits", sides);
+  if (sides && !lines) return fail(c, POMGPU_EINVAL, "set_tides: no lines");
+  for (int q = 0; q < nc; q++) if (!isfinite(omega[q])) return fail(c, POMGPU_EINVAL, "set_tides: omega[%d] is not finite", q);
+  const KP &P = c->P;
+  const int ig = meta->im_global, jg = meta->jm_global;
+  if (!tide_inside(meta->i0, 0, P.im, ig) || !tide_inside(meta->j0, 0, P.jm, jg))
+    return fail(c, POMGPU_EINVAL, "set_tides: the tile's stretch (%d x %d from %d, %d) lies outside the global line (%d x %d)", P.im, P.jm, meta->i0, meta->j0, ig, jg);
+  if (c->wide.x && (!tide_inside(meta->i0, c->wide.ox, c->wide.x->P.im, ig) || !tide_inside(meta->j0, c->wide.oy, c->wide.x->P.jm, jg)))
+    return fail(c, POMGPU_EINVAL, "set_tides: the extended tile's stretch lies outside the global line (%d x %d)", ig, jg);
+  static const int bit_of[4] = {POMGPU_SIDE_WEST, POMGPU_SIDE_EAST, POMGPU_SIDE_SOUTH, POMGPU_SIDE_NORTH}, arg_of[4] = {2, 0, 1, 3};   // W E S N -> the caller's order
+  for (int s = 0; s < 4; s++) {
+    if (!(sides & bit_of[s])) continue;
+    const size_t n = (size_t)nc * (s < 2 ? jg : ig);
+    const char *nm = s == 0 ? "west" : (s == 1 ? "east" : (s == 2 ? "south" : "north"));
+    if (!lines[4 * arg_of[s]] || !lines[4 * arg_of[s] + 1]) return fail(c, POMGPU_EINVAL, "set_tides: the %s side is on and has no elevation line", nm);
+    for (int q = 0; q < 4; q++) {
+      const double *src = lines[4 * arg_of[s] + q];
+      for (size_t e = 0; src && e < n; e++)
+        if (!isfinite(src[e])) return fail(c, POMGPU_EINVAL, "set_tides: a coefficient of the %s side is not finite (line %d, element %zu)", nm, q, e);
+    }
+  }
+  // every refusal is behind us but those of the allocator: the new table is built beside the old one
+  double *nh[4][4] = {};
+  bool ok = true;
+  for (int s = 0; s < 4 && ok; s++) {
+    if (!(sides & bit_of[s])) continue;
+    const size_t n = (size_t)nc * (s < 2 ? jg : ig);
+    for (int q = 0; q < 4 && ok; q++) {
+      nh[s][q] = (double *)calloc(n, sizeof(double));
+      if (!nh[s][q]) { ok = false; break; }
+      const double *src = lines[4 * arg_of[s] + q];
+      if (src) memcpy(nh[s][q], src, n * sizeof(double));
+    }
+  }
+  if (!ok) {
+    for (int s = 0; s < 4; s++) for (int q = 0; q < 4; q++) free(nh[s][q]);
+    return fail(c, POMGPU_ENOMEM, "set_tides: no memory for the lines");
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));                  // the steps that still read the old lines
+  tides_free(c);                                              // from here on the table changes (the analysis goes with the old table)
+  c->ntide = nc;
+  for (int q = 0; q < nc; q++) c->tide_omega[q] = omega[q];
+  for (int s = 0; s < 4; s++) for (int q = 0; q < 4; q++) c->tide_host[s][q] = nh[s][q];
+  c->tide_g[0] = ig; c->tide_g[1] = jg; c->tide_g[2] = meta->i0; c->tide_g[3] = meta->j0;
+  int rc = tide_cut(c, c, 0, 0, sides);
+  if (!rc && c->wide.x) rc = tide_cut(c, c->wide.x, c->wide.ox, c->wide.oy, sides);
+  if (rc) { tides_free(c); return rc; }
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_tide_count(pomgpu_ctx *c) { return c ? c->ntide : 0; }
+extern "C" int pomgpu_tide_phasors(pomgpu_ctx *c, int iint, int iext, double *out) {
+  if (!c || !out) return POMGPU_EINVAL;
+  tide_phasors(c, tide_time(c->con, iint, iext), out);
+  return POMGPU_OK;
+}
+// The phasors of the internal step c->con.iint, every substep's, on the device: ONE launch per step while the table fits a launch's arguments
+// (k_tide.hpp).  Called where a step's external mode begins; a table made for the same iint isplit dti dte time0 is kept
+static int tide_table(pomgpu_ctx *c) {
+  if (!c->ntide || !c->P.tide_sides) return POMGPU_OK;        // no side carries a tide (a table for the analysis alone): nobody reads the phasors
+  const pom_blkcon &k = c->con;
+  const double key[5] = {(double)k.iint, (double)k.isplit, k.dti, k.dte, k.time0};
+  if (c->tide_key_ok && memcmp(key, c->tide_key, sizeof key) == 0) return POMGPU_OK;
+  if (k.isplit < 1) return fail(c, POMGPU_EINVAL, "tides: isplit = %d", k.isplit);
+  const size_t n = (size_t)k.isplit * 2 * c->ntide;
+  if (n > c->tide_tab_cap) {                                  // the first step, or isplit has grown: not on the path of a run
+    double *tab = NULL;
+    if (hipMalloc((void **)&tab, n * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return fail(c, POMGPU_ENOMEM, "tides: no memory for the phasor table"); }
+    if (c->tide_tab) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->tide_tab); }
+    c->tide_tab = tab; c->tide_tab_cap = n;
+    c->P.tide_ph = tab;
+    if (c->wide.x) c->wide.x->P.tide_ph = tab;
+  }
+  std::vector<double> h(n);
+  for (int iext = 1; iext <= k.isplit; iext++) tide_phasors(c, tide_time(k, k.iint, iext), h.data() + (size_t)(iext - 1) * 2 * c->ntide);
+  launch_tide_table(c, c->tide_tab, h.data(), n);
+  memcpy(c->tide_key, key, sizeof key);
+  c->tide_key_ok = 1;
+  return POMGPU_OK;
+}
+// ---- the harmonic analysis ---------------------------------------------------------------------------------------------------------------
+static int harm_zero(pomgpu_ctx *c) {
+  const size_t np = 1 + 2 * (size_t)c->ntide;
+  HIPCHK(c, hipMemsetAsync(c->harm_acc, 0, 3 * np * c->P.n2 * sizeof(double), c->stream));   // +0.0 everywhere, behind whatever still accumulates
+  memset(c->harm_M, 0, sizeof c->harm_M);
+  c->harm_count = 0; c->harm_t[0] = c->harm_t[1] = 0.;
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_set_harmonic_analysis(pomgpu_ctx *c, int on, int every) {
+  if (c) { F32_REFUSE(c, "set_harmonic_analysis"); }
+  NEED_RAW(c);
+  if (!on) { harm_free(c); return POMGPU_OK; }
+  if (!c->ntide) return fail(c, POMGPU_EINVAL, "set_harmonic_analysis: no constituent table (pomgpu_set_tides)");
+  if (every < 1) return fail(c, POMGPU_EINVAL, "set_harmonic_analysis: every = %d", every);
+  const size_t np = 1 + 2 * (size_t)c->ntide, total = 3 * np * c->P.n2;
+  if (total >= ((size_t)1 << 32)) return fail(c, POMGPU_EINVAL, "set_harmonic_analysis: %zu accumulator cells are beyond 32-bit offsets", total);
+  if (!c->harm_acc) {
+    double *acc = NULL, *coef = NULL;
+    if (hipMalloc((void **)&acc, total * sizeof(double)) != hipSuccess || hipMalloc((void **)&coef, np * c->P.n2 * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError(); (void)hipFree(acc);
+      return fail(c, POMGPU_ENOMEM, "set_harmonic_analysis: no memory for the accumulators (%zu MB)", total * sizeof(double) >> 20);
+    }
+    c->harm_acc = acc; c->harm_coef = coef;
+  }
+  c->harm_on = 1; c->harm_every = every;
+  return harm_zero(c);
+}
+// the stage: what mean_accumulate completes first is what this one needs complete (elb uab vab of the current generation)
+static int harm_accumulate(pomgpu_ctx *c) {
+  ext_flush_deferred(c);
+  wide_flush(c);
+  const pom_blkcon &k = c->con;
+  const double t = k.time0 * 86400. + k.dti * (double)k.iint;
+  double ph[2 * POMGPU_TIDEMAX];
+  tide_phasors(c, t, ph);
+  HarmB b;
+  const int np = 1 + 2 * c->ntide;
+  double basis[HARM_MAXB];
+  basis[0] = 1.;
+  for (int q = 0; q < POMGPU_TIDEMAX; q++) { b.cn[q] = q < c->ntide ? ph[2 * q] : 0.; b.sn[q] = q < c->ntide ? ph[2 * q + 1] : 0.; }
+  for (int q = 0; q < c->ntide; q++) { basis[1 + 2 * q] = b.cn[q]; basis[2 + 2 * q] = b.sn[q]; }
+  launch_harm_accum(c, b);
+  for (int p = 0; p < np; p++) for (int q = 0; q < np; q++) c->harm_M[p * np + q] = c->harm_M[p * np + q] + basis[p] * basis[q];
+  if (!c->harm_count) c->harm_t[0] = t;
+  c->harm_t[1] = t;
+  c->harm_count += 1;
+  return POMGPU_OK;
+}
+#define HARM_NEED(c, what)                                                                 \
+  if (c) { F32_REFUSE(c, what); }                                                          \
+  NEED_RAW(c);                                                                             \
+  if (!c->harm_on) return fail(c, POMGPU_EINVAL, what ": the harmonic analysis is off (pomgpu_set_harmonic_analysis)")
+extern "C" int pomgpu_harmonic_accumulate(pomgpu_ctx *c) {
+  HARM_NEED(c, "harmonic_accumulate");
+  return harm_accumulate(c);
+}
+extern "C" int pomgpu_harmonic_count(pomgpu_ctx *c) { return c && c->harm_on ? c->harm_count : -1; }
+extern "C" int pomgpu_harmonic_reset(pomgpu_ctx *c) {
+  HARM_NEED(c, "harmonic_reset");
+  return harm_zero(c);
+}
+extern "C" int pomgpu_harmonic_sums(pomgpu_ctx *c, int field, double *out) {
+  HARM_NEED(c, "harmonic_sums");
+  if (field < 0 || field > 2 || !out) return fail(c, POMGPU_EINVAL, "harmonic_sums: field %d (0 elb, 1 uab, 2 vab) or no host array", field);
+  const size_t np = 1 + 2 * (size_t)c->ntide, n = np * c->P.n2;
+  HIPCHK(c, hipMemcpyAsync(out, c->harm_acc + (size_t)field * n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return POMGPU_OK;
+}
+extern "C" int pomgpu_harmonic_matrix(pomgpu_ctx *c, double *out, double *t2) {
+  HARM_NEED(c, "harmonic_matrix");
+  if (!out) return fail(c, POMGPU_EINVAL, "harmonic_matrix: no host array");
+  const int np = 1 + 2 * c->ntide;
+  memcpy(out, c->harm_M, (size_t)np * np * sizeof(double));
+  if (t2) { t2[0] = c->harm_t[0]; t2[1] = c->harm_t[1]; }
+  return POMGPU_OK;
+}
+// the inverse of the n x n matrix a (row-major) into inv by Gauss-Jordan elimination with partial pivoting; false: singular
+static bool harm_invert(const double *a, int n, double *inv) {
+  double w[HARM_MAXB][2 * HARM_MAXB];
+  for (int p = 0; p < n; p++) for (int q = 0; q < n; q++) { w[p][q] = a[p * n + q]; w[p][n + q] = p == q ? 1. : 0.; }
+  for (int col = 0; col < n; col++) {
+    int piv = col;
+    for (int p = col + 1; p < n; p++) if (fabs(w[p][col]) > fabs(w[piv][col])) piv = p;
+    if (!(fabs(w[piv][col]) > 0.) || !isfinite(w[piv][col])) return false;
+    if (piv != col) for (int q = 0; q < 2 * n; q++) { const double x = w[col][q]; w[col][q] = w[piv][q]; w[piv][q] = x; }
+    const double d = w[col][col];
+    for (int q = 0; q < 2 * n; q++) w[col][q] = w[col][q] / d;
+    for (int p = 0; p < n; p++) {
+      if (p == col) continue;
+      const double f = w[p][col];
+      for (int q = 0; q < 2 * n; q++) w[p][q] = w[p][q] - f * w[col][q];
+    }
+  }
+  for (int p = 0; p < n; p++) for (int q = 0; q < n; q++) { inv[p * n + q] = w[p][n + q]; if (!isfinite(inv[p * n + q])) return false; }
+  return true;
+}
+extern "C" int pomgpu_harmonic_solve(pomgpu_ctx *c, int field, double *coef) {
+  HARM_NEED(c, "harmonic_solve");
+  if (field < 0 || field > 2 || !coef) return fail(c, POMGPU_EINVAL, "harmonic_solve: field %d (0 elb, 1 uab, 2 vab) or no host array", field);
+  const int np = 1 + 2 * c->ntide;
+  HarmInv inv;
+  memset(&inv, 0, sizeof inv);
+  if (c->harm_count < np || !harm_invert(c->harm_M, np, inv.a))
+    return fail(c, POMGPU_EINVAL, "harmonic_solve: the normal matrix of %d samples is singular (%d unknowns)", c->harm_count, np);
+  const size_t n = (size_t)np * c->P.n2;
+  launch_harm_solve(c, inv, c->harm_acc + (size_t)field * n, c->harm_coef);
+  HIPCHK(c, hipMemcpyAsync(coef, c->harm_coef, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return POMGPU_OK;
+}
+int pomgpu_harmonic_planes(pomgpu_ctx *c, const double **planes) {
+  HARM_NEED(c, "write_harmonics");
+  const int np = 1 + 2 * c->ntide;
+  HarmInv inv;
+  memset(&inv, 0, sizeof inv);
+  if (c->harm_count < np || !harm_invert(c->harm_M, np, inv.a))
+    return fail(c, POMGPU_EINVAL, "write_harmonics: the normal matrix of %d samples is singular (%d unknowns)", c->harm_count, np);
+  const size_t n = (size_t)np * c->P.n2;
+  if (!c->harm_file && hipMalloc((void **)&c->harm_file, 3 * n * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError(); c->harm_file = NULL;
+    return fail(c, POMGPU_ENOMEM, "write_harmonics: no memory for the file's planes (%zu MB)", 3 * n * sizeof(double) >> 20);
+  }
+  for (int f = 0; f < 3; f++) {                               // harm_coef is reused field after field: the stream orders the launches
+    launch_harm_solve(c, inv, c->harm_acc + (size_t)f * n, c->harm_coef);
+    launch_harm_constants(c, c->harm_coef, c->harm_file + (size_t)f * n);
+  }
+  *planes = c->harm_file;
+  return POMGPU_OK;
+}
 static int advance(pomgpu_ctx *c, int more_steps_follow);
 extern "C" int pomgpu_advance(pomgpu_ctx *c) { return advance(c, 0); }
 static int advance(pomgpu_ctx *c, int more_steps_follow) {    // advance.f:6-59
@@ -2653,6 +2955,7 @@ static int advance(pomgpu_ctx *c, int more_steps_follow) {    // advance.f:6-59
     c->wr_deferred = 0;
     if ((rc = wr_on_side(c, 1))) return rc;
   }
+  if ((rc = tide_table(c))) return rc;                        // the tide's phasors of this step's substeps: ONE launch, none without a tide
   const int ph_ext = prof_phase_open(c);                      // "phase_external": the isplit substeps of mode_external (advance.f:27-29)
   if (!ext_loop_all(c))
   for (int iext = 1; iext <= c->con.isplit; iext++) {
@@ -2666,6 +2969,7 @@ static int advance(pomgpu_ctx *c, int more_steps_follow) {    // advance.f:6-59
   if ((rc = mode_internal(c, more_steps_follow))) return rc;
   if (c->mean_acc && (rc = mean_accumulate(c))) return rc;    // the time-mean output, where advance.f:38 writes
   if (c->nflt && body) float_stage(c);                        // the floats move with the u, v, w this step has left: ONE launch
+  if (c->harm_on && c->con.iint % c->harm_every == 0 && (rc = harm_accumulate(c))) return rc;   // the harmonic analysis: ONE launch per sampled step
   launch_check_velocity(c);   // result stays on the device; error flag is merged at the next get_con
   prof_phase_close(c, ph_step, "phase_step");
   return POMGPU_OK;
@@ -2749,6 +3053,8 @@ extern "C" int pomgpu_tune_placement(pomgpu_ctx *c, int steps, int max_try, doub
     return fail(c, POMGPU_EINVAL, "tune_placement: passive tracers are registered and the trial steps would move them -- tune first, register tracers afterwards");
   if (c->nflt)                                                // ... and the floats
     return fail(c, POMGPU_EINVAL, "tune_placement: floats are registered and the trial steps would move them -- tune first, upload floats afterwards");
+  if (c->ntide || c->harm_on)                                 // ... and the tide and its analysis: the trial steps are real steps
+    return fail(c, POMGPU_EINVAL, "tune_placement: a tide table or the harmonic analysis is on -- tune first, register tides afterwards");
 #ifdef POMGPU_EMU
   (void)steps; (void)max_try; (void)ms_out; (void)front_mib_out; (void)pad_mib_out;
   return POMGPU_OK;
@@ -2980,7 +3286,16 @@ extern "C" int pomgpu_bcond(pomgpu_ctx *c, int idx) {
   NEED(c);
   switch (idx) {
     case 1: launch_bcond1(c); break;
-    case 2: launch_ext_uvaf(c, 0); break;
+    case 2: {
+      if (c->ntide) {                                         // the tide's phasors are those of substep iext of step iint
+        if (c->con.iext < 1 || c->con.iext > c->con.isplit) return fail(c, POMGPU_EINVAL, "bcond(2) with a tide: iext = %d is not a substep of 1..%d", c->con.iext, c->con.isplit);
+        c->P.iext = c->con.iext;
+        const int rct = tide_table(c);
+        if (rct) return rct;
+      }
+      launch_ext_uvaf(c, 0);
+      break;
+    }
     case 4: launch_bcond4_edges(c); launch_mask_ts(c); break;
     case 5: launch_mask_w(c); break;
     case 6: launch_bcond6_edges(c); launch_mask_q(c); break;

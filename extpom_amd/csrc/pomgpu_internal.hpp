@@ -21,6 +21,7 @@
 #define POMGPU_NCOEF2 25   // derived 2-D coefficient arrays
 #define POMGPU_MAXREC 8
 #define POMGPU_TRMAX 8     // passive tracers per context (POMGPU_MAXTRACERS, include/pomgpu.h)
+#define POMGPU_TIDEMAX 8   // tidal constituents per context (POMGPU_MAXTIDES, include/pomgpu.h)
 #define POMGPU_KBMAX 128   // per-column private arrays in the tridiagonal kernels
 #define POMGPU_CTX_2D 1
 // bits of the device error word (pomgpu_ctx::d_err)
@@ -63,6 +64,12 @@ struct KP {
   // where the current aam lives: its blk3d slot, or the context's spare array after a k_advct_col<*, true> that left the new values there
   // (pomgpu_ctx::aam_parity, aam_buffers).  The column kernels of mode_internal read aam through it; everybody else reads the slot
   const double *aamc;
+  // the tide of the open boundaries (pomgpu_set_tides; tide_add, k_ext.hip): ntide constituents on the sides of tide_sides (POMGPU_SIDE_*
+  // bits).  ntide == 0: nothing below is read.  tide_ph: this internal step's phasors, cos and sin of constituent c at substep iext at
+  // [((iext - 1) * ntide + c) * 2].  tide_j: the coefficient lines of the west and east side, [side][c][elC elS unC unS][tide_ldj] along j;
+  // tide_i: south and north, along i.  tide_ldj, tide_ldi are the tile's jml, iml and stay so in a row window (row_window moves tide_j)
+  int ntide, tide_sides, tide_ldj, tide_ldi;
+  const double *tide_ph, *tide_j, *tide_i;
 };
 enum pomgpu_x2 { X2_ua, X2_va, X2_d, X2_el, X2_elb, X2_uab, X2_vab };
 
@@ -870,6 +877,27 @@ struct pomgpu_ctx {
   int nflt;
   double *flt_x, *flt_y, *flt_s, *flt_smp;
   int *flt_status, *flt_kind, *flt_id;
+  // tides (pomgpu_set_tides, include/pomgpu.h; KP::ntide above).  tide_host[side][q]: the caller's GLOBAL lines, side in the order W E S N, q =
+  // elC elS unC unS, ntide x (jm_global | im_global) doubles each (NULL: an OFF side; unC unS of a side that gave none are zeros) -- kept so
+  // that the extended tile of the wide-halo mode can be cut whenever it is made.  tide_g: im_global jm_global i0 j0 of the registration.
+  // tide_dev: this context's cut lines (KP::tide_j, tide_i point into it).  tide_tab: the phasor table of one internal step on the device,
+  // tide_tab_cap doubles; tide_key: the iint isplit dti dte time0 it was made for (tide_table, pomgpu_api.hip)
+  int ntide;
+  double tide_omega[POMGPU_TIDEMAX];
+  double *tide_host[4][4];
+  int tide_g[4];
+  double *tide_dev, *tide_tab;
+  size_t tide_tab_cap;
+  double tide_key[5];
+  int tide_key_ok;
+  // the harmonic analysis (pomgpu_set_harmonic_analysis): harm_acc = 3 fields (elb uab vab) x (1 + 2 ntide) planes of n2 doubles, plane-major;
+  // harm_M: the normal matrix of the basis [1, cn0, sn0, ...], (1 + 2 ntide)^2 doubles, row-major, summed on the host in the order of the
+  // samples; harm_count samples between harm_t[0] and harm_t[1] (seconds).  harm_coef: pomgpu_harmonic_solve's planes on the device
+  int harm_on, harm_every, harm_count;
+  double *harm_acc, *harm_coef;
+  double *harm_file;          // the planes of the harmonics file, 3 fields x (mean, nc amplitudes, nc phases), made when one is written (pomgpu_harmonic_planes)
+  double harm_M[(1 + 2 * POMGPU_TIDEMAX) * (1 + 2 * POMGPU_TIDEMAX)];
+  double harm_t[2];
   char err[512];
 };
 // The register-resident column kernels (k_vert.hip: their level loops are unrolled for a template bound, with_kbt) serve this context's
@@ -1066,6 +1094,9 @@ int pomgpu_materialize(pomgpu_ctx *c);                                          
 // n floats from host arrays, as pomgpu_float_upload registers them (pomgpu_api.hip); `what` names the caller in a refusal; status: entries other
 // than ACTIVE are kept over the admission's verdict (pomgpu_read_floats, cdf_in.hip), NULL = none
 int pomgpu_float_register(pomgpu_ctx *c, const char *what, int n, const double *x, const double *y, const double *sig, const int *kind, const int *id, const int *status);
+// the harmonics file's planes (cdf_out.hip: pomgpu_write_harmonics): solves the three fields and leaves, per field, the mean, nc amplitude and nc
+// phase planes (degrees in [0, 360)) on the device, 1 + 2 nc planes of n2 doubles per field at *planes; 0 or a pomgpu_status (pomgpu_api.hip)
+int pomgpu_harmonic_planes(pomgpu_ctx *c, const double **planes);
 void pomgpu_mirrors_written(pomgpu_ctx *c);                                    // the restart reader has written blk2d / blk3d mirrors on the device: what pomgpu_upload_2d / _3d invalidate (pomgpu_api.hip)
 void pomgpu_cold_tail(pomgpu_ctx *c, void (*update_initial)(pomgpu_ctx *), void (*sums)(pomgpu_ctx *));   // pomgpu_cold_start's 3-D tail in the reference's order (pomgpu_api.hip): dens twice, update_initial, baropg by npg, drx2d dry2d; then what pomgpu_upload invalidates
 int pomgpu_side_stream(pomgpu_ctx *c);                                          // create the side stream and its events (pomgpu_api.hip); 1 = there

@@ -269,6 +269,92 @@ subroutine float_step
   if (pomgpu_float_step(pom_ctx) /= 0) error_status = 1
 end subroutine
 
+! Tides (no counterpart in the reference; include/pomgpu.h "tides"): pom_tides_put after pomgpu_upload_state -- and after
+! pomgpu_tune_placement, which refuses while a table is registered -- registers nc constituents, omega in rad/s, on the open sides named by
+! the bits of sides (1 east, 2 south, 4 west, 8 north).  el_amp, el_pha, un_amp, un_pha are (nline, nc, 4), the last index east south west
+! north, nline >= max(im_global, jm_global): the GLOBAL lines, the same on every rank, amplitude in metres (un: the depth-mean NORMAL velocity
+! in m/s in the model's +i / +j sense) and Greenwich-style phase g in degrees, A cos(omega t - g).  with_un = .false.: un is zero.  nc = 0
+! clears the table.  The conversion C = A cos g, S = A sin g is made here on the host.  pom_harmonics(on, every) switches the harmonic
+! analysis of elb uab vab on; harmonic_step is its stage for a host that strings the routines together: call it after mode_internal,
+! mean_accumulate and float_step.  The files: read_tides_pnetcdf and write_harmonics_pnetcdf (pom_gpu_io.f90).
+subroutine pom_tides_put(nc, omega, sides, nline, el_amp, el_pha, un_amp, un_pha, with_un)
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  integer, intent(in) :: nc, sides, nline
+  double precision, intent(in), target :: omega(*)
+  double precision, intent(in) :: el_amp(nline, max(nc, 1), 4), el_pha(nline, max(nc, 1), 4), un_amp(nline, max(nc, 1), 4), un_pha(nline, max(nc, 1), 4)
+  logical, intent(in) :: with_un
+  double precision, allocatable, target :: pk(:)   ! the 16 lines the C interface takes, (n_global, nc) contiguous each, one behind the other
+  type(c_ptr), target :: lines(16)
+  type(pomgpu_file_meta) :: m
+  double precision :: gel, gun
+  integer :: ks, kc, ka, kn, ko
+  m%title = c_null_ptr; m%time_start = c_null_ptr; m%stats = c_null_ptr; m%create = 0
+  m%im_global = im_global; m%jm_global = jm_global
+  m%i0 = i_global(1); m%j0 = j_global(1)
+  if (nc <= 0) then
+    if (pomgpu_set_tides(pom_ctx, 0_c_int, c_null_ptr, 0_c_int, c_null_ptr, m) /= 0) error_status = 1
+    pom_harm_every = 0                       ! the analysis goes with its table
+    return
+  end if
+  allocate(pk(16*max(im_global, jm_global)*nc))
+  pk = 0.d0
+  lines = c_null_ptr
+  ko = 0
+  do ks = 1, 4
+    if (iand(sides, ishft(1, ks-1)) == 0) cycle
+    kn = jm_global
+    if (ks == 2 .or. ks == 4) kn = im_global
+    lines(4*(ks-1)+1) = c_loc(pk(ko+1))
+    lines(4*(ks-1)+2) = c_loc(pk(ko+kn*nc+1))
+    lines(4*(ks-1)+3) = c_loc(pk(ko+2*kn*nc+1))
+    lines(4*(ks-1)+4) = c_loc(pk(ko+3*kn*nc+1))
+    do kc = 1, nc
+      do ka = 1, kn
+        gel = el_pha(ka, kc, ks)*(3.14159265358979323846d0/180.d0)
+        pk(ko+(kc-1)*kn+ka) = el_amp(ka, kc, ks)*cos(gel)
+        pk(ko+kn*nc+(kc-1)*kn+ka) = el_amp(ka, kc, ks)*sin(gel)
+        if (with_un) then
+          gun = un_pha(ka, kc, ks)*(3.14159265358979323846d0/180.d0)
+          pk(ko+2*kn*nc+(kc-1)*kn+ka) = un_amp(ka, kc, ks)*cos(gun)
+          pk(ko+3*kn*nc+(kc-1)*kn+ka) = un_amp(ka, kc, ks)*sin(gun)
+        end if
+      end do
+    end do
+    ko = ko + 4*kn*nc
+  end do
+  if (pomgpu_set_tides(pom_ctx, int(nc, c_int), c_loc(omega), int(sides, c_int), c_loc(lines), m) /= 0) error_status = 1
+  deallocate(pk)
+end subroutine
+
+subroutine pom_harmonics(on, every)
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  logical, intent(in) :: on
+  integer, intent(in) :: every
+  integer(c_int) :: ion
+  ion = 0
+  if (on) ion = 1
+  if (pomgpu_set_harmonic_analysis(pom_ctx, ion, int(every, c_int)) /= 0) then
+    error_status = 1
+    pom_harm_every = 0
+  else
+    pom_harm_every = 0
+    if (on) pom_harm_every = every
+  end if
+end subroutine
+
+subroutine harmonic_step
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  if (pom_harm_every <= 0) return
+  if (mod(iint, pom_harm_every) /= 0) return
+  if (pomgpu_harmonic_accumulate(pom_ctx) /= 0) error_status = 1
+end subroutine
+
 subroutine check_velocity
   use pomgpu_iface
   implicit none

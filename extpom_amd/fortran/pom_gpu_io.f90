@@ -259,6 +259,77 @@ subroutine write_floats_pnetcdf(kind)
   if (pomgpu_write_floats(pom_ctx, c_loc(cname), m) /= 0) error_status = 1
 end subroutine
 
+! The tide file (include/pomgpu.h: pomgpu_set_tide_file): <wrk_pth>in/<netcdf_file>.tide.nc, where it exists, registered as pom_tides_put
+! would -- omega(ncon) and per side el_amp.<side> el_pha.<side> [un_amp.<side> un_pha.<side>].  A refusal is printed and sets error_status.
+subroutine read_tides_pnetcdf
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  type(pomgpu_file_meta) :: m
+  character(len=400) :: fname
+  character(kind=c_char, len=401), target :: cname
+  character(kind=c_char), pointer :: msg(:)
+  type(c_ptr) :: pm
+  integer :: n
+  logical :: there
+  write(fname, '(a,''in/'',a,''.tide.nc'')') trim(wrk_pth), trim(netcdf_file)
+  inquire(file=trim(fname), exist=there)
+  if (.not. there) return
+  cname = trim(fname)//c_null_char
+  if (my_task == 0) write(*,'(/''reading file '',a)') trim(fname)
+  m%title = c_null_ptr; m%time_start = c_null_ptr; m%stats = c_null_ptr; m%create = 0
+  m%im_global = im_global; m%jm_global = jm_global
+  m%i0 = i_global(1); m%j0 = j_global(1)
+  if (pomgpu_set_tide_file(pom_ctx, c_loc(cname), m) /= 0) then
+    error_status = 1
+    pm = pomgpu_last_error(pom_ctx)
+    if (c_associated(pm)) then
+      call c_f_pointer(pm, msg, (/512/))
+      n = 0
+      do while (n < 511)
+        if (msg(n+1) == c_null_char) exit
+        n = n + 1
+      end do
+      write(*,'(/i4,''] Error: read_tides_pnetcdf: '',511a1)') my_task, msg(1:n)
+    end if
+  end if
+end subroutine
+
+! The harmonics file (pomgpu_write_harmonics): <wrk_pth>out/<netcdf_file>.harmonics.nc, mean, amplitude and phase maps of elb uab vab per
+! constituent; every rank writes its patch as in pomgpu_write_file, rank 0 lays the file out first.  Joined before it returns (it is written
+! at the end of a run).  Nothing happens while the analysis is off.
+subroutine write_harmonics_pnetcdf
+  use pomgpu_iface
+  implicit none
+  include 'pom.h'
+  type(pomgpu_file_meta) :: m
+  character(len=400) :: fname
+  character(kind=c_char, len=401), target :: cname
+  character(kind=c_char, len=41), target :: ctitle
+  character(kind=c_char, len=27), target :: cstart
+  integer :: pass
+  if (pomgpu_harmonic_count(pom_ctx) < 0) return
+  write(fname, '(a,''out/'',a,''.harmonics.nc'')') trim(wrk_pth), trim(netcdf_file)
+  cname = trim(fname)//c_null_char
+  ctitle = trim(title)//c_null_char
+  cstart = trim(time_start)//c_null_char
+  call pomgpu_push_con
+  if (my_task == 0) write(*,'(/''writing file '',a)') trim(fname)
+  m%title = c_loc(ctitle); m%time_start = c_loc(cstart); m%stats = c_null_ptr
+  m%im_global = im_global; m%jm_global = jm_global
+  m%i0 = i_global(1); m%j0 = j_global(1)
+  do pass = 1, 2
+    m%create = 0
+    if (pass == 1 .and. my_task == 0) m%create = 1
+    if ((pass == 1) .eqv. (my_task == 0)) then
+      if (pomgpu_write_harmonics(pom_ctx, c_loc(cname), m) /= 0) error_status = 1
+    end if
+    call pomgpu_barrier_mpi
+  end do
+  if (pomgpu_io_wait(pom_ctx) /= 0) error_status = 1
+  call pomgpu_barrier_mpi
+end subroutine
+
 ! <wrk_pth>in/<netcdf_file>.floats.nc, where it exists, registered as pom_floats_put would (pomgpu_read_floats): x y sig are required,
 ! status kind id optional -- a file with x y sig alone is an initial file any tool can write.  A refusal is printed as the restart reader's
 ! is and sets error_status.

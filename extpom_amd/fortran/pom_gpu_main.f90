@@ -31,6 +31,10 @@
 !        ... --cold | --cold-z <state.out> <nsteps> --floats   (Lagrangian floats: registered from <wrk_pth>in/<netcdf_file>.floats.nc where it
 !                                                                exists; wherever an output file is written, <wrk_pth>out/<netcdf_file>.floats.<nnnn>.nc
 !                                                                beside it; <wrk_pth>out/<netcdf_file>.floats.rst.nc at the end of the run)
+!        ... --cold | --cold-z <state.out> <nsteps> --tides    (the tide of the open boundaries: the table of <wrk_pth>in/<netcdf_file>.tide.nc)
+!        ... --cold | --cold-z <state.out> <nsteps> --harmonics [every]   (the harmonic analysis of elb uab vab with that table, every
+!                                                                `every`-th step (default 1); <wrk_pth>out/<netcdf_file>.harmonics.nc at the end
+!                                                                of the run; a run whose tide comes in the lbry file names --tides for the table)
 ! The water files <wrk_pth>in/<netcdf_file>.water.NNNN.nc need no flag: they are registered when record 0000's exists.
 program pom_gpu_main
   use pomgpu_iface
@@ -41,8 +45,9 @@ program pom_gpu_main
   integer :: nsteps, nrec, n, rc, n2, n3, nbd, ntrac
   double precision :: vtot, atot, mtot, stot, tavg, savg, eavg, ekin
   double precision, allocatable, target :: tr(:,:,:,:), sr(:,:,:,:)
-  character(len=256) :: fin, fout, arg3
-  logical :: cold, mean, sss, floats
+  character(len=256) :: fin, fout, arg3, arg4
+  logical :: cold, mean, sss, floats, tides, harm
+  integer :: hevery, ios
 
   call get_command_argument(1, fin)
   call get_command_argument(2, fout)
@@ -51,7 +56,7 @@ program pom_gpu_main
   nbd = 8*jm_local + 8*im_local + (12+12+6+6)*0   ! filled below
   nbd = 20*jm_local + 20*im_local + 18*jm_local*kb + 18*im_local*kb   ! bdry: 20 J, 20 I... see pom_layout.h
   cold = trim(fin) == '--cold' .or. trim(fin) == '--cold-z'
-  mean = .false.; sss = .false.; ntrac = 0; floats = .false.
+  mean = .false.; sss = .false.; ntrac = 0; floats = .false.; tides = .false.; harm = .false.; hevery = 1
   if (trim(fin) == '--cold-z') then         ! the init and the clim file are on z levels (initialize.f:410-422)
     pom_init_on_z = .true.; pom_clim_on_z = .true.
   end if
@@ -65,6 +70,19 @@ program pom_gpu_main
       if (trim(arg3) == '--mean') mean = .true.
       if (trim(arg3) == '--sss') sss = .true.
       if (trim(arg3) == '--floats') floats = .true.
+      if (trim(arg3) == '--tides') tides = .true.
+      if (trim(arg3) == '--harmonics') then
+        harm = .true.
+        if (n < command_argument_count()) then     ! an optional number behind it
+          call get_command_argument(n + 1, arg4)
+          read(arg4, *, iostat=ios) hevery
+          if (ios == 0) then
+            n = n + 1
+          else
+            hevery = 1
+          end if
+        end if
+      end if
       if (trim(arg3) == '--lbry-sides') then
         n = n + 1
         call get_command_argument(n, arg3)
@@ -132,6 +150,8 @@ program pom_gpu_main
     call read_tracers_pnetcdf                ! <wrk_pth>in/<netcdf_file>.tracer.nc, where it exists
   end if
   if (floats) call read_floats_pnetcdf       ! <wrk_pth>in/<netcdf_file>.floats.nc, where it exists
+  if (tides .or. harm) call read_tides_pnetcdf   ! <wrk_pth>in/<netcdf_file>.tide.nc, where it exists
+  if (harm) call pom_harmonics(.true., hevery)
   if (mean) call pom_output_mean(.true.)
   if (sss) call pom_surface_sss(.true.)
   do n = 1, nsteps                          ! pom.f:17-19
@@ -147,6 +167,7 @@ program pom_gpu_main
   end do
   if (ntrac > 0) call write_tracers_pnetcdf(0)   ! <wrk_pth>out/<netcdf_file>.tracer.rst.nc: trb, tr and the work array trf
   if (floats) call write_floats_pnetcdf(0)       ! <wrk_pth>out/<netcdf_file>.floats.rst.nc: output and checkpoint in one
+  if (harm) call write_harmonics_pnetcdf         ! <wrk_pth>out/<netcdf_file>.harmonics.nc
   if (pom_mean_on) call pom_output_mean(.false.)
   my_task = 0; master_task = 0
   call domain_stats(vtot, atot, mtot, stot, tavg, savg, eavg, ekin)   ! print_section's sums, no state download needed
@@ -191,6 +212,7 @@ subroutine advance_hot
   call mode_internal
   call mean_accumulate                       ! the time-mean output, where advance.f:38 writes (nothing while it is off)
   call float_step                            ! the Lagrangian floats (nothing without them)
+  call harmonic_step                         ! the harmonic analysis (nothing while it is off)
   call check_velocity
 end subroutine
 

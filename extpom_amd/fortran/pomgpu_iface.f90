@@ -21,6 +21,8 @@ module pomgpu_iface
   integer, save :: pom_lbry_sides = 3
   ! the time-mean output is on (pom_output_mean): `advance` accumulates behind mode_internal, write_output_pnetcdf writes the mean file
   logical, save :: pom_mean_on = .false.
+  ! the harmonic analysis samples every pom_harm_every-th internal step (pom_harmonics; 0: off): harmonic_step asks it
+  integer, save :: pom_harm_every = 0
   type, bind(C) :: pomgpu_file_meta               ! include/pomgpu.h
     type(c_ptr) :: title, time_start
     integer(c_int) :: im_global, jm_global, i0, j0, create
@@ -188,6 +190,28 @@ module pomgpu_iface
     end function
     integer(c_int) function pomgpu_read_floats(ctx, path, meta, time_out, iint_out) bind(C, name='pomgpu_read_floats')
       import; type(c_ptr), value :: ctx, path, time_out, iint_out; type(pomgpu_file_meta) :: meta
+    end function
+    ! tides (include/pomgpu.h): lines = 16 pointers, 4 * side + q, side 0 east 1 south 2 west 3 north, q = elC elS unC unS, each (n_global, nc)
+    integer(c_int) function pomgpu_set_tides(ctx, nc, omega, sides, lines, meta) bind(C, name='pomgpu_set_tides')
+      import; type(c_ptr), value :: ctx, omega, lines; integer(c_int), value :: nc, sides; type(pomgpu_file_meta) :: meta
+    end function
+    integer(c_int) function pomgpu_set_tide_file(ctx, path, meta) bind(C, name='pomgpu_set_tide_file')
+      import; type(c_ptr), value :: ctx, path; type(pomgpu_file_meta) :: meta
+    end function
+    integer(c_int) function pomgpu_tide_count(ctx) bind(C, name='pomgpu_tide_count')
+      import; type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function pomgpu_set_harmonic_analysis(ctx, on, every) bind(C, name='pomgpu_set_harmonic_analysis')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: on, every
+    end function
+    integer(c_int) function pomgpu_harmonic_accumulate(ctx) bind(C, name='pomgpu_harmonic_accumulate')
+      import; type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function pomgpu_harmonic_count(ctx) bind(C, name='pomgpu_harmonic_count')
+      import; type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function pomgpu_write_harmonics(ctx, path, meta) bind(C, name='pomgpu_write_harmonics')
+      import; type(c_ptr), value :: ctx, path; type(pomgpu_file_meta) :: meta
     end function
     integer(c_int) function pomgpu_write_restart(ctx, path, meta) bind(C, name='pomgpu_write_restart')
       import; type(c_ptr), value :: ctx, path; type(pomgpu_file_meta) :: meta

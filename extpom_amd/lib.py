@@ -126,6 +126,18 @@ _SIGS = {
     "pomgpu_float_sample": (_I, [_P, _P]),
     "pomgpu_write_floats": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
     "pomgpu_read_floats": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "pomgpu_set_tides": (_I, [_P, _I, _P, _I, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(FileMeta)]),
+    "pomgpu_tide_count": (_I, [_P]),
+    "pomgpu_tide_phasors": (_I, [_P, _I, _I, _P]),
+    "pomgpu_set_harmonic_analysis": (_I, [_P, _I, _I]),
+    "pomgpu_harmonic_accumulate": (_I, [_P]),
+    "pomgpu_harmonic_count": (_I, [_P]),
+    "pomgpu_harmonic_sums": (_I, [_P, _I, _P]),
+    "pomgpu_harmonic_matrix": (_I, [_P, _P, _P]),
+    "pomgpu_harmonic_solve": (_I, [_P, _I, _P]),
+    "pomgpu_harmonic_reset": (_I, [_P]),
+    "pomgpu_write_harmonics": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
+    "pomgpu_set_tide_file": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
     "pomgpu_write_restart":(_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),
     "pomgpu_read_restart": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(FileMeta), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "pomgpu_set_forcing_files": (_I, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(FileMeta)]),

@@ -271,10 +271,14 @@ class PomGpu:
         time means of uab vab elb u v t s rho w since set_mean_output or the last such file in place of their values now.
         kind = "tracer_restart" | "tracer_output" | "tracer_output_mean": the tracers' own files (pomgpu_write_tracers); trstats: the
         rank-reduced (ntr, 4) statistics of the two output kinds, None = this tile's own.  kind = "floats": the float file
-        (pomgpu_write_floats), output and checkpoint of the Lagrangian floats in one"""
+        (pomgpu_write_floats), output and checkpoint of the Lagrangian floats in one.  kind = "harmonics": mean, amplitude and phase maps of elb uab
+        vab per constituent from the harmonic analysis (pomgpu_write_harmonics); writing resets nothing"""
         st = self.st
         m = _lib.FileMeta(title.encode(), time_start.encode(), im_global or st.im, jm_global or st.jm, st.i_off + 1, st.j_off + 1,
                           1 if create else 0, (ctypes.c_double * 8)(*stats) if stats is not None else None)
+        if kind == "harmonics":
+            self._chk(self.L.pomgpu_write_harmonics(self.h, str(path).encode(), ctypes.byref(m)), "write_harmonics")
+            return
         if kind == "floats":
             self._chk(self.L.pomgpu_write_floats(self.h, str(path).encode(), ctypes.byref(m)), "write_floats")
             return
@@ -440,6 +444,113 @@ class PomGpu:
         t, ii = ctypes.c_double(), ctypes.c_double()
         self._chk(self.L.pomgpu_read_floats(self.h, str(path).encode(), ctypes.byref(m), ctypes.byref(t), ctypes.byref(ii)), "read_floats")
         return t.value, ii.value
+
+    # ---- tides (pomgpu.h "tides") -------------------------------------------------------------
+    TIDE_SIDES = ("east", "south", "west", "north")             # the order of the POMGPU_SIDE_* bits and of pomgpu_set_tides' lines
+    HARMONIC_FIELDS = ("elb", "uab", "vab")
+
+    @staticmethod
+    def tide_coefficients(amp, pha):
+        """amplitude A and Greenwich-style phase g in degrees, A cos(omega t - g), as the C interface's C = A cos g, S = A sin g"""
+        import math
+        amp = np.asarray(amp, dtype=np.float64)
+        g = np.asarray(pha, dtype=np.float64) * (math.pi / 180.0)
+        cos, sin = np.frompyfunc(math.cos, 1, 1), np.frompyfunc(math.sin, 1, 1)      # the C library's, as pomgpu_set_tide_file converts
+        return amp * cos(g).astype(np.float64), amp * sin(g).astype(np.float64)
+
+    def set_tides(self, omega=(), im_global=None, jm_global=None, **sides):
+        """pomgpu_set_tides: omega in rad/s, one per constituent (none: the table is cleared); per open side that carries a tide
+        east= / south= / west= / north= dict(el_amp, el_pha[, un_amp, un_pha]), each (ncon, jm_global | im_global): the elevation in metres and
+        the depth-mean NORMAL velocity in m/s in the model's +i / +j sense, as amplitude and phase in degrees, A cos(omega t - g).  The
+        GLOBAL lines, the same on every rank: the library cuts this tile's stretch at (i_off+1, j_off+1) and the extended tile's."""
+        st = self.st
+        omega = np.ascontiguousarray(omega, dtype=np.float64).ravel()
+        nc = omega.size
+        ig, jg = im_global or st.im, jm_global or st.jm
+        unknown = set(sides) - set(self.TIDE_SIDES)
+        if unknown:
+            raise ValueError(f"set_tides: {sorted(unknown)} is not one of {' '.join(self.TIDE_SIDES)}")
+        keep, ptrs, bits = [], [None] * 16, 0
+        for s, name in enumerate(self.TIDE_SIDES):
+            d = sides.get(name)
+            if d is None:
+                continue
+            bits |= 1 << s
+            n = jg if name in ("east", "west") else ig
+            for q0, (ka, kp) in enumerate((("el_amp", "el_pha"), ("un_amp", "un_pha"))):
+                if d.get(ka) is None and d.get(kp) is None:
+                    continue
+                if d.get(ka) is None or d.get(kp) is None:
+                    raise ValueError(f"set_tides: {name} needs both {ka} and {kp}")
+                C, S = self.tide_coefficients(d[ka], d[kp])
+                for q, a in ((2 * q0, C), (2 * q0 + 1, S)):
+                    a = np.ascontiguousarray(a, dtype=np.float64)
+                    if a.shape != (nc, n):
+                        raise ValueError(f"set_tides: {name} {ka} is {a.shape}, not (ncon, n_global) = {(nc, n)}")
+                    keep.append(a)
+                    ptrs[4 * s + q] = a.ctypes.data
+        m = _lib.FileMeta(b"", b"", ig, jg, st.i_off + 1, st.j_off + 1, 0, None)
+        arr = (ctypes.c_void_p * 16)(*ptrs)
+        self._chk(self.L.pomgpu_set_tides(self.h, nc, self._p(omega) if nc else None, bits, arr, ctypes.byref(m)), "set_tides")
+
+    def set_tide_file(self, path, im_global=None, jm_global=None):
+        """pomgpu_set_tide_file: the table from a classic NetCDF file -- omega(ncon) and per side el_amp.<side> el_pha.<side> [un_amp.<side>
+        un_pha.<side>], (ncon, jm_global | im_global) -- as set_tides would register it"""
+        st = self.st
+        m = _lib.FileMeta(b"", b"", im_global or st.im, jm_global or st.jm, st.i_off + 1, st.j_off + 1, 0, None)
+        self._chk(self.L.pomgpu_set_tide_file(self.h, str(path).encode(), ctypes.byref(m)), "set_tide_file")
+
+    def tide_count(self) -> int:
+        return int(self.L.pomgpu_tide_count(self.h))
+
+    def tide_phasors(self, iint: int, iext: int):
+        """pomgpu_tide_phasors: (ncon, 2) -- cos and sin of omega t at substep iext of internal step iint, as the host evaluates them"""
+        out = np.empty((max(self.tide_count(), 1), 2))
+        self._chk(self.L.pomgpu_tide_phasors(self.h, int(iint), int(iext), self._p(out)), "tide_phasors")
+        return out[:self.tide_count()]
+
+    def set_harmonic_analysis(self, on: bool = True, every: int = 1):
+        """pomgpu_set_harmonic_analysis: from now on every internal step with iint % every == 0 adds elb uab vab, times 1 and times cos / sin
+        of every constituent of the tide table, to fp64 sums on the device; calling it again zeroes them, on=False frees them"""
+        self._chk(self.L.pomgpu_set_harmonic_analysis(self.h, 1 if on else 0, int(every)), "set_harmonic_analysis")
+
+    def harmonic_accumulate(self):
+        """pomgpu_harmonic_accumulate, for a host that strings the routines together (advance and run do it themselves)"""
+        self._chk(self.L.pomgpu_harmonic_accumulate(self.h), "harmonic_accumulate")
+
+    def harmonic_count(self) -> int:
+        return int(self.L.pomgpu_harmonic_count(self.h))
+
+    def harmonic_reset(self):
+        self._chk(self.L.pomgpu_harmonic_reset(self.h), "harmonic_reset")
+
+    def _harm_planes(self):
+        return np.empty((1 + 2 * self.tide_count(), self.st.jm_local, self.st.im_local))
+
+    def harmonic_sums(self, name: str):
+        """pomgpu_harmonic_sums: (2 ncon + 1, jm_local, im_local) -- the sums of f, f cos, f sin, ... of one of HARMONIC_FIELDS"""
+        out = self._harm_planes()
+        self._chk(self.L.pomgpu_harmonic_sums(self.h, self.HARMONIC_FIELDS.index(name), self._p(out)), "harmonic_sums")
+        return out
+
+    def harmonic_matrix(self):
+        """pomgpu_harmonic_matrix: the (2 ncon + 1)^2 normal matrix and (t_first, t_last) of the samples in seconds"""
+        n = 1 + 2 * self.tide_count()
+        out, t2 = np.empty((n, n)), np.empty(2)
+        self._chk(self.L.pomgpu_harmonic_matrix(self.h, self._p(out), self._p(t2)), "harmonic_matrix")
+        return out, (float(t2[0]), float(t2[1]))
+
+    def harmonic_solve(self, name: str):
+        """pomgpu_harmonic_solve: (2 ncon + 1, jm_local, im_local) -- the mean, then C and S of every constituent"""
+        out = self._harm_planes()
+        self._chk(self.L.pomgpu_harmonic_solve(self.h, self.HARMONIC_FIELDS.index(name), self._p(out)), "harmonic_solve")
+        return out
+
+    def harmonic_constants(self, name: str):
+        """(mean, amp, pha) of harmonic_solve: amp (ncon, jm_local, im_local), pha in degrees in [0, 360): g of A cos(omega t - g)"""
+        c = self.harmonic_solve(name)
+        C, S = c[1::2], c[2::2]
+        return c[0], np.hypot(C, S), np.mod(np.degrees(np.arctan2(S, C)), 360.0)
 
     def read_restart(self, path, im_global=None, jm_global=None):
         """read_restart_pnetcdf (io_pnetcdf.F:2420-2768) without PnetCDF: this tile's patch of the 37 restart fields from a classic

@@ -681,6 +681,72 @@ int pomgpu_float_sample(pomgpu_ctx *ctx, double *out5n);
 int pomgpu_write_floats(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta);
 int pomgpu_read_floats(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta, double *time_out, double *iint_out);
 
+/* ---- tides: harmonic open-boundary forcing and harmonic analysis (no counterpart in the reference; optional, off by default: with no
+ * table registered every byte and every launch is as without them) ---------------------------------------------------------------------------
+ * One table of nc <= POMGPU_MAXTIDES constituents, omega[c] in rad/s, serves the forcing and the analysis.
+ * pomgpu_set_tides(ctx, nc, omega, sides, lines, meta): nc == 0 clears the table (and switches the analysis off).  sides: the POMGPU_SIDE_*
+ * bits of the open boundaries that carry a tide (0: a table for the analysis alone).  lines[4 * s + q], s = 0 east, 1 south, 2 west, 3 north
+ * (the order of the bits), q = 0..3 = elC elS unC unS: HOST arrays of nc x n_global doubles, constituent-major, n_global = jm_global for east /
+ * west and im_global for south / north -- the GLOBAL line, the same on every rank; entries of an OFF side are not looked at; unC, unS may be
+ * NULL: zero.  elC elS are elevation coefficients in metres, unC unS those of the depth-mean NORMAL velocity in m/s in the model's +i / +j
+ * sense (not "outward").  meta: im_global jm_global i0 j0 are used; the library cuts the tile's stretch and, in the wide-halo external mode,
+ * the extended tile's -- no message round, and the boundary messages carry nothing new.  The lines are copied; the call synchronises.
+ * The value of constituent c is C * cos(omega[c] * t) + S * sin(omega[c] * t); amplitude A and Greenwich-style phase g in degrees,
+ * A * cos(omega * t - g), are C = A cos g, S = A sin g (the Python and Fortran layers convert on the host).
+ * Where the tide enters: bcond(2) of substep iext of internal step iint (bounds_forcing.f:43-83).  Where the reference reads elw(j) the library
+ * reads e = elw(j), then e = e + (elC[c][j] * cw[c] + elS[c][j] * sw[c]) for c = 0 .. nc-1 in that order; uabw(j) alike with unC unS; the
+ * other three sides alike with ele uabe, els vabs, eln vabn.  The tangential values (vabw vabe uabs uabn) are untouched.  The STORED boundary
+ * arrays are never modified: a download gives what lateral_bc or the host left.  ramp, dum, dvm act afterwards as they do without a tide, so
+ * lramp ramps the tide too.  Every path of the external mode does this, also the stand-alone pomgpu_mode_external and pomgpu_bcond(2).
+ * Phasors: cw[c] = cos(omega[c] * t), sw[c] = sin(omega[c] * t), t = (time0 * 86400. + dti * (double)(iint - 1)) + dte * (double)iext seconds,
+ * evaluated in fp64 ON THE HOST with the C library, as cor is.  pomgpu_tide_phasors(ctx, iint, iext, out) returns them, out[2c] = cw[c],
+ * out[2c + 1] = sw[c].  A step's isplit x nc x 2 phasors reach the device as the arguments of ONE launch per internal step (k_tide_table,
+ * while isplit * nc <= 240 -- isplit 30 at nc 8; a longer table takes one launch per 480 doubles); nothing is added per substep and
+ * pomgpu_run stays free of host-device synchronisation.
+ * pomgpu_tide_count: nc.
+ * Harmonic analysis.  pomgpu_set_harmonic_analysis(ctx, on, every): from now on, at the end of every internal step with iint % every == 0 --
+ * in pomgpu_advance / pomgpu_run behind the floats' stage and in front of check_velocity, in every mode -- ONE launch (k_harm_accum) adds f,
+ * f * cn[c] and f * sn[c] of f = elb, uab, vab (what the mean output samples, read from the current generation) to 1 + 2 nc fp64 planes per
+ * field, cn[c] = cos(omega[c] * t_n), sn[c] = sin(omega[c] * t_n), t_n = time0 * 86400. + dti * (double)iint from the host as kernel
+ * arguments.  The host adds the outer product of the same basis b = [1, cn0, sn0, cn1, sn1, ...] to the (2 nc + 1)^2 normal matrix, row by
+ * row.  on = 1 (again) zeroes sums, matrix and count; on = 0 frees them.  No lazily kept array is formed by the stage.
+ * pomgpu_harmonic_accumulate: the stage alone, for a host that strings the routines together (after pomgpu_mode_internal); it samples
+ * whatever iint says, `every` is the caller's business there.
+ * pomgpu_harmonic_count: samples so far, -1 while off.  pomgpu_harmonic_sums(ctx, field, out): field 0 elb, 1 uab, 2 vab; out = (2 nc + 1)
+ * planes of im_local x jm_local doubles, plane p = the sum of f * b[p].  pomgpu_harmonic_matrix(ctx, out, t2): the matrix, row-major, and
+ * t2[0], t2[1] = t_n of the first and last sample (t2 may be NULL).  pomgpu_harmonic_solve(ctx, field, coef): the host inverts the matrix
+ * (Gauss-Jordan with partial pivoting, fp64), a second kernel (k_harm_solve) applies the inverse per cell: coef = 2 nc + 1 planes, the mean,
+ * then C and S of every constituent: f ~ mean + sum C cos(omega t) + S sin(omega t); amplitude hypot(C, S), phase g = atan2(S, C).
+ * pomgpu_harmonic_reset: zeroes sums, matrix and count.  Nothing else resets them.
+ * Refused with POMGPU_EINVAL, error_status = 1 and the cause in pomgpu_last_error, before anything changes: nc outside 0..POMGPU_MAXTIDES; a
+ * NULL omega or meta with nc > 0; an omega or coefficient that is not finite; a NULL elevation line of an ON side; a tile stretch (or the
+ * extended tile's) outside the global line; the two fp32 study builds; the analysis with no table, every < 1, or a singular matrix (fewer
+ * samples than unknowns).  pomgpu_tune_placement refuses while a tide table or the analysis is on -- its trial steps are real steps.
+ * pomgpu_write_harmonics: one CDF-2 file through the asynchronous patch writer (every rank its patch, as pomgpu_write_output), description
+ * "harmonics file": dimensions ncon y x; omega(ncon), count, t_first, t_last (scalars, seconds), and for f = elb uab vab: f_mean(y,x),
+ * f_amp(ncon,y,x), f_pha(ncon,y,x), all NC_DOUBLE; the phase is g of A cos(omega t - g) in degrees in [0, 360), formed on the device
+ * (k_harm_constants: hypot and atan2 of k_harm_solve's C and S).  Writing resets nothing.  Refused like pomgpu_harmonic_solve.
+ * pomgpu_set_tide_file: registers the table of a classic file (CDF-1 or CDF-2) as pomgpu_set_tides would.  omega(ncon), NC_DOUBLE, and per side
+ * that has them el_amp.<side> el_pha.<side> and optionally un_amp.<side> un_pha.<side>, <side> = east south west north, each (ncon, jm_global |
+ * im_global) NC_DOUBLE, amplitude and phase in degrees, are found by name; a side without el lines is OFF; anything else in the file is ignored.
+ * The conversion is C = A cos(g pi / 180), S = A sin(g pi / 180) with the C library.  Refused before anything changes: a file it cannot open,
+ * any other magic, omega absent or not one dimension of 1..POMGPU_MAXTIDES, an amplitude without its phase, un lines without el lines, a variable
+ * of another type or shape, a record variable, one that reaches beyond the file; then pomgpu_set_tides' own refusals.
+ * Not built: the Fortran wrappers and the driver's flags, sums that survive a restart, 3-D currents, nodal corrections, the tidal potential. */
+#define POMGPU_MAXTIDES 8
+int pomgpu_set_tides(pomgpu_ctx *ctx, int nc, const double *omega, int sides, const double *const *lines16, const pomgpu_file_meta *meta);
+int pomgpu_tide_count(pomgpu_ctx *ctx);
+int pomgpu_tide_phasors(pomgpu_ctx *ctx, int iint, int iext, double *out2nc);
+int pomgpu_set_harmonic_analysis(pomgpu_ctx *ctx, int on, int every);
+int pomgpu_harmonic_accumulate(pomgpu_ctx *ctx);
+int pomgpu_harmonic_count(pomgpu_ctx *ctx);
+int pomgpu_harmonic_sums(pomgpu_ctx *ctx, int field, double *out);
+int pomgpu_harmonic_matrix(pomgpu_ctx *ctx, double *out, double *t2);
+int pomgpu_harmonic_solve(pomgpu_ctx *ctx, int field, double *coef);
+int pomgpu_harmonic_reset(pomgpu_ctx *ctx);
+int pomgpu_write_harmonics(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta);
+int pomgpu_set_tide_file(pomgpu_ctx *ctx, const char *path, const pomgpu_file_meta *meta);
+
 /* ---- the hot path: kernels (solver.f, bounds_forcing.f), device-resident ---------------- */
 int pomgpu_advave(pomgpu_ctx *ctx);              /* solver.f:6-198   */
 int pomgpu_advct(pomgpu_ctx *ctx);               /* solver.f:201-408 */
